@@ -8,8 +8,11 @@ exits with its code; launched by the driver under torch.distributed.run it is on
 Rank 0 prints ONE JSON line.  A "step" = forward + backward + gradient all-reduce + Adam on one batch
 of synthetic 256x256 RGB x 16-frame windows (BASELINE.json configs[1]: batch 32 per GPU), inputs
 resident in HBM before the timed region.  ``value`` = global_batch * seq_len * steps / wall time of the
-timed region (barrier + synchronize on both sides, max over ranks).
+timed region (barrier + synchronize on both sides, max over ranks).  ``--dump-outputs DIR``: what the last timed step handed
+its caller (loss, predictions, the updated variables) as float32 .npy files under DIR (dump_outputs).
 
+A plain run measures the headline and nothing else.  Everything below, and the first-step loss check against the committed
+oracle value (``loss_check``), runs only with ``--full``.
 Extra objects (N = 1): ``layers`` (every conv launch of the step timed alone: median of >= 30 HIP-event
 samples of 5 launches each: FLOP, us, TFLOP/s, fraction of the fp32 MFMA peak), ``roofline`` (the kernel with the largest
 share of the step, taken from that table, plus the same by kernel family), ``hbm`` (dynimg calls and Adam against the
@@ -51,6 +54,11 @@ def parse_args():
   ap.add_argument('--channels', type=int, default=3)
   ap.add_argument('--model', default='geeco-f', choices=['geeco-f', 'e2e_vmc'])
   ap.add_argument('--no-graph', action='store_true', help='launch eagerly instead of replaying hipGraphs')
+  ap.add_argument('--full', action='store_true',
+                  help='after the headline, also the loss check, the per-layer / roofline / hbm tables, the CPU baseline, the other '
+                       'legs (N = 1) and the comm report (N > 1); the --skip-* options below pick among them')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='write what the last timed step computed (loss, predictions, updated variables) as DIR/<name>.npy')
   ap.add_argument('--skip-cpu', action='store_true', help='skip the cpu_baseline leg')
   ap.add_argument('--skip-layers', action='store_true', help='skip the per-layer / roofline / hbm legs (profiling runs)')
   ap.add_argument('--cpu-steps', type=int, default=60, help='upper bound; the leg stops after ~12 s of CPU work')
@@ -283,6 +291,32 @@ def dominant_roofline(rows):
           'family': {'kernel': fname, 'launches_per_step': f['launches'], 'achieved': round(fach, 2),
                      'frac': round(fach / PEAK_F32_MFMA_TFLOPS, 4), 'us_per_step': round(f['us'], 1),
                      'share_of_conv_time': round(f['us'] / total, 4)}}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(model, out_dir):
+  """What the timed step hands its caller, as it stands after the last timed step, one float32 .npy file per array under
+  `out_dir`: ``loss.npy`` and the loss parts (``loss_<head>.npy``), the predictions of the last forward
+  (``pred_<head>.npy``, one row per window of the batch) and every variable after the optimiser update
+  (``var.<scope.name>.npy``, '/' of the variable name written as '.'; 30 MB for the default model).  The inputs are the
+  seeded ones of synthetic_batch and the weights those of store.initialize(seed=0), so two builds run with the same
+  arguments can be compared file by file."""
+  import numpy as np
+  import torch
+  torch.cuda.synchronize()
+  arrays = {k: v.detach().reshape(1) for k, v in model.loss_parts().items()}
+  arrays.update({'pred_' + k: v for k, v in model.predictions().items()})
+  arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+  arrays.update({'var.' + k.replace('/', '.'): v for k, v in model.store.to_numpy('params').items()})
+  total = sum(a.nbytes for a in arrays.values())
+  if total > DUMP_MAX_BYTES:
+    raise RuntimeError('--dump-outputs: %d bytes exceed the %d-byte limit' % (total, DUMP_MAX_BYTES))
+  os.makedirs(out_dir, exist_ok=True)
+  for k, a in arrays.items():
+    np.save(os.path.join(out_dir, k + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+  log('outputs of the last timed step: %d arrays, %.1f MB in %s' % (len(arrays), total / 1e6, out_dir))
 
 
 def csrc_sha16():
@@ -1074,6 +1108,8 @@ def main():
     if world > 1:
       out['config']['dp_form'] = form
       out['ranks'] = {'ms_per_step': [round(v, 4) for v in r['rank_ms']], 'devices': details, 'distinct_devices': len(set(idents))}
+    if not args.full:
+      return out, True
     chk, ok = check_losses(args, first_loss, r['final_loss'], r['total_steps'])
     out['loss_check'] = chk
     return out, ok
@@ -1090,6 +1126,8 @@ def main():
   first_loss = r['first_loss']
   form, full, trial, dog, comm, identical = safe_form, {}, {}, None, None, {}
   log('timed region: %d steps in %.3f s' % (args.steps, r['dt']))
+  if args.dump_outputs and rank == 0:      # before anything else runs a step on this model
+    dump_outputs(model, args.dump_outputs)
   if world > 1:
     from geeco_amd.runtime import DP_CANDIDATES_CAPTURED, DP_CANDIDATES_SAFE, pick_dp_runner
     ms = r['dt'] / args.steps * 1e3
@@ -1142,7 +1180,7 @@ def main():
               if rank == 0:
                 dog.provisional = headline(r, form)[0]
           del cand
-      if not args.skip_comm_report:
+      if args.full and not args.skip_comm_report:
         dog.phase = 'comm report'
         comm = comm_report(args, model, r['runner'], dev, world, r['dt'] / args.steps * 1e3)
     except Exception as e:      # a capture that failed (runtime.CaptureFailed) or anything else behind the safe form's measurement
@@ -1174,7 +1212,7 @@ def main():
                        'same for the one-graph forms -> value = the fastest full measurement -> comm report' % safe_form)
       comm['rccl'] = rccl_info(rccl_log)
       out['comm'] = comm
-    if not args.skip_layers:      # rank 0's GPU alone, after the timed region (any N: the per-GPU work is the same)
+    if args.full and not args.skip_layers:      # rank 0's GPU alone, after the timed region (any N: the per-GPU work is the same)
       samples = max(30, min(args.steps, 50))
       rows = layer_table(model, samples)
       out['roofline'] = dominant_roofline(rows)
@@ -1188,7 +1226,8 @@ def main():
       out['step_frac_of_f32_mfma_peak'] = round(step_flop(args.channels, model.enc.G * model.enc.Nf) / (ms_step * 1e-3) / 1e12
                                                 / PEAK_F32_MFMA_TFLOPS, 4)
     xdog = None
-    if world == 1:
+    extras = world == 1 and args.full
+    if extras:
       # everything the contract asks of the line is in `out` from here on; the legs below only add to it
       if not args.skip_cpu:
         out['cpu_baseline'] = cpu_baseline(args)
@@ -1200,19 +1239,19 @@ def main():
       xdog.provisional = dict(out)
       if args.extras_watchdog_s > 0:
         xdog.arm()
-    if world == 1 and not args.skip_dp_one_rank:
+    if extras and not args.skip_dp_one_rank:
       xdog.phase = 'dp_one_rank'
       out['dp_one_rank'] = dp_one_rank_report(args, model, runner, dev)
       xdog.provisional = dict(out)
       log('dp_one_rank: %s' % json.dumps({k: out['dp_one_rank'].get(k) for k in ('status', 'single_graph_ms', 'ms_per_step', 'delta_vs_single_graph_us', 'allreduce_us_one_rank')}))
-    if world == 1 and not args.skip_other_configs:
+    if extras and not args.skip_other_configs:
       del runner, r
       xdog.phase = 'other_configs'
       out['other_configs'], ok2 = other_configs(args, dev)
       if not ok2:
         rc = 4
       xdog.provisional = dict(out)
-    if world == 1 and not (args.skip_input_pipeline and args.skip_inference) and args.model == 'geeco-f' and args.channels == 3:
+    if extras and not (args.skip_input_pipeline and args.skip_inference) and args.model == 'geeco-f' and args.channels == 3:
       import shutil
       import tempfile
       model = None

@@ -2,12 +2,12 @@
 # same-box A/B of library builds / env settings with the WHOLE per-layer table: ab_layers.sh "" "GEECO_LIB=libgeeco_hip_x.so" ...
 # prints, per setting, the step median and every conv launch's us (median of 30 x 5 launches)
 export GEECO_DEV=1
-mkdir -p gpurun_out/ab
+tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
 for e in "$@"; do
-  env $e timeout -k 10 200 python bench.py --steps 60 --warmup 10 --skip-cpu --skip-other-configs > gpurun_out/ab/l.json 2>gpurun_out/ab/l.err || { tail -5 gpurun_out/ab/l.err; continue; }
-  python - "$e" <<'PY'
+  env $e timeout -k 10 200 python bench.py --full --steps 60 --warmup 10 --skip-cpu --skip-other-configs > $tmp/l.json 2>$tmp/l.err || { tail -5 $tmp/l.err; continue; }
+  python - "$e" "$tmp/l.json" <<'PY'
 import json, sys
-d = json.loads(open('gpurun_out/ab/l.json').read().strip().splitlines()[-1])
+d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 print('[%s] step median %.4f ms' % (sys.argv[1], d['step_ms']['median']))
 print('   ' + ' '.join('%s:%s=%.1f' % (r['layer'][4:], r['op'][:5], r['us']) for r in d['layers']))
 PY

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Joins a bench.py JSON line (``layers``) with a per-dispatch PMC report (scripts/dev/pmc_report.py) of ONE step into
+"""Joins a ``bench.py --full`` JSON line (``layers``) with a per-dispatch PMC report (scripts/dev/pmc_report.py) of ONE step into
 the per-launch roofline table kept under profiles/rNN/.
 
   python scripts/dev/roofline_table.py profiles/r02/d_bench.json profiles/r02/d_pmc.txt d > profiles/r02/d_roofline_table.md

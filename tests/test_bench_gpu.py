@@ -58,7 +58,7 @@ def test_bench_two_ranks_rehearsal_and_shared_gpu_refusal(tmp_path):
     env.pop(k, None)
   base = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1']
   tail = [os.path.join(root, 'tests', '_dp_launch.py'), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1',
-          '--batch', '2', '--seq-len', '4', '--skip-cpu']
+          '--batch', '2', '--seq-len', '4', '--full', '--skip-cpu']
   out = subprocess.run(base + ['--master-port', str(18000 + os.getpid() % 500)] + tail, capture_output=True, text=True, timeout=600, env=env)
   assert out.returncode != 0 and 'distinct GPU' in out.stderr, out.stderr[-2000:]
   out = subprocess.run(base + ['--master-port', str(18500 + os.getpid() % 500)] + tail + ['--allow-shared-gpu'],
@@ -103,7 +103,7 @@ def test_bench_one_gpu_line_and_dp_one_rank_leg():
   for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
     env.pop(k, None)
   out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '6', '--warmup', '2', '--batch', '2', '--seq-len', '4',
-                        '--skip-cpu', '--skip-other-configs', '--skip-input-pipeline', '--skip-inference'],
+                        '--full', '--skip-cpu', '--skip-other-configs', '--skip-input-pipeline', '--skip-inference'],
                        capture_output=True, text=True, timeout=600, env=env)
   assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
   lines = out.stdout.splitlines()
@@ -131,10 +131,47 @@ def test_bench_one_gpu_line_survives_a_stalled_extra_leg():
   for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
     env.pop(k, None)
   out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '6', '--warmup', '2', '--batch', '2', '--seq-len', '4',
-                        '--skip-cpu', '--extras-watchdog-s', '0.05'], capture_output=True, text=True, timeout=600, env=env)
+                        '--full', '--skip-cpu', '--extras-watchdog-s', '0.05'], capture_output=True, text=True, timeout=600, env=env)
   assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
   lines = out.stdout.splitlines()
   assert len(lines) == 1, lines[:5]
   d = json.loads(lines[0])
   assert d['value'] > 0 and d['roofline']['frac'] > 0 and 'dp_one_rank' not in d
   assert d['extras'].startswith('WATCHDOG') and 'dp_one_rank' in d['extras'] and 'WATCHDOG' in out.stderr
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+  """``python bench.py`` without --full: exactly --steps timed steps, and the line carries the headline alone (no tables, no loss
+  check, no extra legs).  --dump-outputs writes what the last timed step computed as float32 .npy: the loss (equal to the
+  line's final_loss), one file per prediction head (one row per window) and one per variable of the model, 64 MB at most."""
+  import json
+  import subprocess
+  import numpy as np
+  from geeco_amd.graph import model_variable_shapes
+  from geeco_amd.params import create_e2evmc_config
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0')
+  for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
+    env.pop(k, None)
+  dump = tmp_path / 'outputs'
+  out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '5', '--warmup', '1', '--batch', '2',
+                        '--seq-len', '4', '--dump-outputs', str(dump)], capture_output=True, text=True, timeout=600, env=env)
+  assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+  lines = out.stdout.splitlines()
+  assert len(lines) == 1, lines[:5]
+  d = json.loads(lines[0])
+  assert 'timed region: 5 steps in' in out.stderr and d['steps'] == 5 and d['n_gpus'] == 1
+  assert d['unit'] == 'frames/s' and d['higher_is_better'] is True and d['dtype'] == 'f32' and d['metric'].startswith('train-step frames/sec')
+  assert d['ms_per_step'] > 0 and abs(d['value'] * d['ms_per_step'] * 1e-3 / (2 * 4) - 1) < 1e-2
+  assert not set(d) & {'loss_check', 'roofline', 'layers', 'hbm', 'encoder_forward', 'step_frac_of_f32_mfma_peak', 'cpu_baseline',
+                       'dp_one_rank', 'other_configs', 'input_pipeline', 'inference', 'extras'}, sorted(d)
+  got = {f[:-4]: np.load(str(dump / f)) for f in os.listdir(str(dump))}
+  assert all(f.endswith('.npy') for f in os.listdir(str(dump))) and all(a.dtype == np.float32 for a in got.values())
+  assert sum(a.nbytes for a in got.values()) <= 64 << 20
+  assert got['loss'].shape == (1,) and abs(float(got['loss'][0]) - d['final_loss']) <= 1e-6 * max(1.0, abs(d['final_loss']))
+  cfg = create_e2evmc_config(dict(proc_obs='dynimg', proc_tgt='dyndiff', window_size=4, img_channels=3, batch_size=2))
+  shapes = dict(model_variable_shapes(cfg, True))
+  assert {k for k in got if k.startswith('var.')} == {'var.' + k.replace('/', '.') for k in shapes}
+  assert all(got['var.' + k.replace('/', '.')].shape == tuple(s) for k, s in shapes.items())
+  preds = [k for k in got if k.startswith('pred_')]
+  assert preds and all(got[k].shape[0] == 2 and np.isfinite(got[k]).all() for k in preds)
