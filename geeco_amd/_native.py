@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(_HERE, _dev.env('GEECO_LIB', 'libgeeco_hip.so'))   # GEE
 
 
 GEECO_EINVAL, GEECO_ENOSUP = -1, -2      # include/geeco_hip.h
-ABI_VERSION = 6        # GEECO_ABI_VERSION of include/geeco_hip.h this binding was written against
+ABI_VERSION = 7       # GEECO_ABI_VERSION of include/geeco_hip.h this binding was written against
 
 
 class GeecoNativeError(RuntimeError):
@@ -65,6 +65,10 @@ SIGNATURES = {
     'geeco_dynimg_rgbd_fwd': (_I, [_P, _P, _L, _L, _P, _P, _L, _L, _P, _I, _I, _L, _P, _P, _P]),
     'geeco_pack_pixels': (_I, [_P, _L, _P, _L, _I, _L, _I, _I, _I, _P, _P]),
     'geeco_gather_windows': (_I, [_P, _I, _P, _I, _I, _L, _F, _P, _P]),
+    'geeco_predict_range_check': (_I, [_P, _I, _L, _I, _F, _F, _P, _P]),
+    'geeco_predict_push_dense': (_I, [_P, _I, _P, _P, _P, _I, _I, _L, _I, _I, _P, _P, _P, _P]),
+    'geeco_predict_push_ring': (_I, [_P, _P, _P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P]),
+    'geeco_predict_pack': (_I, [_P, _I, _I, _I, POINTER(_I), POINTER(_I), POINTER(_I), _P, _I, _P, _P, _P, _P, _L, _I, _P, _P]),
     'geeco_conv3x3_fwd': (_I, [_P, _P, _P, _P, _I, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     'geeco_conv3x3_fwd_state': (_I, [_P, _P, _P, _P, _I, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _I, _I, _P, _L, _P]),
     'geeco_conv3x3_fwd_ws_bytes': (_L, [_I, _I, _I, _I, _I, _I, _I]),

@@ -19,7 +19,7 @@ extra_flags() {
 }
 rm -rf build && mkdir -p build
 pids=()
-for f in conv_gemm conv_halo conv_wgrad conv_wgrad_halo conv_dgrad_lds dynimg decoder misc; do
+for f in conv_gemm conv_halo conv_wgrad conv_wgrad_halo conv_dgrad_lds dynimg decoder misc predict_io; do
   $HIPCC $FLAGS $(extra_flags $f) -c $f.hip -o build/$f.o &
   pids+=($!)
 done

@@ -1,0 +1,418 @@
+// Input and output stages of the batched predictor (geeco_amd/batched_predictor.py): B control loops stepped by one call.
+//
+// Per env the semantics are the batch-1 predictor's (reference src/models/e2evmc/predictor.py:127-209): a window of the last
+// K frames, padded with the first frame after a reset; frames range-checked on channels 0..2; the gripper logits re-mapped
+// to argmax - 1.  One call = one H2D of a staging block, one replayed graph (range check -> window push -> forward -> output
+// pack), one D2H.  All four stages are HBM streaming (or tiny): 16-byte loads and stores, one thread per fixed set of pixels.
+//
+// The control words `ctl` [B + 1] int32: ctl[b] = 1 when env b's frame failed the range check, ctl[B] = 1 when any did.  The
+// range check only ever sets them; the output pack copies them out and zeroes them again, so every call starts from zeros.
+#include "geeco_common.h"
+
+#define PIO_MAXK 64       // the window lengths the input kernels of the models take (dynimg.hip: DYN_MAXK)
+
+// float(u8) / 255.0f with the IEEE division: bitwise the `divisor 255` conversion of geeco_gather_windows (dynimg.hip)
+__device__ __forceinline__ float pio_u8(unsigned v) { return (float)v / 255.0f; }
+
+// ---- 1. frame range check ---------------------------------------------------------------------------------------------
+// channels 0..2 of every env's new float frame inside [lo, hi]; a NaN fails (NaN compares false, as np.amin turns NaN)
+template <int C>
+__global__ __launch_bounds__(256) void range_check_kernel(const float* __restrict__ frames, long long HW, float lo, float hi,
+                                                          int* __restrict__ ctl, int B) {
+  const int b = blockIdx.y;
+  const float* f = frames + (long long)b * HW * C;
+  const long long n4 = HW * C / 4;           // float4 units of the env's frame (HW * C % 4 == 0 on this path)
+  int bad = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(f) + i);
+    if (C == 4) {            // one float4 = one pixel: r, g, b, depth (depth is not checked, predictor.py:135)
+      bad |= !(v.x >= lo && v.x <= hi) | !(v.y >= lo && v.y <= hi) | !(v.z >= lo && v.z <= hi);
+    } else {
+      bad |= !(v.x >= lo && v.x <= hi) | !(v.y >= lo && v.y <= hi) | !(v.z >= lo && v.z <= hi) | !(v.w >= lo && v.w <= hi);
+    }
+  }
+  if (__syncthreads_or(bad) && threadIdx.x == 0) {
+    ctl[b] = 1;                // plain stores of the same value from every block that saw a bad pixel
+    ctl[B] = 1;
+  }
+}
+
+// any shape (HW * C % 4 != 0): one element per step
+template <int C>
+__global__ __launch_bounds__(256) void range_check_scalar_kernel(const float* __restrict__ frames, long long HW, float lo,
+                                                                 float hi, int* __restrict__ ctl, int B) {
+  const int b = blockIdx.y;
+  const float* f = frames + (long long)b * HW * C;
+  int bad = 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < HW * C; i += (long long)gridDim.x * 256) {
+    const float v = f[i];
+    if (i % C < 3) bad |= !(v >= lo && v <= hi);
+  }
+  if (__syncthreads_or(bad) && threadIdx.x == 0) {
+    ctl[b] = 1;
+    ctl[B] = 1;
+  }
+}
+
+extern "C" int geeco_predict_range_check(const float* frames, int B, int64_t HW, int C, float lo, float hi, int* ctl,
+                                         void* stream) {
+  GEECO_CHECK_ARG(frames && ctl, "predict_range_check: null pointer");
+  GEECO_CHECK_ARG(B >= 1, "predict_range_check: B=%d must be >= 1", B);
+  GEECO_CHECK_ARG(C == 3 || C == 4, "predict_range_check: C=%d must be 3 or 4", C);
+  GEECO_CHECK_ARG(HW >= 1, "predict_range_check: HW=%lld", (long long)HW);
+  const bool vec = (HW * C) % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 15) == 0;
+  const long long work = vec ? HW * C / 4 : HW * C;
+  const int nblk = (int)std::min<long long>(cdiv64(work, 256 * 4), 64);
+  dim3 grid((unsigned)nblk, (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+  if (vec) {
+    if (C == 3) hipLaunchKernelGGL(range_check_kernel<3>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
+    else hipLaunchKernelGGL(range_check_kernel<4>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
+  } else {
+    if (C == 3) hipLaunchKernelGGL(range_check_scalar_kernel<3>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
+    else hipLaunchKernelGGL(range_check_scalar_kernel<4>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
+  }
+  GEECO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- joint-state window (both push forms): the last block of each env shifts its [K][J] window -------------------------
+__device__ __forceinline__ void push_jnt(const float* __restrict__ jnt, int reset, int b, int K, int J, float* __restrict__ jw) {
+  for (int j = threadIdx.x; j < J; j += blockDim.x) {
+    const float v = jnt[(long long)b * J + j];
+    float* w = jw + (long long)b * K * J + j;
+    if (reset) {
+      for (int t = 0; t < K; ++t) w[(long long)t * J] = v;
+    } else {
+      for (int t = 0; t + 1 < K; ++t) w[(long long)t * J] = w[(long long)(t + 1) * J];
+      w[(long long)(K - 1) * J] = v;
+    }
+  }
+}
+
+// ---- 2. window push, dense form -------------------------------------------------------------------------------------
+// rgb [B][K][HW][3], depth [B][K][HW] (C == 4: split out of the [HW][4] frame in registers), jnt_state [B][K][J].
+// A thread owns PIX pixels of one env and walks t = 0..K-1 in order: it reads slot t + 1 before it writes slot t, and no
+// other thread touches those pixels, so the shift is in place and race-free.
+template <int PIX, int C, bool U8>
+__device__ __forceinline__ void load_new(const void* frames, int b, long long HW, long long u, float (&px)[PIX * 3],
+                                         float (&dp)[PIX]) {
+  if (U8) {        // C == 3
+    const unsigned char* f = reinterpret_cast<const unsigned char*>(frames) + (long long)b * HW * 3 + u * PIX * 3;
+    if (PIX == 4) {
+      const unsigned* w = reinterpret_cast<const unsigned*>(f);
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        const unsigned x = w[q];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) px[q * 4 + k] = pio_u8((x >> (8 * k)) & 255u);
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < PIX * 3; ++k) px[k] = pio_u8(f[k]);
+    }
+    return;
+  }
+  const float* f = reinterpret_cast<const float*>(frames) + (long long)b * HW * C + u * PIX * C;
+  float v[PIX * C];
+  if (PIX == 4) {
+#pragma unroll
+    for (int q = 0; q < C; ++q) {
+      const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(f) + q);
+      v[q * 4 + 0] = x.x;
+      v[q * 4 + 1] = x.y;
+      v[q * 4 + 2] = x.z;
+      v[q * 4 + 3] = x.w;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PIX * C; ++k) v[k] = f[k];
+  }
+#pragma unroll
+  for (int p = 0; p < PIX; ++p) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) px[p * 3 + c] = v[p * C + c];
+    if (C == 4) dp[p] = v[p * C + 3];
+  }
+}
+
+template <int PIX, int C>
+__device__ __forceinline__ void slot_load(const float* rgb, const float* dep, float (&px)[PIX * 3], float (&dp)[PIX]) {
+  if (PIX == 4) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const f32x4 x = reinterpret_cast<const f32x4*>(rgb)[q];
+      px[q * 4 + 0] = x.x;
+      px[q * 4 + 1] = x.y;
+      px[q * 4 + 2] = x.z;
+      px[q * 4 + 3] = x.w;
+    }
+    if (C == 4) {
+      const f32x4 x = *reinterpret_cast<const f32x4*>(dep);
+      dp[0] = x.x;
+      dp[1] = x.y;
+      dp[2] = x.z;
+      dp[3] = x.w;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < PIX * 3; ++k) px[k] = rgb[k];
+    if (C == 4) {
+#pragma unroll
+      for (int k = 0; k < PIX; ++k) dp[k] = dep[k];
+    }
+  }
+}
+
+template <int PIX, int C>
+__device__ __forceinline__ void slot_store(float* rgb, float* dep, const float (&px)[PIX * 3], const float (&dp)[PIX]) {
+  if (PIX == 4) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q)
+      reinterpret_cast<f32x4*>(rgb)[q] = f32x4{px[q * 4 + 0], px[q * 4 + 1], px[q * 4 + 2], px[q * 4 + 3]};
+    if (C == 4) *reinterpret_cast<f32x4*>(dep) = f32x4{dp[0], dp[1], dp[2], dp[3]};
+  } else {
+#pragma unroll
+    for (int k = 0; k < PIX * 3; ++k) rgb[k] = px[k];
+    if (C == 4) {
+#pragma unroll
+      for (int k = 0; k < PIX; ++k) dep[k] = dp[k];
+    }
+  }
+}
+
+template <int PIX, int C, bool U8>
+__global__ __launch_bounds__(256) void push_dense_kernel(const void* __restrict__ frames, const float* __restrict__ jnt,
+                                                         const int* __restrict__ reset, const int* __restrict__ any_bad, int K,
+                                                         long long HW, int J, float* __restrict__ rgb, float* __restrict__ depth,
+                                                         float* __restrict__ jnt_state) {
+  if (*any_bad) return;      // a frame failed the range check: no env's window moves
+  const int b = blockIdx.y;
+  const int rs = reset[b];
+  if (blockIdx.x == gridDim.x - 1) {
+    push_jnt(jnt, rs, b, K, J, jnt_state);
+    return;
+  }
+  const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= HW / PIX) return;
+  float nv[PIX * 3], nd[PIX];
+  load_new<PIX, C, U8>(frames, b, HW, u, nv, nd);
+  float* r = rgb + (long long)b * K * HW * 3 + u * PIX * 3;
+  float* d = C == 4 ? depth + (long long)b * K * HW + u * PIX : nullptr;
+  if (!rs) {
+    for (int t = 0; t + 1 < K; ++t) {
+      float px[PIX * 3], dp[PIX];
+      slot_load<PIX, C>(r + (long long)(t + 1) * HW * 3, C == 4 ? d + (long long)(t + 1) * HW : nullptr, px, dp);
+      slot_store<PIX, C>(r + (long long)t * HW * 3, C == 4 ? d + (long long)t * HW : nullptr, px, dp);
+    }
+    slot_store<PIX, C>(r + (long long)(K - 1) * HW * 3, C == 4 ? d + (long long)(K - 1) * HW : nullptr, nv, nd);
+  } else {                   // the first frame after a reset pads the whole window (predictor.py:197-198)
+    for (int t = 0; t < K; ++t)
+      slot_store<PIX, C>(r + (long long)t * HW * 3, C == 4 ? d + (long long)t * HW : nullptr, nv, nd);
+  }
+}
+
+template <int PIX>
+static void launch_push_dense(dim3 grid, hipStream_t s, const void* frames, int u8, int C, const float* jnt, const int* reset,
+                              const int* any_bad, int K, long long HW, int J, float* rgb, float* depth, float* jnt_state) {
+  if (u8)
+    hipLaunchKernelGGL((push_dense_kernel<PIX, 3, true>), grid, dim3(256), 0, s, frames, jnt, reset, any_bad, K, HW, J, rgb,
+                       depth, jnt_state);
+  else if (C == 3)
+    hipLaunchKernelGGL((push_dense_kernel<PIX, 3, false>), grid, dim3(256), 0, s, frames, jnt, reset, any_bad, K, HW, J, rgb,
+                       depth, jnt_state);
+  else
+    hipLaunchKernelGGL((push_dense_kernel<PIX, 4, false>), grid, dim3(256), 0, s, frames, jnt, reset, any_bad, K, HW, J, rgb,
+                       depth, jnt_state);
+}
+
+extern "C" int geeco_predict_push_dense(const void* frames, int frames_u8, const float* jnt, const int* reset, const int* any_bad,
+                                        int B, int K, int64_t HW, int C, int J, float* rgb, float* depth, float* jnt_state,
+                                        void* stream) {
+  GEECO_CHECK_ARG(frames && jnt && reset && any_bad && rgb && jnt_state && (C != 4 || depth),
+                  "predict_push_dense: null pointer");
+  GEECO_CHECK_ARG(B >= 1, "predict_push_dense: B=%d must be >= 1", B);
+  GEECO_CHECK_ARG(K >= 1 && K <= PIO_MAXK, "predict_push_dense: K=%d outside 1..%d", K, PIO_MAXK);
+  GEECO_CHECK_ARG(C == 3 || C == 4, "predict_push_dense: C=%d must be 3 or 4", C);
+  GEECO_CHECK_ARG(!frames_u8 || C == 3, "predict_push_dense: uint8 frames are RGB (C=3), got C=%d", C);
+  GEECO_CHECK_ARG(HW >= 1 && J >= 1, "predict_push_dense: HW=%lld J=%d", (long long)HW, J);
+  const uintptr_t al = reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(rgb) |
+                       reinterpret_cast<uintptr_t>(depth);
+  const bool vec = HW % 4 == 0 && (al & 15) == 0;
+  const int pix = vec ? 4 : 1;
+  dim3 grid((unsigned)(cdiv64(HW / pix, 256) + 1), (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+  if (vec) launch_push_dense<4>(grid, s, frames, frames_u8, C, jnt, reset, any_bad, K, HW, J, rgb, depth, jnt_state);
+  else launch_push_dense<1>(grid, s, frames, frames_u8, C, jnt, reset, any_bad, K, HW, J, rgb, depth, jnt_state);
+  GEECO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- 3. window push, ring form --------------------------------------------------------------------------------------
+// ring [B][2K][FB] uint8 (FB = HW * 3 bytes per frame), mirrored: logical position q lives in slots q and q + K.  heads[b] =
+// the position the next frame goes to.  A frame written at p (slots p and p + K) makes slots p + 1 .. p + K the env's window
+// oldest first, always contiguous; the advance kernel writes that start into win_table[b] and moves the head.  No frame is
+// ever moved: per env and call FB bytes are read and 2 FB written (2K FB after a reset: every slot gets the frame).
+template <typename V>
+__global__ __launch_bounds__(256) void push_ring_kernel(const unsigned char* __restrict__ frames, const float* __restrict__ jnt,
+                                                        const int* __restrict__ reset, const int* __restrict__ any_bad,
+                                                        const int* __restrict__ heads, int K, long long FB, int J,
+                                                        unsigned char* __restrict__ ring, float* __restrict__ jnt_state) {
+  if (*any_bad) return;
+  const int b = blockIdx.y;
+  const int rs = reset[b];
+  if (blockIdx.x == gridDim.x - 1) {
+    push_jnt(jnt, rs, b, K, J, jnt_state);
+    return;
+  }
+  const long long sv = FB / (long long)sizeof(V);      // units of V per frame = the slot stride
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= sv) return;
+  const V v = __builtin_nontemporal_load(reinterpret_cast<const V*>(frames + (long long)b * FB) + i);
+  V* r = reinterpret_cast<V*>(ring + (long long)b * 2 * K * FB) + i;
+  if (rs) {
+    for (int t = 0; t < 2 * K; ++t) r[t * sv] = v;
+  } else {
+    const int p = heads[b];
+    r[p * sv] = v;
+    r[(p + K) * sv] = v;
+  }
+}
+
+__global__ void ring_advance_kernel(const int* __restrict__ any_bad, int B, int K, long long FB, const unsigned char* ring,
+                                    int* __restrict__ heads, long long* __restrict__ win_table) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B || *any_bad) return;
+  const int p = heads[b];
+  win_table[b] = (long long)(uintptr_t)(ring + ((long long)b * 2 * K + p + 1) * FB);
+  heads[b] = p + 1 == K ? 0 : p + 1;
+}
+
+extern "C" int geeco_predict_push_ring(const unsigned char* frames, const float* jnt, const int* reset, const int* any_bad,
+                                       int B, int K, int64_t HW, int J, unsigned char* ring, int* heads, int64_t* win_table,
+                                       float* jnt_state, void* stream) {
+  GEECO_CHECK_ARG(frames && jnt && reset && any_bad && ring && heads && win_table && jnt_state,
+                  "predict_push_ring: null pointer");
+  GEECO_CHECK_ARG(B >= 1, "predict_push_ring: B=%d must be >= 1", B);
+  GEECO_CHECK_ARG(K >= 1 && K <= PIO_MAXK, "predict_push_ring: K=%d outside 1..%d", K, PIO_MAXK);
+  GEECO_CHECK_ARG(HW >= 4 && HW % 4 == 0, "predict_push_ring: HW=%lld must be a multiple of 4 (4-byte aligned ring frames)",
+                  (long long)HW);
+  GEECO_CHECK_ARG(J >= 1, "predict_push_ring: J=%d", J);
+  GEECO_CHECK_ARG(((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(ring)) & 3) == 0,
+                  "predict_push_ring: frames and ring must be 4-byte aligned");
+  const long long FB = HW * 3;
+  const bool v16 = FB % 16 == 0 && ((reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(ring)) & 15) == 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (v16) {
+    typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
+    dim3 grid((unsigned)(cdiv64(FB / 16, 256) + 1), (unsigned)B);
+    hipLaunchKernelGGL(push_ring_kernel<u32x4>, grid, dim3(256), 0, s, frames, jnt, reset, any_bad, heads, K, FB, J, ring,
+                       jnt_state);
+  } else {
+    dim3 grid((unsigned)(cdiv64(FB / 4, 256) + 1), (unsigned)B);
+    hipLaunchKernelGGL(push_ring_kernel<unsigned>, grid, dim3(256), 0, s, frames, jnt, reset, any_bad, heads, K, FB, J, ring,
+                       jnt_state);
+  }
+  GEECO_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ring_advance_kernel, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, s, any_bad, B, K, FB,
+                     (const unsigned char*)ring, heads, (long long*)win_table);
+  GEECO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- 4. output pack ---------------------------------------------------------------------------------------------------
+// preds [B][P] (the decoder's heads side by side) -> out [B][F] in the order the API returns: each segment is a copy of
+// `len` columns from `src`, or (argmax) ONE column = argmax over `len` logits - 1 (np.argmax: the first maximum; a NaN wins as
+// the first maximum does there).  The control words go to ctl_out and are zeroed for the next call.  img0 / img1 (optional):
+// [B][HW][4] channel-padded images -> img_out [nimg][B][HW][C].
+struct PackSegs {
+  int src[GEECO_PREDICT_PACK_MAXSEG], len[GEECO_PREDICT_PACK_MAXSEG], argmax[GEECO_PREDICT_PACK_MAXSEG];
+  int n;
+};
+
+__global__ __launch_bounds__(256) void pack_preds_kernel(const float* __restrict__ preds, int P, int B, PackSegs sg, int F,
+                                                         float* __restrict__ out, int* __restrict__ ctl, int* __restrict__ ctl_out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b <= B) {
+    ctl_out[b] = ctl[b];
+    ctl[b] = 0;
+  }
+  if (b >= B) return;
+  const float* p = preds + (long long)b * P;
+  float* o = out + (long long)b * F;
+  int col = 0;
+  for (int s = 0; s < sg.n; ++s) {
+    const float* q = p + sg.src[s];
+    if (sg.argmax[s]) {
+      int best = 0;
+      float bv = q[0];
+      for (int i = 1; i < sg.len[s] && bv == bv; ++i) {
+        const float v = q[i];
+        if (v > bv || v != v) {
+          bv = v;
+          best = i;
+        }
+      }
+      o[col++] = (float)(best - 1);
+    } else {
+      for (int i = 0; i < sg.len[s]; ++i) o[col++] = q[i];
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void pack_image_kernel(const float* __restrict__ img, long long HW, int C, float* __restrict__ out) {
+  const int b = blockIdx.y;
+  const long long px = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (px >= HW) return;
+  const f32x4 v = reinterpret_cast<const f32x4*>(img + (long long)b * HW * 4)[px];
+  float* o = out + ((long long)b * HW + px) * C;
+  if (C == 4) {
+    *reinterpret_cast<f32x4*>(o) = v;
+  } else {
+    o[0] = v.x;
+    o[1] = v.y;
+    o[2] = v.z;
+  }
+}
+
+extern "C" int geeco_predict_pack(const float* preds, int P, int B, int nseg, const int* seg_src, const int* seg_len,
+                                  const int* seg_argmax, float* out, int F, int* ctl, int* ctl_out, const float* img0,
+                                  const float* img1, int64_t HW, int C, float* img_out, void* stream) {
+  GEECO_CHECK_ARG(preds && out && ctl && ctl_out && seg_src && seg_len && seg_argmax, "predict_pack: null pointer");
+  GEECO_CHECK_ARG(B >= 1, "predict_pack: B=%d must be >= 1", B);
+  GEECO_CHECK_ARG(nseg >= 1 && nseg <= GEECO_PREDICT_PACK_MAXSEG, "predict_pack: nseg=%d outside 1..%d", nseg,
+                  GEECO_PREDICT_PACK_MAXSEG);
+  PackSegs sg;
+  sg.n = nseg;
+  int f = 0;
+  for (int s = 0; s < nseg; ++s) {
+    GEECO_CHECK_ARG(seg_len[s] >= 1 && seg_src[s] >= 0 && seg_src[s] + seg_len[s] <= P,
+                    "predict_pack: segment %d [%d, +%d) outside the %d prediction columns", s, seg_src[s], seg_len[s], P);
+    sg.src[s] = seg_src[s];
+    sg.len[s] = seg_len[s];
+    sg.argmax[s] = seg_argmax[s] != 0;
+    f += sg.argmax[s] ? 1 : seg_len[s];
+  }
+  GEECO_CHECK_ARG(f == F, "predict_pack: the segments give %d output columns, F=%d", f, F);
+  if (img0 || img1) {
+    GEECO_CHECK_ARG(img_out, "predict_pack: null pointer (img_out)");
+    GEECO_CHECK_ARG(C == 3 || C == 4, "predict_pack: C=%d must be 3 or 4", C);
+    GEECO_CHECK_ARG(HW >= 1, "predict_pack: HW=%lld", (long long)HW);
+    GEECO_CHECK_ARG(((reinterpret_cast<uintptr_t>(img0) | reinterpret_cast<uintptr_t>(img1) |
+                      reinterpret_cast<uintptr_t>(img_out)) & 15) == 0, "predict_pack: images must be 16-byte aligned");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(pack_preds_kernel, dim3((unsigned)cdiv(B + 1, 256)), dim3(256), 0, s, preds, P, B, sg, F, out, ctl,
+                     ctl_out);
+  GEECO_LAUNCH_CHECK();
+  const float* src[2] = {img0, img1};
+  int k = 0;
+  for (int i = 0; i < 2; ++i) {
+    if (!src[i]) continue;
+    hipLaunchKernelGGL(pack_image_kernel, dim3((unsigned)cdiv64(HW, 256), (unsigned)B), dim3(256), 0, s, src[i],
+                       (long long)HW, C, img_out + (long long)k * B * HW * C);
+    GEECO_LAUNCH_CHECK();
+    ++k;
+  }
+  return 0;
+}

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define GEECO_ABI_VERSION 6   /* = the build round that last changed the entry points or their calling conventions */
+#define GEECO_ABI_VERSION 7  /* = the build round that last changed the entry points or their calling conventions */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -113,6 +113,35 @@ int geeco_pack_pixels(const float* src, int64_t src_sample_stride, const float* 
  * device; divisor 255 reproduces `rgb /= 255.0` (geeco_gym.py:312) bit-exactly, 1 copies. */
 int geeco_gather_windows(const void* src, int src_is_u8, const int* starts_dev, int N, int K,
                          int64_t frame_elems, float divisor, float* out, void* stream);
+
+/* ---- batched predictor I/O: B control loops per call (reference predictor.py:127-209 per env) ----------------------
+ * The ingest and output stages of one replayed graph (geeco_amd/batched_predictor.py): range check -> window push ->
+ * forward -> pack.  `ctl` = B + 1 int32 control words on the device: ctl[b] = 1 when env b's frame failed the range check,
+ * ctl[B] = 1 when any did.  The range check only sets them, the pushes do nothing while ctl[B] is set (no env's window moves),
+ * and geeco_predict_pack copies them to ctl_out and zeroes them for the next call.  K: 1..64; C: 3 (RGB) or 4 (RGB-D). */
+/* Channels 0..2 of every env's new frame ([B][HW][C] float32) inside [lo, hi] (predictor.py:135-138; NaN fails). */
+int geeco_predict_range_check(const float* frames, int B, int64_t HW, int C, float lo, float hi, int* ctl, void* stream);
+/* Dense window push, in place: rgb [B][K][HW][3], depth [B][K][HW] (C == 4; split out of the [HW][4] frame), jnt_state
+ * [B][K][J].  reset[b] != 0: all K slots get the new frame (predictor.py:197-198), else slots shift down by one and slot K-1
+ * gets it (:144-146).  frames: [B][HW][C] float32, or uint8 when frames_u8 (C == 3; divided by 255 bitwise as
+ * geeco_gather_windows(divisor 255)). */
+int geeco_predict_push_dense(const void* frames, int frames_u8, const float* jnt, const int* reset, const int* any_bad,
+                             int B, int K, int64_t HW, int C, int J, float* rgb, float* depth, float* jnt_state, void* stream);
+/* Ring window push for uint8 RGB frames: ring [B][2K][HW * 3] bytes, mirrored (a frame goes to slots p and p + K), so an env's
+ * window is always K contiguous frames; win_table[b] (int64, device) gets its start address, the input kernel of the model
+ * (geeco_goal_dynimgs_u8_fwd) reads it when it runs.  heads [B] int32 on the device: the next slot of each env, advanced by
+ * the launch itself (a replayed graph moves on by itself).  HW % 4 == 0.  jnt_state [B][K][J] is pushed densely. */
+int geeco_predict_push_ring(const unsigned char* frames, const float* jnt, const int* reset, const int* any_bad, int B, int K,
+                            int64_t HW, int J, unsigned char* ring, int* heads, int64_t* win_table, float* jnt_state,
+                            void* stream);
+/* Output pack (predictor.py:157-189): preds [B][P] -> out [B][F].  Segment s copies seg_len[s] columns from seg_src[s], or,
+ * when seg_argmax[s], writes ONE column argmax - 1 over those logits (first maximum on ties, as np.argmax).  img0 / img1
+ * (may be NULL): [B][HW][4] channel-padded images -> img_out [nimg][B][HW][C] (dynbuff / dyndiff endpoints).  The seg_*
+ * arrays are host memory, nseg <= GEECO_PREDICT_PACK_MAXSEG. */
+#define GEECO_PREDICT_PACK_MAXSEG 8
+int geeco_predict_pack(const float* preds, int P, int B, int nseg, const int* seg_src, const int* seg_len, const int* seg_argmax,
+                       float* out, int F, int* ctl, int* ctl_out, const float* img0, const float* img1, int64_t HW, int C,
+                       float* img_out, void* stream);
 
 /* ---- conv encoder: graph.py:76-115 (tf.layers.conv2d 3x3, padding='SAME', bias, ReLU) ----------
  * x [G][N][H][W][Cin], w [G][3][3][Cin][Cout] (HWIO), b [G][Cout], y [G][N][Ho][Wo][Cout],

@@ -19,7 +19,7 @@ extra_flags() {      # as geeco_amd/csrc/build.sh
   esac
 }
 pids=()
-for f in conv_gemm conv_halo conv_wgrad conv_wgrad_halo conv_dgrad_lds dynimg decoder misc; do
+for f in conv_gemm conv_halo conv_wgrad conv_wgrad_halo conv_dgrad_lds dynimg decoder misc predict_io; do
   /opt/rocm/bin/hipcc $FLAGS $(extra_flags $f) -c $f.hip -o $B/$f.o &
   pids+=($!)
 done
