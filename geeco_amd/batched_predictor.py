@@ -11,6 +11,11 @@ One ``predict`` = one H2D of a pinned staging block (frames, joint states, pendi
 window push, the model's forward at N = B, output pack: csrc/predict_io.hip) and one D2H of the packed outputs.  The K-frame
 windows live in HBM: dense fp32 windows shifted in place, or -- uint8 frames on a model whose input kernel reads uint8 windows
 (geeco-f RGB) -- a mirrored uint8 ring per env whose window start the graph itself advances.
+
+``incremental=True`` (the per-frame controllers: e2e_vmc, goal_e2evmc 'sequence' x 'constant' / 'residual') keeps no frame window
+at all: per env a ring of the last K encoder FEATURE vectors and joint states (graph.E2EVMCStep / GoalE2EVMCStep).  A call
+encodes only the B new frames; the graph is range check, newest-frame pack, encoder at N = B, feature push + state gather,
+decoder, output pack.  Same methods, errors and returned dict.
 """
 from __future__ import annotations
 
@@ -92,7 +97,7 @@ class _BatchedPredictorBase:
   _goal = False
 
   def __init__(self, model_dir, num_envs, checkpoint_name=None, memcap=0.8, device=None, frame_dtype='float32',
-               debug_images=False):
+               debug_images=False, incremental=False):
     B = int(num_envs)
     if B < 1:
       raise ValueError('num_envs must be >= 1, got %d' % B)
@@ -103,6 +108,20 @@ class _BatchedPredictorBase:
     cfg['batch_size'] = B
     self._cfg = cfg = create_e2evmc_config(cfg)
     self._u8 = fd == np.dtype(np.uint8)
+    self._incremental = bool(incremental)
+    if self._incremental:
+      if not self._goal:
+        ctor = graph.E2EVMCStep
+      elif cfg.proc_obs == 'sequence' and cfg.proc_tgt in ('constant', 'residual'):
+        ctor = graph.GoalE2EVMCStep
+      elif cfg.proc_obs == 'sequence':
+        raise ValueError("incremental=True does not take proc_obs='sequence' with proc_tgt='%s': the cached DynDiff features depend "
+                         "on the goal, a goal change needs the K raw frames encoded again" % (cfg.proc_tgt,))
+      else:
+        raise ValueError("incremental=True caches per-frame encoder features: proc_obs='%s' has none (three encoder passes per "
+                         "call whatever the window size)" % (cfg.proc_obs,))
+    else:
+      ctor = graph.GoalE2EVMC if self._goal else graph.E2EVMC
     if self._u8 and cfg.img_channels != 3:
       raise ValueError('uint8 frames are for RGB models (img_channels == 3); an RGB-D model takes float32 frames [H, W, 4]')
     if not torch.cuda.is_available():
@@ -117,11 +136,10 @@ class _BatchedPredictorBase:
     H, W, C, K, J = cfg.img_height, cfg.img_width, cfg.img_channels, cfg.window_size, cfg.dim_jnt_state
     self._dims = (B, H, W, C, K, J)
     with torch.cuda.device(dev):
-      ctor = graph.GoalE2EVMC if self._goal else graph.E2EVMC
       m = self._model = ctor(cfg, B, dev, training=False)
       _restore(m.store, model_dir, checkpoint_name)
       # uint8 frames on a model whose input kernel reads uint8 windows: the mirrored ring (no fp32 window is ever written)
-      self._ring = self._u8 and 'rgb' in m.u8_window_keys
+      self._ring = self._u8 and not self._incremental and 'rgb' in m.u8_window_keys
       stage = _Layout()
       stage.add('frames', (B, H, W, C), fd)
       stage.add('jnt', (B, J), np.float32)
@@ -142,7 +160,7 @@ class _BatchedPredictorBase:
       else:
         self._segs = [(k,) + cols[k] + (False,) for k in ('cmd_vel', 'cmd_ee', 'cmd_grp', 'pos_ee', 'pos_obj')]
       F = sum(1 if a else n for _, _, n, a in self._segs)
-      self._imgs = self._debug_sources() if debug_images else []
+      self._imgs = self._debug_sources() if debug_images and not self._incremental else []   # step models compute no images
       out = _Layout()
       out.add('out', (B, F), np.float32)
       out.add('ctl', (B + 1,), np.int32)
@@ -185,7 +203,10 @@ class _BatchedPredictorBase:
   @property
   def window_form(self):
     """'ring': the mirrored uint8 ring the model's input kernel reads through its address table (uint8 frames on a model with
-    uint8 window inputs, geeco-f RGB); 'dense': the model's fp32 windows, shifted in place."""
+    uint8 window inputs, geeco-f RGB); 'dense': the model's fp32 windows, shifted in place; 'features': no frame window, per env
+    a ring of the last K encoder feature vectors (incremental=True)."""
+    if self._incremental:
+      return 'features'
     return 'ring' if self._ring else 'dense'
 
   def frame_buffer(self):
@@ -199,6 +220,10 @@ class _BatchedPredictorBase:
     HW, m, d, ctl = H * W, self._model, self._d, self._ctl
     if not self._u8:
       ops.predict_range_check_into(ctl, d['frames'], B, HW, C, self._lo, self._hi)
+    if self._incremental:
+      m.step(d['frames'], d['jnt'], d['reset'], ctl)      # newest-frame pack, encoder at N = B, feature push + gather, decoder
+      ops.predict_pack_into(self._do['out'], self._do['ctl'], m.decoder.preds, ctl, B, [s[1:] for s in self._segs])
+      return
     inp = m.inputs
     if self._ring:
       ops.predict_push_ring_into(self._ring_buf, self._heads, self._win_table, inp['jnt_state'], d['frames'], d['jnt'],
@@ -298,8 +323,14 @@ class BatchedGoalE2EVMCPredictor(_BatchedPredictorBase):
       raise ValueError('goal frames must be [%d, %d, %d, >=%d], got %s' % (len(ids), H, W, C, tuple(t.shape)))
     t = np.ascontiguousarray(t[..., :C])
     idx = torch.as_tensor(ids, device=self._dev)
-    inp = self._model.inputs
     with torch.cuda.device(self._dev):
+      if self._incremental:      # the goals' features, once per goal: the per-call graph only reads them
+        tf = t.astype(np.float32) / np.float32(255.0) if self._u8 else t.astype(np.float32)   # the device's u8 division
+        if len(ids):
+          self._model.encode_targets(torch.from_numpy(tf).to(self._dev), idx)
+        self._goal_set[ids] = True
+        return
+      inp = self._model.inputs
       if self._ring:
         self._tgt_u8[idx] = torch.from_numpy(t.reshape(len(ids), -1)).to(self._dev)
       else:

@@ -10,6 +10,7 @@
 #include "geeco_common.h"
 
 #define PIO_MAXK 64       // the window lengths the input kernels of the models take (dynimg.hip: DYN_MAXK)
+#define GEECO_PREDICT_FEAT_THREADS 1024      // one block per env in the feature push + gather
 
 // float(u8) / 255.0f with the IEEE division: bitwise the `divisor 255` conversion of geeco_gather_windows (dynimg.hip)
 __device__ __forceinline__ float pio_u8(unsigned v) { return (float)v / 255.0f; }
@@ -316,6 +317,173 @@ extern "C" int geeco_predict_push_ring(const unsigned char* frames, const float*
   GEECO_LAUNCH_CHECK();
   hipLaunchKernelGGL(ring_advance_kernel, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, s, any_bad, B, K, FB,
                      (const unsigned char*)ring, heads, (long long*)win_table);
+  GEECO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- 3b. incremental mode: newest-frame input pack -------------------------------------------------------------------
+// The incremental predictor (batched_predictor.py, incremental=True) keeps no frame window: a call encodes only the B new
+// frames.  frames [B][HW][C] (float32, or uint8 with C == 3) -> the encoder input x_in [B][HW][4]: RGB gets a zero fourth
+// channel, RGB-D keeps depth there (the values geeco_pack_pixels gives for the dense windows' newest slot).
+template <int PIX, int C, bool U8>
+__global__ __launch_bounds__(256) void pack_newest_kernel(const void* __restrict__ frames, long long HW, float* __restrict__ x_in) {
+  const int b = blockIdx.y;
+  const long long u = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= HW / PIX) return;
+  float px[PIX * 3], dp[PIX];
+  load_new<PIX, C, U8>(frames, b, HW, u, px, dp);
+  f32x4* o = reinterpret_cast<f32x4*>(x_in + ((long long)b * HW + u * PIX) * 4);
+#pragma unroll
+  for (int p = 0; p < PIX; ++p) o[p] = f32x4{px[p * 3 + 0], px[p * 3 + 1], px[p * 3 + 2], C == 4 ? dp[p] : 0.f};
+}
+
+template <int PIX>
+static void launch_pack_newest(dim3 grid, hipStream_t s, const void* frames, int u8, int C, long long HW, float* x_in) {
+  if (u8) hipLaunchKernelGGL((pack_newest_kernel<PIX, 3, true>), grid, dim3(256), 0, s, frames, HW, x_in);
+  else if (C == 3) hipLaunchKernelGGL((pack_newest_kernel<PIX, 3, false>), grid, dim3(256), 0, s, frames, HW, x_in);
+  else hipLaunchKernelGGL((pack_newest_kernel<PIX, 4, false>), grid, dim3(256), 0, s, frames, HW, x_in);
+}
+
+extern "C" int geeco_predict_pack_newest(const void* frames, int frames_u8, int B, int64_t HW, int C, float* x_in, void* stream) {
+  GEECO_CHECK_ARG(frames && x_in, "predict_pack_newest: null pointer");
+  GEECO_CHECK_ARG(B >= 1, "predict_pack_newest: B=%d must be >= 1", B);
+  GEECO_CHECK_ARG(C == 3 || C == 4, "predict_pack_newest: C=%d must be 3 or 4", C);
+  GEECO_CHECK_ARG(!frames_u8 || C == 3, "predict_pack_newest: uint8 frames are RGB (C=3), got C=%d", C);
+  GEECO_CHECK_ARG(HW >= 1, "predict_pack_newest: HW=%lld", (long long)HW);
+  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(x_in) & 15) == 0, "predict_pack_newest: x_in must be 16-byte aligned");
+  const bool vec = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(frames) & 15) == 0;
+  const int pix = vec ? 4 : 1;
+  dim3 grid((unsigned)cdiv64(HW / pix, 256), (unsigned)B);
+  hipStream_t s = (hipStream_t)stream;
+  if (vec) launch_pack_newest<4>(grid, s, frames, frames_u8, C, (long long)HW, x_in);
+  else launch_pack_newest<1>(grid, s, frames, frames_u8, C, (long long)HW, x_in);
+  GEECO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- 3c. incremental mode: feature push + state gather ------------------------------------------------------------------
+// Per env a ring of the last K encoder feature vectors, feat_ring [B][K][cells][ch], and joint states, jnt_ring [B][K][J];
+// heads[b] = the slot the next frame's features go to.  One block per env: it writes the new feature / joint state into slot
+// p = heads[b] (into every slot where reset[b]: first-frame padding), writes the decoder's states[t][b] for t = 0..K-1 from
+// slots p + 1, .., p + K - 1, p (mod K; oldest first) and moves the head on.  The new values are taken from the inputs, the
+// K - 1 older ones from slots this launch does not write, so no thread reads what another one writes; the head is read by
+// every thread before the block's barrier and written by one thread after it.  Column layout of a cell, the one
+// geeco_state_concat_fwd gives: plain [feat | jnt], constant [feat | jnt | tgt], residual [tgt - feat | jnt].
+// V = floats per load of the feature sources (4: ch % 4 == 0 and 16-byte aligned bases).  The state rows are stored one float
+// per lane: with J = 7 a cell's columns start at odd offsets, a 16-byte store has nowhere aligned to go.
+template <int V>
+__device__ __forceinline__ void ld_feat(const float* p, float (&v)[V]) {
+  if (V == 4) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(p);
+    v[0] = x.x;
+    v[1] = x.y;
+    v[2] = x.z;
+    v[3] = x.w;
+  } else {
+    v[0] = *p;
+  }
+}
+
+template <int V>
+__global__ __launch_bounds__(GEECO_PREDICT_FEAT_THREADS) void push_features_kernel(
+    const float* __restrict__ feat, const float* __restrict__ jnt, const int* __restrict__ reset, const int* __restrict__ any_bad,
+    const float* __restrict__ tgt, int mode, int B, int K, int cells, int ch, int J, float* __restrict__ feat_ring,
+    float* __restrict__ jnt_ring, int* __restrict__ heads, float* __restrict__ states, long long state_stride) {
+  if (*any_bad) return;      // a frame failed the range check: no ring, no head moves
+  const int b = blockIdx.x;
+  const int rs = reset[b];
+  int p = heads[b];
+  if ((unsigned)p >= (unsigned)K) p = 0;     // heads come zero-filled and only this kernel moves them; never index past a ring
+  const int FE = cells * ch;                 // floats of one feature vector
+  const int Ctot = ch + J + (mode == GEECO_PREDICT_FEAT_CONSTANT ? ch : 0);
+  const int jnt_off = ch;
+  const float* fnew = feat + (long long)b * FE;
+  const float* tg = mode == GEECO_PREDICT_FEAT_PLAIN ? nullptr : tgt + (long long)b * FE;
+  float* fr = feat_ring + (long long)b * K * FE;
+  float* jr = jnt_ring + (long long)b * K * J;
+  const int nq = FE / V;                     // feature units of V floats (ch % V == 0: a unit stays inside one cell)
+  // 1. ring write: slot p, or all K slots after a reset
+  const int s0 = rs ? 0 : p, ns = rs ? K : 1;
+  for (int i = threadIdx.x; i < ns * nq; i += blockDim.x) {
+    const int s = i / nq, q = i - s * nq;
+    float v[V];
+    ld_feat<V>(fnew + q * V, v);
+    float* o = fr + (long long)(s0 + s) * FE + q * V;
+    if (V == 4) *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+    else o[0] = v[0];
+  }
+  for (int i = threadIdx.x; i < ns * J; i += blockDim.x) {
+    const int s = i / J, j = i - s * J;
+    jr[(s0 + s) * J + j] = jnt[(long long)b * J + j];
+  }
+  // 2. gather, oldest first; slot p (and every slot after a reset) comes from the inputs
+  for (int i = threadIdx.x; i < K * nq; i += blockDim.x) {
+    const int t = i / nq, q = i - t * nq;
+    int slot = p + 1 + t;
+    if (slot >= K) slot -= K;
+    const bool fresh = rs || slot == p;
+    float v[V];
+    ld_feat<V>(fresh ? fnew + q * V : fr + (long long)slot * FE + q * V, v);
+    const int cell = (q * V) / ch, c = q * V - cell * ch;
+    float* o = states + ((long long)t * B + b) * state_stride + cell * Ctot + c;
+    if (mode == GEECO_PREDICT_FEAT_PLAIN) {
+#pragma unroll
+      for (int k = 0; k < V; ++k) o[k] = v[k];
+    } else {
+      float g[V];
+      ld_feat<V>(tg + q * V, g);
+      if (mode == GEECO_PREDICT_FEAT_CONSTANT) {
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+          o[k] = v[k];
+          o[ch + J + k] = g[k];
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < V; ++k) o[k] = g[k] - v[k];
+      }
+    }
+  }
+  const int CJ = cells * J;
+  for (int i = threadIdx.x; i < K * CJ; i += blockDim.x) {
+    const int t = i / CJ, r = i - t * CJ;
+    const int cell = r / J, j = r - cell * J;
+    int slot = p + 1 + t;
+    if (slot >= K) slot -= K;
+    const bool fresh = rs || slot == p;
+    states[((long long)t * B + b) * state_stride + cell * Ctot + jnt_off + j] = fresh ? jnt[(long long)b * J + j] : jr[slot * J + j];
+  }
+  // 3. the head moves on: every thread of the block has read it before this barrier
+  __syncthreads();
+  if (threadIdx.x == 0) heads[b] = p + 1 == K ? 0 : p + 1;
+}
+
+extern "C" int geeco_predict_push_features(const float* feat, const float* jnt, const int* reset, const int* any_bad,
+                                           const float* tgt_feat, int mode, int B, int K, int cells, int ch, int J,
+                                           float* feat_ring, float* jnt_ring, int* heads, float* states, int64_t state_stride,
+                                           void* stream) {
+  GEECO_CHECK_ARG(feat && jnt && reset && any_bad && feat_ring && jnt_ring && heads && states,
+                  "predict_push_features: null pointer");
+  GEECO_CHECK_ARG(mode == GEECO_PREDICT_FEAT_PLAIN || mode == GEECO_PREDICT_FEAT_CONSTANT || mode == GEECO_PREDICT_FEAT_RESIDUAL,
+                  "predict_push_features: mode=%d must be 0 (plain), 1 (constant) or 2 (residual)", mode);
+  GEECO_CHECK_ARG(mode == GEECO_PREDICT_FEAT_PLAIN || tgt_feat, "predict_push_features: null pointer (tgt_feat, mode %d)", mode);
+  GEECO_CHECK_ARG(B >= 1, "predict_push_features: B=%d must be >= 1", B);
+  GEECO_CHECK_ARG(K >= 1 && K <= PIO_MAXK, "predict_push_features: K=%d outside 1..%d", K, PIO_MAXK);
+  GEECO_CHECK_ARG(cells >= 1 && ch >= 1 && J >= 1 && (int64_t)cells * ch <= (1 << 24), "predict_push_features: cells=%d ch=%d J=%d",
+                  cells, ch, J);
+  const int64_t Ctot = (int64_t)ch + J + (mode == GEECO_PREDICT_FEAT_CONSTANT ? ch : 0);
+  GEECO_CHECK_ARG(state_stride >= cells * Ctot, "predict_push_features: state_stride=%lld below cells * %lld columns",
+                  (long long)state_stride, (long long)Ctot);
+  const uintptr_t al = reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(tgt_feat) |
+                       reinterpret_cast<uintptr_t>(feat_ring);
+  const bool vec = ch % 4 == 0 && (al & 15) == 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (vec)
+    hipLaunchKernelGGL(push_features_kernel<4>, dim3((unsigned)B), dim3(GEECO_PREDICT_FEAT_THREADS), 0, s, feat, jnt, reset,
+                       any_bad, tgt_feat, mode, B, K, cells, ch, J, feat_ring, jnt_ring, heads, states, (long long)state_stride);
+  else
+    hipLaunchKernelGGL(push_features_kernel<1>, dim3((unsigned)B), dim3(GEECO_PREDICT_FEAT_THREADS), 0, s, feat, jnt, reset,
+                       any_bad, tgt_feat, mode, B, K, cells, ch, J, feat_ring, jnt_ring, heads, states, (long long)state_stride);
   GEECO_LAUNCH_CHECK();
   return 0;
 }

@@ -192,6 +192,25 @@ def predict_pack_into(out, ctl_out, preds, ctl, B, segs, imgs=(), HW=0, C=0, img
         'geeco_predict_pack')
 
 
+PREDICT_FEAT_MODES = {'plain': 0, 'constant': 1, 'residual': 2}     # GEECO_PREDICT_FEAT_* of include/geeco_hip.h
+
+
+def predict_pack_newest_into(x_in, frames, B, HW, C):
+  """frames [B][HW][C] (float32, or uint8 with C == 3: divided by 255 as the dense push does) -> encoder input x_in [B][HW][4]."""
+  check(_lib().geeco_predict_pack_newest(_p(frames), 1 if frames.dtype == torch.uint8 else 0, B, HW, C, _p(x_in), _stream()),
+        'geeco_predict_pack_newest')
+
+
+def predict_push_features_into(states, feat_ring, jnt_ring, heads, feat, jnt, reset, ctl, mode, B, K, cells, ch, J, state_stride,
+                               tgt_feat=None):
+  """Pushes the new features [B][cells][ch] / joint states [B][J] into the rings [B][K][..] (every slot where reset[b]), writes
+  states [K][B][state_stride] oldest first in the columns of state_concat_fwd_into for ``mode`` ('plain', 'constant',
+  'residual') and advances heads [B]; nothing moves while ctl[B] is set."""
+  check(_lib().geeco_predict_push_features(_p(feat), _p(jnt), _p(reset), _p(ctl[B:B + 1]), _p(tgt_feat), PREDICT_FEAT_MODES[mode],
+                                           B, K, cells, ch, J, _p(feat_ring), _p(jnt_ring), _p(heads), _p(states), state_stride,
+                                           _stream()), 'geeco_predict_push_features')
+
+
 # --------------------------------------------------------------------------------------------
 # conv encoder
 # --------------------------------------------------------------------------------------------

@@ -7,6 +7,10 @@ padded with the first frame after a reset (:192-200); frames must be [H, W, C] i
 the gripper logits are re-mapped to {-1, 0, 1} (:183-189); ``dynbuff`` / ``dyndiff`` debug images are
 returned when the model computes them (:167-170).  The frame buffer lives in HBM: a new frame is
 uploaded once and the window is shifted on the device; the forward pass is a replayed hipGraph.
+
+``incremental=True`` (per-frame models: e2e_vmc, goal_e2evmc 'sequence' x 'constant' / 'residual') drives a one-env incremental
+core of ``batched_predictor``: a call encodes the new frame only, the features of the window's older frames wait in a ring on
+the device.  Same methods, same returned dict.
 """
 from __future__ import annotations
 
@@ -40,8 +44,17 @@ def _latest_tf_bundle(model_dir):
 class _PredictorBase:
   _goal = False
 
-  def __init__(self, model_dir, checkpoint_name=None, memcap=0.8, device=None):
+  def __init__(self, model_dir, checkpoint_name=None, memcap=0.8, device=None, incremental=False):
     self._model_dir = model_dir
+    self._core = None
+    if incremental:
+      from . import batched_predictor as bp       # imports this module: resolved at call time
+      cls = bp.BatchedGoalE2EVMCPredictor if self._goal else bp.BatchedE2EVMCPredictor
+      self._core = cls(model_dir, 1, checkpoint_name=checkpoint_name, memcap=memcap, device=device, incremental=True)
+      self._cfg, self._model = self._core.cfg, self._core._model
+      self._buffer_size = self._cfg.window_size
+      self._target_set = False
+      return
     cfg = load_model_config(model_dir, 'e2evmc_config')
     cfg['batch_size'] = 1   # one prediction at a time (predictor.py:56)
     self._cfg = create_e2evmc_config(cfg)
@@ -117,10 +130,20 @@ class _PredictorBase:
 
   def predict(self, rgb_frame, jnt_state):
     """Feeds the frame (padding the buffer after a reset) and returns the predictions."""
+    if self._core is not None:
+      if self._goal and not self._target_set:
+        raise RuntimeError('set_goal(tgt_frame) must be called before predict()')
+      self._check_frame(rgb_frame)
+      out = self._core.predict(np.ascontiguousarray(rgb_frame, dtype=np.float32)[None],
+                               np.asarray(jnt_state, dtype=np.float32).reshape(1, -1))
+      return {k: v[0] for k, v in out.items()}
     self._feed_frame(rgb_frame, jnt_state)
     return self._predict_command()
 
   def reset(self):
+    if self._core is not None:
+      self._core.reset()
+      return
     self._filled = 0
 
 
@@ -144,6 +167,10 @@ class GoalE2EVMCPredictor(_PredictorBase):
     """Sets the target frame (predictor.py:206-209)."""
     C = self._cfg.img_channels
     t = np.ascontiguousarray(tgt_frame[:, :, :C], dtype=np.float32)
+    if self._core is not None:
+      self._core.set_goal(t[None])
+      self._target_set = True
+      return
     inp = self._model.inputs
     inp['target_rgb'][0].copy_(torch.from_numpy(t[..., :3]))
     if C == 4:

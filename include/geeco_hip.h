@@ -143,6 +143,26 @@ int geeco_predict_pack(const float* preds, int P, int B, int nseg, const int* se
                        float* out, int F, int* ctl, int* ctl_out, const float* img0, const float* img1, int64_t HW, int C,
                        float* img_out, void* stream);
 
+/* ---- incremental predictor: per-frame encoder features cached on the device (batched_predictor.py, incremental=True) ----
+ * The per-frame controllers (e2e_vmc; goal_e2evmc 'sequence' x 'constant' / 'residual') encode only the B new frames of a call;
+ * the features of the K - 1 older frames of every window wait in a ring. */
+/* Newest-frame input pack: frames [B][HW][C] (float32, or uint8 when frames_u8: C == 3, divided by 255 bitwise as
+ * geeco_predict_push_dense does) -> the encoder input x_in [B][HW][4]; channel 3 = depth (C == 4) or 0. */
+int geeco_predict_pack_newest(const void* frames, int frames_u8, int B, int64_t HW, int C, float* x_in, void* stream);
+/* Feature push + state gather, one launch.  feat [B][cells][ch]: the encoder's features of the new frames; jnt [B][J].  On the
+ * device: feat_ring [B][K][cells][ch], jnt_ring [B][K][J], heads [B] int32 (zero-filled once) = the slot of each env's next
+ * frame, advanced by the launch itself.  reset[b] != 0: all K slots of env b get the new feature / joint state
+ * (predictor.py:192-200), else slot heads[b] does.  Then states[t][b] ([K][B][state_stride]) is written for t = 0..K-1, oldest
+ * frame first, with the columns of geeco_state_concat_fwd per cell: PLAIN [feat | jnt] (jnt_pos 1), CONSTANT [feat | jnt | tgt]
+ * (jnt_pos 1, two maps), RESIDUAL [tgt - feat | jnt] (sub_from); tgt_feat [B][cells][ch] (NULL for PLAIN).  Nothing moves and
+ * nothing is written while *any_bad is set.  K: 1..64. */
+#define GEECO_PREDICT_FEAT_PLAIN 0
+#define GEECO_PREDICT_FEAT_CONSTANT 1
+#define GEECO_PREDICT_FEAT_RESIDUAL 2
+int geeco_predict_push_features(const float* feat, const float* jnt, const int* reset, const int* any_bad, const float* tgt_feat,
+                                int mode, int B, int K, int cells, int ch, int J, float* feat_ring, float* jnt_ring, int* heads,
+                                float* states, int64_t state_stride, void* stream);
+
 /* ---- conv encoder: graph.py:76-115 (tf.layers.conv2d 3x3, padding='SAME', bias, ReLU) ----------
  * x [G][N][H][W][Cin], w [G][3][3][Cin][Cout] (HWIO), b [G][Cout], y [G][N][Ho][Wo][Cout],
  * Ho = ceil(H/stride); TF SAME padding (pad_before = pad_total/2, i.e. 0 top/left for stride 2 on
