@@ -1,7 +1,8 @@
 """Batched predictor API: B control loops (simulator envs) stepped by ONE call.
 
-``BatchedGoalE2EVMCPredictor`` / ``BatchedE2EVMCPredictor`` are the batched counterparts of ``predictor.GoalE2EVMCPredictor`` /
-``E2EVMCPredictor`` (reference ``src/models/e2evmc/predictor.py``).  Per env the semantics are the batch-1 predictor's
+``BatchedGoalE2EVMCPredictor`` / ``BatchedE2EVMCPredictor`` are the batched counterparts of the reference's
+``GoalE2EVMCPredictor`` / ``E2EVMCPredictor`` (``src/models/e2evmc/predictor.py``) and the one predictor engine of this package:
+the batch-1 classes of ``predictor`` are views of it with ``num_envs=1``.  Per env the semantics are the reference's
 (:127-209): a window of the last ``window_size`` frames, padded with the first frame after a reset; frames [H, W, C] with
 channels 0..2 in [0 - 1e-6, 1 + 1e-6]; the gripper logits re-mapped to argmax - 1 in cartesian mode; the reference's five
 outputs in velocity mode; ``dynbuff`` / ``dyndiff`` when the model computes them (and ``debug_images=True``).  Every output gets
@@ -19,18 +20,16 @@ decoder, output pack.  Same methods, errors and returned dict.
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
 from . import estimator as est
 from . import graph, ops
 from .params import create_e2evmc_config
-from .predictor import TOL_FRAME_RANGE, _latest_tf_bundle
 from .runtime import _CAPTURE_MODE, CAPTURE_LOCK
 from .utils import load_model_config
 
+TOL_FRAME_RANGE = 1e-6  # tolerance for value range of fed frames (predictor.py:18)
 _ALIGN = 256
 _TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8, np.dtype(np.int32): torch.int32}
 
@@ -78,21 +77,6 @@ class _AddressTable:
     return self
 
 
-def _restore(store, model_dir, checkpoint_name):
-  """The checkpoint lookup of predictor._PredictorBase: a native .pt checkpoint, or a TF-1.15 tensor bundle."""
-  ckpt = os.path.join(model_dir, checkpoint_name) if checkpoint_name else est.latest_checkpoint(model_dir)
-  if ckpt is None and not checkpoint_name:
-    ckpt = _latest_tf_bundle(model_dir)
-  if ckpt is None:
-    raise FileNotFoundError('no checkpoint in %s' % model_dir)
-  if os.path.exists(ckpt + '.pt'):
-    est.load_checkpoint(store, ckpt)
-  else:
-    from . import tf_checkpoint
-    tf_checkpoint.import_checkpoint(store, ckpt, load_optimizer=False)
-  print('>>> Restored model parameters from %s' % (ckpt,))
-
-
 class _BatchedPredictorBase:
   _goal = False
 
@@ -137,39 +121,12 @@ class _BatchedPredictorBase:
     self._dims = (B, H, W, C, K, J)
     with torch.cuda.device(dev):
       m = self._model = ctor(cfg, B, dev, training=False)
-      _restore(m.store, model_dir, checkpoint_name)
+      est.restore_for_inference(m.store, model_dir, checkpoint_name)
       # uint8 frames on a model whose input kernel reads uint8 windows: the mirrored ring (no fp32 window is ever written)
       self._ring = self._u8 and not self._incremental and 'rgb' in m.u8_window_keys
-      stage = _Layout()
-      stage.add('frames', (B, H, W, C), fd)
-      stage.add('jnt', (B, J), np.float32)
-      stage.add('reset', (B,), np.int32)
-      self._h_stage = torch.empty(stage.size, dtype=torch.uint8, pin_memory=True)
-      self._d_stage = torch.zeros(stage.size, dtype=torch.uint8, device=dev)
-      self._h = stage.host(self._h_stage)
-      self._d = stage.device(self._d_stage)
-      self._ctl = torch.zeros(B + 1, dtype=torch.int32, device=dev)
-      # outputs in the order the API returns them: (name, source column, width, argmax - 1)
-      off, cols = 0, {}
-      for _, key, size, _, _ in m.decoder.heads:
-        cols[key] = (off, size)
-        off += size
-      if cfg.control_mode == 'cartesian':
-        self._segs = [('cmd_ee',) + cols['cmd_ee'] + (False,), ('cmd_grp',) + cols['logits_cmd_grp'] + (True,),
-                      ('pos_ee',) + cols['pos_ee'] + (False,), ('pos_obj',) + cols['pos_obj'] + (False,)]
-      else:
-        self._segs = [(k,) + cols[k] + (False,) for k in ('cmd_vel', 'cmd_ee', 'cmd_grp', 'pos_ee', 'pos_obj')]
-      F = sum(1 if a else n for _, _, n, a in self._segs)
-      self._imgs = self._debug_sources() if debug_images and not self._incremental else []   # step models compute no images
-      out = _Layout()
-      out.add('out', (B, F), np.float32)
-      out.add('ctl', (B + 1,), np.int32)
-      if self._imgs:
-        out.add('images', (len(self._imgs), B, H, W, C), np.float32)
-      self._h_outblk = torch.empty(out.size, dtype=torch.uint8, pin_memory=True)
-      self._d_outblk = torch.zeros(out.size, dtype=torch.uint8, device=dev)
-      self._ho = out.host(self._h_outblk)
-      self._do = out.device(self._d_outblk)
+      self._make_staging_block()
+      self._ctl = torch.zeros(B + 1, dtype=torch.int32, device=dev)      # per env "frame out of range", then "any env"
+      self._make_output_block(debug_images)
       if self._ring:
         self._ring_buf = torch.zeros(B, 2 * K, H * W * 3, dtype=torch.uint8, device=dev)
         self._heads = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -192,6 +149,45 @@ class _BatchedPredictorBase:
         with torch.cuda.graph(self._graph, capture_error_mode=_CAPTURE_MODE):
           self._call_body()
       torch.cuda.synchronize(dev)
+
+  def _make_staging_block(self):
+    """What one call uploads: frames, joint states and pending resets in one pinned block and its device twin."""
+    B, H, W, C, K, J = self._dims
+    dev, fd = self._dev, self._fdtype
+    stage = _Layout()
+    stage.add('frames', (B, H, W, C), fd)
+    stage.add('jnt', (B, J), np.float32)
+    stage.add('reset', (B,), np.int32)
+    self._h_stage = torch.empty(stage.size, dtype=torch.uint8, pin_memory=True)
+    self._d_stage = torch.zeros(stage.size, dtype=torch.uint8, device=dev)
+    self._h = stage.host(self._h_stage)
+    self._d = stage.device(self._d_stage)
+
+  def _make_output_block(self, debug_images):
+    """What one call downloads: the packed outputs, the range-check words and the debug images, in one block."""
+    B, H, W, C, K, J = self._dims
+    dev, cfg, m = self._dev, self._cfg, self._model
+    # outputs in the order the API returns them: (name, source column, width, argmax - 1)
+    off, cols = 0, {}
+    for _, key, size, _, _ in m.decoder.heads:
+      cols[key] = (off, size)
+      off += size
+    if cfg.control_mode == 'cartesian':
+      self._segs = [('cmd_ee',) + cols['cmd_ee'] + (False,), ('cmd_grp',) + cols['logits_cmd_grp'] + (True,),
+                    ('pos_ee',) + cols['pos_ee'] + (False,), ('pos_obj',) + cols['pos_obj'] + (False,)]
+    else:
+      self._segs = [(k,) + cols[k] + (False,) for k in ('cmd_vel', 'cmd_ee', 'cmd_grp', 'pos_ee', 'pos_obj')]
+    F = sum(1 if a else n for _, _, n, a in self._segs)
+    self._imgs = self._debug_sources() if debug_images and not self._incremental else []   # step models compute no images
+    out = _Layout()
+    out.add('out', (B, F), np.float32)
+    out.add('ctl', (B + 1,), np.int32)
+    if self._imgs:
+      out.add('images', (len(self._imgs), B, H, W, C), np.float32)
+    self._h_outblk = torch.empty(out.size, dtype=torch.uint8, pin_memory=True)
+    self._d_outblk = torch.zeros(out.size, dtype=torch.uint8, device=dev)
+    self._ho = out.host(self._h_outblk)
+    self._do = out.device(self._d_outblk)
 
   def _debug_sources(self):
     return []

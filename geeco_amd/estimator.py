@@ -134,6 +134,20 @@ def load_checkpoint(store, prefix):
     tf_checkpoint.import_checkpoint(store, prefix, load_optimizer=True)
 
 
+def restore_for_inference(store, model_dir, checkpoint_name=None):
+  """The predictors' restore (predictor.py:85-95): the named checkpoint, else the latest one of the directory -- a native
+  .pt file, or a TensorFlow-1.15 tensor bundle (e.g. the published geeco_models_icra21 weights).  Parameters only."""
+  ckpt = os.path.join(model_dir, checkpoint_name) if checkpoint_name else latest_checkpoint(model_dir)
+  if ckpt is None:
+    raise FileNotFoundError('no checkpoint in %s' % model_dir)
+  if os.path.exists(ckpt + '.pt'):
+    load_checkpoint(store, ckpt)
+  else:
+    from . import tf_checkpoint
+    tf_checkpoint.import_checkpoint(store, ckpt, load_optimizer=False)
+  print('>>> Restored model parameters from %s' % (ckpt,))
+
+
 # ================================================================================================
 # model_fn (estimator.py:14-141 and 144-279)
 # ================================================================================================

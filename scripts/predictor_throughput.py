@@ -1,4 +1,5 @@
-"""Control steps per second: batch-1 predictor vs the batched predictor (geeco_amd/batched_predictor.py).
+"""Control steps per second: the batch-1 API (predictor.py: a one-env view of the batched predictor, with the host-side frame
+check) vs B envs per call on the same engine (geeco_amd/batched_predictor.py).
 
 Random-weight checkpoints as bench.py's inference leg builds them; geeco-f (dynimg + dyndiff, RGB) and e2e_vmc at 256^2,
 K = 16; B in {1, 8, 32, 64}; float32 and uint8 frames from pinned host arrays.  Every timed call ends in the call's own

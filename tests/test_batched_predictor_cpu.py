@@ -45,7 +45,8 @@ class WindowModel:
 
 
 class Batch1Window:
-  """The batch-1 predictor's frame buffer (predictor.py:_feed_frame; reference predictor.py:144-146, 192-200)."""
+  """The reference's frame buffer (its predictor.py:144-146, 192-200): the newest frame replaces the oldest, the first frame after
+  a reset fills the whole window.  The window kernels are tested against it bitwise."""
 
   def __init__(self, K):
     self.K, self.buf, self.filled = K, None, 0

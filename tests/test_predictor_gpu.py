@@ -43,21 +43,25 @@ def test_predictor_matches_oracle(dev, tmp_path, goal):
   ocfg = O.make_config(batch_size=1, **kw)
   Pt = {k: torch.tensor(v, dtype=torch.float64) for k, v in P.items()}
   window = []
-  for t in range(5):
-    out = pred.predict(frames[t], jnts[t])
-    window.append((frames[t], jnts[t]))
+  for t, i in enumerate([0, 1, 2, 3, 4, 3, 1, 4, 2]):
+    if t == 5:                                            # reset() in mid-stream: the next frame pads the whole window again
+      pred.reset()
+      window = []
+    fresh = not window
+    out = pred.predict(frames[i], jnts[i])
+    window.append((frames[i], jnts[i]))
     while len(window) < 3:
-      window.append((frames[t], jnts[t]))                 # first-frame padding after reset
+      window.append((frames[i], jnts[i]))                 # first-frame padding after reset
     window = window[-3:]
     feats = {'rgb': torch.tensor(np.stack([w[0] for w in window])[None], dtype=torch.float64),
              'jnt_state': torch.tensor(np.stack([w[1] for w in window])[None], dtype=torch.float64)}
     if goal:
       feats['target_rgb'] = torch.tensor(tgt[None, :, :, :3], dtype=torch.float64)
     ref, ep = O.model_forward(feats, Pt, ocfg, goal)
-    # t == 0 with a goal model: the padded window holds ONE frame K times, so the dynamic image is
+    # first call after a reset with a goal model: the padded window holds ONE frame K times, so the dynamic image is
     # sum(alpha) * frame = rounding noise divided by (noise range + 1e-6): ill-conditioned in any
     # precision (also in the TF reference); only shapes are checked there.
-    noise = goal and t == 0
+    noise = goal and fresh
     for k in ('cmd_ee', 'pos_ee', 'pos_obj'):
       np.testing.assert_allclose(out[k], ref[k][0].numpy(), rtol=1e-4, atol=5e-2 if noise else 2e-5,
                                  err_msg='%s @%d' % (k, t))
