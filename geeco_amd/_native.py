@@ -10,10 +10,19 @@ import ctypes
 import os
 from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_void_p, POINTER, Structure
 
-from . import _dev
-
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, _dev.env('GEECO_LIB', 'libgeeco_hip.so'))   # GEECO_DEV=1 GEECO_LIB=...: A/B builds side by side
+
+
+def lib_path():
+  """libgeeco_hip.so next to this file.  ``GEECO_DEV=1 GEECO_LIB=NAME`` loads another build from the same directory
+  instead (the A/B and instrumentation builds of scripts/dev/build_variant.sh and build_stamps.sh); without GEECO_DEV=1
+  GEECO_LIB is ignored.  No other environment variable changes what the package runs."""
+  dev = os.environ.get('GEECO_DEV')
+  name = os.environ.get('GEECO_LIB', 'libgeeco_hip.so') if dev and dev != '0' else 'libgeeco_hip.so'
+  return os.path.join(_HERE, name)
+
+
+LIB_PATH = lib_path()
 
 
 GEECO_EINVAL, GEECO_ENOSUP = -1, -2      # include/geeco_hip.h

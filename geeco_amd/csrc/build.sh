@@ -1,6 +1,6 @@
 #!/bin/bash
-# Builds the C-ABI shared library for gfx950 in-tree (geeco_amd/libgeeco_hip.so): the PRODUCT kernel set only -- no GEECO_*
-# switch is compiled in and no kernel that only a switch could select (those live in scripts/dev/build_dev_lib.sh's library).
+# Builds the C-ABI shared library for gfx950 in-tree (geeco_amd/libgeeco_hip.so): the only kernel set there is, one measured
+# path per stage; the library reads no environment variable (the retired A/B switches: scripts/dev/SWITCHES.md).
 set -euo pipefail
 cd "$(dirname "$0")"
 OUT=../libgeeco_hip.so

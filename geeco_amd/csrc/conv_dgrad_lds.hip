@@ -44,7 +44,7 @@ struct DgradLdsParams {
   int stagger;           // waves 4-7 issue their DMA pieces mid-chunk
 };
 
-__device__ __forceinline__ bool getenv_stagger(const DgradLdsParams& p) { return p.stagger != 0; }
+__device__ __forceinline__ bool staggered(const DgradLdsParams& p) { return p.stagger != 0; }
 
 // A group = PR x PC = 16 class pixels; a tile = 8 groups stacked in y (FR frames per tile: 1 for wide images, 2 when a
 // frame holds only 4 groups).  NCIT = ci tiles of 16 per block: 4 (64 channels, 94 KB of LDS, one block per CU) or 2 (32
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (NCIT == 4 ? 2 : 4)) void co
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  const bool late = wid >= NW / 2 && getenv_stagger(p);
+  const bool late = wid >= NW / 2 && staggered(p);
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   f32x4 acc[4][NCIT];                               // [class py * 2 + px][ci tile]
   int buf = 0;
@@ -296,8 +296,7 @@ static int launch_dgrad_lds(const DgradLdsParams& p, int blocks, hipStream_t str
 
 // does the dispatcher below take this shape (given the HWIO kernel)?  Such layers never read the transposed copy.
 int geeco_dgrad_lds_handles(int H, int W, int Cin, int Cout, int stride) {
-  static const int disabled = (geeco_dev_getenv("GEECO_NO_HALO") || geeco_dev_getenv("GEECO_NO_DGRAD_LDS")) ? 1 : 0;
-  if (disabled || stride != 2 || (H & 1) || (W & 1) || Cin % 64 != 0 || Cout % 16 != 0 || Cout < 32) return 0;
+  if (stride != 2 || (H & 1) || (W & 1) || Cin % 64 != 0 || Cout % 16 != 0 || Cout < 32) return 0;
   const int Ho = H / 2, Wo = W / 2;
   if (!((Ho % 8 == 0 && Wo % 16 == 0) || (Ho == 8 && Wo == 8))) return 0;
   if ((long long)H * W * Cin >= (1ll << 31) || (long long)Ho * Wo * Cout >= (1ll << 31) || 9ll * Cin * Cout >= (1ll << 30)) return 0;      // (weight granules are addressed by 32-bit BYTE offsets)
@@ -339,31 +338,21 @@ static int dgrad_lds_impl(const float* dz, const float* w_hwio, const float* yma
                           int64_t gs_fields, float* dx, int groups, int64_t gs_dz, int64_t gs_w, int64_t gs_dx, int N, int H,
                           int W, int Cin, int Cout, int stride, hipStream_t stream, int* handled) {
   *handled = 0;
-  static const int disabled = (geeco_dev_getenv("GEECO_NO_HALO") || geeco_dev_getenv("GEECO_NO_DGRAD_LDS")) ? 1 : 0;
-  if (disabled || !w_hwio || stride != 2 || (H & 1) || (W & 1) || Cin % 64 != 0 || Cout % 16 != 0 || Cout < 32) return 0;
+  if (!w_hwio || stride != 2 || (H & 1) || (W & 1) || Cin % 64 != 0 || Cout % 16 != 0 || Cout < 32) return 0;
   const int Ho = H / 2, Wo = W / 2;
   int variant = 0;
   if (Ho % 8 == 0 && Wo % 16 == 0) variant = 1;          // 8 groups of 1 x 16 class pixels: a 16 x 32 input-pixel tile
-  else if (Ho == 8 && Wo == 8) variant = 2;               // 2 x 8 groups: a tile = two whole frames
+  else if (Ho == 8 && Wo == 8) variant = 2;               // 8 x 8 class pixels per frame: one-frame tiles
   if (!variant) return 0;
   if ((long long)H * W * Cin >= (1ll << 31) || (long long)Ho * Wo * Cout >= (1ll << 31) || 9ll * Cin * Cout >= (1ll << 30)) return 0;      // (weight granules are addressed by 32-bit BYTE offsets)
   DgradLdsParams p = {};
   p.dz = dz; p.w = w_hwio; p.mask = ymask; p.fields = fields; p.gs_fields = gs_fields; p.dx = dx; p.gs_dz = gs_dz; p.gs_w = gs_w; p.gs_dx = gs_dx;
   p.N = N; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.Cin = Cin; p.Cout = Cout;
-  static const int no_stagger = geeco_dev_getenv("GEECO_DGRAD_NO_STAGGER") ? 1 : 0;
-  p.stagger = !no_stagger;
-  long long tiles;
-  if (variant == 1) {
-    p.tiles_y = Ho / 8; p.tiles_x = Wo / 16;
-    tiles = (long long)N * p.tiles_y * p.tiles_x;
-  } else {
-    p.tiles_y = 1; p.tiles_x = 1;
-    tiles = (N + 1) / 2;
-  }
-  static const int no_small = geeco_dev_getenv("GEECO_DGRAD_NO_SMALL") ? 1 : 0;
-  if (variant == 2 && !no_small) {
+  p.stagger = 1;
+  if (variant == 2) {
     // 8 x 8 class pixels per frame: one-frame tiles of 4 groups, 32-channel items, 256-thread blocks, three per CU.  The
     // two-frame / 8-wave form has only groups * (Cin / 64) * N / 2 items (conv6 of the bench: 144 for 256 CUs).
+    p.tiles_y = 1; p.tiles_x = 1;
     p.tiles_per_group = N;
     p.n_cib = Cin / 32;
     const long long items = (long long)groups * p.n_cib * N;
@@ -376,33 +365,25 @@ static int dgrad_lds_impl(const float* dz, const float* w_hwio, const float* yma
     *handled = 1;
     return 0;
   }
+  p.tiles_y = Ho / 8; p.tiles_x = Wo / 16;
+  const long long tiles = (long long)N * p.tiles_y * p.tiles_x;
   p.tiles_per_group = (int)tiles;
   // 64-channel items (one block per CU) or 32-channel items (two blocks per CU): whichever spreads the launch more evenly
   // over the 256 CUs; cost of an item in CU-time: 1 resp. 1/2.  Ties go to the 64-channel form (more reuse per staged byte).
   const long long items64 = (long long)groups * (Cin / 64) * tiles;
   if (items64 * 2 >= (1ll << 30)) return 0;
-  static const int force_ncit = geeco_dev_getenv("GEECO_DGRAD_NCIT") ? atoi(geeco_dev_getenv("GEECO_DGRAD_NCIT")) : 0;
   const double span64 = (double)((items64 + 255) / 256), span32 = 0.5 * (double)((2 * items64 + 255) / 256);
-  const bool use32 = force_ncit == 2 || (force_ncit != 4 && span32 < span64);
   int rc;
-  if (use32) {
+  if (span32 < span64) {
     p.n_cib = Cin / 32;
     p.items = (int)(2 * items64);
     const int blocks = p.items < 512 ? p.items : 512;
-#ifdef GEECO_DEV_KERNELS      // variant 2 only gets here with GEECO_DGRAD_NO_SMALL (two-frame tiles of the 8 x 8 layers)
-    rc = variant == 1 ? launch_dgrad_lds<1, 16, 1, 2>(p, blocks, stream) : launch_dgrad_lds<2, 8, 2, 2>(p, blocks, stream);
-#else
     rc = launch_dgrad_lds<1, 16, 1, 2>(p, blocks, stream);
-#endif
   } else {
     p.n_cib = Cin / 64;
     p.items = (int)items64;
     const int blocks = p.items < 256 ? p.items : 256;
-#ifdef GEECO_DEV_KERNELS
-    rc = variant == 1 ? launch_dgrad_lds<1, 16, 1, 4>(p, blocks, stream) : launch_dgrad_lds<2, 8, 2, 4>(p, blocks, stream);
-#else
     rc = launch_dgrad_lds<1, 16, 1, 4>(p, blocks, stream);
-#endif
   }
   if (rc) return rc;
   GEECO_LAUNCH_CHECK();

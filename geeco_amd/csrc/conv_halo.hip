@@ -28,8 +28,7 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 
 // ------------------------------------------------------------------------------------------------
 // conv2-type forward: stride 2, CIN == 32, COUT % 16 == 0, tile = 4 x 16 output pixels.
-// LDS: W as [tap][cq][co][4] (b128 B-fragments); halo (2 buffers, filled by LDS-DMA) as
-// [row][pixel pair][16 float4 = 2 pixels x 8 channel quads, XOR-swizzled by the pair index]:
+// LDS: halo (filled by LDS-DMA) as [row][pixel pair][16 float4 = 2 pixels x 8 channel quads, XOR-swizzled by the pair index]:
 // a pixel's 128 bytes are fetched by 8 consecutive lanes and the b128 A-fragments of 16 consecutive
 // output columns (input pixels 2 r + kx) fall on distinct 16-byte slots.
 // ------------------------------------------------------------------------------------------------
@@ -101,216 +100,14 @@ typedef __attribute__((address_space(3))) void* lptr_t;
 // Barrier that also retires this wave's LDS-DMA (global_load_lds) writes before anyone reads them.
 __device__ __forceinline__ void dma_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// RW: the wave's kernel fragments (9 taps x COUT / 16 float4 = 108 registers) stay in VGPRs for the block's
-// lifetime, so the K loop reads ONE ds_read_b128 per 12 MFMAs instead of four; costs the second block per CU.
-template <int CIN, int COUT, bool RW>
-__global__ __launch_bounds__(512, RW ? 1 : 2) void conv_s2_halo_fwd_kernel(const HaloFwdParams p) {
-  constexpr int NT = 512;                             // 8 waves = 4 output rows x 2 halves of the channel (K) range
-  constexpr int TH = 4, TW = 16;
-  constexpr int CQ = CIN / 4;
-  static_assert(CQ == 8, "pair-swizzled halo image is laid out for 8 channel quads");
-  // Halo image (filled by LDS-DMA, no VGPR staging): row hy = 17 pixel PAIRS x 16 float4; the 16 quads of
-  // a pair (2 pixels x 8 quads) are XOR-swizzled by (pair & 15) so that the b128 fragment reads of 16
-  // consecutive output columns (input pixels 2 r + kx) hit distinct 16-byte slots.
-  constexpr int HY = 2 * TH + 1;
-  constexpr int ROW = 17 * 16;                        // float4 per halo row
-  constexpr int HALO_USED = HY * ROW;                 // 2448
-  constexpr int NDMA = (HALO_USED + 63) / 64;         // 1 KiB LDS-DMA pieces per tile (39)
-  constexpr int HALO_F4 = NDMA * 64;                  // 2496 (the last piece spills into padding)
-  constexpr int NSLOT = (NDMA + 7) / 8;               // pieces per wave
-  constexpr int W_F4 = 9 * CQ * COUT;
-  constexpr int TI = COUT / 16;
-  constexpr int KB = CIN / 16;
-  constexpr int KBW = KB / 2;                         // 16-channel blocks per wave
-  constexpr int NIT = 9 * KBW;
-  constexpr int RED_F4 = 4 * TI * 64;                 // partial accumulators of waves 4..7
-  static_assert(KB % 2 == 0, "K split");
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  f32x4* sW = reinterpret_cast<f32x4*>(smem);
-  f32x4* sH = sW + W_F4;                              // 2 halo buffers
-  f32x4* sR = sH + 2 * HALO_F4;                       // 2 reduction buffers
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int r = lane & 15, q = lane >> 4;
-  const int strip = wid & 3, khalf = wid >> 2;
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-
-  // contiguous tile range per block (neighbouring tiles share halo rows in L2; no divisions in the loop)
-  const long long per = (p.ntiles + gridDim.x - 1) / gridDim.x;
-  long long tile = (long long)blockIdx.x * per;
-  long long tend = tile + per < p.ntiles ? tile + per : p.ntiles;
-  if (tile >= tend) return;
-  int g, n, ty, tx;
-  {
-    g = (int)(tile / p.tiles_per_group);
-    int rem = (int)(tile - (long long)g * p.tiles_per_group);
-    int per_img = p.tiles_x * p.tiles_y;
-    n = rem / per_img;
-    rem -= n * per_img;
-    ty = rem / p.tiles_x;
-    tx = rem - ty * p.tiles_x;
-  }
-  auto advance = [&](int& g_, int& n_, int& ty_, int& tx_) {
-    if (++tx_ == p.tiles_x) {
-      tx_ = 0;
-      if (++ty_ == p.tiles_y) {
-        ty_ = 0;
-        if (++n_ == p.N) {
-          n_ = 0;
-          ++g_;
-        }
-      }
-    }
-  };
-
-  // this wave's LDS-DMA pieces: piece k = wid + 8 i covers halo slots [64 k, 64 k + 64); lane -> (hy, hx, cq)
-  __builtin_assume(wid >= 0 && wid < 8);
-  int d_src[NSLOT];
-  short d_hy[NSLOT], d_hx[NSLOT];
-#pragma unroll
-  for (int i = 0; i < NSLOT; ++i) {
-    const int sl = (wid + 8 * i) * 64 + lane;
-    const int row = sl / ROW, rem = sl - row * ROW;
-    const int pair = rem >> 4, u = (rem & 15) ^ (pair & 15);
-    const int hx = 2 * pair + (u >> 3), cq = u & 7;
-    const bool ok = sl < HALO_USED && hx <= 2 * TW;
-    d_hy[i] = (short)(ok ? row : 30000);              // out-of-range marker fails the per-tile bounds test
-    d_hx[i] = (short)hx;
-    d_src[i] = (row * p.W + hx) * CIN + cq * 4;
-  }
-  auto dma_halo = [&](int buf, int g_, int n_, int ty_, int tx_) {
-    const int iy0 = ty_ * TH * 2, ix0 = tx_ * TW * 2;      // TF SAME, stride 2, even input: pad_before = 0
-    const float* xg = p.x + (long long)g_ * p.gs_x + (((long long)n_ * p.H + iy0) * p.W + ix0) * CIN;
-#pragma unroll
-    for (int i = 0; i < NSLOT; ++i) {
-      if (wid + 8 * i < NDMA) {                         // wave-uniform
-        const bool v = iy0 + d_hy[i] < p.H && ix0 + d_hx[i] < p.W;
-        const float* src = v ? xg + d_src[i] : g_zero_page;
-        f32x4* dst = sH + buf * HALO_F4 + (wid + 8 * i) * 64;
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
-      }
-    }
-  };
-  auto load_weights = [&](int g_) {
-    const float* wg = p.w + (long long)g_ * p.gs_w;
-    // HWIO [tap][c][co] -> LDS [tap][c/4][co][c%4]
-    for (int e = tid; e < 9 * CIN * COUT; e += NT) {
-      int co = e % COUT;
-      int tc = e / COUT;               // tap*CIN + c
-      int c = tc % CIN, tap = tc / CIN;
-      smem[((tap * CQ + (c >> 2)) * COUT + co) * 4 + (c & 3)] = wg[e];
-    }
-  };
-
-  dma_halo(0, g, n, ty, tx);
-  load_weights(g);
-  int g_w = g;
-  f32x4 bias_r[TI];
-#pragma unroll
-  for (int i = 0; i < TI; ++i) bias_r[i] = *reinterpret_cast<const f32x4*>(p.bias + (long long)g * p.gs_b + i * 16 + 4 * q);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  // lane r = output column of row `strip`; this wave sums channels [khalf*CIN/2, (khalf+1)*CIN/2)
-  const int cq_lane = khalf * KBW * 4 + q;
-  const f32x4* hB = sW + cq_lane * COUT + r;
-  f32x4 wreg[RW ? NIT : 1][TI];
-  auto load_wreg = [&]() {
-    if constexpr (RW) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int tap = it / KBW, kb = it - tap * KBW;
-#pragma unroll
-        for (int i = 0; i < TI; ++i) wreg[it][i] = hB[(tap * CQ + kb * 4) * COUT + i * 16];
-      }
-    }
-  };
-  load_wreg();
-  int buf = 0;
-  for (;;) {
-    const bool more = tile + 1 < tend;
-    int g2 = g, n2 = n, ty2 = ty, tx2 = tx;
-    if (more) {
-      advance(g2, n2, ty2, tx2);
-      dma_halo(buf ^ 1, g2, n2, ty2, tx2);     // lands in the other buffer while this tile computes
-    }
-    const bool reload_w = more && g2 != g_w;
-    f32x4 acc[TI];
-#pragma unroll
-    for (int i = 0; i < TI; ++i) acc[i] = zero4;
-    const f32x4* hA = sH + buf * HALO_F4 + (2 * strip) * ROW;
-    f32x4 a_cur, b_cur[TI], a_nxt, b_nxt[TI];
-    auto frag = [&](int it, f32x4& a, f32x4 (&b)[TI]) {
-      const int tap = it / KBW, kb = it - tap * KBW;
-      const int ky = tap / 3, kx = tap - ky * 3;
-      const int pair = r + (kx >> 1);
-      a = hA[ky * ROW + pair * 16 + (((((kx & 1) << 3) | (cq_lane + 4 * kb))) ^ (pair & 15))];
-      if constexpr (!RW) {
-#pragma unroll
-        for (int i = 0; i < TI; ++i) b[i] = hB[(tap * CQ + kb * 4) * COUT + i * 16];
-      }
-    };
-    frag(0, a_cur, b_cur);
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      if (it + 1 < NIT) frag(it + 1, a_nxt, b_nxt);
-      __builtin_amdgcn_sched_barrier(0);   // keep the prefetch reads ABOVE this group's MFMAs
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-          acc[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(RW ? wreg[RW ? it : 0][i][s] : b_cur[i][s], a_cur[s], acc[i], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-      a_cur = a_nxt;
-      if constexpr (!RW) {
-#pragma unroll
-        for (int i = 0; i < TI; ++i) b_cur[i] = b_nxt[i];
-      }
-    }
-    f32x4* red = sR + (int)(tile & 1) * RED_F4;
-    if (khalf == 1) {
-#pragma unroll
-      for (int i = 0; i < TI; ++i) red[(strip * TI + i) * 64 + lane] = acc[i];
-    }
-    dma_barrier();   // partial sums visible; next halo landed; everyone is done with buf and sW
-    if (khalf == 0) {
-      // epilogue: pixel (oy, ox) = (ty*4 + strip, tx*16 + r); channels 16 i + 4 q .. +3
-      const int oy = ty * TH + strip, ox = tx * TW + r;
-      const bool ok = oy < p.Ho && ox < p.Wo;
-      float* yo = p.y + (long long)g * p.gs_y + (((long long)n * p.Ho + oy) * p.Wo + ox) * COUT;
-#pragma unroll
-      for (int i = 0; i < TI; ++i) {
-        f32x4 v = acc[i] + red[(strip * TI + i) * 64 + lane] + bias_r[i];
-        if (p.relu) {
-          v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
-        }
-        if (ok) *reinterpret_cast<f32x4*>(yo + i * 16 + 4 * q) = v;
-      }
-    }
-    if (!more) break;
-    if (reload_w) {             // the range crosses into the next encoder: refresh the resident weights
-      load_weights(g2);
-      g_w = g2;
-#pragma unroll
-      for (int i = 0; i < TI; ++i)
-        bias_r[i] = *reinterpret_cast<const f32x4*>(p.bias + (long long)g2 * p.gs_b + i * 16 + 4 * q);
-      __syncthreads();
-      load_wreg();
-    }
-    g = g2; n = n2; ty = ty2; tx = tx2;
-    buf ^= 1;
-    ++tile;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------
-// Warp-specialised conv2 forward (the default): 8 compute waves (4 output rows x 2 K halves, kernel fragments
+// Warp-specialised conv2 forward: 8 compute waves (4 output rows x 2 K halves, kernel fragments
 // in registers, loaded straight from the HWIO kernel) + LW loader waves that do nothing but issue the LDS-DMA of
 // the halos TWO tiles ahead into a ring of three buffers; the output strip is transposed through LDS so that
 // every store instruction writes 1 KiB of consecutive bytes.
-// Why (in-kernel timelines, scripts/dev/halo_stamps.py): in the variant above an LDS-DMA instruction holds the
-// issuing wave for ~300-600 cycles, ~3k cycles per tile on the compute waves that issue the 39 pieces; they reach
+// Why (in-kernel timelines, scripts/dev/halo_stamps.py): in the earlier form without loader waves (deleted, DESIGN.md
+// §5.8) an LDS-DMA instruction holds the issuing wave for ~300-600 cycles, ~3k cycles per tile on the compute waves
+// that issue the 39 pieces; they reach
 // the tile barrier late and their partners idle (tile period 9.6k cycles for 6.9k cycles of MFMA work per SIMD).
 // With loaders the compute waves' MFMA phase is 3.7k cycles (3.5k ideal); what remains is the CU's vector
 // memory pipe: 39 KB in + 12 KB out per tile pass through it at ~5.5 B/clk whoever issues them (the epilogue's
@@ -582,39 +379,9 @@ static int launch_s2_halo_fwd_ws(HaloFwdParams& p, hipStream_t s) {
   return 0;
 }
 
-#ifdef GEECO_DEV_KERNELS      // the pre-warp-specialised conv2 forward (GEECO_HALO_WS=0, GEECO_HALO_RW): development build only
-template <int CIN, int COUT, bool RW>
-static int launch_s2_halo_fwd_v(HaloFwdParams& p, hipStream_t s) {
-  constexpr int CQ = CIN / 4;
-  constexpr int HALO_F4 = ((9 * 17 * 16 + 63) / 64) * 64;
-  const size_t lds = (size_t)(9 * CQ * COUT + 2 * HALO_F4 + 2 * 4 * (COUT / 16) * 64) * 16;
-  static std::atomic<bool> attr_set{false};   // idempotent attribute call: racing threads at worst repeat it
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_s2_halo_fwd_kernel<CIN, COUT, RW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      geeco_set_error("hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
-  long long blocks = p.ntiles < 256 ? p.ntiles : 256;
-  geeco_note_kernel("conv_s2_halo_fwd_kernel<%d, %d, %s>", CIN, COUT, RW ? "true" : "false");
-  hipLaunchKernelGGL((conv_s2_halo_fwd_kernel<CIN, COUT, RW>), dim3((unsigned)blocks), dim3(512), lds, s, p);
-  GEECO_LAUNCH_CHECK();
-  return 0;
-}
-#endif
-
 template <int CIN, int COUT>
 static int launch_s2_halo_fwd(HaloFwdParams& p, hipStream_t s) {
-#ifdef GEECO_DEV_KERNELS
-  static const int rw = geeco_dev_getenv("GEECO_HALO_RW") ? atoi(geeco_dev_getenv("GEECO_HALO_RW")) : 1;   // measured +2.4..3.6 % on the launch
-  // loader waves (0 = the kernels above): 4 measured +3.5 % on the launch, 2 are too few (-5 %)
-  static const int ws = geeco_dev_getenv("GEECO_HALO_WS") ? atoi(geeco_dev_getenv("GEECO_HALO_WS")) : 4;
-  if (ws == 2) return launch_s2_halo_fwd_ws<CIN, COUT, 2>(p, s);
-  if (ws != 4) return rw ? launch_s2_halo_fwd_v<CIN, COUT, true>(p, s) : launch_s2_halo_fwd_v<CIN, COUT, false>(p, s);
-#endif
+  // 4 loader waves measured +3.5 % on the launch against none, 2 are too few (-5 %)
   return launch_s2_halo_fwd_ws<CIN, COUT, 4>(p, s);      // 8 compute waves + 4 loader waves
 }
 
@@ -845,10 +612,8 @@ static int launch_s2_halo_fwd_chunked(HaloFwdParams& p, hipStream_t s) {
 // does the dispatcher below take this shape?  (geeco_conv3x3_fwd_state asks: a layer these kernels serve must not go through
 // the gather GEMM there while every other path runs it through them)
 int geeco_halo_fwd_handles(int H, int W, int Cin, int Cout, int stride) {
-  static const int disabled = geeco_dev_getenv("GEECO_NO_HALO") ? 1 : 0;
-  static const int no_chunked = geeco_dev_getenv("GEECO_NO_HALO3") ? 1 : 0;
-  if (disabled || stride != 2 || (H % 2) || (W % 2)) return 0;
-  return (Cin == 32 && Cout == 48) || (Cin == 48 && Cout == 64 && !no_chunked);
+  if (stride != 2 || (H % 2) || (W % 2)) return 0;
+  return (Cin == 32 && Cout == 48) || (Cin == 48 && Cout == 64);
 }
 
 // Returns 1 if handled, 0 if the shape is not covered (caller falls back to the gather-GEMM),
@@ -1161,7 +926,6 @@ struct BottomSlices {
 // bench shape, fused bottom: 85 x 49 tiles with the last two blocks short or empty and the 256th CU idle becomes
 // 85 x 48 + 1 x (3 x 16); conv2's filter gradient 97 -> 96 tiles per block.  Otherwise ceil(T / S0) tiles per block.
 static BottomSlices bottom_slices(int groups, long long T, bool for_ws = false) {
-  static const int no_rem = geeco_dev_getenv("GEECO_NO_REMAINDER_BLOCK") ? 1 : 0;
   const int cus = 256 - (for_ws ? 0 : geeco_call_reserved_cus());
   BottomSlices b;
   b.S0 = cus / groups < 1 ? 1 : cus / groups;
@@ -1170,7 +934,7 @@ static BottomSlices bottom_slices(int groups, long long T, bool for_ws = false) 
     b.per = 0; b.S = b.S0 + 1; b.blocks = b.S0 * groups + 1;
     return b;
   }
-  if (!no_rem && rem > 0 && fl >= 1 && cus - b.S0 * groups >= 1 && rem * groups <= fl) {
+  if (rem > 0 && fl >= 1 && cus - b.S0 * groups >= 1 && rem * groups <= fl) {
     b.per = (int)fl; b.S = b.S0 + 1; b.blocks = b.S0 * groups + 1;
   } else {
     b.per = (int)((T + b.S0 - 1) / b.S0); b.S = b.S0; b.blocks = b.S0 * groups;
@@ -1188,8 +952,6 @@ int geeco_try_halo_wgrad(const float* x, const float* dz, float* dw, float* db, 
                          int64_t gs_dz, int64_t gs_dw, int64_t gs_db, int N, int H, int W, int Cin, int Cout,
                          int stride, void* ws, hipStream_t stream, int* handled) {
   *handled = 0;
-  static const int disabled = geeco_dev_getenv("GEECO_NO_HALO") ? 1 : 0;
-  if (disabled) return 0;
   if (stride == 2 && Cin == 32 && Cout == 48 && (H % 2 == 0) && (W % 2 == 0)) {
     HaloWgradParams p = {};
     p.x = x; p.dz = dz; p.part = (float*)ws; p.gs_x = gs_x; p.gs_dz = gs_dz;
@@ -2263,20 +2025,16 @@ extern "C" int geeco_conv2_dgrad_conv1_wgrad_bits(const float* dz2, const float*
 
 // does the dispatcher below take this shape (given the HWIO kernel)?  Such layers never read the transposed copy.
 int geeco_halo_dgrad_handles(int H, int W, int Cin, int Cout, int stride) {
-  static const int disabled = geeco_dev_getenv("GEECO_NO_HALO") ? 1 : 0;
-  static const int no_chunked = geeco_dev_getenv("GEECO_NO_HALO3") ? 1 : 0;
-  if (disabled || stride != 2 || (H % 2) || (W % 2)) return 0;
-  return (!no_chunked && Cin == 48 && Cout == 64) || (Cin == 32 && Cout == 48);
+  if (stride != 2 || (H % 2) || (W % 2)) return 0;
+  return (Cin == 48 && Cout == 64) || (Cin == 32 && Cout == 48);
 }
 
 int geeco_try_halo_dgrad(const float* dz, const float* w_hwio, const float* ymask, float* dx, int groups,
                          int64_t gs_dz, int64_t gs_w, int64_t gs_dx, int N, int H, int W, int Cin, int Cout,
                          int stride, hipStream_t stream, int* handled) {
   *handled = 0;
-  static const int disabled = geeco_dev_getenv("GEECO_NO_HALO") ? 1 : 0;
-  if (disabled || !w_hwio) return 0;
-  static const int no_chunked = geeco_dev_getenv("GEECO_NO_HALO3") ? 1 : 0;
-  if (!no_chunked && stride == 2 && Cin == 48 && Cout == 64 && (H % 2 == 0) && (W % 2 == 0)) {
+  if (!w_hwio) return 0;
+  if (stride == 2 && Cin == 48 && Cout == 64 && (H % 2 == 0) && (W % 2 == 0)) {
     HaloDgradParams p = {};
     p.dz = dz; p.w = w_hwio; p.mask = ymask; p.dx = dx;
     p.gs_dz = gs_dz; p.gs_w = gs_w; p.gs_dx = gs_dx;
@@ -2489,8 +2247,7 @@ static int launch_conv1_fwd(const float* x, const float* w, const float* b, floa
                             int relu, hipStream_t stream, int w_cin = 4);
 
 int geeco_conv1_fwd_handles(int Cin, int Cout, int stride) {
-  static const int disabled = geeco_dev_getenv("GEECO_NO_HALO") ? 1 : 0;
-  return !disabled && stride == 1 && Cin == 4 && Cout == 32;
+  return stride == 1 && Cin == 4 && Cout == 32;
 }
 
 int geeco_try_conv1_fwd(const float* x, const float* w, const float* b, float* y, int groups, int64_t gs_x,
@@ -2596,11 +2353,10 @@ static int launch_conv1_fwd(const float* x, const float* w, const float* b, floa
   p.bits = bits; p.gs_bits = gs_bits; p.Wp = (int)geeco_relu_bits_pitch(W); p.Hp = (int)geeco_relu_bits_rows(H);
   p.N = N; p.H = H; p.W = W; p.tiles_x = cdiv(W, 32); p.tiles_y = cdiv(H, 8); p.relu = relu;
   const int ntiles = N * p.tiles_x * p.tiles_y;
-  static const int bpg = geeco_dev_getenv("GEECO_C1_BLOCKS") ? atoi(geeco_dev_getenv("GEECO_C1_BLOCKS")) : 768;   // blocks per encoder (256..2048 within 5 %)
+  constexpr int bpg = 768;   // blocks per encoder (256..2048 within 5 %)
   dim3 grid((unsigned)(ntiles < bpg ? ntiles : bpg), (unsigned)groups);
   geeco_note_kernel("conv1_halo_fwd_kernel");
-  static const int no_pack = geeco_dev_getenv("GEECO_C1_NO_PACK3") ? 1 : 0;
-  if (w_cin == 3 && !no_pack)
+  if (w_cin == 3)
     hipLaunchKernelGGL(conv1_halo_fwd_kernel<true>, grid, dim3(256), 0, stream, p);
   else
     hipLaunchKernelGGL(conv1_halo_fwd_kernel<false>, grid, dim3(256), 0, stream, p);
@@ -2778,8 +2534,7 @@ int geeco_try_conv1_wgrad(const float* x, const float* dz, float* dw, float* db,
                           int64_t gs_dz, int64_t gs_dw, int64_t gs_db, int N, int H, int W, int Cin, int Cout,
                           int stride, void* ws, hipStream_t stream, int* handled) {
   *handled = 0;
-  static const int disabled = geeco_dev_getenv("GEECO_NO_HALO") ? 1 : 0;
-  if (disabled || !(stride == 1 && Cin == 4 && Cout == 32)) return 0;
+  if (!(stride == 1 && Cin == 4 && Cout == 32)) return 0;
   Conv1WgradParams p = {};
   p.x = x; p.dz = dz; p.part = (float*)ws; p.gs_x = gs_x; p.gs_dz = gs_dz;
   p.N = N; p.H = H; p.W = W; p.tiles_x = cdiv(W, 16); p.tiles_y = cdiv(H, 4);

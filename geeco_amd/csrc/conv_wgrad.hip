@@ -224,12 +224,10 @@ void geeco_wgrad_plan(int groups, int N, int H, int W, int Cin, int Cout, int st
   p->stride = stride; p->pt = pt; p->pl = pl;
   p->M = (long long)N * Ho * Wo;
   p->Krows = 9 * Cin;
-  int BC = (Cout % 128 == 0) ? 128 : (Cout % 64 == 0) ? 64 : (Cout % 48 == 0) ? 48 : (Cout % 32 == 0) ? 32 : 16;
-  // 128-row tiles halve the dz traffic per MFMA; use them unless padding 9*Cin up to 128 wastes > 12 %
-  int BR = (BC >= 64 && (long long)cdiv(p->Krows, 128) * 128 * 100 <= (long long)p->Krows * 112) ? 128 : 64;
-  // measured on MI355X: the 128-row / 128-col tiles lose ~1.5 % of the step (occupancy beats traffic here)
-  static const int big_tiles = geeco_dev_getenv("GEECO_WGRAD_BIG") ? 1 : 0;
-  if (!big_tiles) { BR = 64; if (BC == 128) BC = 64; }
+  // 64-row tiles and at most 64 columns: 128-row / 128-column tiles halve the dz traffic per MFMA but measured on MI355X
+  // ~1.5 % of the step slower (occupancy beats traffic here)
+  const int BC = (Cout % 64 == 0) ? 64 : (Cout % 48 == 0) ? 48 : (Cout % 32 == 0) ? 32 : 16;
+  constexpr int BR = 64;
   *bc = BC + 1000 * BR;
   p->row_tiles = cdiv(p->Krows, BR);
   p->col_tiles = cdiv(Cout, BC);
@@ -286,11 +284,6 @@ extern "C" int geeco_conv3x3_wgrad(const float* x, const float* dz, float* dw, f
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)p.S, (unsigned)(p.row_tiles * p.col_tiles), (unsigned)groups);
   switch (BC) {
-#ifdef GEECO_DEV_KERNELS      // GEECO_WGRAD_BIG: 128-row / 128-column tiles (measured ~1.5 % of the step slower)
-    case 128128: geeco_note_kernel("conv_wgrad_kernel<128, 128, 16>"); hipLaunchKernelGGL((conv_wgrad_kernel<128, 128, 16>), grid, dim3(256), 0, s, p); break;
-    case 128064: geeco_note_kernel("conv_wgrad_kernel<128, 64, 16>"); hipLaunchKernelGGL((conv_wgrad_kernel<128, 64, 16>), grid, dim3(256), 0, s, p); break;
-    case 64128: geeco_note_kernel("conv_wgrad_kernel<64, 128, 16>"); hipLaunchKernelGGL((conv_wgrad_kernel<64, 128, 16>), grid, dim3(256), 0, s, p); break;
-#endif
     case 64064: geeco_note_kernel("conv_wgrad_kernel<64, 64, 32>"); hipLaunchKernelGGL((conv_wgrad_kernel<64, 64, 32>), grid, dim3(256), 0, s, p); break;
     case 64048: geeco_note_kernel("conv_wgrad_kernel<64, 48, 32>"); hipLaunchKernelGGL((conv_wgrad_kernel<64, 48, 32>), grid, dim3(256), 0, s, p); break;
     case 64032: geeco_note_kernel("conv_wgrad_kernel<64, 32, 64>"); hipLaunchKernelGGL((conv_wgrad_kernel<64, 32, 64>), grid, dim3(256), 0, s, p); break;

@@ -55,8 +55,8 @@ void geeco_launch_wgrad_reduce(const float* part, float* dw, float* db, long lon
 // Wide co blocks (COT = 3, 4) halve the number of blocks that fetch the same x halo: a 64-channel co block needs
 // 47 KB of DMA per 9.2k cycles of MFMA work per SIMD (conv4: 5.1 B/clk/CU - the ingest limit next to MFMA waves), a
 // 128-channel one 55 KB per 18.4k.
-// NBUF = 2: halo / dz double buffered, one block per CU;  NBUF = 1: single buffers (half the LDS), the host launches
-// TWO blocks per CU (MINW waves per SIMD in total) which fill each other's DMA waits and barrier stalls.
+// NBUF = 2: halo / dz double buffered, one block per CU (the host launches only this form);  NBUF = 1: single buffers
+// (half the LDS) for TWO blocks per CU, measured slower (scripts/dev/SWITCHES.md, GEECO_WGRAD_BPC).
 template <int NCI, int NCO, int COT, int TH, int TW, int XPQ, bool SWZ, int NBUF, int MINW>
 __global__ __launch_bounds__(64 * NCI * NCO, MINW) void conv_s2_wgrad_lds_kernel(const WgradHaloParams p) {
   constexpr int NW = NCI * NCO, NT = 64 * NW;
@@ -292,20 +292,17 @@ struct WgradHaloPlan {
   int variant;       // 0 = not handled; 1 = CIB 48 (conv3 type), TW 16; 4 = CIB 48, TW 8; 2 = CIB 64, TW 16; 3 = CIB 64, TW 8;
                      // 5 = CIB 32 x COB 128, TW 8
   int TH, TW, n_cib, n_cob, S;
-  int bpc;           // blocks per CU: 1 = double-buffered images, 2 = single-buffered
 };
 
 static WgradHaloPlan wgrad_halo_plan(int groups, int N, int H, int W, int Cin, int Cout, int stride) {
   WgradHaloPlan pl = {};
-  static const int disabled = (geeco_dev_getenv("GEECO_NO_HALO") || geeco_dev_getenv("GEECO_NO_WGRAD_LDS")) ? 1 : 0;
-  if (disabled || stride != 2 || (H & 1) || (W & 1) || Cout % 64 != 0) return pl;
+  if (stride != 2 || (H & 1) || (W & 1) || Cout % 64 != 0) return pl;
   const int Ho = H / 2, Wo = W / 2;
   if (Wo < 8 || Ho < 2) return pl;                        // the tiny top layers stay with the gather kernel
   // tile shape: 2 x 16 or 4 x 8 output pixels (same LDS); the squarer one has 7 % less halo ((9 x 17) / (8 x 16) = 1.20
   // input pixels fetched per input pixel used, against (5 x 33) / (4 x 32) = 1.29)
   // (measured, bench shapes: conv3 209.8 -> 203.5 us, conv4 142.3 -> 139.0, conv5 116.5 -> 113.9)
-  static const int sq_env = geeco_dev_getenv("GEECO_WGRAD_SQUARE") ? atoi(geeco_dev_getenv("GEECO_WGRAD_SQUARE")) : 1;
-  const bool wide = Wo >= 16 && !(sq_env && Ho >= 4);
+  const bool wide = Wo >= 16 && Ho < 4;
   if (Cin == 48 && Wo >= 16) {
     pl.variant = wide ? 1 : 4; pl.TH = wide ? 2 : 4; pl.TW = wide ? 16 : 8; pl.n_cib = 1;
   } else if (Cin % 64 == 0) {
@@ -324,24 +321,20 @@ static WgradHaloPlan wgrad_halo_plan(int groups, int N, int H, int W, int Cin, i
   // One block per CU (its LDS images take > 80 KB).  Blocks are dealt round-robin to the 8 XCDs and the n_cob co
   // blocks of a slice sit on one XCD: a launch must not put more than 32 blocks on any XCD, or that XCD runs two
   // rounds while the others idle (measured on conv5: 33 blocks on four XCDs took 200 us instead of 100).
-  static const int bpc_env = geeco_dev_getenv("GEECO_WGRAD_BPC") ? atoi(geeco_dev_getenv("GEECO_WGRAD_BPC")) : 0;
-  pl.bpc = bpc_env == 1 || bpc_env == 2 ? bpc_env : 1;
   // 32 x 128 blocks of dw instead of 64 x 64 (same slab bytes): 35.6 KB of DMA per tile instead of 47 KB for the same
   // MFMA work - the 64 x 64 blocks sit at the CU's ingest limit (5.1 B/clk next to MFMA waves)
-  static const int cob128 = geeco_dev_getenv("GEECO_WGRAD_NO_COB128") ? 0 : 1;
-  if (cob128 && pl.bpc == 1 && pl.variant == 3 && Cout % 128 == 0) {
+  if (pl.variant == 3 && Cout % 128 == 0) {
     pl.variant = 5;
     pl.n_cib = Cin / 32;
     pl.n_cob = Cout / 128;
   }
   // 64 x 96 blocks where 128 does not divide Cout (conv5: 192 = 2 x 96): 256 blocks instead of 240 and 27 MFMAs per 12
   // fragment reads instead of 18 per 11, against 1.5x the slab bytes: 114.4 -> 111.6 us, the step -2.5 us
-  static const int cob96 = geeco_dev_getenv("GEECO_WGRAD_NO_COB96") ? 0 : 1;
-  if (cob96 && pl.bpc == 1 && pl.variant == 3 && Cout % 96 == 0) {
+  if (pl.variant == 3 && Cout % 96 == 0) {
     pl.variant = 6;
     pl.n_cob = Cout / 96;
   }
-  int S = (8 * (32 * pl.bpc / pl.n_cob)) / (groups * pl.n_cib);
+  int S = (8 * (32 / pl.n_cob)) / (groups * pl.n_cib);
   if (S < 1) S = 1;
   if (S > tiles) S = (int)tiles;
   pl.S = S;
@@ -358,7 +351,7 @@ template <int NCI, int NCO, int COT, int TH, int TW, int XPQ, bool SWZ, int NBUF
 static int launch_wgrad_lds(const WgradHaloParams& p, int blocks, hipStream_t stream) {
   constexpr int X_F4 = ((2 * TH + 1) * (2 * TW + 1) * XPQ + 63) / 64 * 64;
   constexpr size_t lds = (size_t)(NBUF * X_F4 + NBUF * TH * TW * 4 * NCO * COT) * 16;
-  static_assert(lds * (3 - NBUF) <= 160 * 1024, "LDS budget (two blocks per CU when single-buffered)");
+  static_assert(lds <= 160 * 1024, "LDS budget");
   static int attr_state = 0;          // 0 = not set; set once (idempotent: racing threads set the same value)
   if (__atomic_load_n(&attr_state, __ATOMIC_ACQUIRE) == 0) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_s2_wgrad_lds_kernel<NCI, NCO, COT, TH, TW, XPQ, SWZ, NBUF, MINW>),
@@ -405,26 +398,13 @@ int geeco_try_wgrad_lds(const float* x, const float* dz, float* dw, float* db, i
   p.n_sigma = groups * pl.n_cib * pl.S;
   const int blocks = 8 * cdiv(p.n_sigma, 8) * pl.n_cob;
   int rc = 0;
-  if (pl.bpc == 1) {
-    switch (pl.variant) {
-      case 1: rc = launch_wgrad_lds<3, 4, 1, 2, 16, 14, false, 2, 3>(p, blocks, stream); break;
-      case 4: rc = launch_wgrad_lds<3, 4, 1, 4, 8, 14, false, 2, 3>(p, blocks, stream); break;
-      case 2: rc = launch_wgrad_lds<4, 2, 2, 2, 16, 16, true, 2, 2>(p, blocks, stream); break;
-      case 5: rc = launch_wgrad_lds<2, 4, 2, 4, 8, 10, false, 2, 2>(p, blocks, stream); break;
-      case 6: rc = launch_wgrad_lds<4, 2, 3, 4, 8, 16, true, 2, 2>(p, blocks, stream); break;
-      default: rc = launch_wgrad_lds<4, 2, 2, 4, 8, 16, true, 2, 2>(p, blocks, stream); break;
-    }
-  } else {
-#ifdef GEECO_DEV_KERNELS      // GEECO_WGRAD_BPC=2: single-buffered images, two blocks per CU
-    switch (pl.variant) {
-      case 1: rc = launch_wgrad_lds<3, 4, 1, 2, 16, 14, false, 1, 6>(p, blocks, stream); break;
-      case 4: rc = launch_wgrad_lds<3, 4, 1, 4, 8, 14, false, 1, 6>(p, blocks, stream); break;
-      case 2: rc = launch_wgrad_lds<4, 2, 2, 2, 16, 16, true, 1, 4>(p, blocks, stream); break;
-      default: rc = launch_wgrad_lds<4, 2, 2, 4, 8, 16, true, 1, 4>(p, blocks, stream); break;
-    }
-#else
-    return 0;                 // (unreachable: the product plan never asks for two blocks per CU)
-#endif
+  switch (pl.variant) {
+    case 1: rc = launch_wgrad_lds<3, 4, 1, 2, 16, 14, false, 2, 3>(p, blocks, stream); break;
+    case 4: rc = launch_wgrad_lds<3, 4, 1, 4, 8, 14, false, 2, 3>(p, blocks, stream); break;
+    case 2: rc = launch_wgrad_lds<4, 2, 2, 2, 16, 16, true, 2, 2>(p, blocks, stream); break;
+    case 5: rc = launch_wgrad_lds<2, 4, 2, 4, 8, 10, false, 2, 2>(p, blocks, stream); break;
+    case 6: rc = launch_wgrad_lds<4, 2, 3, 4, 8, 16, true, 2, 2>(p, blocks, stream); break;
+    default: rc = launch_wgrad_lds<4, 2, 2, 4, 8, 16, true, 2, 2>(p, blocks, stream); break;
   }
   if (rc) return rc;
   GEECO_LAUNCH_CHECK();

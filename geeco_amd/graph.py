@@ -15,11 +15,10 @@ launch over all groups; RGB inputs are channel-padded to 4 so conv1 gathers floa
 from __future__ import annotations
 
 import collections
-import os
 
 import torch
 
-from . import _dev, _native, ops
+from . import _native, ops
 from .variables import ENC_FILTERS, ENC_STRIDES, VariableStore, decoder_shapes, encoder_shapes
 
 _CELLS = 4   # the reference hard-codes the 2x2 tiling of the joint state (graph.py:139,163,188)
@@ -77,25 +76,19 @@ class ConvEncoderStack:
     self.dim_outs = [int(d) for d in dim_out] if isinstance(dim_out, (list, tuple)) else [int(dim_out)] * len(self.scopes)
     self.split_top = len(set(self.dim_outs)) > 1
     dim_out = max(self.dim_outs)
-    # Backward schedule: ONE stream by default.  Round 1 ran the filter-gradient launches of the upper layers on two side
-    # streams beside the input-gradient chain (+1-2 % then: the gather wgrad kernel left MFMA slack for its neighbour);
-    # with the LDS-staged wgrad kernels every big launch fills the chip by itself and the two schedules measure the same
-    # (3.717 vs 3.719 ms), so the simpler one is the default.  GEECO_MULTI_STREAM=1 restores the side streams.
-    self.two_streams = _dev.env('GEECO_MULTI_STREAM') is not None
-    # conv7's + conv8's filter gradients in one launch (GEECO_NO_WGRAD_PAIR: two)
-    self.pair_top = _dev.env('GEECO_NO_WGRAD_PAIR') is None
-    # ... and conv7's input gradient in the same grid (GEECO_NO_TOP_BWD: its own launch)
-    # (GEECO_TOP_BWD=2: two heterogeneous launches instead, conv8's pair then conv7's)
-    self.hetero_top = 0 if _dev.env('GEECO_NO_TOP_BWD') is not None else int(_dev.env('GEECO_TOP_BWD', '1'))
-    self.w8_done = False
-    # the filter-gradient kernels' slab sums of a backward part go into one launch (GEECO_NO_BATCH_REDUCE: one per layer)
-    self.batch_reduce = _dev.env('GEECO_NO_BATCH_REDUCE') is None
+    # Backward schedule: ONE stream.  Round 1 ran the filter-gradient launches of the upper layers on two side streams
+    # beside the input-gradient chain (+1-2 % then: the gather wgrad kernel left MFMA slack for its neighbour); with the
+    # LDS-staged wgrad kernels every big launch fills the chip by itself and the two schedules measured the same (3.717 vs
+    # 3.719 ms), so the side streams were retired (scripts/dev/SWITCHES.md).
+    # conv7's + conv8's filter gradients and conv7's input gradient go into one grid (launch_top_bwd); bench.py reads
+    # these two to label that row of its per-layer table
+    self.pair_top = True
+    self.hetero_top = 1
     self.derived_version = -1
     # Only the FIRST training stack built on a store may rely on the post-Adam refresh of its derived
     # weight copies; eval / predict stacks and any later training stack (e.g. the model built for a
     # ragged final batch) share the parameters but not the copies, so they re-derive on every forward.
-    self.lazy_refresh = (training and getattr(store, 'primary_stack', None) is None and
-                         _dev.env('GEECO_EAGER_DERIVED') is None)
+    self.lazy_refresh = training and getattr(store, 'primary_stack', None) is None
     if self.lazy_refresh:
       store.primary_stack = self
     self.Cpad = -(-Cin // 4) * 4
@@ -138,31 +131,28 @@ class ConvEncoderStack:
     if training:
       # encoder bottom fused backward (conv2 dgrad + conv1 wgrad): the reference encoder's shapes, even sizes
       L0, L1 = self.layers[0], self.layers[1]
-      self.fused_bottom = (_dev.env('GEECO_NO_FUSED_BOTTOM') is None and _dev.env('GEECO_NO_HALO') is None
-                           and self.Cpad == 4 and self.Cin in (3, 4) and L0['Cout'] == 32 and L0['stride'] == 1
+      self.fused_bottom = (self.Cpad == 4 and self.Cin in (3, 4) and L0['Cout'] == 32 and L0['stride'] == 1
                            and L1['Cout'] == 48 and L1['stride'] == 2 and L1['H'] % 2 == 0 and L1['W'] % 2 == 0)
       # the fused bottom only needs the SIGN of conv1's output (ReluGrad): conv1's forward writes one bit word per pixel
-      # next to y1 and the backward reads those 25 MB instead of the 805 MB of y1 (GEECO_NO_RELU_BITS: read y1)
-      self.relu_bits = self.fused_bottom and _dev.env('GEECO_NO_RELU_BITS') is None
+      # next to y1 and the backward reads those 25 MB instead of the 805 MB of y1
+      self.relu_bits = self.fused_bottom
       # with the fused bottom and the sign bits nothing reads the channel-padded copy of conv1's kernel any more: conv1's
       # forward takes the RGB variable itself (together with the gather GEMM reading HWIO kernels this leaves NO weight
       # copy to re-derive after Adam: one launch less per step)
-      if self.relu_bits and self.Cin == 3 and _dev.env('GEECO_PAD1_COPY') is None:
+      if self.relu_bits and self.Cin == 3:
         self.pad1_copy = False
       if self.relu_bits:
         self.bits1 = torch.zeros(G, Nf, ops.relu_bits_rows(L0['H']), ops.relu_bits_pitch(L0['W']), dtype=torch.int32, device=dev)
       # the same one layer up: conv2's forward leaves 16-bit sign fields of y2 for conv3's input-gradient kernel
       L2 = self.layers[2]
-      self.relu_fields = (_dev.env('GEECO_NO_RELU_BITS') is None and _dev.env('GEECO_NO_HALO') is None
-                          and _dev.env('GEECO_NO_HALO3') is None and _dev.env('GEECO_HALO_WS') is None
-                          and (L1['Cin'], L1['Cout'], L1['stride']) == (32, 48, 2)
+      self.relu_fields = ((L1['Cin'], L1['Cout'], L1['stride']) == (32, 48, 2)
                           and (L2['Cin'], L2['Cout'], L2['stride']) == (48, 64, 2)
                           and L1['H'] % 2 == 0 and L1['W'] % 2 == 0 and L2['H'] % 2 == 0 and L2['W'] % 2 == 0)
       if self.relu_fields:
         self.fields2 = torch.zeros(G, ops.relu_fields_elems(Nf, L2['H'], L2['W']), dtype=torch.int16, device=dev)
       # ... and conv3's forward leaves byte sign fields of y3 for conv4's LDS-staged input-gradient kernel
       L3 = self.layers[3]
-      self.relu_fields3 = (self.relu_fields and _dev.env('GEECO_NO_DGRAD_LDS') is None and _dev.env('GEECO_NO_FIELDS3') is None and L3['Cin'] == 64
+      self.relu_fields3 = (self.relu_fields and L3['Cin'] == 64
                            and L3['stride'] == 2 and ops.conv3x3_dgrad_relu_fields_supported(L3['H'], L3['W'], L3['Cin'], L3['Cout'], 2))
       if self.relu_fields3:
         self.fields3 = torch.zeros(G, Nf, L3['H'], L3['W'], L3['Cin'] // 8, dtype=torch.uint8, device=dev)
@@ -182,22 +172,20 @@ class ConvEncoderStack:
         self.wt[7] = [torch.empty(3, 3, d, L7['Cin'], **f32) if nw else None for d, nw in zip(self.dim_outs, self.needs_wt7)]
       if self.pad1:
         self.dw1p = torch.zeros(G, 3, 3, self.Cpad, self.layers[0]['Cout'], **f32)
-      # wgrads of different layers may run concurrently (different streams): one split-K workspace each
-      nside = int(_dev.env('GEECO_WGRAD_STREAMS', '2'))   # measured: 1 -> 2 streams +1.1 %, 3 slower
-      self.wgrad1_on_main = _dev.env('GEECO_WGRAD1_SIDE') is None
-      # the LDS-halo wgrad kernels of conv1 / conv2 want whole CUs: beside the dgrad chain they only slow it
-      # down (measured: layers below 2 serial +0.8 %, below 3 +0.1 %, below 4 -0.5 %)
-      self.serial_below = int(_dev.env('GEECO_SERIAL_BELOW', '2'))
+      # one split-K workspace per layer: the slab sums that _ModelBase.backward_and_apply runs beside the fused bottom
+      # read conv3..conv8's workspaces while conv2's filter gradient writes its own
       self.ws_l = [torch.empty(ops.conv3x3_wgrad_ws_bytes(G, Nf, L['H'], L['W'], L['Cin'], L['Cout'], L['stride']) // 4 + 4,
                                **f32) for L in self.layers]
       self.ws = self.ws_l[0]
       dsb = max(ops.conv3x3_dgrad_ws_bytes(G, Nf, L['H'], L['W'], L['Cin'], L['Cout'], L['stride'])
                 for L in self.layers[1:])
       self.dws = torch.empty(dsb // 4 + 4, **f32)
-      # wgrad(l) and dgrad(l) only share their input dz[l]: the dgrad chain stays on the main stream and
-      # the wgrads alternate between side streams (branches of the captured hipGraph), so the small top
-      # layers overlap instead of leaving CUs idle in their tails
-      self.sides = [torch.cuda.Stream(device=dev) for _ in range(nside)] if dev.type == 'cuda' else []
+      # Two streams, created here as when they carried the filter gradients of a multi-stream backward.  The optimiser's early
+      # piece runs on the first beside the backward's bottom (_ModelBase.backward_and_apply); the second carries no work.  It
+      # stays because the streams a process creates later (RCCL's, the data-parallel runner's) land on other hardware queues
+      # without it: with one stream here 8 of the 11 forms of bench.py's dp_one_rank measured 3-12 us per step slower, beyond the
+      # spread of four runs (profiles/one_path/README.md)
+      self.sides = [torch.cuda.Stream(device=dev) for _ in range(2)] if dev.type == 'cuda' else []
       if self.fused_bottom:
         self.fws_fused = torch.empty(ops.conv2_dgrad_conv1_wgrad_ws_bytes(G) // 4 + 4, **f32)
     fsb = max(ops.conv3x3_fwd_ws_bytes(G, Nf, L['H'], L['W'], L['Cin'], L['Cout'], L['stride']) for L in self.layers)
@@ -278,8 +266,6 @@ class ConvEncoderStack:
     self.derived_version = self.store.version
 
   # -- single launches (also timed one by one by bench.py's per-layer table) ---------------------------
-  # the state concat of a one-step decoder inside conv8's split-K epilogue (GEECO_NO_CONCAT_IN_TOP: its own launch)
-  concat_in_top = _dev.env('GEECO_NO_CONCAT_IN_TOP') is None
 
   def launch_fwd(self, l):
     G, Nf, L = self.G, self.Nf, self.layers[l]
@@ -352,7 +338,7 @@ class ConvEncoderStack:
 
   def launch_top_bwd(self, l, wgrads, pending=None):
     """Layer l's input gradient AND the filter gradients of layers ``wgrads`` as one heterogeneous launch (independent work
-    that needs only dz[l]): l = 6 with (6, 7), or l = 7 with (7,) followed by l = 6 with (6,)."""
+    that needs only dz[l]): l = 6 with (6, 7)."""
     L = self.layers[l]
     wt = self.wt[l]
     d = dict(dx=self.dz[l - 1], dz=self.dz[l], wt=wt, ymask=self.acts[l - 1], w=self._w(l), gs_dz=self.dz[l][0].numel(),
@@ -374,17 +360,12 @@ class ConvEncoderStack:
     x = self.acts[l - 1]
     dz = self.dz[l]
     if l == 1 and self.fused_bottom:
-      # the kernel writes conv1's gradient in the variable's own [3][3][Cin][32] layout (no padded copy to repack)
-      if self.relu_bits:
-        ops.conv2_dgrad_conv1_wgrad_bits_into(self._dw(0), self._db(0), dz, self._w(1), self.bits1, self.x_in, G,
-                                              dz[0].numel(), self.gs_p, self.bits1[0].numel(), self.x_in[0].numel(),
-                                              self._gs_g(0), self._gs_g(0), Nf, L['H'], L['W'], self.fws_fused,
-                                              real_channels=self.Cin, pending=pending, reserved_cus=self.reserved_cus)
-        return
-      ops.conv2_dgrad_conv1_wgrad_into(self._dw(0), self._db(0), dz, self._w(1), x, self.x_in, G, dz[0].numel(), self.gs_p,
-                                       x[0].numel(), self.x_in[0].numel(), self._gs_g(0), self._gs_g(0), Nf, L['H'], L['W'],
-                                       self.fws_fused, real_channels=self.Cin, pending=pending,
-                                       reserved_cus=self.reserved_cus if pending is not None else 0)
+      # the kernel writes conv1's gradient in the variable's own [3][3][Cin][32] layout (no padded copy to repack) and reads
+      # the sign bits of conv1's output (relu_bits) for its ReluGrad
+      ops.conv2_dgrad_conv1_wgrad_bits_into(self._dw(0), self._db(0), dz, self._w(1), self.bits1, self.x_in, G,
+                                            dz[0].numel(), self.gs_p, self.bits1[0].numel(), self.x_in[0].numel(),
+                                            self._gs_g(0), self._gs_g(0), Nf, L['H'], L['W'], self.fws_fused,
+                                            real_channels=self.Cin, pending=pending, reserved_cus=self.reserved_cus)
       return
     wt = self.wt[l]
     dx = self.dz[l - 1]
@@ -408,7 +389,8 @@ class ConvEncoderStack:
     top = len(self.layers) - 1
     for l in range(top):
       self.launch_fwd(l)
-    if state is not None and self.concat_in_top and not self.split_top:
+    # the state concat of a one-step decoder rides in conv8's split-K epilogue
+    if state is not None and not self.split_top:
       G, Nf, L = self.G, self.Nf, self.layers[top]
       x, y = self.acts[top - 1], self.acts[top]
       if ops.conv3x3_fwd_state_into(y, x, self._w(top), self._b(top), G, x[0].numel(), self.gs_p, self.gs_p, y[0].numel(), Nf,
@@ -427,42 +409,25 @@ class ConvEncoderStack:
     ``before_bottom``: called right before the LAST launch of the chain, conv2's input gradient (+ conv1's filter gradient when
     the bottom is fused) -- _ModelBase.backward_and_apply releases the optimiser's early piece onto a second stream there."""
     assert defer_sums is None or prepare is None
-    main = torch.cuda.current_stream()
-    sides = self.sides if self.two_streams else []
-    pending = [] if self.batch_reduce else None   # slab sums of all layers of this part: one launch at the end
-    # conv8's filter gradient waits for conv7's: one launch for both (independent work batched into one grid)
-    pair_top = (hi == 7 and lo <= 6 and not self.split_top and not sides and self.pair_top
+    pending = []   # slab sums of all layers of this part: one launch at the end
+    # conv7's input gradient and conv7's / conv8's filter gradients need only conv8's input gradient: one grid for the three
+    pair_top = (hi == 7 and lo <= 6 and not self.split_top
                 and self.layers[6]['stride'] == self.layers[7]['stride'] == 2)
     if lead_dgrad is not None:
       self.launch_dgrad(lead_dgrad, pending)
     for l in range(hi, lo - 1, -1):
       if pair_top and l == 7:
-        self.w8_done = self.hetero_top == 2 and self.launch_top_bwd(7, (7,), pending)
-        if not self.w8_done:
-          self.launch_dgrad(7, pending)
-        continue
-      if pair_top and l == 6 and self.w8_done:
-        if not self.launch_top_bwd(6, (6,), pending):
-          self.launch_wgrad(6, pending)
-          self.launch_dgrad(6, pending)
+        self.launch_dgrad(7, pending)
         continue
       if pair_top and l == 6:
-        if self.hetero_top and self.launch_top_bwd(6, (6, 7), pending):
+        if self.launch_top_bwd(6, (6, 7), pending):
           continue
         if not self.launch_wgrad_top_pair(pending):
           self.launch_wgrad(7, pending)
           self.launch_wgrad(6, pending)
         self.launch_dgrad(6, pending)
         continue
-      # wgrad(l) of the upper layers is off the critical path (the dgrad chain on `main`): it goes to a side
-      # stream; the bottom layers' (LDS-halo kernels, one or two blocks per CU) stay on `main`
-      side = None
-      if sides and not (l == 0 and self.wgrad1_on_main) and l >= self.serial_below:
-        side = sides[l % len(sides)]
-      if side is not None:
-        side.wait_stream(main)          # dz[l] is ready
-      with torch.cuda.stream(side if side is not None else main):
-        self.launch_wgrad(l, pending)
+      self.launch_wgrad(l, pending)
       if l == 0 or (l == lo and defer_dgrad):
         break   # conv1's input is data: no dgrad / the next part opens with this layer's
       if l == 1 and before_bottom is not None:
@@ -470,19 +435,15 @@ class ConvEncoderStack:
       self.launch_dgrad(l, pending)
       if l == 1 and self.fused_bottom:
         break
-    for side in sides:
-      main.wait_stream(side)
-    if defer_sums is not None and pending is not None:
+    if defer_sums is not None:
       defer_sums.extend(pending)
       return
-    if pending or (prepare is not None and pending is not None):
+    if pending or prepare is not None:
       ops.slab_reduce_batch(pending, prepare)
-    elif prepare is not None:
-      ops.adam_prepare(*prepare)
 
   SPLIT = 2   # backward(part='upper') = layers 7..SPLIT, 'bottom' = SPLIT-1..0
-  # ... except layer SPLIT's INPUT gradient, which opens the bottom part (GEECO_DP_DGRAD_IN_UPPER: round 4's cut)
-  DEFER_SPLIT_DGRAD = _dev.env('GEECO_DP_DGRAD_IN_UPPER') is None
+  # ... except layer SPLIT's INPUT gradient, which opens the bottom part (round 4 cut after it)
+  DEFER_SPLIT_DGRAD = True
 
 
 # ================================================================================================
@@ -532,12 +493,6 @@ class LSTMDecoder:
     self.gemm_ws = torch.empty(max(ops.gemm_ws_bytes(*s) for s in gemm_shapes) // 4 + 4, **f32)
     self.targets, self.target_strides = None, None     # bound by the model
     self.loss_scale = 1.0
-    # one-step decoders: weight / bias / input gradients (+ the state-concat backward) as TWO launches instead of five
-    # dependent ones (GEECO_DEV=1 GEECO_NO_LSTM_BATCH: the separate launches)
-    self.one_launch_bwd = _dev.env('GEECO_NO_LSTM_BATCH') is None
-    self.one_launch_fwd = _dev.env('GEECO_NO_LSTM_FWD_FUSE') is None   # ... and the forward's slab sum inside the gate kernel
-    # round 5: gate math + fc1 + heads + losses (+ their backward down to the gate gradients) per sample in ONE launch
-    self.fused_step = _dev.env('GEECO_NO_STEP_HEADS') is None
     self.heads_pending, self.dz_from_heads = None, False
 
   def _v(self, n):
@@ -557,9 +512,9 @@ class LSTMDecoder:
       hkw = dict(d_fc1_w=self._g('fc1/kernel'), d_fc1_b=self._g('fc1/bias'),
                  d_heads_w=[self._g(n + '/kernel') for n in names], d_heads_b=[self._g(n + '/bias') for n in names])
     self.heads_pending = None
-    if T == 1 and self.one_launch_fwd and self.one_launch_bwd and self.fused_step:
-      # one step from a zero state: gate GEMM + ONE per-sample launch for the slab sum, the gate math, fc1, the heads, the loss
-      # terms and (training) everything back to the gate gradients dz; the batch sums (weight / bias gradients, loss means)
+    if T == 1:
+      # one step from a zero state (round 5): gate GEMM + ONE per-sample launch for the slab sum, the gate math, fc1, the heads,
+      # the loss terms and (training) everything back to the gate gradients dz; the batch sums (weight / bias gradients, loss means)
       # ride in the first grid of backward()'s launch pair -- losses / those gradients are final after backward()
       pend = _native.HeadsFinish() if backward_too else None
       if ops.lstm_step_heads_into(self.z[0], self.c[0], self.h[0], self.gates[0], self.states[0], Wx, bias, N, H, D, D, 4 * H,
@@ -572,8 +527,8 @@ class LSTMDecoder:
         self.dz_from_heads = backward_too
         return
     self.dz_from_heads = False
-    if T == 1 and self.one_launch_fwd:
-      # one step from a zero state: the slab sum of the gate GEMM rides in the gate kernel (bitwise the same)
+    if T == 1:
+      # (shapes outside the fused step) the slab sum of the gate GEMM rides in the gate kernel (bitwise the same)
       ops.lstm_input_step_fwd_into(self.z[0], self.c[0], self.h[0], self.gates[0], self.states[0], Wx, bias, N, H, D, D, 4 * H,
                                    self.gemm_ws)
       T = 0
@@ -600,8 +555,9 @@ class LSTMDecoder:
     W = self._v('lstm_cell/kernel')
     Wx, Wh = W[:D], W[D:]
     dW = self._g('lstm_cell/kernel')
-    if T == 1 and self.one_launch_bwd:
-      # one step from a zero state: dWh = h_prev^T dz = 0 (the arena's rows stay zero); everything else in ONE launch
+    if T == 1:
+      # one step from a zero state: dWh = h_prev^T dz = 0 (the arena's rows stay zero); weight / bias / input gradients (+ the
+      # state-concat backward) in ONE launch instead of five dependent ones
       if not self.dz_from_heads:       # (the fused forward left dz itself)
         ops.lstm_gates_bwd_into(self.dz[0], None, self.gates[0], None, self.c[0], self.dh, None, N, H)
       kw = dict(feats_fwd=concat['feats'], dfeats=concat['dfeats'], feat_ch=concat['feat_ch'], jnt_pos=concat['jnt_pos'],
@@ -671,9 +627,8 @@ class _ModelBase:
     # RGB-D: rgb || depth (estimator.py:36,169,172).  The dynimg branch of the goal model forms the concat inside its
     # input kernels (no packed copy of all N * K frames: 1.07 GB read + 1.43 GB written per step at K = 32); the other
     # graphs pack once per step.
-    self.last_from_dynimg = _dev.env('GEECO_PACK_CURRENT') is None   # current frame's padded copy out of the buffer-image kernel
-    self.split_rgbd = (self.C == 4 and goal and cfg.proc_obs == 'dynimg' and (H * W) % 4 == 0 and
-                       _dev.env('GEECO_PACK_RGBD') is None)
+    self.last_from_dynimg = True   # current frame's padded copy out of the buffer-image kernel (bench.py reads it)
+    self.split_rgbd = self.C == 4 and goal and cfg.proc_obs == 'dynimg' and (H * W) % 4 == 0
     if self.C == 4 and not self.split_rgbd:
       self.obs4 = torch.empty(N, K, H, W, 4, **f32)
       if goal:
@@ -766,12 +721,12 @@ class _ModelBase:
     self._refresh_after_update()
 
   def can_apply_beside_bottom(self):
-    """backward_and_apply needs the slab sums batched per part (the default) and a CUDA device."""
-    return bool(self.enc.training and self.enc.batch_reduce and not self.enc.two_streams and self.store.params.is_cuda)
+    """backward_and_apply needs a training encoder on a CUDA device."""
+    return bool(self.enc.training and self.store.params.is_cuda)
 
   def optimizer_stream(self):
-    """The second stream of backward_and_apply: one of the encoder's filter-gradient side streams, idle from conv2's filter gradient
-    on (a process gets 4 hardware queues by default; a stream more would share one with another stream -- RCCL's, perhaps)."""
+    """The second stream of backward_and_apply: the first of the training encoder's two streams (a process gets 4 hardware queues
+    by default; a stream more would share one with another stream -- RCCL's, perhaps)."""
     side = getattr(self, '_opt_stream', None)
     if side is None:
       sides = getattr(self.enc, 'sides', None)
@@ -797,13 +752,9 @@ class _ModelBase:
     slots and gradients (tests/test_model_gpu.py)."""
     side = self.optimizer_stream()
     main = torch.cuda.current_stream()
-    what = _dev.env('GEECO_BESIDE', 'both')      # development A/B: which of the two pieces goes beside the bottom
     sums = []
     self.backward(part='upper', defer_sums=sums)
     prepare = self._prepare_args(True)
-    if what == 'adam':
-      ops.slab_reduce_batch(sums, prepare)
-      prepare = None
     g = self.store.grads
     ev = torch.cuda.Event()
     marked = []
@@ -823,13 +774,9 @@ class _ModelBase:
     # the bottom's block cannot become resident on a CU until they have drained, and the bottom ends 35-45 us late (measured).
     side.wait_event(ev)
     with torch.cuda.stream(side):
-      if sums or prepare is not None:
-        ops.slab_reduce_batch(sums, prepare)
-      if what != 'reduce':
-        self.apply_gradients_of([(g[off:off + n], off, n) for off, n in early], last=False)
-    main.wait_stream(side)
-    if what == 'reduce':
+      ops.slab_reduce_batch(sums, prepare)
       self.apply_gradients_of([(g[off:off + n], off, n) for off, n in early], last=False)
+    main.wait_stream(side)
     self.apply_gradients_of([(g[off:off + n], off, n) for off, n in late], last=True)
 
   def _refresh_after_update(self):
@@ -919,8 +866,7 @@ class GoalE2EVMC(_ModelBase):
     self.dyn_ws2 = ops.goal_dynimgs_ws(N, H * W, self.device)      # control block of the one-pass input stage (zero-filled once)
     # geeco-f reads its K-frame window ONCE, in the input kernel: that kernel can take the episodes' resident uint8 frames
     # directly (RGB, or RGB of RGB-D with depth dense), see ops.goal_dynimgs_u8_into
-    if (self.mode == 'dynimg' and self.last_from_dynimg and (H * W) % 4 == 0 and (C == 3 or self.split_rgbd) and
-        _dev.env('GEECO_NO_U8_WINDOWS') is None):
+    if self.mode == 'dynimg' and (H * W) % 4 == 0 and (C == 3 or self.split_rgbd):
       self.u8_window_keys = ('rgb', 'target_rgb')
 
   def _encode_dynimg_state(self):
@@ -953,15 +899,9 @@ class GoalE2EVMC(_ModelBase):
       if u8:
         ops.goal_dynimgs_u8_into(x_in[0], x_in[1], x_in[2], rgb.table, inp['target_rgb'].table, K, N, HW, self.dyn_ws2,
                                  depth=dep, tgt_depth=inp['target_depth'], dsample_stride=K * HW, dframe_stride=HW)
-      elif self.last_from_dynimg:
+      else:
         ops.goal_dynimgs_into(x_in[0], x_in[1], x_in[2], rgb, inp['target_rgb'], K, N, HW, self.dyn_ws2, K * HW * 3, HW * 3,
                               depth=dep, tgt_depth=inp['target_depth'], dsample_stride=K * HW, dframe_stride=HW)
-      else:
-        cur_rgb, cur_dep = rgb[:, K - 1], dep[:, K - 1]
-        ops.pack_pixels_into(x_in[0], cur_rgb, K * HW * 3, N, HW, 3, 4, cur_dep, K * HW, 1)
-        ops.dynimg_rgbd_into(x_in[1], rgb, dep, K, N, HW, self.dyn_ws, K * HW * 3, HW * 3, K * HW, HW)
-        ops.dynimg_rgbd_into(x_in[2], cur_rgb, cur_dep, 2, N, HW, self.dyn_ws, K * HW * 3, 0, K * HW, 0,
-                             rgb2=inp['target_rgb'], depth2=inp['target_depth'])
       self._encode_dynimg_state()
       d.forward(backward_too)
       self._finish_forward()
@@ -973,7 +913,7 @@ class GoalE2EVMC(_ModelBase):
       if u8:
         ops.goal_dynimgs_u8_into(x_in[0], x_in[1], x_in[2], self.inputs['rgb'].table, self.inputs['target_rgb'].table, K, N,
                                  HW, self.dyn_ws2)
-      elif C == 3 and HW % 4 == 0 and self.last_from_dynimg:
+      elif C == 3 and HW % 4 == 0:
         # ONE launch: the pass over the window has the current frame in registers (its channel-padded copy and the pair image come
         # from there) and keeps both images in registers across their per-sample min / max
         ops.goal_dynimgs_into(x_in[0], x_in[1], x_in[2], frames, tgt, K, N, HW, self.dyn_ws2, K * HW * C, HW * C)

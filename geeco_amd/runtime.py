@@ -23,7 +23,6 @@ import threading
 
 import torch
 
-from . import _dev
 from . import dist as gdist
 
 # hipGraph capture in the default ("global") mode is invalidated by a hipMalloc / synchronous copy issued by ANOTHER
@@ -126,17 +125,16 @@ class TrainStepRunner:
     # follow with their gradients read straight from the staging buffer (no unpack copies).  The three-graph form runs the same two
     # pieces back to back as its part 3 (round 6; it kept the unpack copies + one whole Adam launch before).
     self.split_adam = (self.dp and self.staging is not None and hasattr(model, 'apply_gradients_of')
-                       and 1 <= len(self.early) <= 8 and 1 <= len(self.late) <= 8 and _dev.env('GEECO_NO_SPLIT_ADAM') is None)
+                       and 1 <= len(self.early) <= 8 and 1 <= len(self.late) <= 8)
     # Single GPU: the optimiser's streaming work (slab sums of conv3..conv8, Adam over 99 % of the arena) runs on a second stream
     # beside the fused encoder-bottom backward instead of behind it (graph._ModelBase.backward_and_apply; bitwise the plain step)
     self.beside_bottom = (not self.dp and hasattr(model, 'backward_and_apply') and model.can_apply_beside_bottom()
-                          and 1 <= len(self.early) <= 8 and 1 <= len(self.late) <= 8 and _dev.env('GEECO_NO_ADAM_BESIDE_BOTTOM') is None)
+                          and 1 <= len(self.early) <= 8 and 1 <= len(self.late) <= 8)
     # ... and the ONE-GRAPH forms of the data-parallel step (and their eager warm-up steps) do the same with Adam's early piece.  RCCL only:
     # with gloo the form is three graphs anyway, and two gloo ranks that share one GPU (the rehearsals of tests/) run 10 x slower once
     # every process drives one more hardware queue -- the side stream is otherwise only ever used inside captures.
     self.dp_beside_bottom = (self.dp and self.overlap and self.capture_exchange and self.split_adam and self.redirected
-                             and hasattr(model, 'can_apply_beside_bottom') and model.can_apply_beside_bottom() and gdist.backend() == 'nccl'
-                             and _dev.env('GEECO_NO_DP_ADAM_BESIDE') is None)
+                             and hasattr(model, 'can_apply_beside_bottom') and model.can_apply_beside_bottom() and gdist.backend() == 'nccl')
     if self.redirected and self.early:
       lo = min(off for off, _ in self.early)
       hi = max(off + n for off, n in self.early)

@@ -31,9 +31,9 @@ extern "C" {
 
 int geeco_abi_version(void);
 const char* geeco_last_error(void);
-/* 0: the product library (csrc/build.sh): only the kernels the measured-best path launches, no environment variable is ever
- * read.  1: the development build (scripts/dev/build_dev_lib.sh, -DGEECO_DEV_KERNELS), which also holds every A/B kernel
- * variant and reads the GEECO_* switches of scripts/dev/SWITCHES.md when GEECO_DEV=1 is set. */
+/* Always 0.  The library has one build (csrc/build.sh) holding only the kernels the measured-best path launches; it reads no
+ * environment variable.  The development build that returned 1 and its switches were retired (scripts/dev/SWITCHES.md);
+ * the entry point stays for ABI compatibility. */
 int geeco_has_dev_kernels(void);
 
 /* Diagnostics (bench.py's per-layer table): between _begin and _end on one host thread every

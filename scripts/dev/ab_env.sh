@@ -1,7 +1,7 @@
 #!/bin/bash
-# same-box A/B of env / library settings: ab_env.sh "VAR=1 VAR2=x" "GEECO_LIB=libgeeco_hip_x.so" ... ("" = defaults); prints
+# same-box A/B of library builds / runtime env settings: ab_env.sh "" "GEECO_LIB=libgeeco_hip_x.so" "VAR=x" ... ("" = defaults); prints
 # frames/s, median step ms, conv1 fwd us and the in-step input-stage row, twice per setting (alternating)
-export GEECO_DEV=1   # the product reads GEECO_* switches only under GEECO_DEV=1
+export GEECO_DEV=1   # a GEECO_LIB=... leg loads another library build only under GEECO_DEV=1
 tmp=$(mktemp -d); trap 'rm -rf "$tmp"' EXIT
 for rep in 1 2; do
 for e in "$@"; do

@@ -1,6 +1,6 @@
 #!/bin/bash
-# same-box A/B of env settings on the STEP alone (no tables): ab_step.sh "" "VAR=1" ...; frames/s and step median, alternating, 3 reps
-export GEECO_DEV=1
+# same-box A/B of library builds / runtime env settings on the STEP alone (no tables): ab_step.sh "" "GEECO_LIB=libgeeco_hip_x.so" ...; frames/s and step median, alternating, 3 reps
+export GEECO_DEV=1   # a GEECO_LIB=... leg loads another library build only under GEECO_DEV=1
 mkdir -p gpurun_out/ab
 for rep in 1 2 3; do
 for e in "$@"; do

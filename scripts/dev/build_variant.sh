@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds the CURRENT csrc tree as geeco_amd/libgeeco_hip<suffix>.so with extra compiler flags, for same-box A/B runs
 # (GEECO_DEV=1 GEECO_LIB=libgeeco_hip<suffix>.so python bench.py ...).  usage: build_variant.sh _noskew -DFB_SKEW=0
-# (the PRODUCT kernel set; with the development variants and switches: build_dev_lib.sh)
+# (the PRODUCT kernel set: the only one there is)
 set -euo pipefail
 SUF=$1; shift
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)

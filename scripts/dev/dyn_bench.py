@@ -11,4 +11,4 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 e0.record()
 for _ in range(20): f()
 e1.record(); e1.synchronize()
-print(os.environ.get('GEECO_DYN_NT', '-'), 'dynimg K=16: %.1f us' % (e0.elapsed_time(e1) / 20 * 1e3))
+print(os.environ.get('GEECO_LIB', '-'), 'dynimg K=16: %.1f us' % (e0.elapsed_time(e1) / 20 * 1e3))

@@ -86,31 +86,33 @@ def test_stale_library_is_refused_by_version(tmp_path, monkeypatch):
 
 
 def test_dev_switches_are_ignored_without_geeco_dev(monkeypatch):
-  """GEECO_* A/B switches are development tooling: without GEECO_DEV=1 neither the Python side nor the library reads
-  them (a stray variable in a production environment must not change which kernels run)."""
-  from geeco_amd import _dev
-  monkeypatch.delenv('GEECO_DEV', raising=False)
-  monkeypatch.setenv('GEECO_NO_FUSED_BOTTOM', '1')
-  assert not _dev.enabled() and _dev.env('GEECO_NO_FUSED_BOTTOM') is None and _dev.env('GEECO_WGRAD_STREAMS', '2') == '2'
-  monkeypatch.setenv('GEECO_DEV', '1')
-  assert _dev.enabled() and _dev.env('GEECO_NO_FUSED_BOTTOM') == '1'
-  monkeypatch.setenv('GEECO_DEV', '0')
-  assert not _dev.enabled()
-  # the library: no getenv of a GEECO_ switch outside the one gate
+  """The GEECO_* A/B switches are retired (scripts/dev/SWITCHES.md): the library reads no environment variable at all, and
+  the Python side reads only GEECO_DEV / GEECO_LIB, in _native.py, to load another build of the library -- and a GEECO_LIB
+  without GEECO_DEV=1 (a stray variable in a production environment) does not change which library is loaded."""
   import glob
-  for path in glob.glob(os.path.join(ROOT, 'geeco_amd', 'csrc', '*.hip')) + glob.glob(os.path.join(ROOT, 'geeco_amd', 'csrc', '*.cpp')):
-    src = open(path).read()
-    direct = re.findall(r'(?<![_a-z])getenv\("(GEECO_[A-Z0-9_]+)"', src)
-    assert direct in ([], ['GEECO_DEV']), (path, direct)
+  for ext in ('hip', 'cpp', 'h'):
+    for path in glob.glob(os.path.join(ROOT, 'geeco_amd', 'csrc', '*.' + ext)):
+      assert 'getenv' not in open(path).read(), path
   for path in glob.glob(os.path.join(ROOT, 'geeco_amd', '*.py')):
-    if not path.endswith('_dev.py'):
-      assert not re.findall(r"os\.environ\.get\('GEECO_", open(path).read()), path
+    src = open(path).read()
+    reads = set(re.findall(r"""(?:environ(?:\.get)?|getenv)\s*[\[(]\s*['"](GEECO_[A-Z0-9_]*)""", src))
+    allowed = {'GEECO_DEV', 'GEECO_LIB'} if os.path.basename(path) == '_native.py' else set()
+    assert reads <= allowed, (path, reads)
+  from geeco_amd import _native
+  product = os.path.join(ROOT, 'geeco_amd', 'libgeeco_hip.so')
+  monkeypatch.setenv('GEECO_LIB', 'libgeeco_hip_other.so')
+  monkeypatch.delenv('GEECO_DEV', raising=False)
+  assert _native.lib_path() == product
+  monkeypatch.setenv('GEECO_DEV', '0')
+  assert _native.lib_path() == product
+  monkeypatch.setenv('GEECO_DEV', '1')
+  assert _native.lib_path() == os.path.join(ROOT, 'geeco_amd', 'libgeeco_hip_other.so')
 
 
 def test_product_library_holds_no_switches_and_no_development_kernels():
   """the shipped library is the path that runs.  It reports itself as the product build, the name of no
-  GEECO_* switch occurs in it (geeco_dev_getenv is the constant nullptr there: nothing reads the environment), and none of
-  the kernels only a switch could select was compiled in (the development build, scripts/dev/build_dev_lib.sh, has them)."""
+  retired GEECO_* switch occurs in it (nothing reads the environment), and none of the kernels only a switch could select is
+  compiled in (they were deleted with the switches)."""
   from geeco_amd import _native
   lib = _native.load()
   assert lib.geeco_has_dev_kernels() == 0

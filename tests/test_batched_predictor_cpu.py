@@ -82,11 +82,10 @@ def test_entries_declared_exported_typed_at_abi_7():
 
 
 def test_every_library_build_compiles_predict_io():
-  """Every recipe that builds a libgeeco_hip*.so from csrc (product, development, variant, stamps) compiles the same product
+  """Every recipe that builds a libgeeco_hip*.so from csrc (product, variant, stamps) compiles the same product
   sources: a library without predict_io would report ABI 7 yet lack its entries, and _native.load() refuses it."""
   product = None
-  for rel in ('geeco_amd/csrc/build.sh', 'scripts/dev/build_dev_lib.sh', 'scripts/dev/build_variant.sh',
-              'scripts/dev/build_stamps.sh'):
+  for rel in ('geeco_amd/csrc/build.sh', 'scripts/dev/build_variant.sh', 'scripts/dev/build_stamps.sh'):
     m = re.search(r'^for f in ([a-z0-9_ ]+); do', open(os.path.join(ROOT, rel)).read(), flags=re.M)
     assert m, rel
     files = m.group(1).split()

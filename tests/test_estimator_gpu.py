@@ -188,15 +188,15 @@ def test_batch_that_mixes_uint8_and_float_episodes(dev, tmp_path):
   np.testing.assert_allclose(res[0]['loss'], res[1]['loss'], rtol=1e-6)
 
 
-def test_u8_window_addresses_equal_dense_windows(dev, tmp_path):
+def test_u8_window_addresses_equal_dense_windows(dev, tmp_path, monkeypatch):
   """geeco-f on HBM-resident episodes: the model's input kernel follows window addresses into the uint8 frames
   (input_fn.WindowFeed.pointers(), no fp32 window tensor, no gather launch); training and evaluation are BITWISE what the
-  dense path (geeco_gather_windows into a float32 buffer, GEECO_NO_U8_WINDOWS) computes - RGB and RGB-D, batches that span
+  dense path (geeco_gather_windows into a float32 buffer: a model that declares no u8_window_keys) computes - RGB and RGB-D, batches that span
   two episodes, a ragged last batch, graph replay across repointed tables."""
   import sys
   sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
   from test_host_logic_cpu import _make_dataset
-  from geeco_amd import estimator as est, _dev
+  from geeco_amd import estimator as est, graph
   from geeco_amd.input_fn import EPISODE_CACHE, WindowFeed, pickplace_input_fn
   from geeco_amd.params import create_e2evmc_config
   root = str(tmp_path / 'ds')
@@ -210,17 +210,18 @@ def test_u8_window_addresses_equal_dense_windows(dev, tmp_path):
     res = []
     for dense in (False, True):
       EPISODE_CACHE.clear()
-      old = dict(os.environ)
-      if dense:
-        os.environ.update(GEECO_DEV='1', GEECO_NO_U8_WINDOWS='1')
-      try:
+      with monkeypatch.context() as m:
+        if dense:
+          init = graph.GoalE2EVMC.__init__
+
+          def dense_init(self, *a, **k):
+            init(self, *a, **k)
+            self.u8_window_keys = ()
+          m.setattr(graph.GoalE2EVMC, '__init__', dense_init)
         e = est.Estimator(est.goal_e2evmc_model_fn, None, est.RunConfig(init_seed=5), params)
         for _ in range(2):          # epoch 2 comes from the episode cache
           e.train(input_fn=lambda: pickplace_input_fn(root, 'default', 'train', seed=3, **kw))
         ev = e.evaluate(input_fn=lambda: pickplace_input_fn(root, 'default', 'eval', **kw))
-      finally:
-        os.environ.clear()
-        os.environ.update(old)
       feeds = [f for (spec, fbuf, lbuf) in e._specs.values() for f in fbuf.values() if isinstance(f, WindowFeed)]
       took = {(f.table is not None, f.buffer is not None) for f in feeds if f.frame_shape[-1] == 3}
       assert took == ({(False, True)} if dense else {(True, False)}), took
