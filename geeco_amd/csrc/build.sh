@@ -14,12 +14,12 @@ FLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -Wall -Wno-unused-function -ml
 extra_flags() {
   case $1 in
     conv_gemm) echo "-mllvm -amdgpu-sched-strategy=max-ilp" ;;
-    conv_halo|conv_dgrad_lds) echo "-mllvm -amdgpu-use-amdgpu-trackers=1" ;;
+    conv_halo_*|conv_dgrad_lds) echo "-mllvm -amdgpu-use-amdgpu-trackers=1" ;;
   esac
 }
 rm -rf build && mkdir -p build
 pids=()
-for f in conv_gemm conv_halo conv_wgrad conv_wgrad_halo conv_dgrad_lds dynimg decoder misc predict_io; do
+for f in conv_gemm conv_halo_conv1 conv_halo_s2_fwd conv_halo_s2_bwd conv_halo_bottom conv_wgrad conv_wgrad_halo conv_dgrad_lds dynimg decoder misc predict_io; do
   $HIPCC $FLAGS $(extra_flags $f) -c $f.hip -o build/$f.o &
   pids+=($!)
 done

@@ -19,14 +19,9 @@
 // MFMA v_mfma_f32_16x16x4_f32, row i = ci, column j = pixel, k = 4 consecutive co: both operands are ds_read_b128 of
 // naturally contiguous data (weights: 16 ci rows x 64 B; dz: 16 pixels x 64 B), each feeding 4 MFMAs; a lane ends up
 // with 4 consecutive NHWC channels of one pixel = one 16-byte masked store.
-#include "geeco_common.h"
-#include <atomic>
+#include "conv_halo_common.h"
+#include "conv_internal.h"
 #include <stdlib.h>
-
-static __device__ float g_zero_page[64];   // source of the DMA lanes that fall outside the image
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 struct DgradLdsParams {
   const float* dz;       // [G][N][Ho][Wo][Cout]
@@ -279,16 +274,7 @@ static int launch_dgrad_lds(const DgradLdsParams& p, int blocks, hipStream_t str
   constexpr int ZP_F4 = (4 * ((FR * IR * IC + 15) / 16 * 16) + 63) / 64 * 64;
   constexpr size_t lds = (size_t)(2 * 9 * NCIT * 64 + 2 * ZP_F4) * 16;
   static_assert(lds * (NW == 4 ? 3 : (NCIT == 4 ? 1 : 2)) <= 160 * 1024, "LDS budget");
-  static std::atomic<bool> attr_set{false};   // idempotent attribute call: racing threads at worst repeat it
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_s2_dgrad_lds_kernel<PR, PC, FR, NCIT, NW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      geeco_set_error("hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
+  if (int rc = geeco_lds_opt_in<&conv_s2_dgrad_lds_kernel<PR, PC, FR, NCIT, NW>>(lds)) return rc;
   geeco_note_kernel("conv_s2_dgrad_lds_kernel<%d, %d, %d, %d, %d>", PR, PC, FR, NCIT, NW);
   hipLaunchKernelGGL((conv_s2_dgrad_lds_kernel<PR, PC, FR, NCIT, NW>), dim3((unsigned)blocks), dim3(64 * NW), lds, stream, p);
   return 0;

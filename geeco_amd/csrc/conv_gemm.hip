@@ -23,6 +23,7 @@
 //       land in different bank halves (conflict free).
 #include "geeco_common.h"
 #include "conv_wgrad_body.h"
+#include "conv_internal.h"
 #include <type_traits>
 #include <stdlib.h>
 #include <stdio.h>
@@ -30,22 +31,6 @@
 
 // One parity class of a launch (forward: a single class with all 9 taps; dgrad of a stride-s conv:
 // s*s classes, each with its own subset of taps and its own sub-grid of destination pixels).
-int geeco_try_halo_fwd(const float* x, const float* w, const float* b, float* y, int groups, int64_t gs_x,
-                       int64_t gs_w, int64_t gs_b, int64_t gs_y, int N, int H, int W, int Cin, int Cout, int stride,
-                       int relu, hipStream_t stream, int* handled);
-
-int geeco_halo_fwd_handles(int H, int W, int Cin, int Cout, int stride);
-int geeco_conv1_fwd_handles(int Cin, int Cout, int stride);
-int geeco_try_conv1_fwd(const float* x, const float* w, const float* b, float* y, int groups, int64_t gs_x,
-                        int64_t gs_w, int64_t gs_b, int64_t gs_y, int N, int H, int W, int Cin, int Cout, int stride,
-                        int relu, hipStream_t stream, int* handled);
-int geeco_try_dgrad_lds(const float* dz, const float* w_hwio, const float* ymask, float* dx, int groups, int64_t gs_dz,
-                        int64_t gs_w, int64_t gs_dx, int N, int H, int W, int Cin, int Cout, int stride,
-                        hipStream_t stream, int* handled);
-int geeco_try_halo_dgrad(const float* dz, const float* w_hwio, const float* ymask, float* dx, int groups,
-                         int64_t gs_dz, int64_t gs_w, int64_t gs_dx, int N, int H, int W, int Cin, int Cout,
-                         int stride, hipStream_t stream, int* handled);
-
 struct ConvClass {
   long long M;          // N*Hc*Wc rows
   int Hc, Wc;           // iteration grid: rows enumerate (n, Y', X')
@@ -839,9 +824,6 @@ extern "C" int geeco_conv3x3_fwd_state(const float* x, const float* w, const flo
   sc.Ctot = Ctot; sc.jnt_off = jnt_off; sc.J = J; sc.cells = cells;
   return launch_conv_gemm(p, groups, ws, (hipStream_t)stream, &sc);
 }
-
-int geeco_halo_dgrad_handles(int H, int W, int Cin, int Cout, int stride);
-int geeco_dgrad_lds_handles(int H, int W, int Cin, int Cout, int stride);
 
 // The gather GEMM reads the HWIO kernel itself (transposing it on the way into LDS) where its K-steps stay inside one
 // tap: Cout a multiple of 16 that fits the zero page.  Only the remaining shapes need the per-tap transposed copy.

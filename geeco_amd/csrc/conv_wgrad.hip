@@ -18,6 +18,7 @@
 #include "geeco_common.h"
 #include <stdlib.h>
 #include "conv_wgrad_body.h"
+#include "conv_internal.h"
 
 template <int BR, int BC, int MK>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
@@ -200,21 +201,6 @@ static int slab_reduce_batch_impl(const geeco_slab_reduce* items, int n, int64_t
   GEECO_LAUNCH_CHECK();
   return 0;
 }
-
-int64_t geeco_halo_wgrad_ws_bytes(int groups, int N, int H, int W, int Cin, int Cout, int stride);
-int geeco_try_halo_wgrad(const float* x, const float* dz, float* dw, float* db, int groups, int64_t gs_x,
-                         int64_t gs_dz, int64_t gs_dw, int64_t gs_db, int N, int H, int W, int Cin, int Cout,
-                         int stride, void* ws, hipStream_t stream, int* handled);
-
-int64_t geeco_conv1_wgrad_ws_bytes(int groups, int Cin, int Cout, int stride);
-int geeco_try_conv1_wgrad(const float* x, const float* dz, float* dw, float* db, int groups, int64_t gs_x,
-                          int64_t gs_dz, int64_t gs_dw, int64_t gs_db, int N, int H, int W, int Cin, int Cout,
-                          int stride, void* ws, hipStream_t stream, int* handled);
-
-int64_t geeco_wgrad_lds_ws_bytes(int groups, int N, int H, int W, int Cin, int Cout, int stride);
-int geeco_try_wgrad_lds(const float* x, const float* dz, float* dw, float* db, int groups, int64_t gs_x, int64_t gs_dz,
-                        int64_t gs_dw, int64_t gs_db, int N, int H, int W, int Cin, int Cout, int stride, void* ws,
-                        hipStream_t stream, int* handled);
 
 void geeco_wgrad_plan(int groups, int N, int H, int W, int Cin, int Cout, int stride, WgradParams* p, int* bc) {
   int Ho, Wo, pt, pl;

@@ -26,14 +26,9 @@
 //       CIB = 64, XPQ = 14 (pitch 56 floats = 8 mod 16) unswizzled for CIB = 48: the ds_read_b32 of a B fragment
 //       (16 channels x the 4 columns 2 (4 s + q) + kx) then covers 2 x 16 distinct banks per 32-lane group;
 //   dz  [pixel][16 granules], granule index XOR-ed by (pixel & 1) << 2 (A fragment: 16 channels x 4 pixels).
-#include "geeco_common.h"
+#include "conv_halo_common.h"      // g_zero_page also feeds the DMA lanes on pad granules here
+#include "conv_internal.h"
 #include <stdlib.h>
-
-static __device__ float g_zero_page[64];   // source of the DMA lanes that fall outside the image (TF SAME zero padding) or on pad granules
-
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 
 struct WgradHaloParams {
   const float* x;
@@ -47,9 +42,6 @@ struct WgradHaloParams {
   int n_cib, n_cob;          // ci / co blocks
   int n_sigma;               // G * n_cib * S  (slices dealt round-robin to the XCDs)
 };
-
-void geeco_launch_wgrad_reduce(const float* part, float* dw, float* db, long long gs_dw, long long gs_db, int S,
-                               long long KC, int Cout, int groups, hipStream_t s);
 
 // CIB = 16 NCI input channels per block; COB = 16 NCO COT output channels per block (64, 96 or 128); NW = NCI * NCO waves.
 // Wide co blocks (COT = 3, 4) halve the number of blocks that fetch the same x halo: a 64-channel co block needs
@@ -352,16 +344,7 @@ static int launch_wgrad_lds(const WgradHaloParams& p, int blocks, hipStream_t st
   constexpr int X_F4 = ((2 * TH + 1) * (2 * TW + 1) * XPQ + 63) / 64 * 64;
   constexpr size_t lds = (size_t)(NBUF * X_F4 + NBUF * TH * TW * 4 * NCO * COT) * 16;
   static_assert(lds <= 160 * 1024, "LDS budget");
-  static int attr_state = 0;          // 0 = not set; set once (idempotent: racing threads set the same value)
-  if (__atomic_load_n(&attr_state, __ATOMIC_ACQUIRE) == 0) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_s2_wgrad_lds_kernel<NCI, NCO, COT, TH, TW, XPQ, SWZ, NBUF, MINW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      geeco_set_error("hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
-      return (int)e;
-    }
-    __atomic_store_n(&attr_state, 1, __ATOMIC_RELEASE);
-  }
+  if (int rc = geeco_lds_opt_in<&conv_s2_wgrad_lds_kernel<NCI, NCO, COT, TH, TW, XPQ, SWZ, NBUF, MINW>>(lds)) return rc;
   geeco_note_kernel("conv_s2_wgrad_lds_kernel<%d, %d, %d, %d, %d, %d, %s, %d, %d>", NCI, NCO, COT, TH, TW, XPQ, SWZ ? "true" : "false", NBUF, MINW);
   hipLaunchKernelGGL((conv_s2_wgrad_lds_kernel<NCI, NCO, COT, TH, TW, XPQ, SWZ, NBUF, MINW>), dim3((unsigned)blocks), dim3(64 * NCI * NCO), lds,
                      stream, p);

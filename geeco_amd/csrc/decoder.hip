@@ -3,7 +3,6 @@
 // Replaces reference src/models/e2evmc/graph.py:123-192 (concats), :198-260 (lstm_decoder),
 // :452-500 (losses) and the loss composition of src/models/e2evmc/estimator.py:206-239.
 #include "geeco_common.h"
-#include <atomic>
 #include <stdlib.h>
 
 // =====================================================================================================
@@ -1100,16 +1099,7 @@ static int heads_fill(HeadsParams* pp, const float* h, const float* fc1_w, const
 
 template <bool FUSE, int G>
 static int launch_heads_sample_g(const HeadsParams& p, const StepFuse& sf, hipStream_t stream) {
-  static std::atomic<bool> attr_set{false};   // idempotent attribute call: racing threads at worst repeat it
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&heads_sample_kernel<FUSE, G>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)HS_LDS_BYTES);
-    if (e != hipSuccess) {
-      geeco_set_error("hipFuncSetAttribute(%zu B LDS) failed: %s", HS_LDS_BYTES, hipGetErrorString(e));
-      return (int)e;
-    }
-    attr_set = true;
-  }
+  if (int rc = geeco_lds_opt_in<&heads_sample_kernel<FUSE, G>>(HS_LDS_BYTES)) return rc;
   geeco_note_kernel("heads_sample_kernel<%s>", FUSE ? "true" : "false");
   hipLaunchKernelGGL((heads_sample_kernel<FUSE, G>), dim3((unsigned)p.N), dim3(HS_THREADS), HS_LDS_BYTES, stream, p, sf);
   GEECO_LAUNCH_CHECK();

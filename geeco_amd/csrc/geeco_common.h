@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <atomic>
 
 #include "../../include/geeco_hip.h"
 
@@ -37,6 +38,22 @@ void geeco_leave_reserved_cus(void);
       return (int)e_;                                                \
     }                                                                \
   } while (0)
+
+// Once-per-kernel opt-in to `lds` bytes of dynamic LDS before the first launch: one flag per kernel instantiation; the
+// attribute call is idempotent, racing threads at worst repeat it.  Returns 0 or the HIP error (message set).
+template <auto KERNEL>
+static int geeco_lds_opt_in(size_t lds) {
+  static std::atomic<bool> attr_set{false};
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+      geeco_set_error("hipFuncSetAttribute(%zu B LDS) failed: %s", lds, hipGetErrorString(e));
+      return (int)e;
+    }
+    attr_set = true;
+  }
+  return 0;
+}
 
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }

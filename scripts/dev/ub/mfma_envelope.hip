@@ -2,7 +2,7 @@
 // the bytes it has to move -- the "envelope" the per-kernel roofline fractions should be read against.  Round 5's loop
 // (mfma_power.hip: every compute wave issues its own global loads, one ds_read_b128 per MFMA) reached 101 TFLOP/s beside
 // 3.2 TB/s while conv2's forward reaches 115 at the same traffic: a loop the product beats bounds nothing.  This one has the
-// product's structure (conv_s2_halo_fwd_ws_kernel, csrc/conv_halo.hip) and NONE of its address arithmetic, bounds tests,
+// product's structure (conv_s2_halo_fwd_ws_kernel, csrc/conv_halo_s2_fwd.hip) and NONE of its address arithmetic, bounds tests,
 // bias / ReLU / sign words or tile bookkeeping:
 //   * one block per CU (256 blocks), 8 compute waves (two per SIMD) + LW loader waves;
 //   * the loaders do nothing but LDS-DMA (global_load_lds, 1 KiB per instruction) IN pieces per tile into a ring of three LDS
@@ -31,7 +31,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 
-// in-kernel timeline (as conv_halo.hip's HSTAMP): [block][K half][64] s_memtime of lane 0 of waves 0 and 4, six stamps per tile for the first ten tiles
+// in-kernel timeline (as conv_halo_s2_fwd.hip's HSTAMP): [block][K half][64] s_memtime of lane 0 of waves 0 and 4, six stamps per tile for the first ten tiles
 __device__ unsigned long long g_stamps[256 * 2 * 64];
 #define ESTAMP(i) do { if (NMF == 107 + 1 && GEOM >= 2 && STORE != 2 && STORE != 5 && lane == 0 && (wid & 3) == 0 && (i) < 64) g_stamps[(blockIdx.x * 2 + (wid >> 2)) * 64 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 
