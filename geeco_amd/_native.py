@@ -133,6 +133,7 @@ SIGNATURES = {
     'geeco_lstm_step_heads_fwd_bwd': (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _PP, _PP, POINTER(_I),
                                            POINTER(_I), POINTER(_F), _PP, POINTER(_L), _F, _I, _P, _P, _I, _P, _P, _P, _PP, _PP,
                                            _P, _P, _P]),
+    'geeco_lstm_seq_heads_fwd': (_I, [_P, _L, _P, _L, _P, _P, _P, _I, _PP, _PP, POINTER(_I), _I, _I, _I, _I, _P, _P, _P, _P]),
     'geeco_adam_prepare': (_I, [_P, _F, _F, _F, _P, _P]),
     'geeco_adam_tf': (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _P]),
     'geeco_adam_tf_segments': (_I, [_P, _P, _P, _P, _P, _I, _P, _F, _F, _F, _F, _F, _P]),

@@ -120,7 +120,8 @@ class _BatchedPredictorBase:
     H, W, C, K, J = cfg.img_height, cfg.img_width, cfg.img_channels, cfg.window_size, cfg.dim_jnt_state
     self._dims = (B, H, W, C, K, J)
     with torch.cuda.device(dev):
-      m = self._model = ctor(cfg, B, dev, training=False)
+      # the per-frame controllers' K-step decoder as one launch (geeco-f runs T = 1: its decoder ignores the argument)
+      m = self._model = ctor(cfg, B, dev, training=False, one_launch_decoder=True)
       est.restore_for_inference(m.store, model_dir, checkpoint_name)
       # uint8 frames on a model whose input kernel reads uint8 windows: the mirrored ring (no fp32 window is ever written)
       self._ring = self._u8 and not self._incremental and 'rgb' in m.u8_window_keys

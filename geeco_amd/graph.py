@@ -466,23 +466,27 @@ def head_table(cfg):
 class LSTMDecoder:
   """T LSTM steps over states [T][N][D] from a zero state, fc1 + heads on the last output."""
 
-  def __init__(self, store: VariableStore, scope, cfg, N, T, D, training):
+  def __init__(self, store: VariableStore, scope, cfg, N, T, D, training, one_launch=False):
+    """``one_launch`` (inference decoders with T > 1 only; the batched predictor engine sets it): forward(False) is the hoisted
+    input projection + ONE launch for the T steps, fc1 and the heads (ops.lstm_seq_heads_into).  No per-step gates / c / h history
+    is kept, no loss terms are computed and ``targets`` are not read; ``losses`` stays zero."""
     self.store, self.scope, self.cfg, self.N, self.T, self.D = store, scope, cfg, N, T, D
     self.H, self.F = cfg.dim_h_lstm, cfg.dim_h_fc
     self.training = training
+    self.one_launch = bool(one_launch) and not training and T > 1
     self.heads = head_table(cfg)
     self.OT = sum(h[2] for h in self.heads)
     dev = store.device
     f32 = dict(dtype=torch.float32, device=dev)
     H, F = self.H, self.F
     self.states = torch.empty(T, N, D, **f32)
-    self.z = torch.empty(T, N, 4 * H, **f32)
-    self.gates = torch.empty(T, N, 4 * H, **f32)
-    self.c = torch.empty(T, N, H, **f32)
-    self.h = torch.empty(T, N, H, **f32)
     self.preds = torch.empty(N, self.OT, **f32)
     self.losses = torch.zeros(8, **f32)
-    self.heads_ws = torch.empty(ops.heads_ws_bytes(N, H, F) // 4 + 4, **f32)
+    if self.one_launch:
+      self.zx = torch.empty(T, N, 4 * H, **f32)      # X Wx of all steps: all the one-launch kernel reads besides the weights
+      self.z = self.gates = self.c = self.h = self.heads_ws = None
+    else:
+      self._alloc_chain()
     gemm_shapes = [(T * N, 4 * H, D), (N, 4 * H, H)]
     if training:
       self.dstates = torch.empty(T, N, D, **f32)
@@ -494,6 +498,16 @@ class LSTMDecoder:
     self.targets, self.target_strides = None, None     # bound by the model
     self.loss_scale = 1.0
     self.heads_pending, self.dz_from_heads = None, False
+
+  def _alloc_chain(self):
+    """The per-step buffers of the launch-per-step chain."""
+    N, T, H = self.N, self.T, self.H
+    f32 = dict(dtype=torch.float32, device=self.store.device)
+    self.z = torch.empty(T, N, 4 * H, **f32)
+    self.gates = torch.empty(T, N, 4 * H, **f32)
+    self.c = torch.empty(T, N, H, **f32)
+    self.h = torch.empty(T, N, H, **f32)
+    self.heads_ws = torch.empty(ops.heads_ws_bytes(N, H, self.F) // 4 + 4, **f32)
 
   def _v(self, n):
     return self.store.var('%s/%s' % (self.scope, n))
@@ -512,6 +526,16 @@ class LSTMDecoder:
       hkw = dict(d_fc1_w=self._g('fc1/kernel'), d_fc1_b=self._g('fc1/bias'),
                  d_heads_w=[self._g(n + '/kernel') for n in names], d_heads_b=[self._g(n + '/bias') for n in names])
     self.heads_pending = None
+    if self.one_launch and not backward_too:
+      # inference, T > 1: the hoisted input projection, then ONE launch for the T steps, fc1 and the heads (Wh register-resident,
+      # one workgroup per sample) instead of ~3 dependent launches per step
+      ops.gemm_into(self.zx, self.states, Wx, T * N, 4 * H, D, D, 4 * H, 4 * H, ws=self.gemm_ws)
+      if ops.lstm_seq_heads_into(self.preds, self.zx, Wh, bias, self._v('fc1/kernel'), self._v('fc1/bias'),
+                                 [self._v(n + '/kernel') for n in names], [self._v(n + '/bias') for n in names],
+                                 [h[2] for h in self.heads], N, T, H, F, 4 * H, 4 * H):
+        return
+      self.one_launch, self.zx = False, None      # sizes the kernel does not serve: today's chain from here on
+      self._alloc_chain()
     if T == 1:
       # one step from a zero state (round 5): gate GEMM + ONE per-sample launch for the slab sum, the gate math, fc1, the heads,
       # the loss terms and (training) everything back to the gate gradients dz; the batch sums (weight / bias gradients, loss means)
@@ -836,7 +860,7 @@ class _ModelBase:
 class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None):
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False):
     super().__init__(cfg, N, device, goal=True, training=training, store=store)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
@@ -860,7 +884,7 @@ class GoalE2EVMC(_ModelBase):
       dims = self.feat_ch
     self.enc = ConvEncoderStack(self.store, scopes, Nf, H, W, C, dims, training)
     D = _CELLS * (sum(self.feat_ch) + jn)
-    self.decoder = LSTMDecoder(self.store, root + '/LSTMDecoder', cfg, N, T, D, training)
+    self.decoder = LSTMDecoder(self.store, root + '/LSTMDecoder', cfg, N, T, D, training, one_launch=one_launch_decoder)
     self._bind_labels()
     self.dyn_ws = ops.dynimg_ws(N, H * W * 4, self.device)
     self.dyn_ws2 = ops.goal_dynimgs_ws(N, H * W, self.device)      # control block of the one-pass input stage (zero-filled once)
@@ -1006,13 +1030,13 @@ class GoalE2EVMC(_ModelBase):
 class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None):
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False):
     super().__init__(cfg, N, device, goal=False, training=training, store=store)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     # frames are processed time-major ([K][N]) so that step t's features are one dense block
     self.enc = ConvEncoderStack(self.store, ['VMC/ConvEncoder'], K * N, H, W, C, 256, training)
     D = _CELLS * (256 + cfg.dim_jnt_state)
-    self.decoder = LSTMDecoder(self.store, 'VMC/LSTMDecoder', cfg, N, K, D, training)
+    self.decoder = LSTMDecoder(self.store, 'VMC/LSTMDecoder', cfg, N, K, D, training, one_launch=one_launch_decoder)
     self._bind_labels()
 
   def forward(self, backward_too=False):
@@ -1066,7 +1090,7 @@ class _StepModelBase:
   runs the decoder (T = K).  Same ``VariableStore`` layout as the full model: checkpoints restore unchanged.  There is no
   [N][K][H][W][C] window and no K * N-frame activation buffer."""
 
-  def __init__(self, cfg, N, device, goal, scope, ch, mode, training=False, store=None):
+  def __init__(self, cfg, N, device, goal, scope, ch, mode, training=False, store=None, one_launch_decoder=False):
     if training:
       raise ValueError('%s is inference-only: training=True needs the full model (E2EVMC / GoalE2EVMC)' % type(self).__name__)
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, False
@@ -1081,10 +1105,11 @@ class _StepModelBase:
     N, K, jn = self.N, self.K, cfg.dim_jnt_state
     self.enc = ConvEncoderStack(self.store, [scope + '/ConvEncoder'], N, self.H, self.W, self.C, ch, False)
     D = _CELLS * (ch + jn + (ch if mode == 'constant' else 0))
-    self.decoder = d = LSTMDecoder(self.store, scope + '/LSTMDecoder', cfg, N, K, D, False)
+    self.decoder = d = LSTMDecoder(self.store, scope + '/LSTMDecoder', cfg, N, K, D, False, one_launch=one_launch_decoder)
     f32 = dict(dtype=torch.float32, device=self.device)
     d.states.zero_()
-    # the heads kernel computes loss terms beside the predictions: zero labels nobody reads
+    # the heads kernel of the step chain computes loss terms beside the predictions: zero labels nobody reads (the one-launch
+    # decoder does not touch them)
     width = max(8, max(h[2] for h in d.heads))
     self._no_labels = torch.zeros(N, width, **f32)
     d.targets = [self._no_labels] * len(d.heads)
@@ -1122,8 +1147,8 @@ class _StepModelBase:
 class E2EVMCStep(_StepModelBase):
   """``e2e_vmc`` one frame per call: state_t = [feat_t | jnt_t] per cell (state_concatenation, graph.py:123-144)."""
 
-  def __init__(self, cfg, N, device, training=False, store=None):
-    super().__init__(cfg, N, device, False, 'VMC', 256, 'plain', training, store)
+  def __init__(self, cfg, N, device, training=False, store=None, one_launch_decoder=False):
+    super().__init__(cfg, N, device, False, 'VMC', 256, 'plain', training, store, one_launch_decoder)
 
 
 class GoalE2EVMCStep(_StepModelBase):
@@ -1132,14 +1157,14 @@ class GoalE2EVMCStep(_StepModelBase):
   subtraction happens in the gather, so a new goal changes every state of the window exactly.  The target's features are
   computed when the goal is set (``encode_targets``), not per call."""
 
-  def __init__(self, cfg, N, device, training=False, store=None):
+  def __init__(self, cfg, N, device, training=False, store=None, one_launch_decoder=False):
     if cfg.proc_obs != 'sequence':
       raise ValueError("incremental mode caches per-frame encoder features: proc_obs='%s' has none (three encoder passes per call "
                        "whatever the window size)" % (cfg.proc_obs,))
     if cfg.proc_tgt not in ('constant', 'residual'):
       raise ValueError("incremental mode does not take proc_tgt='%s': the cached DynDiff features depend on the goal, a goal "
                        "change needs the K raw frames encoded again" % (cfg.proc_tgt,))
-    super().__init__(cfg, N, device, True, 'GoalVMC', cfg.dim_s_obs, cfg.proc_tgt, training, store)
+    super().__init__(cfg, N, device, True, 'GoalVMC', cfg.dim_s_obs, cfg.proc_tgt, training, store, one_launch_decoder)
     self.mode = 'seq_' + cfg.proc_tgt
 
   def encode_targets(self, tgt_frames, env_ids):

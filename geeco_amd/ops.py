@@ -595,6 +595,21 @@ def lstm_step_heads_into(z, c, h, gates, x, wx, bias, N, H, D, ldx, ldw, gemm_ws
   return True
 
 
+def lstm_seq_heads_into(preds, zx, wh, bias, fc1_w, fc1_b, heads_w, heads_b, head_size, N, T, H, Hfc, ldz, ldw, h_last=None,
+                        c_last=None):
+  """Inference decoder after the hoisted input projection in ONE launch: T LSTM steps from the zero state over ``zx`` [T][N][4H]
+  (row stride ``ldz``; X Wx without bias), fc1 and the heads on the last output -> ``preds`` [N][sum sizes]; ``h_last`` / ``c_last``
+  [N][H] optionally receive the final state.  Returns False (nothing launched) for shapes the kernel does not serve: the caller
+  then runs the step chain (gemm_into + lstm_gates_fwd_into per step, heads_loss_into)."""
+  nh = len(heads_w)
+  rc = _lib().geeco_lstm_seq_heads_fwd(_p(zx), ldz, _p(wh), ldw, _p(bias), _p(fc1_w), _p(fc1_b), nh, _parr(heads_w), _parr(heads_b),
+                                       _iarr(head_size), N, T, H, Hfc, _p(preds), _p(h_last), _p(c_last), _stream())
+  if rc == _native.GEECO_ENOSUP:
+    return False
+  check(rc, 'geeco_lstm_seq_heads_fwd')
+  return True
+
+
 # --------------------------------------------------------------------------------------------
 # optimiser
 # --------------------------------------------------------------------------------------------

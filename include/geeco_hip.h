@@ -25,6 +25,7 @@ extern "C" {
 #endif
 
 #define GEECO_ABI_VERSION 7  /* = the build round that last changed the entry points or their calling conventions */
+/* added within 7 (additive: no existing entry point or convention changed): geeco_lstm_seq_heads_fwd */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -455,6 +456,25 @@ int geeco_lstm_step_heads_fwd_bwd(const float* x, int64_t ldx, const float* wx, 
                                   float* preds, float* losses, int backward, float* dz, float* d_fc1_w, float* d_fc1_b,
                                   float* const* d_heads_w, float* const* d_heads_b, float* heads_ws,
                                   geeco_heads_finish* pending, void* stream);
+
+/* The INFERENCE decoder of the per-frame controllers (e2e_vmc, goal_e2evmc 'sequence': T = window_size steps from the zero state,
+ * graph.py:217-260) after the hoisted input projection, as ONE launch: the T - 1 recurrent h wh products, the gate math of all T
+ * steps, fc1 (ReLU) and the linear heads on h_{T-1}.  Replaces, per call, (T - 1) x geeco_gemm_f32 + T x geeco_lstm_gates_fwd +
+ * geeco_heads_loss_fwd_bwd; no per-step z / gates / c / h history, no losses, no targets.
+ *   zx [T][N][4H] (row t * N + n at zx + (t * N + n) * ldz, ldz >= 4H): X wx WITHOUT bias, as geeco_gemm_f32 leaves it;
+ *   wh [H][4H] (ldw): rows D..D+H-1 of lstm_cell/kernel, addressed in place;  bias [4H];
+ *   fc1_w [H][Hfc], fc1_b [Hfc]; nheads <= 5 heads [Hfc][size_i] / [size_i] as parallel arrays (geeco_heads_loss_fwd_bwd);
+ *   preds [N][sum size_i];  h_last, c_last [N][H]: the final state, either may be NULL.
+ * Arithmetic as the LSTM cell above (gate order i, j, f, o; forget_bias 1): z_0 = zx_0 + bias (step 0 forms no h wh term: T = 1
+ * never reads wh's values), z_t = zx_t + bias + h_{t-1} wh.  One workgroup per sample walks the T steps alone, wh resident in its
+ * registers: no workspace, nothing waits for another block, and a sample's outputs depend on its own zx rows and the weights
+ * only -- bitwise the same for every N and every index n.
+ * GEECO_EINVAL: null pointer, N < 1, T outside 1..64, nheads outside 1..5, sum size_i > 32, ldz / ldw < 4H.
+ * GEECO_ENOSUP (nothing launched) outside H <= 128, Hfc in {64, 128}: the caller runs the separate entry points. */
+int geeco_lstm_seq_heads_fwd(const float* zx, int64_t ldz, const float* wh, int64_t ldw, const float* bias, const float* fc1_w,
+                             const float* fc1_b, int nheads, const float* const* heads_w, const float* const* heads_b,
+                             const int* head_size, int N, int T, int H, int Hfc, float* preds, float* h_last, float* c_last,
+                             void* stream);
 
 /* ---- optimiser: tf.train.AdamOptimizer(lr).minimize, estimator.py:105,243-244 ------------------
  * TF semantics (epsilon outside the bias correction):
