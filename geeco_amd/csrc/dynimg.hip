@@ -788,27 +788,16 @@ extern "C" int64_t geeco_dynimg_ws_bytes(int N, int64_t hwc) {
   return (int64_t)N * (cdiv64(hwc, 256) + 1) * 2 * 4;
 }
 
-static int dynimg_fwd_impl(const float* frames, const float* frames2, int64_t sample_stride, int64_t frame_stride,
-                           const float* alpha_host, int N, int K, int64_t HW, int C, int Cpad, float* out, float* last,
-                           void* ws, void* stream);
-
 extern "C" int geeco_dynimg_fwd(const float* frames, const float* frames2, int64_t sample_stride,
                                 int64_t frame_stride, const float* alpha_host, int N, int K, int64_t HW, int C,
                                 int Cpad, float* out, void* ws, void* stream) {
-  return dynimg_fwd_impl(frames, frames2, sample_stride, frame_stride, alpha_host, N, K, HW, C, Cpad, out, nullptr, ws,
-                         stream);
-}
-
-static int dynimg_fwd_impl(const float* frames, const float* frames2, int64_t sample_stride, int64_t frame_stride,
-                           const float* alpha_host, int N, int K, int64_t HW, int C, int Cpad, float* out, float* last,
-                           void* ws, void* stream) {
   GEECO_CHECK_ARG(frames && alpha_host && out && ws, "dynimg_fwd: null pointer");
   GEECO_CHECK_ARG(K >= 1 && K <= DYN_MAXK, "dynimg_fwd: K=%d outside 1..%d", K, DYN_MAXK);
   GEECO_CHECK_ARG(N >= 1 && HW >= 1 && C >= 1 && C <= Cpad && Cpad <= 8, "dynimg_fwd: bad dims");
   GEECO_CHECK_ARG(!frames2 || K == 2, "dynimg_fwd: frames2 only with K == 2");
   DynParams p = {};
   p.frames = frames; p.frames2 = frames2; p.sample_stride = sample_stride; p.frame_stride = frame_stride;
-  p.N = N; p.K = K; p.HW = HW; p.C = C; p.Cpad = Cpad; p.out = out; p.last = last; p.part = (float*)ws;
+  p.N = N; p.K = K; p.HW = HW; p.C = C; p.Cpad = Cpad; p.out = out; p.part = (float*)ws;
   p.nblk = dyn_nblk(HW, C);
   for (int t = 0; t < K; ++t) p.alpha[t] = alpha_host[t];
   hipStream_t s = (hipStream_t)stream;
@@ -829,22 +818,9 @@ static int dynimg_fwd_impl(const float* frames, const float* frames2, int64_t sa
   return 0;
 }
 
-static int dynimg_rgbd_impl(const float* rgb, const float* rgb2, int64_t sample_stride, int64_t frame_stride,
-                            const float* depth, const float* depth2, int64_t dsample_stride, int64_t dframe_stride,
-                            const float* alpha_host, int N, int K, int64_t HW, float* out, float* last, void* ws,
-                            void* stream);
-
 extern "C" int geeco_dynimg_rgbd_fwd(const float* rgb, const float* rgb2, int64_t sample_stride, int64_t frame_stride,
                                      const float* depth, const float* depth2, int64_t dsample_stride, int64_t dframe_stride,
                                      const float* alpha_host, int N, int K, int64_t HW, float* out, void* ws, void* stream) {
-  return dynimg_rgbd_impl(rgb, rgb2, sample_stride, frame_stride, depth, depth2, dsample_stride, dframe_stride, alpha_host, N,
-                          K, HW, out, nullptr, ws, stream);
-}
-
-static int dynimg_rgbd_impl(const float* rgb, const float* rgb2, int64_t sample_stride, int64_t frame_stride,
-                            const float* depth, const float* depth2, int64_t dsample_stride, int64_t dframe_stride,
-                            const float* alpha_host, int N, int K, int64_t HW, float* out, float* last, void* ws,
-                            void* stream) {
   GEECO_CHECK_ARG(rgb && depth && alpha_host && out && ws, "dynimg_rgbd_fwd: null pointer");
   GEECO_CHECK_ARG(K >= 1 && K <= DYN_MAXK, "dynimg_rgbd_fwd: K=%d outside 1..%d", K, DYN_MAXK);
   GEECO_CHECK_ARG(N >= 1 && HW >= 4 && (HW & 3) == 0, "dynimg_rgbd_fwd: HW=%lld must be a multiple of 4", (long long)HW);
@@ -854,7 +830,7 @@ static int dynimg_rgbd_impl(const float* rgb, const float* rgb2, int64_t sample_
   DynParams p = {};
   p.frames = rgb; p.frames2 = rgb2; p.sample_stride = sample_stride; p.frame_stride = frame_stride;
   p.depth = depth; p.depth2 = depth2; p.dsample_stride = dsample_stride; p.dframe_stride = dframe_stride;
-  p.N = N; p.K = K; p.HW = HW; p.C = 3; p.Cpad = 4; p.out = out; p.last = last; p.part = (float*)ws;
+  p.N = N; p.K = K; p.HW = HW; p.C = 3; p.Cpad = 4; p.out = out; p.part = (float*)ws;
   p.nblk = dyn_nblk(HW, 3);
   for (int t = 0; t < K; ++t) p.alpha[t] = alpha_host[t];
   hipStream_t s = (hipStream_t)stream;

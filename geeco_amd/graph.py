@@ -441,9 +441,8 @@ class ConvEncoderStack:
     if pending or prepare is not None:
       ops.slab_reduce_batch(pending, prepare)
 
-  SPLIT = 2   # backward(part='upper') = layers 7..SPLIT, 'bottom' = SPLIT-1..0
-  # ... except layer SPLIT's INPUT gradient, which opens the bottom part (round 4 cut after it)
-  DEFER_SPLIT_DGRAD = True
+  # backward(part='upper') = layers 7..SPLIT, 'bottom' = SPLIT-1..0, which opens with layer SPLIT's INPUT gradient (round 4 cut after it)
+  SPLIT = 2
 
 
 # ================================================================================================
@@ -471,14 +470,12 @@ class LSTMDecoder:
     input projection + ONE launch for the T steps, fc1 and the heads (ops.lstm_seq_heads_into).  No per-step gates / c / h history
     is kept, no loss terms are computed and ``targets`` are not read; ``losses`` stays zero."""
     self.store, self.scope, self.cfg, self.N, self.T, self.D = store, scope, cfg, N, T, D
-    self.H, self.F = cfg.dim_h_lstm, cfg.dim_h_fc
-    self.training = training
+    self.H, self.F, self.training = cfg.dim_h_lstm, cfg.dim_h_fc, training
     self.one_launch = bool(one_launch) and not training and T > 1
     self.heads = head_table(cfg)
     self.OT = sum(h[2] for h in self.heads)
-    dev = store.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    H, F = self.H, self.F
+    f32 = dict(dtype=torch.float32, device=store.device)
+    H = self.H
     self.states = torch.empty(T, N, D, **f32)
     self.preds = torch.empty(N, self.OT, **f32)
     self.losses = torch.zeros(8, **f32)
@@ -491,12 +488,10 @@ class LSTMDecoder:
     if training:
       self.dstates = torch.empty(T, N, D, **f32)
       self.dz = torch.empty(T, N, 4 * H, **f32)
-      self.dh = torch.empty(N, H, **f32)
-      self.dc = torch.empty(N, H, **f32)
+      self.dh, self.dc = torch.empty(N, H, **f32), torch.empty(N, H, **f32)
       gemm_shapes += [(D, 4 * H, T * N), (H, 4 * H, max((T - 1) * N, 1)), (T * N, D, 4 * H), (N, H, 4 * H)]
     self.gemm_ws = torch.empty(max(ops.gemm_ws_bytes(*s) for s in gemm_shapes) // 4 + 4, **f32)
-    self.targets, self.target_strides = None, None     # bound by the model
-    self.loss_scale = 1.0
+    self.targets, self.target_strides, self.loss_scale = None, None, 1.0     # bound by the model
     self.heads_pending, self.dz_from_heads = None, False
 
   def _alloc_chain(self):
@@ -515,60 +510,70 @@ class LSTMDecoder:
   def _g(self, n):
     return self.store.grad('%s/%s' % (self.scope, n))
 
-  def forward(self, backward_too):
-    N, T, D, H, F = self.N, self.T, self.D, self.H, self.F
+  def _weights(self):
     W = self._v('lstm_cell/kernel')            # [D + H][4H]: rows 0..D-1 multiply x, D.. multiply h
-    Wx, Wh = W[:D], W[D:]
-    bias = self._v('lstm_cell/bias')
+    return W[:self.D], W[self.D:], self._v('lstm_cell/bias')
+
+  def _head_args(self, backward_too):
+    """The head arguments of the ops (variables, sizes, kinds, loss weights, targets) and the gradient views, from the store as it is now."""
     names = [h[0] for h in self.heads]
-    hkw = {}
-    if backward_too:
-      hkw = dict(d_fc1_w=self._g('fc1/kernel'), d_fc1_b=self._g('fc1/bias'),
-                 d_heads_w=[self._g(n + '/kernel') for n in names], d_heads_b=[self._g(n + '/bias') for n in names])
-    self.heads_pending = None
+    args = (self._v('fc1/kernel'), self._v('fc1/bias'), [self._v(n + '/kernel') for n in names], [self._v(n + '/bias') for n in names],
+            *([h[i] for h in self.heads] for i in (2, 3, 4)), self.targets, self.target_strides, float(self.loss_scale))
+    grads = dict(d_fc1_w=self._g('fc1/kernel'), d_fc1_b=self._g('fc1/bias'), d_heads_w=[self._g(n + '/kernel') for n in names],
+                 d_heads_b=[self._g(n + '/bias') for n in names]) if backward_too else {}
+    return args, grads
+
+  def forward(self, backward_too):
+    args, grads = self._head_args(backward_too)
+    self.heads_pending, self.dz_from_heads = None, False
     if self.one_launch and not backward_too:
-      # inference, T > 1: the hoisted input projection, then ONE launch for the T steps, fc1 and the heads (Wh register-resident,
-      # one workgroup per sample) instead of ~3 dependent launches per step
-      ops.gemm_into(self.zx, self.states, Wx, T * N, 4 * H, D, D, 4 * H, 4 * H, ws=self.gemm_ws)
-      if ops.lstm_seq_heads_into(self.preds, self.zx, Wh, bias, self._v('fc1/kernel'), self._v('fc1/bias'),
-                                 [self._v(n + '/kernel') for n in names], [self._v(n + '/bias') for n in names],
-                                 [h[2] for h in self.heads], N, T, H, F, 4 * H, 4 * H):
+      if self._forward_one_launch(args):
         return
       self.one_launch, self.zx = False, None      # sizes the kernel does not serve: today's chain from here on
       self._alloc_chain()
-    if T == 1:
-      # one step from a zero state (round 5): gate GEMM + ONE per-sample launch for the slab sum, the gate math, fc1, the heads,
-      # the loss terms and (training) everything back to the gate gradients dz; the batch sums (weight / bias gradients, loss means)
-      # ride in the first grid of backward()'s launch pair -- losses / those gradients are final after backward()
-      pend = _native.HeadsFinish() if backward_too else None
-      if ops.lstm_step_heads_into(self.z[0], self.c[0], self.h[0], self.gates[0], self.states[0], Wx, bias, N, H, D, D, 4 * H,
-                                  self.gemm_ws, self.preds, self.losses, self._v('fc1/kernel'), self._v('fc1/bias'),
-                                  [self._v(n + '/kernel') for n in names], [self._v(n + '/bias') for n in names],
-                                  [h[2] for h in self.heads], [h[3] for h in self.heads], [h[4] for h in self.heads],
-                                  self.targets, self.target_strides, float(self.loss_scale), F, self.heads_ws,
-                                  dz=self.dz[0] if backward_too else None, pending=pend, **hkw):
-        self.heads_pending = pend if backward_too else None
-        self.dz_from_heads = backward_too
-        return
-    self.dz_from_heads = False
-    if T == 1:
-      # (shapes outside the fused step) the slab sum of the gate GEMM rides in the gate kernel (bitwise the same)
-      ops.lstm_input_step_fwd_into(self.z[0], self.c[0], self.h[0], self.gates[0], self.states[0], Wx, bias, N, H, D, D, 4 * H,
-                                   self.gemm_ws)
-      T = 0
+    if self.T == 1:
+      self._forward_one_step(backward_too, args, grads)
     else:
-      # hoisted input projection for all steps: Z = X Wx
-      ops.gemm_into(self.z, self.states, Wx, T * N, 4 * H, D, D, 4 * H, 4 * H, ws=self.gemm_ws)
+      self._forward_chain(backward_too, args, grads)
+
+  def _forward_one_launch(self, args):
+    """Inference, T > 1: the hoisted input projection, then ONE launch for the T steps, fc1 and the heads (Wh register-resident,
+    one workgroup per sample) instead of ~3 dependent launches per step.  False: the kernel does not serve these sizes."""
+    N, T, D, H = self.N, self.T, self.D, self.H
+    Wx, Wh, bias = self._weights()
+    ops.gemm_into(self.zx, self.states, Wx, T * N, 4 * H, D, D, 4 * H, 4 * H, ws=self.gemm_ws)
+    return ops.lstm_seq_heads_into(self.preds, self.zx, Wh, bias, *args[:5], N, T, H, self.F, 4 * H, 4 * H)
+
+  def _forward_one_step(self, backward_too, args, grads):
+    """One step from a zero state (round 5): gate GEMM + ONE per-sample launch for the slab sum, the gate math, fc1, the heads, the
+    loss terms and (training) everything back to the gate gradients dz; the batch sums (weight / bias gradients, loss means) ride
+    in the first grid of backward()'s launch pair -- losses / those gradients are final after backward()."""
+    Wx, _, bias = self._weights()
+    step = (self.z[0], self.c[0], self.h[0], self.gates[0], self.states[0], Wx, bias, self.N, self.H, self.D, self.D, 4 * self.H,
+            self.gemm_ws)
+    pend = _native.HeadsFinish() if backward_too else None
+    if ops.lstm_step_heads_into(*step, self.preds, self.losses, *args, self.F, self.heads_ws,
+                                dz=self.dz[0] if backward_too else None, pending=pend, **grads):
+      self.heads_pending, self.dz_from_heads = pend, backward_too
+      return
+    # (shapes outside the fused step) the slab sum of the gate GEMM rides in the gate kernel (bitwise the same)
+    ops.lstm_input_step_fwd_into(*step)
+    self._heads_loss(backward_too, args, grads)
+
+  def _forward_chain(self, backward_too, args, grads):
+    N, T, D, H = self.N, self.T, self.D, self.H
+    Wx, Wh, bias = self._weights()
+    # hoisted input projection for all steps: Z = X Wx
+    ops.gemm_into(self.z, self.states, Wx, T * N, 4 * H, D, D, 4 * H, 4 * H, ws=self.gemm_ws)
     for t in range(T):
       if t > 0:
         ops.gemm_into(self.z[t], self.h[t - 1], Wh, N, 4 * H, H, H, 4 * H, 4 * H, accumulate=True, ws=self.gemm_ws)
-      ops.lstm_gates_fwd_into(self.c[t], self.h[t], self.gates[t], self.z[t], bias,
-                              self.c[t - 1] if t > 0 else None, N, H)
-    kw = dict(dh=self.dh, **hkw) if backward_too else {}
-    ops.heads_loss_into(self.preds, self.losses, self.h[self.T - 1], self._v('fc1/kernel'), self._v('fc1/bias'),
-                        [self._v(n + '/kernel') for n in names], [self._v(n + '/bias') for n in names],
-                        [h[2] for h in self.heads], [h[3] for h in self.heads], [h[4] for h in self.heads],
-                        self.targets, self.target_strides, float(self.loss_scale), N, H, F, self.heads_ws, **kw)
+      ops.lstm_gates_fwd_into(self.c[t], self.h[t], self.gates[t], self.z[t], bias, self.c[t - 1] if t > 0 else None, N, H)
+    self._heads_loss(backward_too, args, grads)
+
+  def _heads_loss(self, backward_too, args, grads):
+    kw = dict(dh=self.dh, **grads) if backward_too else {}
+    ops.heads_loss_into(self.preds, self.losses, self.h[self.T - 1], *args, self.N, self.H, self.F, self.heads_ws, **kw)
 
   def backward(self, concat=None):
     """After forward(backward_too=True): fills d(states) and the LSTM variable gradients.  ``concat`` (one-step decoders
@@ -576,8 +581,7 @@ class LSTMDecoder:
     (feature gradients + ReluGrad of conv8) then rides in the same launch as the weight / input gradients and the method
     returns True (else the caller scatters ``dstates`` itself)."""
     N, T, D, H = self.N, self.T, self.D, self.H
-    W = self._v('lstm_cell/kernel')
-    Wx, Wh = W[:D], W[D:]
+    Wx, Wh, _ = self._weights()
     dW = self._g('lstm_cell/kernel')
     if T == 1:
       # one step from a zero state: dWh = h_prev^T dz = 0 (the arena's rows stay zero); weight / bias / input gradients (+ the
@@ -591,15 +595,13 @@ class LSTMDecoder:
       self.heads_pending = None
       return concat is not None
     for t in range(T - 1, -1, -1):
-      last = t == T - 1
-      ops.lstm_gates_bwd_into(self.dz[t], self.dc if t > 0 else None, self.gates[t],
-                              self.c[t - 1] if t > 0 else None, self.c[t], self.dh, None if last else self.dc, N, H)
+      ops.lstm_gates_bwd_into(self.dz[t], self.dc if t > 0 else None, self.gates[t], self.c[t - 1] if t > 0 else None, self.c[t],
+                              self.dh, None if t == T - 1 else self.dc, N, H)
       if t > 0:   # dh_{t-1} = dz_t Wh^T
         ops.gemm_into(self.dh, self.dz[t], Wh, N, H, 4 * H, 4 * H, 4 * H, H, tb=True, ws=self.gemm_ws)
     # dWx = X^T dZ ; dWh = H_prev^T dZ[1:] ; db = colsum(dZ) ; dX = dZ Wx^T
     ops.gemm_into(dW[:D], self.states, self.dz, D, 4 * H, T * N, D, 4 * H, 4 * H, ta=True, ws=self.gemm_ws)
-    if T > 1:
-      ops.gemm_into(dW[D:], self.h, self.dz[1:], H, 4 * H, (T - 1) * N, H, 4 * H, 4 * H, ta=True, ws=self.gemm_ws)
+    ops.gemm_into(dW[D:], self.h, self.dz[1:], H, 4 * H, (T - 1) * N, H, 4 * H, 4 * H, ta=True, ws=self.gemm_ws)
     ops.colsum_into(self._g('lstm_cell/bias'), self.dz, 4 * H, T * N, 4 * H)
     ops.gemm_into(self.dstates, self.dz, Wx, T * N, D, 4 * H, 4 * H, 4 * H, D, tb=True, ws=self.gemm_ws)
     return False
@@ -979,7 +981,7 @@ class GoalE2EVMC(_ModelBase):
     _prepare_args (the optimiser's scalars ride in the slab-sum launch of the part it is passed to -- once per step).
     ``defer_sums`` (part 'upper') / ``before_bottom`` (part 'bottom'): ConvEncoderStack.backward, used by backward_and_apply."""
     if part == 'bottom':
-      self.enc.backward(hi=ConvEncoderStack.SPLIT - 1, lo=0, prepare=self._prepare_args(adam_prepare), lead_dgrad=ConvEncoderStack.SPLIT if ConvEncoderStack.DEFER_SPLIT_DGRAD else None,
+      self.enc.backward(hi=ConvEncoderStack.SPLIT - 1, lo=0, prepare=self._prepare_args(adam_prepare), lead_dgrad=ConvEncoderStack.SPLIT,
                         before_bottom=before_bottom)
       return
     N, K, jn = self.N, self.K, self.cfg.dim_jnt_state
@@ -1010,9 +1012,8 @@ class GoalE2EVMC(_ModelBase):
       df = [self.enc.dfeatures[g].view(K, N, _CELLS, self.feat_ch[g]) for g in range(2)]
       for t in range(K):
         ops.state_concat_bwd_into([df[0][t], df[1][t]], d.dstates[t], d.D, [f[0][t], f[1][t]], self.feat_ch, 1, jn, N, _CELLS)
-    self.enc.backward(hi=7, lo=ConvEncoderStack.SPLIT if part == 'upper' else 0,
-                      prepare=self._prepare_args(adam_prepare and defer_sums is None), defer_dgrad=part == 'upper' and ConvEncoderStack.DEFER_SPLIT_DGRAD,
-                      defer_sums=defer_sums if part == 'upper' else None)
+    self.enc.backward(hi=7, lo=ConvEncoderStack.SPLIT if part == 'upper' else 0, defer_dgrad=part == 'upper',
+                      prepare=self._prepare_args(adam_prepare and defer_sums is None), defer_sums=defer_sums if part == 'upper' else None)
 
   def endpoints(self):
     """dynbuff / dyndiff debug endpoints (graph.py:377,393,401): the LAST computed images."""
@@ -1059,7 +1060,7 @@ class E2EVMC(_ModelBase):
 
   def backward(self, part=None, adam_prepare=False, defer_sums=None, before_bottom=None):
     if part == 'bottom':
-      self.enc.backward(hi=ConvEncoderStack.SPLIT - 1, lo=0, prepare=self._prepare_args(adam_prepare), lead_dgrad=ConvEncoderStack.SPLIT if ConvEncoderStack.DEFER_SPLIT_DGRAD else None,
+      self.enc.backward(hi=ConvEncoderStack.SPLIT - 1, lo=0, prepare=self._prepare_args(adam_prepare), lead_dgrad=ConvEncoderStack.SPLIT,
                         before_bottom=before_bottom)
       return
     N, K = self.N, self.K
@@ -1069,9 +1070,8 @@ class E2EVMC(_ModelBase):
     dfe = self.enc.dfeatures[0].view(K, N, _CELLS, 256)
     for t in range(K):
       ops.state_concat_bwd_into([dfe[t]], d.dstates[t], d.D, [feats[t]], [256], 1, self.cfg.dim_jnt_state, N, _CELLS)
-    self.enc.backward(hi=7, lo=ConvEncoderStack.SPLIT if part == 'upper' else 0,
-                      prepare=self._prepare_args(adam_prepare and defer_sums is None), defer_dgrad=part == 'upper' and ConvEncoderStack.DEFER_SPLIT_DGRAD,
-                      defer_sums=defer_sums if part == 'upper' else None)
+    self.enc.backward(hi=7, lo=ConvEncoderStack.SPLIT if part == 'upper' else 0, defer_dgrad=part == 'upper',
+                      prepare=self._prepare_args(adam_prepare and defer_sums is None), defer_sums=defer_sums if part == 'upper' else None)
 
   def endpoints(self):
     return {'conv8': self.enc.features}

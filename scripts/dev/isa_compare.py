@@ -4,8 +4,10 @@ must not change a kernel).  usage: isa_compare.py PARENT.so THIS.so [--diffs N]
 
 Every gfx950 code object is taken from the .hip_fatbin section (uncompressed clang offload bundles), disassembled with
 llvm-objdump -d and split per function symbol.  Addresses and encodings are dropped, branch targets become offsets inside
-their function, the link-time literal of a pc-relative variable address is masked.  Prints the number of code objects,
-functions and instructions and every function that differs."""
+their function, the link-time literal of a pc-relative variable address is masked, and the s_nop run behind a function's
+last instruction is dropped: it is the padding up to the next function, and behind the last function of a code object's
+.text the 1 KiB prefetch guard the compiler ends every code object with -- which function that is changes with every move
+of a kernel between files.  Prints the number of code objects, functions and instructions and every function that differs."""
 import difflib, re, struct, subprocess, sys, tempfile, os
 
 BIN = '/opt/rocm/llvm/bin/'
@@ -58,6 +60,9 @@ def functions(lib):
           ins = ins.rsplit(' ', 1)[0] + ' <pcrel>'
         if ins and ins != '...':                 # '...': objdump's elision of the zero padding behind a function
           fns[name].append(ins)
+  for ins in fns.values():                     # no function ends in s_nop: what trails its s_endpgm / branch is padding
+    while ins and ins[-1] == 's_nop 0':
+      ins.pop()
   return fns, len(cos)
 
 
