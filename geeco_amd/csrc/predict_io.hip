@@ -7,12 +7,12 @@
 //
 // The control words `ctl` [B + 1] int32: ctl[b] = 1 when env b's frame failed the range check, ctl[B] = 1 when any did.  The
 // range check only ever sets them; the output pack copies them out and zeroes them again, so every call starts from zeros.
-#include "geeco_common.h"
+#include "dynimg_internal.h"
 
-#define PIO_MAXK 64       // the window lengths the input kernels of the models take (dynimg.hip: DYN_MAXK)
+#define PIO_MAXK DYN_MAXK       // the window lengths the input kernels of the models take
 #define GEECO_PREDICT_FEAT_THREADS 1024      // one block per env in the feature push + gather
 
-// float(u8) / 255.0f with the IEEE division: bitwise the `divisor 255` conversion of geeco_gather_windows (dynimg.hip)
+// float(u8) / 255.0f with the IEEE division: bitwise the `divisor 255` conversion of geeco_gather_windows (frame_pack.hip)
 __device__ __forceinline__ float pio_u8(unsigned v) { return (float)v / 255.0f; }
 
 // ---- 1. frame range check ---------------------------------------------------------------------------------------------

@@ -826,7 +826,7 @@ class _ModelBase:
 
   def check_device_errors(self):
     """Raises if a kernel of this model reported an error on the device (today: a block of the one-pass input stage that gave up
-    waiting, csrc/dynimg.hip).  SYNCHRONISES the stream: called where the host reads results anyway (Estimator's loss
+    waiting, csrc/dynimg_goal.hip).  SYNCHRONISES the stream: called where the host reads results anyway (Estimator's loss
     read-outs and epoch ends, bench.py's loss check, ``endpoints``), never inside the step."""
     ws = getattr(self, 'dyn_ws2', None)
     if ws is not None and getattr(self, 'mode', None) == 'dynimg':

@@ -3,12 +3,17 @@
 # scripts/dev/stamps.py).  Dev only: the product build never executes a stamp.
 set -euo pipefail
 cd "$(dirname "$0")/../../geeco_amd/csrc"
+. ./sources.sh      # HIP_SOURCES, KERNEL_FLAGS, BASE_FLAGS (extra_flags is not used here)
 T=$(mktemp -d)
-for f in conv_gemm conv_halo_conv1 conv_halo_s2_fwd conv_halo_s2_bwd conv_halo_bottom conv_wgrad conv_wgrad_halo conv_dgrad_lds dynimg decoder_concat decoder_gemm decoder_lstm decoder_heads decoder_step_bwd decoder_seq misc predict_io; do
-  /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -mllvm -amdgpu-mfma-vgpr-form -DGEECO_STAMPS ${STAMP_FLAGS:-} -c $f.hip -o $T/$f.o &
+SFLAGS="$KERNEL_FLAGS -DGEECO_STAMPS ${STAMP_FLAGS:-}"      # the product flags without WARN_FLAGS
+pids=()
+for f in $HIP_SOURCES; do
+  /opt/rocm/bin/hipcc $SFLAGS -c $f.hip -o $T/$f.o &
+  pids+=($!)
 done
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -x hip -c errors.cpp -o $T/errors.o
-wait
+/opt/rocm/bin/hipcc $BASE_FLAGS -x hip -c errors.cpp -o $T/errors.o &
+pids+=($!)
+for p in "${pids[@]}"; do wait $p; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libgeeco_hip_stamps.so $T/*.o
 rm -rf $T
 echo "built $(realpath ../libgeeco_hip_stamps.so)"

@@ -8,16 +8,11 @@ ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 cd $ROOT/geeco_amd/csrc
 B=build$SUF
 rm -rf $B && mkdir -p $B
-FLAGS="-O3 --offload-arch=gfx950 -fPIC -std=c++17 -Wall -Wno-unused-function -mllvm -amdgpu-mfma-vgpr-form $*"
-extra_flags() {      # as geeco_amd/csrc/build.sh; PLAIN=1: none (to A/B the per-file settings themselves)
-  [ -n "${PLAIN:-}" ] && return
-  case $1 in
-    conv_gemm) echo "-mllvm -amdgpu-sched-strategy=max-ilp" ;;
-    conv_halo_*|conv_dgrad_lds) echo "-mllvm -amdgpu-use-amdgpu-trackers=1" ;;
-  esac
-}
+. ./sources.sh      # HIP_SOURCES, FLAGS, extra_flags
+FLAGS="$FLAGS $*"
+if [ -n "${PLAIN:-}" ]; then extra_flags() { :; }; fi      # PLAIN=1: no per-file settings (to A/B those settings themselves)
 pids=()
-for f in conv_gemm conv_halo_conv1 conv_halo_s2_fwd conv_halo_s2_bwd conv_halo_bottom conv_wgrad conv_wgrad_halo conv_dgrad_lds dynimg decoder_concat decoder_gemm decoder_lstm decoder_heads decoder_step_bwd decoder_seq misc predict_io; do
+for f in $HIP_SOURCES; do
   /opt/rocm/bin/hipcc $FLAGS $(extra_flags $f) -c $f.hip -o $B/$f.o &
   pids+=($!)
 done

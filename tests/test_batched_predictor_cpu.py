@@ -83,15 +83,22 @@ def test_entries_declared_exported_typed_at_abi_7():
 
 def test_every_library_build_compiles_predict_io():
   """Every recipe that builds a libgeeco_hip*.so from csrc (product, variant, stamps) compiles the same product
-  sources: a library without predict_io would report ABI 7 yet lack its entries, and _native.load() refuses it."""
-  product = None
+  sources: a library without predict_io would report ABI 7 yet lack its entries, and _native.load() refuses it.
+  The list is spelled once, in csrc/sources.sh; every recipe sources that file and loops over its list, and none spells
+  a list of its own."""
+  src = open(os.path.join(ROOT, 'geeco_amd/csrc/sources.sh')).read()
+  m = re.search(r'^HIP_SOURCES="([a-z0-9_ ]+)"$', src, flags=re.M)
+  assert m and len(re.findall(r'HIP_SOURCES=', src)) == 1
+  files = m.group(1).split()
+  assert 'predict_io' in files and len(set(files)) == len(files)
+  for f in files:
+    assert os.path.exists(os.path.join(ROOT, 'geeco_amd/csrc', f + '.hip')), f
   for rel in ('geeco_amd/csrc/build.sh', 'scripts/dev/build_variant.sh', 'scripts/dev/build_stamps.sh'):
-    m = re.search(r'^for f in ([a-z0-9_ ]+); do', open(os.path.join(ROOT, rel)).read(), flags=re.M)
-    assert m, rel
-    files = m.group(1).split()
-    assert 'predict_io' in files, rel
-    product = product or files
-    assert files == product, (rel, files, product)
+    text = open(os.path.join(ROOT, rel)).read()
+    assert re.search(r'^\. \./sources\.sh\b', text, flags=re.M), rel
+    loops = re.findall(r'^for f in (.+); do', text, flags=re.M)
+    assert loops == ['$HIP_SOURCES'], (rel, loops)
+    assert 'HIP_SOURCES=' not in text and 'predict_io' not in text, rel
 
 
 def test_argument_checks_need_no_gpu():

@@ -590,7 +590,8 @@ def test_conv2_relu_fields_and_conv3_dgrad_fields(dev, G, N, H, W):
 
 
 @pytest.mark.parametrize('N,K,H,W,C', [(2, 4, 16, 24, 3), (3, 16, 136, 136, 3), (2, 3, 16, 24, 4), (1, 1, 8, 8, 3), (2, 2, 40, 36, 4),
-                                       (25, 3, 256, 256, 3), (26, 2, 128, 256, 4), (5, 2, 100, 164, 3)])
+                                       (25, 3, 256, 256, 3), (26, 2, 128, 256, 4), (5, 2, 100, 164, 3),
+                                       (193, 14, 72, 72, 3), (192, 14, 72, 72, 4)])
 def test_goal_dynimgs_one_pass(dev, N, K, H, W, C):
   """The goal model's input stage (graph.py:386-401) as the step runs it: ONE launch, one pass over the window: the buffer image
   and the pair image of (current frame, target) stay in registers across their per-sample min / max (the blocks of a sample meet
@@ -599,7 +600,9 @@ def test_goal_dynimgs_one_pass(dev, N, K, H, W, C):
   against the fp64 oracle; K = 1 (alpha = [0]: the buffer image is identically 0), rgb and rgb + depth; both block shapes
   (from 192 blocks on, 1024 threads carry TWO samples each, the first one's stores inside the second one's frame loop: the 25-
   sample case has an odd count (the last block pair holds one sample), the 26-sample one is even; 256 x 4 pixels below), a
-  ragged last block (100 x 164); run three times on one control block (every call must leave it zero-filled)."""
+  ragged last block (100 x 164); K = 14 at 72 x 72 with 193 / 192 samples: the smallest big-grid cases whose K - 1 = 13 frames
+  run the software-pipelined frame loop (several ring rounds + a remainder) with the first sample's stores inside it, a ragged
+  second block per sample and an odd sample count; run three times on one control block (every call must leave it zero-filled)."""
   from geeco_amd import ops
   r = np.random.default_rng(57)
   HW = H * W
@@ -646,7 +649,7 @@ def test_goal_dynimgs_one_pass(dev, N, K, H, W, C):
 @pytest.mark.parametrize('N,H,W,u8', [(25, 256, 256, False), (3, 136, 136, False), (26, 256, 256, True)],
                          ids=['two samples per block', 'small blocks', 'uint8 frames'])
 def test_goal_dynimgs_expired_wait_is_loud(dev, N, H, W, u8):
-  """The one-pass input stage never continues on stale min / max (csrc/dynimg.hip): when a block's wait for the other blocks
+  """The one-pass input stage never continues on stale min / max (csrc/dynimg_goal.hip): when a block's wait for the other blocks
   of its sample expires, that sample's images are NaN, the block counts itself into the workspace's sticky error word, and
   geeco_goal_dynimgs_timeouts / model.check_device_errors report it.  The wait cannot be made to expire through the data
   (blocks of a launch start in index order on this hardware, which is exactly why the bound is never reached), so the test
@@ -726,11 +729,13 @@ def test_model_reports_an_expired_input_stage_wait(dev):
 
 
 @pytest.mark.parametrize('N,K,H,W,C', [(2, 4, 16, 24, 3), (3, 16, 136, 136, 3), (2, 3, 16, 24, 4), (1, 1, 8, 8, 3), (4, 2, 40, 36, 4),
-                                       (25, 2, 256, 256, 3), (24, 2, 256, 256, 4)])
+                                       (25, 2, 256, 256, 3), (24, 2, 256, 256, 4), (193, 14, 72, 72, 3), (192, 14, 72, 72, 4)])
 def test_goal_dynimgs_from_resident_u8_frames(dev, N, K, H, W, C):
   """The input stage fed from the episodes' resident uint8 frames through per-sample window addresses
   (geeco_goal_dynimgs_u8_fwd): bitwise the three images of geeco_gather_windows (/ 255, geeco_gym.py:312) followed by
-  geeco_goal_dynimgs_fwd, for overlapping windows of two 'episodes' of different length, every byte value present."""
+  geeco_goal_dynimgs_fwd, for overlapping windows of two 'episodes' of different length, every byte value present (so the
+  Newton-corrected a * (1 / 255) of the uint8 loads is checked against the division for all 256 values).  K = 14 at 72 x 72 with
+  193 / 192 samples: the big-grid kernels of both forms with their pipelined frame loops and a ragged second slot / block."""
   from geeco_amd import ops
   r = np.random.default_rng(61)
   HW = H * W
