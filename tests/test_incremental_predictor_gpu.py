@@ -67,7 +67,7 @@ def test_push_features_kernel_matches_ring_model(dev, mode, ch, B, K):
 
 def test_push_features_states_are_state_concat_columns(dev):
   """The gathered rows are, column for column, what state_concat_fwd_into writes for the same features (the layout the full
-  models feed the decoder)."""
+  models feed the decoder; state_concat_fwd_into itself: test_primitives_gpu.py::test_state_concat_fwd)."""
   from geeco_amd import ops
   B, K, cells, ch, J = 3, 1, 4, 64, 7
   r = np.random.default_rng(5)

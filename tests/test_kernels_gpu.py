@@ -735,7 +735,8 @@ def test_goal_dynimgs_from_resident_u8_frames(dev, N, K, H, W, C):
   (geeco_goal_dynimgs_u8_fwd): bitwise the three images of geeco_gather_windows (/ 255, geeco_gym.py:312) followed by
   geeco_goal_dynimgs_fwd, for overlapping windows of two 'episodes' of different length, every byte value present (so the
   Newton-corrected a * (1 / 255) of the uint8 loads is checked against the division for all 256 values).  K = 14 at 72 x 72 with
-  193 / 192 samples: the big-grid kernels of both forms with their pipelined frame loops and a ragged second slot / block."""
+  193 / 192 samples: the big-grid kernels of both forms with their pipelined frame loops and a ragged second slot / block.
+  (geeco_gather_windows itself is pinned against numpy's division by test_primitives_gpu.py::test_gather_windows.)"""
   from geeco_amd import ops
   r = np.random.default_rng(61)
   HW = H * W
@@ -999,7 +1000,8 @@ def test_lstm_step_bwd_one_launch(dev, N, chs, J):
   split-K + reduce, state_concat_bwd): bitwise (same tile code, same K and slab order), and against fp64; the
   joint-state columns of dX are not scattered anywhere.  N = 160: geeco_gemm_f32 splits dWx's batch dimension from N = 128
   on and the one-launch form does not (include/geeco_hip.h), so dWx is compared to fp64 / to the split form at fp32
-  tolerance there, everything else stays bitwise."""
+  tolerance there, everything else stays bitwise.
+  (The separate launches are pinned by test_primitives_gpu.py::test_gemm_forms, test_colsum and test_state_concat_bwd.)"""
   from geeco_amd import ops
   r = np.random.default_rng(71)
   H4, cells = 512, 4
@@ -1054,7 +1056,8 @@ def test_lstm_step_bwd_one_launch(dev, N, chs, J):
 def test_lstm_input_step_fwd_two_launches(dev, N, H, D):
   """geeco_lstm_input_step_fwd (the cell's first step: gate GEMM, then the gate math with the split-K slab sum inside) against
   geeco_gemm_f32 + geeco_lstm_gates_fwd(c_prev = NULL): bitwise z, c, h, gates (same tile code, K split and slab order), split
-  (D = 3100: 39 slabs at N = 32) and unsplit (D = 40) products, row counts that do not fill a tile; z against fp64."""
+  (D = 3100: 39 slabs at N = 32) and unsplit (D = 40) products, row counts that do not fill a tile; z against fp64.
+  (geeco_gemm_f32 / geeco_lstm_gates_fwd are pinned by test_primitives_gpu.py::test_gemm_forms and test_lstm_gates_fwd.)"""
   from geeco_amd import ops
   r = np.random.default_rng(83)
   x = torch.tensor(r.standard_normal([N, D]).astype(np.float32), device=dev)
@@ -1080,7 +1083,8 @@ def test_lstm_step_heads_one_launch_per_sample(dev, N, D, mode, deferred):
   stands for: geeco_lstm_input_step_fwd + geeco_heads_loss_fwd_bwd + geeco_lstm_gates_bwd.  z, c, h, gates, the predictions,
   every loss and every gradient BITWISE (same per-sample code, same slab / summation orders); with ``deferred`` the batch sums
   ride in geeco_lstm_step_bwd's first grid (pending), whose own outputs stay bitwise those of the call without them; split
-  (39 slabs) and unsplit (D = 40) gate products; forward only (evaluation): predictions and losses."""
+  (39 slabs) and unsplit (D = 40) gate products; forward only (evaluation): predictions and losses.
+  (Of the entry points it stands for, test_primitives_gpu.py::test_lstm_gates_fwd / test_lstm_gates_bwd pin the gate math.)"""
   from geeco_amd import _native, ops
   r = np.random.default_rng(131 + N)
   H = F = 128
@@ -1149,7 +1153,8 @@ def test_lstm_step_heads_one_launch_per_sample(dev, N, D, mode, deferred):
 def test_top_layer_forward_carries_the_state_concat(dev, G, N, C, J):
   """geeco_conv3x3_fwd_state (conv8 + bias + ReLU of all encoders, the one-step decoder's state concat in the epilogue of the
   split-K sum) against geeco_conv3x3_fwd + geeco_state_concat_fwd: features and state bitwise, no state element left
-  unwritten; a shape without a split-K epilogue is declined (False, nothing written)."""
+  unwritten; a shape without a split-K epilogue is declined (False, nothing written).
+  (geeco_state_concat_fwd is pinned by test_primitives_gpu.py::test_state_concat_fwd.)"""
   from geeco_amd import ops
   r = np.random.default_rng(97)
   H = W = 4

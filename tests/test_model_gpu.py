@@ -169,7 +169,8 @@ def test_optimiser_step_in_pieces_is_the_one_pass_step(dev, l2):
   """geeco_adam_tf_segments (data parallel: the variables of the early bucket are updated while the late bucket is on the wire,
   conv1 / conv2 of the encoders follow with their gradients read from the staging buffer): any partition of the arena, with the
   gradients of some pieces living elsewhere, gives bitwise geeco_adam_tf's parameters and moments; ``g_out`` receives the foreign
-  pieces' gradients; pieces that are not multiples of four floats are refused."""
+  pieces' gradients; pieces that are not multiples of four floats are refused.
+  (geeco_adam_tf itself is pinned by test_primitives_gpu.py::test_adam_three_steps, the pieces against fp64 by test_adam_segments.)"""
   from geeco_amd import ops
   r = np.random.default_rng(171)
   n = 4 * 25013
