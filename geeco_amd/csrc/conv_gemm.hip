@@ -22,45 +22,13 @@
 //   sB[k][BN + 4]: ds_read_b32, row pitch = 4 (mod 8) dwords => the two k-rows of a 32-lane half
 //       land in different bank halves (conflict free).
 #include "geeco_common.h"
+#include "conv_gemm_plan.h"
 #include "conv_wgrad_body.h"
 #include "conv_internal.h"
 #include <type_traits>
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
-
-// One parity class of a launch (forward: a single class with all 9 taps; dgrad of a stride-s conv:
-// s*s classes, each with its own subset of taps and its own sub-grid of destination pixels).
-struct ConvClass {
-  long long M;          // N*Hc*Wc rows
-  int Hc, Wc;           // iteration grid: rows enumerate (n, Y', X')
-  int oy0, ox0;         // destination pixel = (Y'*ds + oy0, X'*ds + ox0)
-  int ntaps;
-  int tile0;            // first M-tile (blockIdx.x) of this class
-  int dy[9], dx[9], wslab[9];
-};
-
-struct ConvGemmParams {
-  const float* x;
-  const float* w;
-  const float* bias;
-  const float* mask;
-  float* out;
-  float* part;          // split-K slabs [ksplit][G][N*Hd*Wd][Nout] (ksplit > 1)
-  unsigned long long* stamps;   // -DGEECO_STAMPS builds only: [block][64] s_memtime timeline of thread 0
-  long long gs_x, gs_w, gs_b, gs_out;
-  int N, Hs, Ws, C;     // source tensor [N][Hs][Ws][C]
-  int Hd, Wd, Nout;     // destination tensor [N][Hd][Wd][Nout]
-  int ss;               // source pixel = (Y'*ss + dy, X'*ss + dx)
-  int ds;
-  int relu;
-  int ncls;
-  int ksplit;           // K-steps are dealt to ksplit blocks (blockIdx.y = ntile * ksplit + split)
-  int groups;
-  int bt;               // B operand from the HWIO kernel itself ([tap][n][k]: k contiguous) instead of a per-tap transposed copy
-  int rot;              // != 0: M tiles per class; the M tile index is rotated by it per 256 blocks (see the kernel)
-  ConvClass cls[4];
-};
 
 // UT ("uniform tap"): C % BK == 0, so every K-step lies inside ONE tap; the per-row validity and the
 // source / kernel pointers are then recomputed only when the tap changes (every C/BK steps) and the
@@ -74,7 +42,6 @@ struct ConvGemmParams {
 #define STAMP(i)
 #endif
 
-constexpr int GEMM_ZERO_PAGE = 4096;   // floats: a whole tap of the widest layer the uniform-tap path serves
 static __device__ float g_gemm_zero_page[GEMM_ZERO_PAGE + 64];
 
 // block coordinates of the 3-D launch grid (x = M tile, y = N tile x K split, z = encoder): the body takes them as arguments
@@ -162,7 +129,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvGemmParams& p, const Ge
     for (int j = 0; j < PA; ++j) {
       long long m = m0 + tid / SPR + j * RPP;
       if (m < clsM) {
-        // 32-bit division (launch_conv_gemm checks M < 2^31): the 64-bit form is a ~150-instruction routine
+        // 32-bit division (conv_rows_beyond_32bit: every launch checks M < 2^31): the 64-bit form is a ~150-instruction routine
         long long n = (unsigned)m / (unsigned)HcWc;
         int rem = (int)(m - n * HcWc);
         int yp = rem / clsWc;
@@ -439,7 +406,6 @@ __device__ __forceinline__ void conv_gemm_body(const ConvGemmParams& p, const Ge
 #endif
 }
 
-// Sums the split-K slabs and applies the epilogue (bias, ReLU, mask).  One thread = 4 channels.
 template <int BM, int BN, int BK, int WM, int WN, bool UT>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(const ConvGemmParams p) {
   __shared__ __attribute__((aligned(16))) float smem[conv_gemm_smem_floats<BM, BN, BK>()];
@@ -469,6 +435,7 @@ __global__ __launch_bounds__(256) void conv_top_bwd_kernel(const TopBwdParams pp
   }
 }
 
+// Sums the split-K slabs and applies the epilogue (bias, ReLU, mask).  One thread = 4 channels.
 __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(const ConvGemmParams p) {
   const int g = blockIdx.y;
   const long long npix = (long long)p.N * p.Hd * p.Wd;
@@ -501,17 +468,8 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_kernel(const ConvGem
   *reinterpret_cast<f32x4*>(p.out + (long long)g * p.gs_out + e) = v;
 }
 
-// The top layer's epilogue with the state concat of the one-step decoder in it (graph.py:169-192): besides out[g][n][cell][c]
-// the ReLU'd features go to state[n][cell * Ctot + off[g] + c], and the blocks behind the epilogue's copy the joint state into
-// every cell's columns [jnt_off, jnt_off + J) -- geeco_state_concat_fwd's values, one dependent launch fewer.
-struct StateScatter {
-  float* state;
-  const float* jnt;
-  long long state_stride, jnt_stride;
-  int off[4];
-  int Ctot, jnt_off, J, cells, epi_blocks;
-};
-
+// The same with the state concat of the one-step decoder in it (StateScatter, conv_gemm_plan.h).  The slab sum is a second copy
+// on purpose: as one __device__ function it reorders the instructions of both kernels (profiles/conv_gemm_split/README.md).
 __global__ __launch_bounds__(256) void conv_splitk_epilogue_state_kernel(const ConvGemmParams p, const StateScatter sc) {
   const int g = blockIdx.y;
   if ((int)blockIdx.x >= sc.epi_blocks) {
@@ -556,75 +514,32 @@ __global__ __launch_bounds__(256) void conv_splitk_epilogue_state_kernel(const C
 
 template <int BM, int BN, int BK, int WM, int WN>
 static void launch_cfg(ConvGemmParams& p, int groups, hipStream_t s) {
-  int tiles = 0;
-  for (int c = 0; c < p.ncls; ++c) {
-    p.cls[c].tile0 = tiles;
-    tiles += (int)cdiv64(p.cls[c].M, BM);
-  }
-  dim3 grid((unsigned)tiles, (unsigned)(cdiv(p.Nout, BN) * p.ksplit), (unsigned)groups);
-  {
-    bool equal = p.ncls > 1;                    // rotation by whole classes needs equally many tiles per class
-    for (int c = 1; c < p.ncls; ++c) equal = equal && cdiv64(p.cls[c].M, BM) == cdiv64(p.cls[0].M, BM);
-    p.rot = equal ? tiles / p.ncls : 0;
-  }
-  const bool ut = p.C % BK == 0 && p.C <= GEMM_ZERO_PAGE;   // uniform taps; a tap fits the zero page
-  geeco_note_kernel("conv_gemm_kernel<%d, %d, %d, %d, %d, %s>", BM, BN, BK, WM, WN, ut ? "true" : "false");
-  if (ut)
+  static_assert(BK == GEMM_BK, "conv_plan and conv_gemm_grid count K-steps of GEMM_BK");
+  const ConvGemmGrid gr = conv_gemm_grid(p, BM, BN, groups);
+  const dim3 grid((unsigned)gr.gx, (unsigned)gr.gy, (unsigned)gr.gz);
+  geeco_note_kernel("conv_gemm_kernel<%d, %d, %d, %d, %d, %s>", BM, BN, BK, WM, WN, gr.ut ? "true" : "false");
+  if (gr.ut)
     hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, BK, WM, WN, true>), grid, dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, BK, WM, WN, false>), grid, dim3(256), 0, s, p);
 }
 
-struct ConvPlan {
-  int bm, bn, ksplit;
-};
-
-// Tile choice and split-K factor.  Split only when the launch cannot fill the chip (tiny-M layers
-// conv6..8 and their dgrads): blocks < 256 CUs and enough K-steps to share.
-static ConvPlan conv_plan(const ConvGemmParams& p, int groups) {
-  ConvPlan pl;
-  long long Mtot = 0;
-  int maxtaps = 0;
-  for (int c = 0; c < p.ncls; ++c) {
-    Mtot += p.cls[c].M;
-    if (p.cls[c].ntaps > maxtaps) maxtaps = p.cls[c].ntaps;
+// The slab sum behind a split-K launch (p.ksplit > 1); with `scatter`, the form that carries the state concat.
+static int launch_splitk_epilogue(const ConvGemmParams& p, int groups, hipStream_t s, const StateScatter* scatter) {
+  const long long total4 = (long long)p.N * p.Hd * p.Wd * p.Nout / 4;
+  dim3 grid((unsigned)cdiv64(total4, 256), (unsigned)groups);
+  if (scatter) {
+    StateScatter sc = *scatter;
+    sc.epi_blocks = (int)grid.x;
+    grid.x += (unsigned)cdiv64((long long)p.N * sc.cells * sc.J, 256);
+    geeco_note_kernel("conv_splitk_epilogue_state_kernel");
+    hipLaunchKernelGGL(conv_splitk_epilogue_state_kernel, grid, dim3(256), 0, s, p, sc);
+  } else {
+    geeco_note_kernel("conv_splitk_epilogue_kernel");
+    hipLaunchKernelGGL(conv_splitk_epilogue_kernel, grid, dim3(256), 0, s, p);
   }
-  pl.bn = (p.Nout % 64 == 0) ? 64 : (p.Nout % 48 == 0) ? 48 : (p.Nout % 32 == 0) ? 32 : 16;
-  pl.bm = 128;
-  if (pl.bn == 64 && Mtot * groups < 128 * 256) pl.bm = 64;
-  // 128-wide N tiles halve the gathered A bytes per MFMA; only when they still fill the chip
-  // (round 1: neutral to slower; since the kernel's VALU diet of round 2 the gathered bytes weigh more: -11 us per step)
-  if (p.Nout % 128 == 0 && pl.bm == 128 && (Mtot / 128) * (p.Nout / 128) * groups >= 512) pl.bn = 128;
-  // 96-wide N tiles where they (and not the 64-wide ones) make the block count a whole multiple of the CUs
-  // (conv5 forward: 768 blocks instead of 1152 = 4.5 per CU: -10 us)
-  if (pl.bn == 64 && pl.bm == 64 && p.Nout % 96 == 0 && p.ncls == 1 &&
-      (cdiv64(Mtot, 64) * (p.Nout / 96) * groups) % 256 == 0 && (cdiv64(Mtot, 64) * (p.Nout / 64) * groups) % 256 != 0)
-    pl.bn = 96;
-  long long blocks = 0;
-  for (int c = 0; c < p.ncls; ++c) blocks += cdiv64(p.cls[c].M, pl.bm);
-  blocks *= (long long)cdiv(p.Nout, pl.bn) * groups;
-  const int nk = cdiv(maxtaps * p.C, 16);
-  pl.ksplit = 1;
-  if (blocks < 640 && nk >= 16) {   // fewer than 2.5 blocks per CU: long serial K loops and a ragged tail
-    long long want = cdiv64(1024, blocks);
-    long long maxs = nk / 8;   // at least 8 K-steps per block
-    if (want > maxs) want = maxs;
-    // prefer the factor nearest to that which makes the block count a whole multiple of the 256 CUs: all blocks are
-    // co-resident and dealt evenly (scripts/dev/ub/placement.hip), so a ragged count leaves some CUs with one block
-    // more than the others for the whole launch (conv6 forward: 3 -> 2 splits, 768 blocks, -4 us)
-    long long best = 0;
-    for (long long k = 2; k <= maxs; ++k)
-      if ((blocks * k) % 256 == 0 && blocks * k <= 2048 && (best == 0 || llabs(k - want) < llabs(best - want))) best = k;
-    if (best) want = best;
-    if (want > 1) pl.ksplit = (int)want;
-  }
-  return pl;
-}
-
-static int64_t conv_ws_bytes(const ConvGemmParams& p, int groups) {
-  ConvPlan pl = conv_plan(p, groups);
-  if (pl.ksplit <= 1) return 0;
-  return (int64_t)pl.ksplit * groups * p.N * p.Hd * p.Wd * p.Nout * 4;
+  GEECO_LAUNCH_CHECK();
+  return 0;
 }
 
 #ifdef GEECO_STAMPS
@@ -651,11 +566,10 @@ extern "C" int geeco_debug_dump_stamps(const char* path) {
 #endif
 
 static int launch_conv_gemm(ConvGemmParams& p, int groups, void* ws, hipStream_t s, const StateScatter* scatter = nullptr) {
-  for (int c = 0; c < p.ncls; ++c)
-    if (p.cls[c].M + 256 >= (1ll << 31)) {
-      geeco_set_error("conv3x3: %lld rows per launch exceed the 32-bit row index of the kernel", p.cls[c].M);
-      return (int)hipErrorInvalidValue;
-    }
+  if (const long long rows = conv_rows_beyond_32bit(p)) {
+    geeco_set_error("conv3x3: %lld rows per launch exceed the 32-bit row index of the kernel", rows);
+    return (int)hipErrorInvalidValue;
+  }
 #ifdef GEECO_STAMPS
   p.stamps = geeco_stamp_buffer();
 #endif
@@ -682,78 +596,24 @@ static int launch_conv_gemm(ConvGemmParams& p, int groups, void* ws, hipStream_t
     launch_cfg<128, 16, 16, 4, 1>(p, groups, s);
   }
   GEECO_LAUNCH_CHECK();
-  if (p.ksplit > 1) {
-    const long long total4 = (long long)p.N * p.Hd * p.Wd * p.Nout / 4;
-    dim3 grid((unsigned)cdiv64(total4, 256), (unsigned)groups);
-    if (scatter) {
-      StateScatter sc = *scatter;
-      sc.epi_blocks = (int)grid.x;
-      grid.x += (unsigned)cdiv64((long long)p.N * sc.cells * sc.J, 256);
-      geeco_note_kernel("conv_splitk_epilogue_state_kernel");
-      hipLaunchKernelGGL(conv_splitk_epilogue_state_kernel, grid, dim3(256), 0, s, p, sc);
-    } else {
-      geeco_note_kernel("conv_splitk_epilogue_kernel");
-      hipLaunchKernelGGL(conv_splitk_epilogue_kernel, grid, dim3(256), 0, s, p);
-    }
-    GEECO_LAUNCH_CHECK();
-  }
-  return 0;
+  return p.ksplit > 1 ? launch_splitk_epilogue(p, groups, s, scatter) : 0;
 }
 
-static int fill_fwd(ConvGemmParams* p, int N, int H, int W, int Cin, int Cout, int stride) {
-  int Ho, Wo, pt, pl;
-  same_pad(H, 3, stride, &Ho, &pt);
-  same_pad(W, 3, stride, &Wo, &pl);
-  p->N = N; p->Hs = H; p->Ws = W; p->C = Cin;
-  p->Hd = Ho; p->Wd = Wo; p->Nout = Cout;
-  p->ss = stride; p->ds = 1; p->ncls = 1;
-  ConvClass& c = p->cls[0];
-  c.Hc = Ho; c.Wc = Wo; c.oy0 = 0; c.ox0 = 0; c.ntaps = 9;
-  c.M = (long long)N * Ho * Wo;
-  for (int ky = 0; ky < 3; ++ky)
-    for (int kx = 0; kx < 3; ++kx) {
-      c.dy[ky * 3 + kx] = ky - pt;
-      c.dx[ky * 3 + kx] = kx - pl;
-      c.wslab[ky * 3 + kx] = ky * 3 + kx;
-    }
-  return 0;
+// Which kernel family serves a layer, once per direction: every entry point below asks here, so a layer runs the same kernel
+// on every path (the bitwise statements of the tests rest on it).  Forward: LDS-halo, conv1's, else this file's gather GEMM.
+enum ConvFamily { CONV_HALO, CONV_CONV1, CONV_DGRAD_LDS, CONV_GATHER_GEMM };
+
+static ConvFamily conv_fwd_family(int H, int W, int Cin, int Cout, int stride) {
+  if (geeco_halo_fwd_handles(H, W, Cin, Cout, stride)) return CONV_HALO;
+  if (geeco_conv1_fwd_handles(Cin, Cout, stride)) return CONV_CONV1;
+  return CONV_GATHER_GEMM;
 }
 
-static int fill_dgrad(ConvGemmParams* p, int N, int H, int W, int Cin, int Cout, int stride) {
-  int Ho, Wo, pt, pl;
-  same_pad(H, 3, stride, &Ho, &pt);
-  same_pad(W, 3, stride, &Wo, &pl);
-  const int s = stride;
-  p->N = N; p->Hs = Ho; p->Ws = Wo; p->C = Cout;
-  p->Hd = H; p->Wd = W; p->Nout = Cin;
-  p->ss = 1; p->ds = s; p->relu = 0;
-  int nc = 0;
-  for (int py = 0; py < s; ++py)
-    for (int px = 0; px < s; ++px) {
-      ConvClass c = {};
-      c.Hc = (H - py + s - 1) / s;
-      c.Wc = (W - px + s - 1) / s;
-      c.oy0 = py; c.ox0 = px;
-      int nt = 0;
-      for (int ky = 0; ky < 3; ++ky) {
-        int vy = py + pt - ky;
-        if (((vy % s) + s) % s != 0) continue;
-        for (int kx = 0; kx < 3; ++kx) {
-          int vx = px + pl - kx;
-          if (((vx % s) + s) % s != 0) continue;
-          c.dy[nt] = (vy >= 0 ? vy : vy - (s - 1)) / s;   // exact (vy % s == 0)
-          c.dx[nt] = (vx >= 0 ? vx : vx - (s - 1)) / s;
-          c.wslab[nt] = ky * 3 + kx;
-          ++nt;
-        }
-      }
-      c.ntaps = nt;
-      c.M = (long long)N * c.Hc * c.Wc;
-      if (c.M <= 0) continue;
-      p->cls[nc++] = c;
-    }
-  p->ncls = nc;
-  return 0;
+// Input gradient: LDS-halo, LDS-staged, else the gather GEMM.
+static ConvFamily conv_dgrad_family(int H, int W, int Cin, int Cout, int stride) {
+  if (geeco_halo_dgrad_handles(H, W, Cin, Cout, stride)) return CONV_HALO;
+  if (geeco_dgrad_lds_handles(H, W, Cin, Cout, stride)) return CONV_DGRAD_LDS;
+  return CONV_GATHER_GEMM;
 }
 
 extern "C" int64_t geeco_conv3x3_fwd_ws_bytes(int groups, int N, int H, int W, int Cin, int Cout, int stride) {
@@ -778,19 +638,18 @@ extern "C" int geeco_conv3x3_fwd(const float* x, const float* w, const float* b,
   GEECO_CHECK_ARG(Cout % 16 == 0, "conv3x3_fwd: Cout=%d must be a multiple of 16", Cout);
   GEECO_CHECK_ARG(stride >= 1 && stride <= 4, "conv3x3_fwd: stride=%d", stride);
   {
-    int handled = 0;
-    int rc = geeco_try_halo_fwd(x, w, b, y, groups, gs_x, gs_w, gs_b, gs_y, N, H, W, Cin, Cout, stride, relu,
-                                (hipStream_t)stream, &handled);
-    if (rc || handled) return rc;
-    rc = geeco_try_conv1_fwd(x, w, b, y, groups, gs_x, gs_w, gs_b, gs_y, N, H, W, Cin, Cout, stride, relu,
-                             (hipStream_t)stream, &handled);
-    if (rc || handled) return rc;
+    const ConvFamily fam = conv_fwd_family(H, W, Cin, Cout, stride);
+    int handled = 0, rc = 0;
+    if (fam == CONV_HALO)
+      rc = geeco_try_halo_fwd(x, w, b, y, groups, gs_x, gs_w, gs_b, gs_y, N, H, W, Cin, Cout, stride, relu,
+                              (hipStream_t)stream, &handled);
+    else if (fam == CONV_CONV1)
+      rc = geeco_try_conv1_fwd(x, w, b, y, groups, gs_x, gs_w, gs_b, gs_y, N, H, W, Cin, Cout, stride, relu,
+                               (hipStream_t)stream, &handled);
+    if (rc || handled) return rc;       // a family that declines (it needs the bias) leaves the layer to the gather GEMM
   }
   ConvGemmParams p = {};
-  fill_fwd(&p, N, H, W, Cin, Cout, stride);
-  p.x = x; p.w = w; p.bias = b; p.mask = nullptr; p.out = y;
-  p.gs_x = gs_x; p.gs_w = gs_w; p.gs_b = gs_b; p.gs_out = gs_y;
-  p.relu = relu;
+  conv_fwd_problem(&p, x, w, b, y, gs_x, gs_w, gs_b, gs_y, N, H, W, Cin, Cout, stride, relu);
   return launch_conv_gemm(p, groups, ws, (hipStream_t)stream);
 }
 
@@ -805,19 +664,14 @@ extern "C" int geeco_conv3x3_fwd_state(const float* x, const float* w, const flo
   GEECO_CHECK_ARG(groups >= 1 && groups <= 4 && N >= 1 && H >= 1 && W >= 1, "conv3x3_fwd_state: bad dims");
   GEECO_CHECK_ARG(Cin % 4 == 0 && Cin >= 4 && Cout % 16 == 0 && stride >= 1 && stride <= 4, "conv3x3_fwd_state: Cin=%d Cout=%d stride=%d", Cin, Cout, stride);
   ConvGemmParams p = {};
-  fill_fwd(&p, N, H, W, Cin, Cout, stride);
+  conv_fwd_problem(&p, x, w, b, y, gs_x, gs_w, gs_b, gs_y, N, H, W, Cin, Cout, stride, 1);
   const int cells = p.Hd * p.Wd;
   GEECO_CHECK_ARG(J >= 1 && jnt_off >= 0 && jnt_off + J <= Ctot && state_stride >= (int64_t)cells * Ctot, "conv3x3_fwd_state: joint columns / state_stride");
   for (int g = 0; g < groups; ++g) {
     GEECO_CHECK_ARG(feat_off[g] >= 0 && feat_off[g] + Cout <= Ctot && (feat_off[g] + Cout <= jnt_off || feat_off[g] >= jnt_off + J),
                     "conv3x3_fwd_state: feature columns of encoder %d", g);
   }
-  // a shape geeco_conv3x3_fwd serves with one of the LDS-halo kernels must not take the gather GEMM here (same layer, same
-  // kernel on every path: the bitwise statements of the tests rest on it) -- ask the dispatchers, as geeco_conv_top_bwd does
-  if (!ws || geeco_halo_fwd_handles(H, W, Cin, Cout, stride) || geeco_conv1_fwd_handles(Cin, Cout, stride)) return GEECO_ENOSUP;
-  p.x = x; p.w = w; p.bias = b; p.mask = nullptr; p.out = y;
-  p.gs_x = gs_x; p.gs_w = gs_w; p.gs_b = gs_b; p.gs_out = gs_y;
-  p.relu = 1;
+  if (!ws || conv_fwd_family(H, W, Cin, Cout, stride) != CONV_GATHER_GEMM) return GEECO_ENOSUP;
   StateScatter sc = {};
   sc.state = state; sc.jnt = jnt; sc.state_stride = state_stride; sc.jnt_stride = jnt_stride;
   for (int g = 0; g < groups; ++g) sc.off[g] = feat_off[g];
@@ -825,15 +679,8 @@ extern "C" int geeco_conv3x3_fwd_state(const float* x, const float* w, const flo
   return launch_conv_gemm(p, groups, ws, (hipStream_t)stream, &sc);
 }
 
-// The gather GEMM reads the HWIO kernel itself (transposing it on the way into LDS) where its K-steps stay inside one
-// tap: Cout a multiple of 16 that fits the zero page.  Only the remaining shapes need the per-tap transposed copy.
-static bool dgrad_reads_hwio(int Cout) {
-  return Cout % 16 == 0 && Cout <= GEMM_ZERO_PAGE;
-}
-
 extern "C" int geeco_conv3x3_dgrad_needs_wt(int H, int W, int Cin, int Cout, int stride) {
-  return !(geeco_halo_dgrad_handles(H, W, Cin, Cout, stride) || geeco_dgrad_lds_handles(H, W, Cin, Cout, stride) ||
-           dgrad_reads_hwio(Cout));
+  return conv_dgrad_family(H, W, Cin, Cout, stride) == CONV_GATHER_GEMM && !dgrad_reads_hwio(Cout);
 }
 
 extern "C" int geeco_conv3x3_dgrad(const float* dz, const float* w, const float* wt, const float* ymask, float* dx,
@@ -845,26 +692,22 @@ extern "C" int geeco_conv3x3_dgrad(const float* dz, const float* w, const float*
   GEECO_CHECK_ARG(Cin % 16 == 0, "conv3x3_dgrad: Cin=%d must be a multiple of 16", Cin);
   GEECO_CHECK_ARG(stride >= 1 && stride <= 2, "conv3x3_dgrad: stride=%d (1 or 2)", stride);
   {
-    int handled = 0;
-    int rc = geeco_try_halo_dgrad(dz, w, ymask, dx, groups, gs_dz, gs_w, gs_dx, N, H, W, Cin, Cout, stride,
-                                  (hipStream_t)stream, &handled);
-    if (rc || handled) return rc;
-    rc = geeco_try_dgrad_lds(dz, w, ymask, dx, groups, gs_dz, gs_w, gs_dx, N, H, W, Cin, Cout, stride,
-                             (hipStream_t)stream, &handled);
-    if (rc || handled) return rc;
+    const ConvFamily fam = conv_dgrad_family(H, W, Cin, Cout, stride);
+    int handled = 0, rc = 0;
+    if (fam == CONV_HALO)
+      rc = geeco_try_halo_dgrad(dz, w, ymask, dx, groups, gs_dz, gs_w, gs_dx, N, H, W, Cin, Cout, stride,
+                                (hipStream_t)stream, &handled);
+    else if (fam == CONV_DGRAD_LDS)
+      rc = geeco_try_dgrad_lds(dz, w, ymask, dx, groups, gs_dz, gs_w, gs_dx, N, H, W, Cin, Cout, stride,
+                               (hipStream_t)stream, &handled);
+    if (rc || handled) return rc;       // a family that declines (it needs the HWIO kernel) leaves the layer to the gather GEMM
   }
   ConvGemmParams p = {};
-  fill_dgrad(&p, N, H, W, Cin, Cout, stride);
-  p.x = dz; p.w = wt; p.bias = nullptr; p.mask = ymask; p.out = dx;
-  p.gs_x = gs_dz; p.gs_w = gs_wt; p.gs_b = 0; p.gs_out = gs_dx;
-  if (w && dgrad_reads_hwio(Cout)) {
-    p.w = w; p.gs_w = gs_w; p.bt = 1;
-  }
+  conv_dgrad_problem(&p, dz, w, wt, ymask, dx, gs_dz, gs_w, gs_wt, gs_dx, N, H, W, Cin, Cout, stride);
   GEECO_CHECK_ARG(p.w, "conv3x3_dgrad: this shape (Cout = %d) needs the per-tap transposed kernel wt", Cout);
   if (p.ncls == 0) return 0;
   return launch_conv_gemm(p, groups, ws, (hipStream_t)stream);
 }
-
 
 // conv7's input gradient + conv7's / conv8's filter gradients as ONE grid (conv_top_bwd_kernel).  The input gradient's arguments as
 // geeco_conv3x3_dgrad (stride 2), the two filter-gradient problems as geeco_conv3x3_wgrad_pair.  GEECO_ENOSUP when any of the three
@@ -878,27 +721,21 @@ extern "C" int geeco_conv_top_bwd(const float* dz, const float* w, const float* 
                                   int groups, int stride, void* stream, geeco_slab_reduce* pending2) {
   GEECO_CHECK_ARG(dz && dx && (wt || w) && ws, "conv_top_bwd: null pointer");
   GEECO_CHECK_ARG(groups >= 1 && N >= 1 && H >= 1 && W >= 1 && Cout % 4 == 0 && Cin % 16 == 0, "conv_top_bwd: bad dims");
-  if (stride != 2 || geeco_halo_dgrad_handles(H, W, Cin, Cout, stride) || geeco_dgrad_lds_handles(H, W, Cin, Cout, stride)) {
+  if (stride != 2 || conv_dgrad_family(H, W, Cin, Cout, stride) != CONV_GATHER_GEMM) {
     geeco_set_error("conv_top_bwd: the input gradient of this shape is not the gather GEMM's");
     return GEECO_ENOSUP;
   }
   TopBwdParams tp = {};
   ConvGemmParams& p = tp.d;
-  fill_dgrad(&p, N, H, W, Cin, Cout, stride);
-  p.x = dz; p.w = wt; p.bias = nullptr; p.mask = ymask; p.out = dx;
-  p.gs_x = gs_dz; p.gs_w = gs_wt; p.gs_b = 0; p.gs_out = gs_dx;
-  if (w && dgrad_reads_hwio(Cout)) {
-    p.w = w; p.gs_w = gs_w; p.bt = 1;
-  }
+  conv_dgrad_problem(&p, dz, w, wt, ymask, dx, gs_dz, gs_w, gs_wt, gs_dx, N, H, W, Cin, Cout, stride);
   if (!p.w || p.ncls == 0) {
     geeco_set_error("conv_top_bwd: this input gradient needs the per-tap transposed kernel / is empty");
     return GEECO_ENOSUP;
   }
-  for (int c = 0; c < p.ncls; ++c)
-    if (p.cls[c].M + 256 >= (1ll << 31)) {
-      geeco_set_error("conv_top_bwd: %lld rows per launch exceed the 32-bit row index of the kernel", p.cls[c].M);
-      return GEECO_ENOSUP;
-    }
+  if (const long long rows = conv_rows_beyond_32bit(p)) {
+    geeco_set_error("conv_top_bwd: %lld rows per launch exceed the 32-bit row index of the kernel", rows);
+    return GEECO_ENOSUP;
+  }
   const ConvPlan pl = conv_plan(p, groups);
   if (pl.bm != 64 || pl.bn != 64) {
     geeco_set_error("conv_top_bwd: the input gradient's plan is not the 64 x 64 x 16 tile kernel");
@@ -912,33 +749,17 @@ extern "C" int geeco_conv_top_bwd(const float* dz, const float* w, const float* 
   p.stamps = nullptr;
 #endif
   p.ksplit = pl.ksplit; p.groups = groups; p.part = (float*)ws;
-  // grid and class rotation exactly as launch_cfg<64, 64, 16, 2, 2> would set them
-  int tiles = 0;
-  for (int c = 0; c < p.ncls; ++c) {
-    p.cls[c].tile0 = tiles;
-    tiles += (int)cdiv64(p.cls[c].M, 64);
-  }
-  {
-    bool equal = p.ncls > 1;
-    for (int c = 1; c < p.ncls; ++c) equal = equal && cdiv64(p.cls[c].M, 64) == cdiv64(p.cls[0].M, 64);
-    p.rot = equal ? tiles / p.ncls : 0;
-  }
-  tp.wblocks = (int)wblocks; tp.gx = tiles; tp.gy = cdiv(p.Nout, 64) * p.ksplit;
-  const bool ut = p.C % 16 == 0 && p.C <= GEMM_ZERO_PAGE;
-  const long long blocks = wblocks + (long long)tp.gx * tp.gy * groups;
+  const ConvGemmGrid gr = conv_gemm_grid(p, 64, 64, groups);      // the grid of launch_cfg<64, 64, 16, 2, 2>, as a range of block indices
+  tp.wblocks = (int)wblocks; tp.gx = gr.gx; tp.gy = gr.gy;
+  const long long blocks = wblocks + (long long)gr.gx * gr.gy * gr.gz;
   hipStream_t s = (hipStream_t)stream;
-  geeco_note_kernel("conv_top_bwd_kernel<%s>", ut ? "true" : "false");
-  if (ut)
+  geeco_note_kernel("conv_top_bwd_kernel<%s>", gr.ut ? "true" : "false");
+  if (gr.ut)
     hipLaunchKernelGGL(conv_top_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, s, tp);
   else
     hipLaunchKernelGGL(conv_top_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, s, tp);
   GEECO_LAUNCH_CHECK();
-  if (p.ksplit > 1) {
-    const long long total4 = (long long)p.N * p.Hd * p.Wd * p.Nout / 4;
-    dim3 grid((unsigned)cdiv64(total4, 256), (unsigned)groups);
-    geeco_note_kernel("conv_splitk_epilogue_kernel");
-    hipLaunchKernelGGL(conv_splitk_epilogue_kernel, grid, dim3(256), 0, s, p);
-    GEECO_LAUNCH_CHECK();
-  }
+  if (p.ksplit > 1)
+    if (int rc = launch_splitk_epilogue(p, groups, s, nullptr)) return rc;
   return geeco_wgrad_pair_finish(tp.w, groups, s, pending2);
 }

@@ -7,6 +7,7 @@
 #include <atomic>
 
 #include "../../include/geeco_hip.h"
+#include "geeco_intmath.h"      // cdiv, cdiv64, same_pad
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -53,18 +54,6 @@ static int geeco_lds_opt_in(size_t lds) {
     attr_set = true;
   }
   return 0;
-}
-
-static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-// TF 'SAME' padding: out = ceil(in/s); pad_total = max((out-1)s + k - in, 0); before = total/2.
-static inline void same_pad(int size, int k, int s, int* out, int* before) {
-  int o = (size + s - 1) / s;
-  int tot = (o - 1) * s + k - size;
-  if (tot < 0) tot = 0;
-  *out = o;
-  *before = tot / 2;
 }
 
 __device__ __forceinline__ float wave_reduce_sum(float v) {

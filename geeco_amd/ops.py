@@ -279,6 +279,15 @@ def conv3x3_wgrad_into(dw, db, x, dz, G, gs_x, gs_dz, gs_dw, gs_db, N, H, W, Cin
     pending.append(item)
 
 
+def _take_pending(items, pending):
+  """Appends copies of the slab sums a paired launch recorded in the ctypes array ``items`` (S > 0) to ``pending``."""
+  for it in items if items is not None else ():
+    if it.S > 0:
+      c = _native.SlabReduce()
+      ctypes.memmove(ctypes.byref(c), ctypes.byref(it), ctypes.sizeof(c))
+      pending.append(c)
+
+
 def conv3x3_wgrad_pair_into(a, b, G, stride, pending=None):
   """Two independent filter gradients in ONE launch (``geeco_conv3x3_wgrad_pair``).  ``a`` / ``b``: dicts with the arguments of
   ``conv3x3_wgrad_into`` (dw, db, x, dz, gs_x, gs_dz, gs_dw, gs_db, N, H, W, Cin, Cout, ws); ``a`` = the longer problem.
@@ -293,12 +302,7 @@ def conv3x3_wgrad_pair_into(a, b, G, stride, pending=None):
   if rc == _native.GEECO_ENOSUP:
     return False
   check(rc, 'geeco_conv3x3_wgrad_pair')
-  if items is not None:
-    for it in items:
-      if it.S > 0:
-        c = _native.SlabReduce()
-        ctypes.memmove(ctypes.byref(c), ctypes.byref(it), ctypes.sizeof(c))
-        pending.append(c)
+  _take_pending(items, pending)
   return True
 
 
@@ -317,12 +321,7 @@ def conv_top_bwd_into(d, a, b, G, stride, pending=None):
   if rc == _native.GEECO_ENOSUP:
     return False
   check(rc, 'geeco_conv_top_bwd')
-  if items is not None:
-    for it in items:
-      if it.S > 0:
-        c = _native.SlabReduce()
-        ctypes.memmove(ctypes.byref(c), ctypes.byref(it), ctypes.sizeof(c))
-        pending.append(c)
+  _take_pending(items, pending)
   return True
 
 

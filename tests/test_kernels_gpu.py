@@ -1282,36 +1282,39 @@ def test_wgrad_pair_conv7_conv8_bitwise(dev, G, N, dim_out):
   assert ops.conv3x3_wgrad_pair_into(bad, probs[1], G, 2) is False
 
 
-@pytest.mark.parametrize('G,N,dim_out', [(3, 32, 256), (1, 5, 256), (2, 3, 128)])
-def test_top_bwd_heterogeneous_grid_bitwise(dev, G, N, dim_out):
+@pytest.mark.parametrize('G,N,dim_out,H', [(3, 32, 256, 8), (1, 5, 256, 8), (2, 3, 128, 8), (1, 32, 256, 7)],
+                         ids=['3-32-256', '1-5-256', '2-3-128', '1-32-256-7x7'])
+def test_top_bwd_heterogeneous_grid_bitwise(dev, G, N, dim_out, H):
   """conv7's input gradient + conv7's / conv8's filter gradients as ONE heterogeneous grid (geeco_conv_top_bwd) against the
   separate launches (geeco_conv3x3_dgrad, 2 x geeco_conv3x3_wgrad): dx, both dw and both db bitwise; the separate input
-  gradient really is the gather GEMM with split K for this shape; a shape the LDS-staged kernels serve is refused."""
+  gradient really is the gather GEMM with split K for this shape; a shape the LDS-staged kernels serve is refused.
+  7 x 7: the four parity classes have 8 / 6 / 6 / 5 tiles of 64 rows, so the grid has no class rotation (rot = 0; equal tile
+  counts, as at 8 x 8, rotate), and the odd size keeps the LDS-halo and LDS-staged kernels out."""
   from geeco_amd import ops
   r = np.random.default_rng(97)
-  # conv7: 8 x 8 x 256 -> 4 x 4 x 256; conv8: 4 x 4 x 256 -> 2 x 2 x dim_out
-  x6 = torch.tensor(r.standard_normal([G, N, 8, 8, 256]).astype(np.float32), device=dev)        # conv7's input (ReluGrad mask of dx)
+  # conv7: H x H x 256 -> 4 x 4 x 256; conv8: 4 x 4 x 256 -> 2 x 2 x dim_out
+  x6 = torch.tensor(r.standard_normal([G, N, H, H, 256]).astype(np.float32), device=dev)        # conv7's input (ReluGrad mask of dx)
   dz7 = torch.tensor(r.standard_normal([G, N, 4, 4, 256]).astype(np.float32), device=dev)
   x7 = torch.tensor(r.standard_normal([G, N, 4, 4, 256]).astype(np.float32), device=dev)        # conv8's input
   dz8 = torch.tensor(r.standard_normal([G, N, 2, 2, dim_out]).astype(np.float32), device=dev)
   w7 = torch.tensor((r.standard_normal([G, 3, 3, 256, 256]) / 48).astype(np.float32), device=dev)
-  dws = torch.empty(ops.conv3x3_dgrad_ws_bytes(G, N, 8, 8, 256, 256, 2) // 4 + 4, device=dev)
-  dx_ref = torch.full((G, N, 8, 8, 256), float('nan'), device=dev)
-  names = ops.kernel_trace(lambda: ops.conv3x3_dgrad_into(dx_ref, dz7, None, x6, G, dz7[0].numel(), 0, dx_ref[0].numel(), N, 8, 8, 256,
+  dws = torch.empty(ops.conv3x3_dgrad_ws_bytes(G, N, H, H, 256, 256, 2) // 4 + 4, device=dev)
+  dx_ref = torch.full((G, N, H, H, 256), float('nan'), device=dev)
+  names = ops.kernel_trace(lambda: ops.conv3x3_dgrad_into(dx_ref, dz7, None, x6, G, dz7[0].numel(), 0, dx_ref[0].numel(), N, H, H, 256,
                                                           256, 2, ws=dws, w=w7, gs_w=w7[0].numel()))
-  assert names[0].startswith('conv_gemm_kernel<64, 64, 16'), names
+  assert names[0].startswith('conv_gemm_kernel<64, 64, 16') and 'conv_splitk_epilogue_kernel' in names, names
   wg = []
-  for x, dz, H, Cout in ((x6, dz7, 8, 256), (x7, dz8, 4, dim_out)):
-    ws = torch.empty(ops.conv3x3_wgrad_ws_bytes(G, N, H, H, 256, Cout, 2) // 4 + 4, device=dev)
+  for x, dz, Hl, Cout in ((x6, dz7, H, 256), (x7, dz8, 4, dim_out)):
+    ws = torch.empty(ops.conv3x3_wgrad_ws_bytes(G, N, Hl, Hl, 256, Cout, 2) // 4 + 4, device=dev)
     dw_ref = torch.full((G, 9 * 256 * Cout), float('nan'), device=dev)
     db_ref = torch.full((G, Cout), float('nan'), device=dev)
-    ops.conv3x3_wgrad_into(dw_ref, db_ref, x, dz, G, x[0].numel(), dz[0].numel(), dw_ref[0].numel(), Cout, N, H, H, 256, Cout, 2, ws)
+    ops.conv3x3_wgrad_into(dw_ref, db_ref, x, dz, G, x[0].numel(), dz[0].numel(), dw_ref[0].numel(), Cout, N, Hl, Hl, 256, Cout, 2, ws)
     wg.append((dw_ref, db_ref, dict(dw=torch.full_like(dw_ref, float('nan')), db=torch.full_like(db_ref, float('nan')), x=x, dz=dz,
-                                    gs_x=x[0].numel(), gs_dz=dz[0].numel(), gs_dw=dw_ref[0].numel(), gs_db=Cout, N=N, H=H, W=H, Cin=256,
+                                    gs_x=x[0].numel(), gs_dz=dz[0].numel(), gs_dw=dw_ref[0].numel(), gs_db=Cout, N=N, H=Hl, W=Hl, Cin=256,
                                     Cout=Cout, ws=torch.empty_like(ws))))
   dx = torch.full_like(dx_ref, float('nan'))
-  d = dict(dx=dx, dz=dz7, wt=None, ymask=x6, w=w7, gs_dz=dz7[0].numel(), gs_w=w7[0].numel(), gs_wt=0, gs_dx=dx[0].numel(), N=N, H=8,
-           W=8, Cin=256, Cout=256, ws=torch.empty_like(dws))
+  d = dict(dx=dx, dz=dz7, wt=None, ymask=x6, w=w7, gs_dz=dz7[0].numel(), gs_w=w7[0].numel(), gs_wt=0, gs_dx=dx[0].numel(), N=N, H=H,
+           W=H, Cin=256, Cout=256, ws=torch.empty_like(dws))
   pending = []
   names = ops.kernel_trace(lambda: ops.conv_top_bwd_into(d, wg[0][2], wg[1][2], G, 2, pending=pending))
   ops.slab_reduce_batch(pending)
