@@ -80,6 +80,9 @@ SIGNATURES = {
     'geeco_predict_pack': (_I, [_P, _I, _I, _I, POINTER(_I), POINTER(_I), POINTER(_I), _P, _I, _P, _P, _P, _P, _L, _I, _P, _P]),
     'geeco_predict_pack_newest': (_I, [_P, _I, _I, _L, _I, _P, _P]),
     'geeco_predict_push_features': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P]),
+    'geeco_pack_frames_by_address': (_I, [_P, _I, _I, _L, _P, _P]),
+    'geeco_window_states_fwd': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
+    'geeco_window_states_bwd': (_I, [_P, _L, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     'geeco_conv3x3_fwd': (_I, [_P, _P, _P, _P, _I, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     'geeco_conv3x3_fwd_state': (_I, [_P, _P, _P, _P, _I, _L, _L, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P, _L, _I, _I, _P, _L, _P]),
     'geeco_conv3x3_fwd_ws_bytes': (_L, [_I, _I, _I, _I, _I, _I, _I]),

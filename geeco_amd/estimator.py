@@ -182,6 +182,17 @@ class _SummarySaverHook:
     print('INFO: loss = %.6f, step = %d' % (parts['loss'], step), flush=True)
 
 
+def shared_frames_capacity(shared, N, K, goal):
+  """Slots of the frame table for ``params['shared_frames']``: an integer is taken as given; True = N + 2 (K - 1), + 2 for the
+  goal model.  N consecutive windows of ONE episode hold N + K - 1 distinct frames; input_fn shuffles episodes, not windows, so
+  a batch no larger than the windows of an episode spans at most two episodes: N + 2 (K - 1) frames, and for the goal model one
+  target frame per episode (the episode's last frame is uploaded beside the windowable ones).  A batch that needs more (batches
+  larger than an episode's windows) makes the feed raise with the number needed: pass that as an integer."""
+  if isinstance(shared, bool):
+    return N + 2 * (K - 1) + (2 if goal else 0)
+  return int(shared)
+
+
 def _model_fn(features, labels, mode, params, goal):
   cfg = params['e2evmc_config']
   if cfg.img_channels not in (3, 4):
@@ -194,12 +205,31 @@ def _model_fn(features, labels, mode, params, goal):
   N = int(rgb.shape[0])
   training = mode == ModeKeys.TRAIN
   ctor = graph.GoalE2EVMC if goal else graph.E2EVMC
-  model = ctor(cfg, N, rgb.device, training=training, store=params.get('_variable_store'))
+  shared = params.get('shared_frames')
+  tables = {}
+  if shared:
+    # params['shared_frames'] (True, or a capacity F): encode each distinct frame of the batch once
+    if gdist.world_size() > 1:
+      raise ValueError("params['shared_frames'] is single-GPU: with %d ranks the gradient exchange of the shared-frame step "
+                       "has not been decided" % gdist.world_size())
+    if getattr(rgb, 'shared', None) is None:
+      raise ValueError("params['shared_frames'] needs the windows as input_fn.DeviceWindows (pickplace_input_fn(device='cuda')): "
+                       "dense 'rgb' tensors hold every frame K times and no frame addresses")
+    F = shared_frames_capacity(shared, N, cfg.window_size, goal)
+    model = ctor(cfg, N, rgb.device, training=training, store=params.get('_variable_store'), shared_frames=F)
+    tables = rgb.frame_table(F, with_targets=goal)
+    model.frames_u8 = rgb.u8
+    for k, v in tables.items():
+      model.inputs[k] = v
+  else:
+    model = ctor(cfg, N, rgb.device, training=training, store=params.get('_variable_store'))
   # adopt the caller's static buffers as the model inputs (placeholders)
   source = lambda k: labels.get(k) if (labels is not None and k in model.label_keys) else features.get(k)
   # all of the model's image inputs that CAN come as window addresses must, or none does
   take_u8 = bool(model.u8_window_keys) and all(getattr(source(k), 'u8', False) for k in model.u8_window_keys)
   for k in list(model.inputs.keys()):
+    if k in tables:
+      continue
     src = source(k)
     if src is None:
       if mode == ModeKeys.PREDICT and k in model.label_keys + ['ee_state', 'obj_state']:
@@ -358,6 +388,7 @@ class Estimator:
     if key in self._specs:
       return self._specs[key]
     dev = self._device()
+    shared = self.params.get('shared_frames')
     # one arena for everything the host writes per batch (states, labels, window address tables): one H2D copy per step
     from .input_fn import FeedArena, WindowFeed
     arena = FeedArena(dev)
@@ -365,7 +396,12 @@ class Estimator:
     for tag, d in (('features', feats), ('labels', labels)):
       for k, v in (d or {}).items():
         if hasattr(v, 'materialize_into'):      # input_fn.DeviceWindows: windows of HBM-resident episodes
-          feeds[tag, k] = WindowFeed(v, arena, (tag, k))
+          kw = {}
+          if shared and (tag, k) == ('features', 'rgb'):
+            # room for the table either model_fn asks for (the goal model's holds the target frames too)
+            has_tgt = hasattr(feats.get('target_rgb'), 'materialize_into')
+            kw = dict(shared_frames=shared_frames_capacity(shared, n, v.K, has_tgt), shared_targets='target_rgb' if has_tgt else None)
+          feeds[tag, k] = WindowFeed(v, arena, (tag, k), **kw)
         elif isinstance(v, np.ndarray) and v.nbytes <= self._ARENA_MAX_BYTES:
           arena.reserve((tag, k), v.shape, v.dtype)
         else:                                   # device tensors (synthetic inputs), dense host windows: a buffer and a copy of their own
@@ -389,7 +425,8 @@ class Estimator:
     # only the buffers the model adopted are fed per batch
     used = {id(v) for v in spec.model.inputs.values()}
     fbuf = _FeedDict(arena, 'features', {k: v for k, v in fbuf.items() if id(v) in used or
-                                         (getattr(v, 'buffer', None) is not None and id(v.buffer) in used)})
+                                         (getattr(v, 'buffer', None) is not None and id(v.buffer) in used) or
+                                         getattr(v, 'feeds_frame_table', False)})
     lbuf = _FeedDict(arena, 'labels', {k: v for k, v in (lbuf or {}).items() if id(v) in used})
     self._specs[key] = (spec, fbuf, lbuf)
     return self._specs[key]
@@ -416,8 +453,8 @@ class Estimator:
       bufs.arena.begin()
     for k, buf in bufs.items():
       src = batch[k]
-      if hasattr(buf, 'feed'):                 # input_fn.WindowFeed: repoint the address table or gather into the dense buffer
-        buf.feed(src)
+      if hasattr(buf, 'feed'):                 # input_fn.WindowFeed: repoint the address / frame tables or gather into the dense buffer
+        buf.feed(src, batch)
       elif bufs.arena.has((bufs.tag, k)):
         bufs.arena.write((bufs.tag, k), src.detach().cpu().numpy() if torch.is_tensor(src) else src)
       elif hasattr(src, 'materialize_into'):

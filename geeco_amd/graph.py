@@ -613,8 +613,9 @@ class LSTMDecoder:
 class _ModelBase:
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
-  def __init__(self, cfg, N, device, goal, training, store=None):
+  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
+    self.shared_frames = self._check_shared_frames(cfg, goal, shared_frames)
     self.device = torch.device(device)
     self.K = cfg.window_size
     self.H, self.W, self.C = cfg.img_height, cfg.img_width, cfg.img_channels
@@ -626,8 +627,18 @@ class _ModelBase:
     self.store = store or VariableStore(shapes, self.device, uniform_scopes=encoder_scopes)
     f32 = dict(dtype=torch.float32, device=self.device)
     N, K, H, W = self.N, self.K, self.H, self.W
+    F = self.shared_frames
+    if F is not None:
+      # shared frames: a table of F resident frames + the windows' slot indices stand in for the dense windows
+      images = {'frame_table': torch.zeros(F, dtype=torch.int64, device=self.device),
+                'frame_index': torch.zeros(N, K, dtype=torch.int32, device=self.device)}
+      if goal:
+        images['target_index'] = torch.zeros(N, dtype=torch.int32, device=self.device)
+      self.frames_u8 = True     # the kind of the table's frames (uint8 / 255 or float32): fixed before the step is captured
+    else:
+      images = {'rgb': torch.zeros(N, K, H, W, 3, **f32)}
     self.inputs = {
-        'rgb': torch.zeros(N, K, H, W, 3, **f32),
+        **images,
         'jnt_state': torch.zeros(N, K, cfg.dim_jnt_state, **f32),
         'ee_state': torch.zeros(N, K, 7, **f32),
         'obj_state': torch.zeros(N, K, 7, **f32),
@@ -644,7 +655,7 @@ class _ModelBase:
       raise ValueError("Unknown control mode '%s'" % (cfg.control_mode,))
     if self.C == 4:
       self.inputs['depth'] = torch.zeros(N, K, H, W, 1, **f32)
-    if goal:
+    if goal and F is None:
       self.inputs['target_rgb'] = torch.zeros(N, H, W, 3, **f32)
       if self.C == 4:
         self.inputs['target_depth'] = torch.zeros(N, H, W, 1, **f32)
@@ -659,6 +670,38 @@ class _ModelBase:
       self.obs4 = torch.empty(N, K, H, W, 4, **f32)
       if goal:
         self.tgt4 = torch.empty(N, H, W, 4, **f32)
+
+  @staticmethod
+  def _check_shared_frames(cfg, goal, shared_frames):
+    """``shared_frames=F``: the encoder runs once per DISTINCT frame of the batch, F slots.  Returns F or None."""
+    if shared_frames is None:
+      return None
+    F = int(shared_frames)
+    if F < 1:
+      raise ValueError('shared_frames=%r: the frame table needs at least one slot' % (shared_frames,))
+    if goal and cfg.proc_obs == 'dynimg':
+      raise ValueError("shared_frames: proc_obs='dynimg' encodes one frame and two dynamic images per window, nothing is shared "
+                       "between windows")
+    if goal and cfg.proc_tgt == 'dyndiff':
+      raise ValueError("shared_frames: proc_tgt='dyndiff' encodes a (frame, target) pair image per window position; it would "
+                       "need a second table")
+    if cfg.img_channels == 4:
+      raise ValueError('shared_frames: img_channels=4 (RGB-D) is not supported, depth is a separate float32 stream')
+    return F
+
+  def _encode_shared(self, mode, ch):
+    """Shared-frame forward up to the decoder's states: pack the table's frames, encode the F slots once, gather."""
+    N, K, F, d, inp = self.N, self.K, self.shared_frames, self.decoder, self.inputs
+    ops.pack_frames_by_address_into(self.enc.x_in[0], inp['frame_table'], F, self.H * self.W, self.frames_u8)
+    self.enc.forward()
+    ops.window_states_fwd_into(d.states, self.enc.features[0], inp['frame_index'], inp['jnt_state'], mode, F, N, K, _CELLS, ch,
+                               self.cfg.dim_jnt_state, d.D, tgt_idx=inp.get('target_index'))
+
+  def _scatter_shared(self, mode, ch):
+    """Its adjoint: d(states) -> the gradient of the F slots' features (ReluGrad of conv8 applied)."""
+    N, K, F, d, inp = self.N, self.K, self.shared_frames, self.decoder, self.inputs
+    ops.window_states_bwd_into(self.enc.dfeatures[0], d.dstates, d.D, inp['frame_index'], self.enc.features[0], mode, F, N, K,
+                               _CELLS, ch, self.cfg.dim_jnt_state, tgt_idx=inp.get('target_index'))
 
   # image inputs this model can read as uint8 frames behind window addresses (input_fn.WindowFeed.pointers()) instead of dense
   # float32 windows; () = none
@@ -862,8 +905,9 @@ class _ModelBase:
 class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False):
-    super().__init__(cfg, N, device, goal=True, training=training, store=store)
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None):
+    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only): see E2EVMC."""
+    super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -877,7 +921,7 @@ class GoalE2EVMC(_ModelBase):
       self.feat_ch = [cfg.dim_s_obs, cfg.dim_s_dyn, cfg.dim_s_diff]
       dims = self.feat_ch
     elif self.mode in ('seq_constant', 'seq_residual'):   # target goes through the SAME ConvEncoder (:354, 364)
-      scopes, Nf, T = [root + '/ConvEncoder'], (K + 1) * N, K
+      scopes, Nf, T = [root + '/ConvEncoder'], self.shared_frames or (K + 1) * N, K
       self.feat_ch = [cfg.dim_s_obs, cfg.dim_s_obs] if self.mode == 'seq_constant' else [cfg.dim_s_obs]
       dims = [cfg.dim_s_obs]
     else:                                  # seq_dyndiff (:371-381)
@@ -888,8 +932,9 @@ class GoalE2EVMC(_ModelBase):
     D = _CELLS * (sum(self.feat_ch) + jn)
     self.decoder = LSTMDecoder(self.store, root + '/LSTMDecoder', cfg, N, T, D, training, one_launch=one_launch_decoder)
     self._bind_labels()
-    self.dyn_ws = ops.dynimg_ws(N, H * W * 4, self.device)
-    self.dyn_ws2 = ops.goal_dynimgs_ws(N, H * W, self.device)      # control block of the one-pass input stage (zero-filled once)
+    if self.shared_frames is None:      # (the shared-frame step forms no dynamic image)
+      self.dyn_ws = ops.dynimg_ws(N, H * W * 4, self.device)
+      self.dyn_ws2 = ops.goal_dynimgs_ws(N, H * W, self.device)      # control block of the one-pass input stage (zero-filled once)
     # geeco-f reads its K-frame window ONCE, in the input kernel: that kernel can take the episodes' resident uint8 frames
     # directly (RGB, or RGB of RGB-D with depth dense), see ops.goal_dynimgs_u8_into
     if self.mode == 'dynimg' and (H * W) % 4 == 0 and (C == 3 or self.split_rgbd):
@@ -916,6 +961,11 @@ class GoalE2EVMC(_ModelBase):
     jn = self.cfg.dim_jnt_state
     jnts = self.inputs['jnt_state']
     d = self.decoder
+    if self.shared_frames is not None:
+      self._encode_shared(self.mode[4:], self.feat_ch[0])
+      d.forward(backward_too)
+      self._finish_forward()
+      return
     u8 = hasattr(self.inputs['rgb'], 'pointers')          # estimator: the Estimator bound window addresses (uint8 frames)
     if u8 and not hasattr(self.inputs['target_rgb'], 'pointers'):
       raise RuntimeError('GoalE2EVMC: rgb comes as window addresses but target_rgb as a dense tensor')
@@ -992,6 +1042,9 @@ class GoalE2EVMC(_ModelBase):
                 cells=_CELLS)
       if not d.backward(concat=cc):
         ops.state_concat_bwd_into(cc['dfeats'], d.dstates[0], d.D, cc['feats'], self.feat_ch, 2, jn, N, _CELLS)
+    elif self.shared_frames is not None:
+      d.backward()
+      self._scatter_shared(self.mode[4:], self.feat_ch[0])
     elif self.mode in ('seq_constant', 'seq_residual'):
       d.backward()
       ch = self.feat_ch[0]
@@ -1031,11 +1084,15 @@ class GoalE2EVMC(_ModelBase):
 class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False):
-    super().__init__(cfg, N, device, goal=False, training=training, store=store)
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None):
+    """``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
+    'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (input_fn.DeviceWindows.frame_table); the encoder
+    runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
+    gradients up to summation order."""
+    super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     # frames are processed time-major ([K][N]) so that step t's features are one dense block
-    self.enc = ConvEncoderStack(self.store, ['VMC/ConvEncoder'], K * N, H, W, C, 256, training)
+    self.enc = ConvEncoderStack(self.store, ['VMC/ConvEncoder'], self.shared_frames or K * N, H, W, C, 256, training)
     D = _CELLS * (256 + cfg.dim_jnt_state)
     self.decoder = LSTMDecoder(self.store, 'VMC/LSTMDecoder', cfg, N, K, D, training, one_launch=one_launch_decoder)
     self._bind_labels()
@@ -1044,6 +1101,11 @@ class E2EVMC(_ModelBase):
     self._begin_step(backward_too)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     HW = H * W
+    if self.shared_frames is not None:
+      self._encode_shared('plain', 256)
+      self.decoder.forward(backward_too)
+      self._finish_forward()
+      return
     x_in = self.enc.x_in[0].view(K, N, H, W, 4)
     frames, _ = self._frames()
     for t in range(K):
@@ -1066,10 +1128,13 @@ class E2EVMC(_ModelBase):
     N, K = self.N, self.K
     d = self.decoder
     d.backward()
-    feats = self.enc.features[0].view(K, N, _CELLS, 256)
-    dfe = self.enc.dfeatures[0].view(K, N, _CELLS, 256)
-    for t in range(K):
-      ops.state_concat_bwd_into([dfe[t]], d.dstates[t], d.D, [feats[t]], [256], 1, self.cfg.dim_jnt_state, N, _CELLS)
+    if self.shared_frames is not None:
+      self._scatter_shared('plain', 256)
+    else:
+      feats = self.enc.features[0].view(K, N, _CELLS, 256)
+      dfe = self.enc.dfeatures[0].view(K, N, _CELLS, 256)
+      for t in range(K):
+        ops.state_concat_bwd_into([dfe[t]], d.dstates[t], d.D, [feats[t]], [256], 1, self.cfg.dim_jnt_state, N, _CELLS)
     self.enc.backward(hi=7, lo=ConvEncoderStack.SPLIT if part == 'upper' else 0, defer_dgrad=part == 'upper',
                       prepare=self._prepare_args(adam_prepare and defer_sums is None), defer_sums=defer_sums if part == 'upper' else None)
 

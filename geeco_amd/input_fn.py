@@ -257,6 +257,18 @@ class DeviceWindows:
     return bool(self.segments) and all(
         f is not None and d == 255.0 and f.dtype == torch.uint8 and f.is_contiguous() for f, _, d in self.segments)
 
+  def _check_resident(self, frames_dev, starts, device):
+    """One segment's frames are uploaded, live on ``device`` (None: not checked here) and hold every window of ``starts``."""
+    if frames_dev is None:
+      raise RuntimeError('DeviceWindows: this image stream was not uploaded (device_keys excluded it)')
+    if device is not None and frames_dev.device != device:
+      raise RuntimeError('DeviceWindows: episode frames live on %s but the model on %s (each rank must upload to its '
+                         'own GPU)' % (frames_dev.device, device))
+    T = frames_dev.shape[0]
+    if len(starts) and (int(starts.min()) < 0 or int(starts.max()) + self.K > T):
+      raise IndexError('DeviceWindows: window [%d, %d) outside the %d resident frames' %
+                       (int(starts.min()), int(starts.max()) + self.K, T))
+
   def addresses(self, device):
     """int64 address of each window's first frame (WindowFeed.pointers(): the input kernel follows them)."""
     fe = int(np.prod(self.frame_shape))
@@ -264,16 +276,71 @@ class DeviceWindows:
     off = 0
     device = resolve_device(device)
     for frames_dev, starts, _ in self.segments:
-      if frames_dev.device != device:
-        raise RuntimeError('DeviceWindows: episode frames live on %s but the model on %s (each rank must upload to its '
-                           'own GPU)' % (frames_dev.device, device))
-      T = frames_dev.shape[0]
-      if len(starts) and (int(starts.min()) < 0 or int(starts.max()) + self.K > T):
-        raise IndexError('DeviceWindows: window [%d, %d) outside the %d resident frames' %
-                         (int(starts.min()), int(starts.max()) + self.K, T))
+      self._check_resident(frames_dev, starts, device)
       out[off:off + len(starts)] = frames_dev.data_ptr() + starts.astype(np.int64) * fe
       off += len(starts)
     return out
+
+  def _frame_addresses(self, device):
+    """int64 [n][K] address of every frame of every window, after the residency and device checks of ``addresses``; also
+    the set of frame kinds met ('u8' / 'f32')."""
+    import torch
+    fe = int(np.prod(self.frame_shape))
+    out = np.empty((self.n, self.K), np.int64)
+    kinds, off = set(), 0
+    for frames_dev, starts, divisor in self.segments:
+      self._check_resident(frames_dev, starts, device)
+      if frames_dev.dtype == torch.uint8 and divisor == 255.0:
+        kinds.add('u8')
+        esz = 1
+      elif frames_dev.dtype == torch.float32 and divisor == 1.0:
+        kinds.add('f32')
+        esz = 4
+      else:
+        raise ValueError('DeviceWindows.frame_table: frames of type %s with divisor %g are neither the uint8 (255) nor the '
+                         'float32 (1) form' % (frames_dev.dtype, divisor))
+      pos = starts.astype(np.int64)[:, None] + np.arange(self.K, dtype=np.int64)[None, :]
+      out[off:off + len(starts)] = frames_dev.data_ptr() + pos * (fe * esz)
+      off += len(starts)
+    return out, kinds
+
+  def frame_table(self, capacity, targets=None, device=None):
+    """The batch's DISTINCT frames, each once (shared-frame training, graph.py ``shared_frames``): returns
+    (addresses int64 [capacity], index int32 [n][K], target_index int32 [n] or None, used).  ``addresses[index[n][t]]`` is the
+    address of window n's frame t and ``addresses[target_index[n]]`` that of window n's frame of ``targets`` (a K = 1
+    DeviceWindows of the same batch, e.g. 'target_rgb'); slots are numbered in first-use order -- this stream's windows row by
+    row, then the targets -- across segments and across the two streams, and the table is zero-padded to ``capacity``
+    (0 = unused slot).  Residency and device checks as ``addresses`` (``device`` None: the segments must share one device).
+    Raises ValueError when the batch mixes uint8 and float32 episodes (the pack kernel takes one kind per call) or needs more
+    than ``capacity`` slots."""
+    if device is not None:
+      device = resolve_device(device)
+    streams = [self] if targets is None else [self, targets]
+    if targets is not None and (targets.n, targets.K, targets.frame_shape) != (self.n, 1, self.frame_shape):
+      raise ValueError('DeviceWindows.frame_table: targets must be %d single frames of shape %s' % (self.n, self.frame_shape))
+    devices = {f.device for dw in streams for f, _, _ in dw.segments if f is not None}
+    if device is None and len(devices) > 1:
+      raise RuntimeError('DeviceWindows: episode frames live on several devices (%s)' % sorted(map(str, devices)))
+    addr, kinds = [], set()
+    for dw in streams:
+      a, k = dw._frame_addresses(device)
+      addr.append(a.ravel())
+      kinds |= k
+    if len(kinds) > 1:
+      raise ValueError('DeviceWindows.frame_table: the batch mixes uint8 and float32 episodes (one frame kind per table)')
+    flat = np.concatenate(addr)
+    uniq, first, inv = np.unique(flat, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind='stable')          # distinct addresses by first use
+    used = len(uniq)
+    if used > capacity:
+      raise ValueError('DeviceWindows.frame_table: the batch holds %d distinct frames, the table has capacity %d' % (used, capacity))
+    slot = np.empty(used, np.int32)
+    slot[order] = np.arange(used, dtype=np.int32)
+    index = slot[inv.ravel()]
+    table = np.zeros(capacity, np.int64)
+    table[:used] = uniq[order]
+    nk = self.n * self.K
+    return table, index[:nk].reshape(self.n, self.K), (index[nk:].copy() if targets is not None else None), used
 
   def materialize_into(self, out):
     import torch
@@ -392,10 +459,19 @@ class WindowFeed:
     * ``dense()``: a float32 [n, K, *frame_shape] buffer filled by geeco_gather_windows per batch.
   ``feed(windows)`` then repoints / refills per batch; both are stream-ordered in front of the replay."""
 
-  def __init__(self, windows, arena, key):
+  def __init__(self, windows, arena, key, shared_frames=None, shared_targets=None):
+    """``shared_frames`` (a capacity F; the 'rgb' slot of a model built with shared_frames=F): the arena also carries the
+    batch's frame table [F], frame index [n][K] and, with ``shared_targets`` (the key of the target stream in the same
+    batch), target index [n] -- see ``frame_table``."""
     self.n, self.K, self.frame_shape, self.squeeze_k = windows.n, windows.K, windows.frame_shape, windows.squeeze_k
     self.arena, self.key, self.device = arena, key, arena.device
     self.u8 = windows.is_u8()
+    self.shared, self.shared_targets, self.feeds_frame_table = shared_frames, shared_targets, False
+    if shared_frames is not None:
+      arena.reserve(key + ('frame_table',), (int(shared_frames),), np.int64)
+      arena.reserve(key + ('frame_index',), (self.n, self.K), np.int32)
+      if shared_targets is not None:
+        arena.reserve(key + ('target_index',), (self.n,), np.int32)
     self.shape = tuple(windows.shape)
     self.table = self.buffer = None
     self._want_table = False
@@ -415,15 +491,51 @@ class WindowFeed:
       self.table = self.arena.view(self.key)
     return self
 
+  def frame_table(self, capacity=None, with_targets=True):
+    """The third form (models built with shared_frames=F): {'frame_table' [capacity], 'frame_index' [n][K][, 'target_index'
+    [n]]} device views of the arena that ``feed`` rewrites per batch from ``DeviceWindows.frame_table``; neither fp32 windows
+    nor per-window address tables are written.  ``capacity`` <= the slots reserved at construction (default: all of them)."""
+    if self.shared is None:
+      raise RuntimeError('WindowFeed.frame_table(): the slot was built without shared_frames')
+    reserved = self.arena.view(self.key + ('frame_table',))
+    capacity = reserved.numel() if capacity is None else int(capacity)
+    if capacity > reserved.numel():
+      raise ValueError('WindowFeed.frame_table(): %d slots asked for, %d reserved' % (capacity, reserved.numel()))
+    if with_targets and self.shared_targets is None:
+      raise RuntimeError('WindowFeed.frame_table(): the batch has no target stream')
+    self.feeds_frame_table, self.shared, self._with_targets = True, capacity, bool(with_targets)
+    out = {'frame_table': reserved[:capacity], 'frame_index': self.arena.view(self.key + ('frame_index',))}
+    if with_targets:
+      out['target_index'] = self.arena.view(self.key + ('target_index',))
+    return out
+
   def dense(self):
     import torch
     if self.buffer is None:
       self.buffer = torch.empty(self.shape, dtype=torch.float32, device=self.device)
     return self.buffer
 
-  def feed(self, windows):
+  def feed(self, windows, batch=None):
+    """``batch``: the dict ``windows`` came from (the shared form looks its target stream up there)."""
     if (windows.n, windows.K, windows.frame_shape) != (self.n, self.K, self.frame_shape):
       raise ValueError('WindowFeed: batch of %s windows does not fit the slot %s' % (tuple(windows.shape), self.shape))
+    if self.feeds_frame_table:
+      targets = None
+      if self._with_targets:
+        targets = (batch or {}).get(self.shared_targets)
+        if not hasattr(targets, 'frame_table'):
+          raise RuntimeError("WindowFeed: the shared frame table needs the batch's '%s' as DeviceWindows" % self.shared_targets)
+      table, index, tindex, _ = windows.frame_table(self.shared, targets, self.device)      # (raises on a mixed batch)
+      if windows.is_u8() != self.u8:
+        raise RuntimeError('WindowFeed: frames of another type than the slot was built for (the Estimator keys its models by the '
+                           'frame type)')
+      reserved = np.zeros(self.arena.view(self.key + ('frame_table',)).numel(), np.int64)
+      reserved[:self.shared] = table
+      self.arena.write(self.key + ('frame_table',), reserved)
+      self.arena.write(self.key + ('frame_index',), index)
+      if tindex is not None:
+        self.arena.write(self.key + ('target_index',), tindex)
+      self._live.append((windows, targets))
     if self.buffer is not None:
       windows.materialize_into(self.buffer.view((self.n, self.K) + self.frame_shape))
     if self._want_table:

@@ -211,6 +211,32 @@ def predict_push_features_into(states, feat_ring, jnt_ring, heads, feat, jnt, re
                                            _stream()), 'geeco_predict_push_features')
 
 
+# -- shared-frame training (csrc/shared_frames.hip; graph.py: shared_frames=F) ------------------------------------------------
+def pack_frames_by_address_into(x_in, table, F, HW, frames_u8):
+  """table [F] int64 device addresses of resident RGB frames (uint8 or float32, one kind per call; 0 = unused slot) -> the
+  encoder input x_in [F][HW][4] (uint8 divided by 255 as gather_windows_into does; zeros for an unused slot)."""
+  assert table.dtype == torch.int64 and table.numel() >= F
+  check(_lib().geeco_pack_frames_by_address(_p(table), F, 1 if frames_u8 else 0, HW, _p(x_in), _stream()),
+        'geeco_pack_frames_by_address')
+
+
+def window_states_fwd_into(states, feat, idx, jnt, mode, F, N, K, cells, ch, J, state_stride, tgt_idx=None):
+  """feat [F][cells][ch] gathered through idx [N][K] (int32) into states [K][N][state_stride], ONE launch, in the columns of
+  state_concat_fwd_into for ``mode`` ('plain', 'constant', 'residual'); tgt_idx [N]: slot of each window's target frame."""
+  assert idx.dtype == torch.int32 and (tgt_idx is None or tgt_idx.dtype == torch.int32)
+  check(_lib().geeco_window_states_fwd(_p(feat), _p(idx), _p(jnt), _p(tgt_idx), PREDICT_FEAT_MODES[mode], F, N, K, cells, ch, J,
+                                       _p(states), state_stride, _stream()), 'geeco_window_states_fwd')
+
+
+def window_states_bwd_into(dfeat, dstates, state_stride, idx, feat, mode, F, N, K, cells, ch, J, tgt_idx=None):
+  """The adjoint of window_states_fwd_into: dfeat [F][cells][ch] <- per slot the sum, in one fixed order, of the feature (and
+  target) columns of dstates [K][N][state_stride] over the window positions that use it, masked by ``feat`` > 0 (the forward's
+  features: ReluGrad of the encoder's last layer, as state_concat_bwd_into).  Unreferenced slots get zeros."""
+  assert idx.dtype == torch.int32 and (tgt_idx is None or tgt_idx.dtype == torch.int32)
+  check(_lib().geeco_window_states_bwd(_p(dstates), state_stride, _p(feat), _p(idx), _p(tgt_idx), PREDICT_FEAT_MODES[mode], F, N, K,
+                                       cells, ch, J, _p(dfeat), _stream()), 'geeco_window_states_bwd')
+
+
 # --------------------------------------------------------------------------------------------
 # conv encoder
 # --------------------------------------------------------------------------------------------

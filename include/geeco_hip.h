@@ -25,7 +25,8 @@ extern "C" {
 #endif
 
 #define GEECO_ABI_VERSION 7  /* = the build round that last changed the entry points or their calling conventions */
-/* added within 7 (additive: no existing entry point or convention changed): geeco_lstm_seq_heads_fwd */
+/* added within 7 (additive: no existing entry point or convention changed): geeco_lstm_seq_heads_fwd,
+ * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -163,6 +164,28 @@ int geeco_predict_pack_newest(const void* frames, int frames_u8, int B, int64_t 
 int geeco_predict_push_features(const float* feat, const float* jnt, const int* reset, const int* any_bad, const float* tgt_feat,
                                 int mode, int B, int K, int cells, int ch, int J, float* feat_ring, float* jnt_ring, int* heads,
                                 float* states, int64_t state_stride, void* stream);
+
+/* ---- shared-frame training of the per-frame controllers (graph.py: E2EVMC / GoalE2EVMC with shared_frames=F) ----
+ * A batch of consecutive windows holds each frame up to K times; conv_encoder sees one frame at a time, so the step encodes a
+ * table of F frame SLOTS once and the windows index it.  All three entries only enqueue on `stream`; none uses atomics. */
+/* table [F] int64 (device): the address of each slot's resident RGB frame ([HW][3]; uint8 when frames_u8, else float32), 0 = an
+ * unused slot.  x_in [F][HW][4] <- the frame with a zero fourth channel (uint8: float(u8) / 255.0f with the IEEE division, bitwise
+ * the conversion of geeco_gather_windows / geeco_predict_pack_newest), zeros for an unused slot.  A frame whose address is not
+ * aligned for the 4-pixel path (4 bytes uint8, 16 float32), or HW % 4 != 0, goes one pixel at a time. */
+int geeco_pack_frames_by_address(const int64_t* table, int F, int frames_u8, int64_t HW, float* x_in, void* stream);
+/* feat [F][cells][ch], idx [N][K] int32 (window position -> slot), jnt [N][K][J], tgt_idx [N] int32 (slot of window n's target
+ * frame; NULL for PLAIN) -> states [K][N][state_stride], ONE launch for all K steps, with the columns geeco_state_concat_fwd
+ * gives per cell: GEECO_PREDICT_FEAT_PLAIN [feat | jnt], _CONSTANT [feat | jnt | tgt], _RESIDUAL [tgt - feat | jnt].  N * K <= 1024.
+ * An index outside [0, F) contributes zeros. */
+int geeco_window_states_fwd(const float* feat, const int* idx, const float* jnt, const int* tgt_idx, int mode, int F, int N, int K,
+                            int cells, int ch, int J, float* states, int64_t state_stride, void* stream);
+/* The adjoint: dfeat[f] = sum over the positions (n, t) with idx[n][t] == f of the feature columns of dstates[t][n] (sign -1 in
+ * RESIDUAL) + sum over the windows n with tgt_idx[n] == f and their K steps of the target columns; one block per slot, summed
+ * in ONE fixed order (positions ascending n then t, then the target windows ascending n, t), so two launches are bitwise equal.
+ * feat: the forward's features; the sum is masked by feat > 0 (ReluGrad of the encoder's last layer, as
+ * geeco_state_concat_bwd).  Slots nobody references get exact zeros. */
+int geeco_window_states_bwd(const float* dstates, int64_t state_stride, const float* feat, const int* idx, const int* tgt_idx,
+                            int mode, int F, int N, int K, int cells, int ch, int J, float* dfeat, void* stream);
 
 /* ---- conv encoder: graph.py:76-115 (tf.layers.conv2d 3x3, padding='SAME', bias, ReLU) ----------
  * x [G][N][H][W][Cin], w [G][3][3][Cin][Cout] (HWIO), b [G][Cout], y [G][N][Ho][Wo][Cout],

@@ -82,6 +82,11 @@ ARGPARSER.add_argument('--dp_form', type=str, default=None,
                             'incl. both all-reduces as ONE hipGraph) '
                             '| overlap_reserve16 | overlap_reserve32 | serial.  bench.py --gpus N reports which is fastest on a node.')
 
+ARGPARSER.add_argument('--shared_frames', default=False, action='store_true',
+                       help="Per-frame controllers (e2e_vmc; goal 'sequence' x 'constant' / 'residual'), one GPU, RGB: encode every "
+                            'distinct frame of a batch once instead of once per window that holds it (same loss and gradients).  Needs '
+                            '--batch_size <= the windows of an episode.')
+
 _OBSERVATION_FORMAT_TO_CHANNELS = {'rgb': 3, 'rgbd': 4}                      # train_e2evmc.py:129-132
 _GOAL_CONDITION_TO_MODEL = {'none': (e2evmc_model_fn, 'VMC'),               # train_e2evmc.py:134-137
                             'target': (goal_e2evmc_model_fn, 'GoalVMC')}
@@ -160,6 +165,8 @@ def main(args):
     import torch.distributed as dist
     dist.barrier()
   estimator_params = {'e2evmc_config': e2evmc_config, 'log_steps': args.log_steps, 'debug': args.debug}
+  if args.shared_frames:
+    estimator_params['shared_frames'] = True
   model_fn, _scope = _GOAL_CONDITION_TO_MODEL[args.goal_condition]
   estimator = est.Estimator(model_fn=model_fn, model_dir=args.model_dir, config=run_config, params=estimator_params)
 
