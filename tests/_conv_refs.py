@@ -1,0 +1,226 @@
+"""fp64 references, rounding bounds, seeded inputs and the case list for the gather GEMM (geeco_amd/csrc/conv_gemm.hip):
+tests/test_conv_gemm_variants_gpu.py holds the device side, tests/test_conv_refs_cpu.py shows that the bounds reject wrong kernels,
+tests/test_conv_cover_cpu.py that the case list (tests/native/conv_gemm_cases.txt) runs every launch variant the model reaches.
+
+Everything here is written from the definition of tf.layers.conv2d(kernel_size=3, padding='SAME') on NHWC tensors with an HWIO
+kernel, not from the kernels: the padded input is built explicitly, the output is the sum over the nine taps of a strided window
+times that tap's [Cin][Cout] matrix, and the input gradient scatters dz times the transposed matrix back to the window's pixels.
+float64 throughout, on the float32 values the device is given.  comparison helpers: tests/_primitive_refs.py.
+"""
+import collections
+import math
+import os
+
+import numpy as np
+import torch
+
+from _primitive_refs import U, assert_within, within, worst_ratio      # noqa: F401  (one import for the tests of this family)
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# TF SAME padding
+# --------------------------------------------------------------------------------------------------------------------------
+def same_pad(size, stride, k=3):
+  """out = ceil(size / stride); pad_total = max((out - 1) * stride + k - size, 0); the smaller half goes on top / left."""
+  out = -(-size // stride)
+  total = max((out - 1) * stride + k - size, 0)
+  return out, total // 2, total - total // 2
+
+
+def _mm(a, b):
+  """[M][K] @ [K][N] in float64 on torch's thread pool (tests/conftest.py sizes it to the cores the job owns)."""
+  return (torch.from_numpy(np.ascontiguousarray(a)) @ torch.from_numpy(np.ascontiguousarray(b))).numpy()
+
+
+def _fwd(x, w, stride):
+  N, H, W, Cin = x.shape
+  Cout = w.shape[3]
+  Ho, pt, pb = same_pad(H, stride)
+  Wo, pl, pr = same_pad(W, stride)
+  xp = np.zeros((N, H + pt + pb, W + pl + pr, Cin))
+  xp[:, pt:pt + H, pl:pl + W] = x
+  y = np.zeros((N * Ho * Wo, Cout))
+  for ky in range(3):
+    for kx in range(3):
+      win = xp[:, ky:ky + (Ho - 1) * stride + 1:stride, kx:kx + (Wo - 1) * stride + 1:stride]
+      y += _mm(win.reshape(N * Ho * Wo, Cin), w[ky, kx])
+  return y.reshape(N, Ho, Wo, Cout)
+
+
+def _dgrad(dz, w, in_hw, stride):
+  N, Ho, Wo, Cout = dz.shape
+  H, W = in_hw
+  Cin = w.shape[2]
+  ho, pt, pb = same_pad(H, stride)
+  wo, pl, pr = same_pad(W, stride)
+  assert (ho, wo) == (Ho, Wo), (dz.shape, in_hw, stride)
+  dxp = np.zeros((N, H + pt + pb, W + pl + pr, Cin))
+  flat = dz.reshape(N * Ho * Wo, Cout)
+  for ky in range(3):
+    for kx in range(3):
+      # y[i][j] takes xp[s i + ky][s j + kx] . w[ky][kx], so that pixel receives dz[i][j] . w[ky][kx]^T
+      dxp[:, ky:ky + (Ho - 1) * stride + 1:stride, kx:kx + (Wo - 1) * stride + 1:stride] += _mm(flat, w[ky, kx].T).reshape(N, Ho, Wo, Cin)
+  return np.ascontiguousarray(dxp[:, pt:pt + H, pl:pl + W])
+
+
+def conv_fwd_ref(x, w, b, stride, relu):
+  """x [N][H][W][Cin], w [3][3][Cin][Cout], b [Cout] or None -> (y, mag, pre): y = relu(pre) or pre, pre = conv + bias, and mag the
+  same operation on |x|, |w|, |b| without ReLU: per element, the sum of the magnitudes of its terms."""
+  x, w = np.asarray(x, np.float64), np.asarray(w, np.float64)
+  b = np.zeros(w.shape[3]) if b is None else np.asarray(b, np.float64)
+  pre = _fwd(x, w, stride) + b
+  mag = _fwd(np.abs(x), np.abs(w), stride) + np.abs(b)
+  return (np.maximum(pre, 0.0) if relu else pre), mag, pre
+
+
+def conv_dgrad_ref(dz, w, in_hw, stride, mask):
+  """dz [N][Ho][Wo][Cout], w [3][3][Cin][Cout] (the forward's HWIO kernel), mask [N][H][W][Cin] or None -> (dx, mag, pre):
+  dx = pre where mask > 0 (everywhere without a mask), else 0; mag as in conv_fwd_ref, without the mask."""
+  dz, w = np.asarray(dz, np.float64), np.asarray(w, np.float64)
+  pre = _dgrad(dz, w, in_hw, stride)
+  mag = _dgrad(np.abs(dz), np.abs(w), in_hw, stride)
+  dx = pre if mask is None else np.where(np.asarray(mask) > 0, pre, 0.0)
+  return dx, mag, pre
+
+
+def dgrad_terms(in_hw, stride, Cout):
+  """[H][W][1]: the number of products in one element of the input gradient = (taps that reach the pixel) * Cout.  Pixel Y of the
+  input is read by output row i through tap ky when s i + ky = Y + pad_top: per axis, the ky in 0..2 congruent to Y + pad_top
+  modulo s (stride 2: one or two, i.e. 1 / 2 / 2 / 4 taps for the four parity classes; stride 1: all nine)."""
+  H, W = in_hw
+  _, pt, _ = same_pad(H, stride)
+  _, pl, _ = same_pad(W, stride)
+  ty = np.array([sum((Y + pt - k) % stride == 0 for k in range(3)) for Y in range(H)])
+  tx = np.array([sum((X + pl - k) % stride == 0 for k in range(3)) for X in range(W)])
+  return (ty[:, None] * tx[None, :])[:, :, None] * float(Cout)
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# bounds
+# --------------------------------------------------------------------------------------------------------------------------
+def conv_bound(mag, terms, S):
+  """(terms + S + 4) U mag per element, U = 2**-24, for an element that is a sum of at most ``terms`` products (forward: 9 Cin;
+  input gradient: the pixel's tap count * Cout, dgrad_terms) computed in float32 in ``S`` split-K slabs.
+    products: each is rounded once, alone or inside a fused multiply-add              -> U mag in all;
+    additions: a sum of n terms takes n - 1 additions in whatever order (MFMA accumulation chains, the order of the K-steps);
+         each moves the result by at most U times a partial sum of magnitudes <= mag   -> (terms - 1) U mag;
+    slabs: S - 1 further additions of partial sums                                    -> (S - 1) U mag;
+    bias: one addition                                                                -> U mag;
+    in all (terms + S) U mag to first order.  The remaining 4 U mag hold the second-order terms, (1 + U)^n - 1 - n U < n^2 U^2:
+    0.33 U at n = 2304 + 18, the longest sum of the case list.
+  The bound is worst case: the rounding errors of a real sum add like a random walk and use about 1 / sqrt(terms) of it.  It still
+  separates: one dropped term of typical size is mag / terms, above the bound until terms^2 reaches 1 / U (terms = 4096)."""
+  return (np.asarray(terms, np.float64) + S + 4.0) * U * mag
+
+
+def conv_expect(pre, mag, terms, S, relu=False, mask=None):
+  """-> (ref, bound, keep) per element for a launch with ReLU (forward) or a mask (input gradient).
+    no ReLU, no mask: ref = pre under conv_bound.
+    ReLU: where pre > bound the float32 sum is positive too: ref = pre under the bound; where pre < -bound it is negative: ref = 0
+         with bound 0; where |pre| <= bound either is possible: the element is left out (keep = False) -- the callers require that
+         share to stay below 0.1 %.
+    mask: the mask is data, not a computed sign: where it is not > 0 the result is 0 with bound 0, elsewhere pre under the bound."""
+  assert not (relu and mask is not None)
+  bound = np.broadcast_to(conv_bound(mag, terms, S), pre.shape).copy()
+  ref = pre.copy()
+  keep = np.ones(pre.shape, bool)
+  if relu:
+    keep = np.abs(pre) > bound
+    neg = pre < -bound
+    ref[neg] = 0.0
+    bound[neg] = 0.0
+  if mask is not None:
+    off = ~(np.asarray(mask) > 0)
+    ref[off] = 0.0
+    bound[off] = 0.0
+  return ref, bound, keep
+
+
+LEFT_OUT_MAX = 1e-3
+
+
+def left_out(keep):
+  return 1.0 - float(np.mean(keep)) if keep.size else 0.0
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# the case list
+# --------------------------------------------------------------------------------------------------------------------------
+CASES_TXT = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'native', 'conv_gemm_cases.txt')
+
+Case = collections.namedtuple('Case', 'index dir G N H W Cin Cout stride flags text plan BM BN ut S planS ncls')
+
+
+def load_cases():
+  """The cases of tests/native/conv_gemm_cases.txt with the variant recorded beside each (tests/test_conv_cover_cpu.py holds that
+  text against what conv_plan / conv_gemm_grid give)."""
+  cases = []
+  for line in open(CASES_TXT):
+    line = line.strip()
+    if not line or line.startswith('#'):
+      continue
+    text, plan = (s.strip() for s in line.split('|'))
+    f = text.split()
+    kv = dict(t.split('=') for t in plan.split()[2:])
+    bm, bn = (int(v) for v in plan.split()[1].split('x'))
+    assert plan.split()[0] == f[0], line
+    cases.append(Case(len(cases), f[0], *(int(v) for v in f[1:8]), frozenset(f[8:]), text, plan, bm, bn, kv['ut'] == '1',
+                      int(kv['S']), int(kv['planS']), int(kv['ncls'])))
+  return cases
+
+
+def case_id(c):
+  return c.text.replace(' ', '-')
+
+
+def kernel_name(c):
+  """The name launch_cfg notes for the case's tile: 2 x 2 waves for the 64-, 96- and 128-wide tiles, 4 x 1 for the narrow ones."""
+  wm, wn = (2, 2) if c.BN >= 64 else (4, 1)
+  return 'conv_gemm_kernel<%d, %d, 16, %d, %d, %s>' % (c.BM, c.BN, wm, wn, 'true' if c.ut else 'false')
+
+
+def out_hw(c):
+  return same_pad(c.H, c.stride)[0], same_pad(c.W, c.stride)[0]
+
+
+def case_inputs(c):
+  """Seeded float32 operands of a case, per group.
+  Forward: x ~ N(0, 1), w ~ N(0, 1 / (9 Cin)) (pre-activations of unit variance), bias of magnitude 2..4 and either sign: a bias
+  near zero would put the pre-activations of its channel around zero, where the sign of a float32 sum is not determined and the
+  element has to be left out; with this bias the negative channels are mostly cut by the ReLU and the left-out share stays under
+  0.1 % up to the 2304-term sums (tests/test_conv_refs_cpu.py checks every case).
+  Input gradient: dz ~ N(0, 1), w ~ N(0, 1 / (9 Cout)), mask ~ N(0, 1) with three tenths exact zeros: positive, zero and negative
+  entries (the kernel's test is mask > 0)."""
+  r = np.random.default_rng(1000 + c.index)
+  G, N, H, W, Cin, Cout = c.G, c.N, c.H, c.W, c.Cin, c.Cout
+  Ho, Wo = out_hw(c)
+  f = lambda a: a.astype(np.float32)
+  if c.dir == 'fwd':
+    x = f(r.standard_normal((G, N, H, W, Cin)))
+    w = f(r.standard_normal((G, 3, 3, Cin, Cout)) / math.sqrt(9 * Cin))
+    b = f(np.sign(r.standard_normal((G, Cout))) * r.uniform(2.0, 4.0, (G, Cout))) if 'bias' in c.flags else None
+    return dict(x=x, w=w, b=b)
+  dz = f(r.standard_normal((G, N, Ho, Wo, Cout)))
+  w = f(r.standard_normal((G, 3, 3, Cin, Cout)) / math.sqrt(9 * Cout))
+  mask = None
+  if 'mask' in c.flags:
+    mask = r.standard_normal((G, N, H, W, Cin))
+    mask[r.uniform(size=mask.shape) < 0.3] = 0.0
+    mask = f(mask)
+  return dict(dz=dz, w=w, mask=mask)
+
+
+def case_expect(c):
+  """(inputs, ref, bound, keep, pre, mag), the last five [G][...].  Not cached: every case is one test's, and the large ones
+  hold some hundred megabytes in float64."""
+  inp = case_inputs(c)
+  out = []
+  for g in range(c.G):
+    if c.dir == 'fwd':
+      _, mag, pre = conv_fwd_ref(inp['x'][g], inp['w'][g], None if inp['b'] is None else inp['b'][g], c.stride, False)
+      out.append(conv_expect(pre, mag, 9 * c.Cin, c.S, relu='relu' in c.flags) + (pre, mag))
+    else:
+      m = None if inp['mask'] is None else inp['mask'][g]
+      _, mag, pre = conv_dgrad_ref(inp['dz'][g], inp['w'][g], (c.H, c.W), c.stride, None)
+      out.append(conv_expect(pre, mag, dgrad_terms((c.H, c.W), c.stride, c.Cout), c.S, mask=m) + (pre, mag))
+  return (inp,) + tuple(np.stack([o[i] for o in out]) for i in range(5))

@@ -35,7 +35,8 @@ CONV_CASES = [
     (1, 10, 10, 16, 64, 1),     # stride 1, 16 channels
     (2, 64, 64, 32, 48, 2),     # conv2 halo kernel, exact tiles
     (3, 40, 72, 32, 48, 2),     # conv2 halo kernel, ragged tiles (Ho = 20, Wo = 36)
-    (16, 64, 64, 64, 128, 2),   # conv4-like at a size that takes the 128x128 tile path
+    (16, 64, 64, 64, 128, 2),   # conv4-like: 64 x 64 tiles in two slabs (Mtot = 16384 < 128 * 256); the <128, *> tiles are held in
+                                # tests/test_conv_gemm_variants_gpu.py
     (8, 32, 32, 128, 192, 2),   # conv5-like (128-row wgrad tiles)
     (8, 64, 64, 128, 192, 2),   # conv5-like with 128 M tiles: the forward takes the 64 x 96 tiles (256 blocks instead of 384)
     (2, 32, 32, 4, 32, 1),      # conv1 shape
