@@ -73,3 +73,62 @@ extern "C" int geeco_gather_windows(const void* src, int src_is_u8, const int* s
   GEECO_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- window builder by address: one launch for windows of any episode, order or frame kind ----------------------------------
+// A batch of SHUFFLED windows (input_fn.pickplace_input_fn(shuffle_windows=True)) holds about one episode per window; the
+// builder above takes one episode per launch.  Here the host hands a table instead:  out[n][k][:] = conv(frame k of the K
+// consecutive frames at addr[n]),  kind[n] = 0: uint8 frames, conv(u8) = float(u8) / 255.0f (bitwise the `divisor 255`
+// conversion above);  kind[n] = 1: float32 frames, a copy.  blockIdx = (unit, k, n): a block serves one frame of one window,
+// so it never straddles kinds, and takes the vector path when ITS window's address is aligned for it (4 bytes for a uint8
+// word, 16 for a float4; frame_elems % 4 == 0 keeps every frame of an aligned window aligned), else one element at a time.
+// HBM streaming: 4- / 16-byte non-temporal loads on the vector path (as pack_frames_kernel, shared_frames.hip), 16-byte stores.
+__global__ __launch_bounds__(256) void gather_windows_by_address_kernel(const long long* __restrict__ addr,
+                                                                        const int* __restrict__ kind, int K,
+                                                                        long long frame_elems, float* __restrict__ out) {
+  const int n = blockIdx.z, k = blockIdx.y;
+  const long long i4 = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i4 >= frame_elems) return;          // (frame_elems % 4 == 0: every remaining thread owns four whole elements)
+  const unsigned long long base = (unsigned long long)addr[n];
+  float* o = out + ((long long)n * K + k) * frame_elems + i4;
+  float e[4];
+  if (kind[n] == 1) {
+    const unsigned long long a = base + ((unsigned long long)k * frame_elems + i4) * 4;
+    if ((base & 15u) == 0) {
+      const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a));
+      e[0] = x.x, e[1] = x.y, e[2] = x.z, e[3] = x.w;
+    } else {
+      const float* s = reinterpret_cast<const float*>(a);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) e[j] = s[j];
+    }
+  } else {
+    const unsigned long long a = base + (unsigned long long)k * frame_elems + i4;
+    if ((base & 3u) == 0) {
+      const unsigned x = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) e[j] = (float)((x >> (8 * j)) & 255u) / 255.0f;
+    } else {
+      const unsigned char* s = reinterpret_cast<const unsigned char*>(a);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) e[j] = (float)s[j] / 255.0f;
+    }
+  }
+  *reinterpret_cast<f32x4*>(o) = f32x4{e[0], e[1], e[2], e[3]};
+}
+
+extern "C" int geeco_gather_windows_by_address(const int64_t* addr, const int* kind, int N, int K, int64_t frame_elems,
+                                               float* out, void* stream) {
+  GEECO_CHECK_ARG(addr && kind && out, "gather_windows_by_address: null pointer");
+  GEECO_CHECK_ARG(N >= 1 && N <= 65535 && K >= 1 && K <= 65535, "gather_windows_by_address: N=%d, K=%d outside 1..65535", N, K);
+  GEECO_CHECK_ARG(frame_elems >= 4 && frame_elems % 4 == 0, "gather_windows_by_address: frame_elems=%lld must be a positive multiple of 4",
+                  (long long)frame_elems);
+  GEECO_CHECK_ARG(cdiv64(frame_elems, 1024) <= 0x7fffffffLL, "gather_windows_by_address: frame_elems=%lld too large", (long long)frame_elems);
+  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "gather_windows_by_address: out must be 16-byte aligned");
+  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(addr) & 7) == 0 && (reinterpret_cast<uintptr_t>(kind) & 3) == 0,
+                  "gather_windows_by_address: the tables must be aligned for their element types");
+  dim3 grid((unsigned)cdiv64(frame_elems, 1024), (unsigned)K, (unsigned)N);
+  hipLaunchKernelGGL(gather_windows_by_address_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)addr, kind, K,
+                     (long long)frame_elems, out);
+  GEECO_LAUNCH_CHECK();
+  return 0;
+}

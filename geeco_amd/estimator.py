@@ -385,10 +385,17 @@ class Estimator:
     # uint8 and float32 resident frames are read by different input kernels (a float32 episode = one whose recorded values
     # were not integral): one model per frame type, sharing the variables
     key += tuple(k for k, v in sorted(feats.items()) if hasattr(v, 'is_u8') and not v.is_u8())
+    # batches of a shuffling input (pickplace_input_fn(shuffle_windows=True)) fill their dense windows by address: feed slots of their own
+    scattered = any(getattr(v, 'scattered', False) for v in feats.values())
+    if scattered:
+      key += ('scattered',)
     if key in self._specs:
       return self._specs[key]
     dev = self._device()
     shared = self.params.get('shared_frames')
+    if shared and scattered:
+      raise ValueError("params['shared_frames'] with a shuffling input (pickplace_input_fn(shuffle_windows=True)): a shuffled batch "
+                       "of N windows holds about N * K distinct frames, so there is nothing to share; drop one of the two options")
     # one arena for everything the host writes per batch (states, labels, window address tables): one H2D copy per step
     from .input_fn import FeedArena, WindowFeed
     arena = FeedArena(dev)
@@ -463,6 +470,15 @@ class Estimator:
         buf.copy_(torch.as_tensor(src), non_blocking=True)
     if alone:
       bufs.arena.flush()
+      Estimator._after_flush(bufs)
+
+  @staticmethod
+  def _after_flush(bufs):
+    """What a feed slot queues BEHIND the arena's copy and in front of the replay (input_fn.WindowFeed.after_flush: the
+    by-address fill of dense windows reads its window table from the arena on the device)."""
+    for buf in (bufs or {}).values():
+      if hasattr(buf, 'after_flush'):
+        buf.after_flush()
 
   @classmethod
   def _feed_step(cls, fbuf, lbuf, feats, labels):
@@ -474,6 +490,8 @@ class Estimator:
         cls._feed(lbuf, labels)
     finally:
       fbuf.arena.flush()
+    cls._after_flush(fbuf)
+    cls._after_flush(lbuf)
 
   # -- public API --------------------------------------------------------------------------------
   def latest_checkpoint(self):

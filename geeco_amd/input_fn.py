@@ -7,6 +7,7 @@ Counterpart of the reference's ``src/data/geeco_gym.py`` live path: ``pickplace_
 feature / label dictionaries (shapes and key names), same ordering semantics: record-level shuffle
 in 'train' mode only, NO sample-level shuffle (it is commented out in the reference, :447-448), so
 a batch holds consecutive windows of one episode; the final batch may be ragged (no drop_remainder).
+``shuffle_windows=True`` opts into the sample-level shuffle of the reference's v1-v3 pipelines (:701-703), see ``shuffle_stream``.
 
 Unlike the reference (which materialises every K-frame window on the host: 84 windows x 12.6 MB
 for K = 16), an episode's frames are kept once and every batch is sliced from them; windows are
@@ -226,6 +227,7 @@ class DeviceWindows:
     self.K, self.frame_shape, self.divisor, self.squeeze_k = K, tuple(frame_shape), float(divisor), squeeze_k
     self.segments = []      # (device tensor [T, frame_elems], np.int32 starts, divisor of THIS segment's frames)
     self.n = 0
+    self.scattered = False  # built by the shuffling assembler (shuffle_windows): about one episode per window, see window_table
 
   def add(self, frames_dev, starts, divisor=None):
     """``divisor``: what the gather divides this segment's frames by (default: the constructor's).  One batch can hold
@@ -249,6 +251,7 @@ class DeviceWindows:
     out = DeviceWindows(a.K, a.frame_shape, a.divisor, a.squeeze_k)
     out.segments = a.segments + b.segments
     out.n = a.n + b.n
+    out.scattered = a.scattered or b.scattered
     return out
 
   def is_u8(self):
@@ -281,24 +284,44 @@ class DeviceWindows:
       off += len(starts)
     return out
 
+  @staticmethod
+  def _frame_kind(frames_dev, divisor, who):
+    """('u8', 1) for uint8 frames with divisor 255, ('f32', 4) for float32 frames with divisor 1: the two forms the kernels that
+    follow addresses convert; anything else raises."""
+    import torch
+    if frames_dev.dtype == torch.uint8 and divisor == 255.0:
+      return 'u8', 1
+    if frames_dev.dtype == torch.float32 and divisor == 1.0:
+      return 'f32', 4
+    raise ValueError('DeviceWindows.%s: frames of type %s with divisor %g are neither the uint8 (255) nor the '
+                     'float32 (1) form' % (who, frames_dev.dtype, divisor))
+
+  def window_table(self, device):
+    """(addresses int64 [n], kinds int32 [n]) for ops.gather_windows_by_address_into: the address of each window's first frame
+    and 0 for uint8 frames (divisor 255) / 1 for float32 frames (divisor 1).  One table may mix the two kinds.  Residency,
+    bounds and device checks as ``addresses``."""
+    fe = int(np.prod(self.frame_shape))
+    addr, kinds = np.empty(self.n, np.int64), np.empty(self.n, np.int32)
+    off = 0
+    device = resolve_device(device)
+    for frames_dev, starts, divisor in self.segments:
+      self._check_resident(frames_dev, starts, device)
+      kind, esz = self._frame_kind(frames_dev, divisor, 'window_table')
+      addr[off:off + len(starts)] = frames_dev.data_ptr() + starts.astype(np.int64) * (fe * esz)
+      kinds[off:off + len(starts)] = 0 if kind == 'u8' else 1
+      off += len(starts)
+    return addr, kinds
+
   def _frame_addresses(self, device):
     """int64 [n][K] address of every frame of every window, after the residency and device checks of ``addresses``; also
     the set of frame kinds met ('u8' / 'f32')."""
-    import torch
     fe = int(np.prod(self.frame_shape))
     out = np.empty((self.n, self.K), np.int64)
     kinds, off = set(), 0
     for frames_dev, starts, divisor in self.segments:
       self._check_resident(frames_dev, starts, device)
-      if frames_dev.dtype == torch.uint8 and divisor == 255.0:
-        kinds.add('u8')
-        esz = 1
-      elif frames_dev.dtype == torch.float32 and divisor == 1.0:
-        kinds.add('f32')
-        esz = 4
-      else:
-        raise ValueError('DeviceWindows.frame_table: frames of type %s with divisor %g are neither the uint8 (255) nor the '
-                         'float32 (1) form' % (frames_dev.dtype, divisor))
+      kind, esz = self._frame_kind(frames_dev, divisor, 'frame_table')
+      kinds.add(kind)
       pos = starts.astype(np.int64)[:, None] + np.arange(self.K, dtype=np.int64)[None, :]
       out[off:off + len(starts)] = frames_dev.data_ptr() + pos * (fe * esz)
       off += len(starts)
@@ -456,8 +479,11 @@ class WindowFeed:
     * ``pointers()``: an int64 device table of per-sample window addresses (an entry of the step's FeedArena); the model's
       input kernel reads the resident uint8 frames itself (ops.goal_dynimgs_u8_into), the fp32 windows are never written.
       Only offered when ``u8`` (every segment of the first batch is uint8 frames with divisor 255).
-    * ``dense()``: a float32 [n, K, *frame_shape] buffer filled by geeco_gather_windows per batch.
-  ``feed(windows)`` then repoints / refills per batch; both are stream-ordered in front of the replay."""
+    * ``dense()``: a float32 [n, K, *frame_shape] buffer filled by geeco_gather_windows per batch, one launch per segment --
+      or, when the slot's first batch came from a shuffling input (``DeviceWindows.scattered``: about one segment per window), by
+      ONE geeco_gather_windows_by_address launch that follows a window table riding in the arena.  The table reaches the device
+      with the arena's copy, so that launch is queued by ``after_flush()``, which the Estimator calls behind ``FeedArena.flush``.
+  ``feed(windows)`` then repoints / refills per batch; everything is stream-ordered in front of the replay."""
 
   def __init__(self, windows, arena, key, shared_frames=None, shared_targets=None):
     """``shared_frames`` (a capacity F; the 'rgb' slot of a model built with shared_frames=F): the arena also carries the
@@ -466,6 +492,7 @@ class WindowFeed:
     self.n, self.K, self.frame_shape, self.squeeze_k = windows.n, windows.K, windows.frame_shape, windows.squeeze_k
     self.arena, self.key, self.device = arena, key, arena.device
     self.u8 = windows.is_u8()
+    self.scattered, self._gather_pending, self._window_tables = bool(getattr(windows, 'scattered', False)), False, None
     self.shared, self.shared_targets, self.feeds_frame_table = shared_frames, shared_targets, False
     if shared_frames is not None:
       arena.reserve(key + ('frame_table',), (int(shared_frames),), np.int64)
@@ -482,6 +509,9 @@ class WindowFeed:
     self._live = collections.deque(maxlen=FeedArena.SLOTS + 1)
     if self.u8:
       arena.reserve(key, (self.n,), np.int64)
+    if self.scattered:
+      arena.reserve(key + ('window_addr',), (self.n,), np.int64)
+      arena.reserve(key + ('window_kind',), (self.n,), np.int32)
 
   def pointers(self):
     if not self.u8:
@@ -536,7 +566,14 @@ class WindowFeed:
       if tindex is not None:
         self.arena.write(self.key + ('target_index',), tindex)
       self._live.append((windows, targets))
-    if self.buffer is not None:
+    self._gather_pending = False
+    if self.buffer is not None and self.scattered:
+      addr, kinds = windows.window_table(self.device)
+      self.arena.write(self.key + ('window_addr',), addr)
+      self.arena.write(self.key + ('window_kind',), kinds)
+      self._live.append(windows)
+      self._gather_pending = True
+    elif self.buffer is not None:
       windows.materialize_into(self.buffer.view((self.n, self.K) + self.frame_shape))
     if self._want_table:
       if not windows.is_u8():
@@ -544,6 +581,18 @@ class WindowFeed:
                            'models by the frame type)')
       self.arena.write(self.key, windows.addresses(self.device))
       self._live.append(windows)
+
+  def after_flush(self):
+    """The by-address fill of the dense buffer, queued behind the arena's copy (which carries this batch's window table) and in
+    front of the replay.  Does nothing for the other forms."""
+    if not self._gather_pending:
+      return
+    from . import ops
+    self._gather_pending = False
+    if self._window_tables is None:       # static views of the sealed arena
+      self._window_tables = (self.arena.view(self.key + ('window_addr',)), self.arena.view(self.key + ('window_kind',)))
+    ops.gather_windows_by_address_into(self.buffer, self._window_tables[0], self._window_tables[1], self.n, self.K,
+                                       int(np.prod(self.frame_shape)))
 
 
 def _concat_feature(a, b):
@@ -711,6 +760,62 @@ def episode_windows(ex, window_size, starts, dev=None):
       t = ex[k]
       feats[k] = _Omitted((n,) + t.shape, t.key) if isinstance(t, _Omitted) else np.broadcast_to(t, (n,) + t.shape).copy()
   labels = {k: ex[k][last] for k in _LABEL_KEYS}
+  return feats, labels
+
+
+def shuffle_stream(items, buffer_size, rng):
+  """tf.data's shuffle-buffer algorithm (``dataset.shuffle(buffer_size)``, geeco_gym.py:701-703) as a lazy generator: the buffer
+  fills with the first ``buffer_size`` items; from then on every incoming item takes the place of a uniformly chosen buffer
+  element, which is emitted; at the end of the stream the buffer drains in uniformly random order.  The item at input position
+  i therefore never leaves before output position i - (buffer_size - 1); ``buffer_size`` = 1 is the identity.  ``rng``: a
+  numpy Generator (only the algorithm is TensorFlow's, not its random stream)."""
+  if buffer_size < 1:
+    raise ValueError('shuffle_stream: buffer_size must be >= 1, got %r' % (buffer_size,))
+  buf = []
+  for item in items:
+    if len(buf) < buffer_size:
+      buf.append(item)
+      continue
+    j = int(rng.integers(len(buf)))
+    out, buf[j] = buf[j], item
+    yield out
+  while buf:
+    j = int(rng.integers(len(buf)))
+    out, buf[j] = buf[j], buf[-1]
+    buf.pop()
+    yield out
+
+
+def _assemble_picks(picks, K):
+  """(features, labels) of a shuffled batch: ``picks`` = ((ex, dev), start) per window, in pick order.  Runs of consecutive picks
+  from one episode go through one ``episode_windows`` call (and share a DeviceWindows segment); the runs are concatenated.  The
+  DeviceWindows are marked ``scattered``."""
+  runs = []       # [(ex, dev), [starts]]
+  for ep, start in picks:
+    if runs and runs[-1][0][0] is ep[0]:
+      runs[-1][1].append(start)
+    else:
+      runs.append([ep, [start]])
+  parts = [episode_windows(ex, K, np.asarray(starts), dev) for (ex, dev), starts in runs]
+
+  def cat(vals):
+    if len(vals) == 1:
+      return vals[0]
+    if isinstance(vals[0], DeviceWindows):
+      out = DeviceWindows(vals[0].K, vals[0].frame_shape, vals[0].divisor, vals[0].squeeze_k)
+      for v in vals:
+        out.segments += v.segments
+        out.n += v.n
+      return out
+    if isinstance(vals[0], _Omitted):
+      return _Omitted((sum(v.shape[0] for v in vals),) + vals[0].shape[1:], vals[0].key)
+    return np.concatenate(vals, axis=0)
+
+  feats = {k: cat([f[k] for f, _ in parts]) for k in parts[0][0]}
+  labels = {k: cat([l[k] for _, l in parts]) for k in parts[0][1]}
+  for v in feats.values():
+    if isinstance(v, DeviceWindows):
+      v.scattered = True
   return feats, labels
 
 
@@ -897,7 +1002,7 @@ def default_reader_threads(world=1):
 
 def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size=4, fetch_target=False,
                        shuffle_buffer=128, batch_size=1, num_epochs=1, num_threads=4, prefetch_size=4, seed=None,
-                       shard=None, device=None, device_keys=None, cache=True):
+                       shard=None, device=None, device_keys=None, cache=True, shuffle_windows=False):
   """Same signature as the reference's pickplace_input_fn (geeco_gym.py:234-279).  Returns an iterable of
   (features, labels) numpy batches.  ``num_threads`` episodes are read in parallel, in order (num_parallel_reads /
   num_parallel_calls of :442-473; None = ``default_reader_threads``: this rank's share of the host cores); ``prefetch_size`` batches are prepared ahead of the consumer (:473).
@@ -906,7 +1011,17 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
   (windows are gathered in HBM); ``device_keys``: which image streams the model reads (default both; ('rgb',) for an
   RGB-only model skips decoding, uploading and caching 26 MB of depth per episode — the 'depth' features then refuse
   to materialise); ``cache``: keep uploaded episodes in HBM across epochs (EPISODE_CACHE; True, False or an
-  EpisodeCache)."""
+  EpisodeCache).
+  ``shuffle_windows`` ('train' mode of an on-disk dataset only; off by default): the sample-level shuffle the reference's v1-v3
+  pipelines run (``dataset.shuffle(buffer_size=shuffle_buffer, seed=seed)``, :701-703; commented out in v4, :446-448).  The
+  window stream -- episodes in their shuffled file order, windows ascending -- passes through ``shuffle_stream`` with a buffer of
+  ``shuffle_buffer`` windows, drained at every epoch boundary (shuffle(...).repeat(...)); the generator is
+  ``default_rng([seed, rank])`` (rank 0 unless sharded; a fresh one for ``seed`` None).  The buffer holds (episode, start) pairs,
+  never pixels: a batch is built from its picks when it is emitted, and on the ``device`` path an episode's resident frames stay
+  referenced while one of its windows waits.  ``dp_schedule`` is the unshuffled one (it depends on counts only).  Without the
+  option ``shuffle_buffer`` is accepted and unused, as before."""
+  if shuffle_windows and int(shuffle_buffer) < 1:
+    raise ValueError('shuffle_windows needs shuffle_buffer >= 1, got %r' % (shuffle_buffer,))
   if encoding != 'v4':
     # v1-v3 are dead code in the reference (undefined PickAndPlaceEncodingV1/2/3 -> NameError)
     raise KeyError(encoding)
@@ -920,6 +1035,7 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
     if shard is not None and seed is None:
       raise ValueError('sharded training input needs one seed shared by all ranks (they must agree on the episode order)')
     np.random.default_rng(seed).shuffle(paths)
+  shuffle_windows = bool(shuffle_windows) and mode == 'train'      # the reference's shuffles are train-only too (:436, :701)
   K = window_size
   dp_schedule = None
   if shard is not None:
@@ -941,6 +1057,33 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
   if device is not None and device.type == 'cuda' and cache:
     ep_cache = cache if isinstance(cache, EpisodeCache) else EPISODE_CACHE
   print('[pickplace_input_fn_v4] #tfrecords: %d' % len(paths))
+
+  def shuffled_batches():
+    import itertools
+    rng = np.random.default_rng(None if seed is None else [seed, shard[0] if shard is not None else 0])
+    source = iter(_EpisodeSource(paths * num_epochs, meta, fetch_target, num_threads, device, image_keys, ep_cache))
+
+    def windows(episodes):
+      for ep in episodes:
+        T = ep[0]['step'].shape[0]
+        if shard is not None and T != meta.episode_length - 1:
+          raise ValueError('an episode holds %d frames, meta_info.json says %d: the data-parallel batch schedule assumes '
+                           'fixed-length episodes' % (T + 1, meta.episode_length))
+        for start in range(T - K + 1):
+          yield ep, start
+
+    picks = []      # the batch being filled; only the batch that straddles an epoch boundary mixes epochs, as without the shuffle
+    try:
+      for _ in range(num_epochs):
+        for pick in shuffle_stream(windows(itertools.islice(source, len(paths))), int(shuffle_buffer), rng):
+          picks.append(pick)
+          if len(picks) == batch_size:
+            yield _assemble_picks(picks, K)
+            picks = []
+      if picks:     # ragged final batch
+        yield _assemble_picks(picks, K)
+    finally:
+      source.close()    # (a generator: runs _EpisodeSource's clean-up now, not when it is collected)
 
   def batches():
     carry_f, carry_l = None, None   # windows left over from the previous episode (batch() spans episodes)
@@ -968,7 +1111,7 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
     if carry_f is not None:   # ragged final batch (dataset.batch without drop_remainder, :471)
       yield carry_f, carry_l
 
-  it = _Prefetcher(batches, prefetch_size, device)
+  it = _Prefetcher(shuffled_batches if shuffle_windows else batches, prefetch_size, device)
   it.dp_schedule = dp_schedule
   return it
 

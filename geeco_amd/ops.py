@@ -161,6 +161,19 @@ def gather_windows_into(out, src, starts_dev, N, K, frame_elems, divisor=1.0):
                                     _stream()), 'geeco_gather_windows')
 
 
+def gather_windows_by_address_into(out, addr, kind, N, K, frame_elems):
+  """out[n][k] <- frame k of the window at addr[n] (int64 device table; kind[n] int32: 0 = uint8 frames / 255, 1 = float32
+  frames copied), ONE launch whatever the windows' order, episodes or kinds; bitwise gather_windows_into per window."""
+  for t, dt in ((addr, torch.int64), (kind, torch.int32)):
+    if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= N and t.device == out.device):
+      raise ValueError('gather_windows_by_address: the tables must be contiguous int64 / int32 tensors of N=%d entries on %s' %
+                       (N, out.device))
+  if out.numel() < N * K * frame_elems:
+    raise ValueError('gather_windows_by_address: output of %d floats for %d x %d frames of %d' % (out.numel(), N, K, frame_elems))
+  check(_lib().geeco_gather_windows_by_address(_p(addr), _p(kind), N, K, frame_elems, _p(out), _stream()),
+        'geeco_gather_windows_by_address')
+
+
 # -- batched predictor I/O (csrc/predict_io.hip; geeco_amd/batched_predictor.py) --------------------------------------------
 def predict_range_check_into(ctl, frames, B, HW, C, lo, hi):
   """ctl[b] = ctl[B] = 1 when channels 0..2 of env b's float32 frame leave [lo, hi] (or hold a NaN); never clears them."""

@@ -26,7 +26,7 @@ extern "C" {
 
 #define GEECO_ABI_VERSION 7  /* = the build round that last changed the entry points or their calling conventions */
 /* added within 7 (additive: no existing entry point or convention changed): geeco_lstm_seq_heads_fwd,
- * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd */
+ * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd, geeco_gather_windows_by_address */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -115,6 +115,16 @@ int geeco_pack_pixels(const float* src, int64_t src_sample_stride, const float* 
  * device; divisor 255 reproduces `rgb /= 255.0` (geeco_gym.py:312) bit-exactly, 1 copies. */
 int geeco_gather_windows(const void* src, int src_is_u8, const int* starts_dev, int N, int K,
                          int64_t frame_elems, float divisor, float* out, void* stream);
+/* The same builder driven by a table, ONE launch for windows of any episode, order or frame kind (a batch of shuffled windows,
+ * input_fn.pickplace_input_fn(shuffle_windows=True); the reference shuffles samples on the host, dataset.shuffle,
+ * src/data/geeco_gym.py:701-703): addr [N] int64 and kind [N] int32 on the device, read when the kernel RUNS (they may ride in
+ * the step's host-to-device block, queued in front of this call).  out[n][k][:] = conv(frame k of the K consecutive frames at
+ * addr[n]); kind[n] = 0: uint8 frames, conv(u8) = float(u8) / 255.0f with the IEEE division, bitwise geeco_gather_windows
+ * (divisor 255); kind[n] = 1: float32 frames, a copy (any other value is read as 0).  Windows may repeat and overlap.
+ * frame_elems >= 4 and % 4 == 0, out 16-byte aligned, N and K <= 65535.  A window whose address is not aligned for the vector
+ * loads (4 bytes uint8, 16 float32; float32 frames are 4-byte aligned in any case) goes one element at a time. */
+int geeco_gather_windows_by_address(const int64_t* addr, const int* kind, int N, int K, int64_t frame_elems, float* out,
+                                    void* stream);
 
 /* ---- batched predictor I/O: B control loops per call (reference predictor.py:127-209 per env) ----------------------
  * The ingest and output stages of one replayed graph (geeco_amd/batched_predictor.py): range check -> window push ->

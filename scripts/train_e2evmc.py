@@ -82,6 +82,10 @@ ARGPARSER.add_argument('--dp_form', type=str, default=None,
                             'incl. both all-reduces as ONE hipGraph) '
                             '| overlap_reserve16 | overlap_reserve32 | serial.  bench.py --gpus N reports which is fastest on a node.')
 
+ARGPARSER.add_argument('--shuffle_windows', default=False, action='store_true',
+                       help='Sample-level shuffle of the training windows through a buffer of --shuffle_buffer windows (the '
+                            "reference's dataset.shuffle, live in its v1-v3 pipelines); without it a batch holds consecutive windows "
+                            'of one episode.  Not with --shared_frames: a shuffled batch has no frames to share.')
 ARGPARSER.add_argument('--shared_frames', default=False, action='store_true',
                        help="Per-frame controllers (e2e_vmc; goal 'sequence' x 'constant' / 'residual'), one GPU, RGB: encode every "
                             'distinct frame of a batch once instead of once per window that holds it (same loss and gradients).  Needs '
@@ -134,6 +138,10 @@ def _export_snapshot(model_dir, eval_results, num_best_ckpt):
 
 
 def main(args):
+  if args.shuffle_windows and args.shared_frames:
+    # (before anything is written or initialised)
+    raise SystemExit('--shuffle_windows and --shared_frames exclude each other: a shuffled batch of N windows holds about N x K '
+                     'distinct frames, so there is nothing for --shared_frames to share')
   gdist.init_from_env()
   rank, world = gdist.rank(), gdist.world_size()
   os.makedirs(name=args.model_dir, exist_ok=True)
@@ -194,7 +202,7 @@ def main(args):
         dataset_dir=args.dataset_dir, split_name=args.split_name, mode=estimator_mode, encoding=args.data_encoding,
         window_size=e2evmc_config.window_size, fetch_target=(args.goal_condition == 'target'),
         shuffle_buffer=args.shuffle_buffer, num_epochs=1, num_threads=reader_threads,
-        prefetch_size=args.prefetch_size,
+        prefetch_size=args.prefetch_size, shuffle_windows=args.shuffle_windows,
         # episodes are uploaded once (to THIS rank's GPU), stay there across epochs (input_fn.EPISODE_CACHE) and windows are
         # gathered in HBM; an RGB model never reads the depth stream
         device=dev,
