@@ -67,7 +67,7 @@ class _Layout:
 
 
 class _AddressTable:
-  """What ``input_fn.WindowFeed.pointers()`` hands a model: ``pointers`` marks the input as window addresses and ``table`` is the
+  """What ``feed.WindowFeed.pointers()`` hands a model: ``pointers`` marks the input as window addresses and ``table`` is the
   int64 device table of per-env addresses its input kernel reads when it runs (graph.GoalE2EVMC.forward)."""
 
   def __init__(self, table, shape):

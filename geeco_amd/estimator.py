@@ -21,11 +21,12 @@ import os
 import re
 import time
 
-import numpy as np
 import torch
 
 from . import dist as gdist
+from . import feed
 from . import graph
+from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
 
 
@@ -213,7 +214,7 @@ def _model_fn(features, labels, mode, params, goal):
       raise ValueError("params['shared_frames'] is single-GPU: with %d ranks the gradient exchange of the shared-frame step "
                        "has not been decided" % gdist.world_size())
     if getattr(rgb, 'shared', None) is None:
-      raise ValueError("params['shared_frames'] needs the windows as input_fn.DeviceWindows (pickplace_input_fn(device='cuda')): "
+      raise ValueError("params['shared_frames'] needs the windows as DeviceWindows (pickplace_input_fn(device='cuda')): "
                        "dense 'rgb' tensors hold every frame K times and no frame addresses")
     F = shared_frames_capacity(shared, N, cfg.window_size, goal)
     model = ctor(cfg, N, rgb.device, training=training, store=params.get('_variable_store'), shared_frames=F)
@@ -236,7 +237,7 @@ def _model_fn(features, labels, mode, params, goal):
         continue   # label-side inputs are not needed for predictions
       raise KeyError("model_fn: missing input '%s'" % k)
     if hasattr(src, 'pointers'):
-      # input_fn.WindowFeed (windows of HBM-resident episodes): a model whose input kernel follows window addresses takes the
+      # feed.WindowFeed, or the predictors' stand-in (windows of HBM-resident episodes): a model whose input kernel follows window addresses takes the
       # address table and the fp32 windows are never written; any other model gets the dense buffer the gather fills
       if tuple(src.shape) != tuple(model.inputs[k].shape):
         raise ValueError("model_fn: input '%s' must have shape %s, got %s" % (k, tuple(model.inputs[k].shape), tuple(src.shape)))
@@ -299,14 +300,6 @@ def _eval_metric_fn(model):
       out['cmd_grp'] = ((p['logits_cmd_grp'].argmax(dim=-1) == label).float().sum(), float(label.numel()))
     return out
   return batch_stats
-
-
-class _FeedDict(dict):
-  """name -> static buffer (a view of the spec's FeedArena, or an input_fn.WindowFeed) of the features or the labels."""
-
-  def __init__(self, arena, tag, items):
-    super().__init__(items)
-    self.arena, self.tag = arena, tag
 
 
 # ================================================================================================
@@ -384,41 +377,19 @@ class Estimator:
     key = (mode, n) if loss_scale == 1.0 else (mode, n, round(float(loss_scale), 9))
     # uint8 and float32 resident frames are read by different input kernels (a float32 episode = one whose recorded values
     # were not integral): one model per frame type, sharing the variables
-    key += tuple(k for k, v in sorted(feats.items()) if hasattr(v, 'is_u8') and not v.is_u8())
+    key += tuple(k for k, v in sorted(feats.items()) if isinstance(v, DeviceWindows) and not v.is_u8())
     # batches of a shuffling input (pickplace_input_fn(shuffle_windows=True)) fill their dense windows by address: feed slots of their own
-    scattered = any(getattr(v, 'scattered', False) for v in feats.values())
+    scattered = any(isinstance(v, DeviceWindows) and v.scattered for v in feats.values())
     if scattered:
       key += ('scattered',)
     if key in self._specs:
       return self._specs[key]
-    dev = self._device()
     shared = self.params.get('shared_frames')
     if shared and scattered:
       raise ValueError("params['shared_frames'] with a shuffling input (pickplace_input_fn(shuffle_windows=True)): a shuffled batch "
                        "of N windows holds about N * K distinct frames, so there is nothing to share; drop one of the two options")
-    # one arena for everything the host writes per batch (states, labels, window address tables): one H2D copy per step
-    from .input_fn import FeedArena, WindowFeed
-    arena = FeedArena(dev)
-    feeds = {}
-    for tag, d in (('features', feats), ('labels', labels)):
-      for k, v in (d or {}).items():
-        if hasattr(v, 'materialize_into'):      # input_fn.DeviceWindows: windows of HBM-resident episodes
-          kw = {}
-          if shared and (tag, k) == ('features', 'rgb'):
-            # room for the table either model_fn asks for (the goal model's holds the target frames too)
-            has_tgt = hasattr(feats.get('target_rgb'), 'materialize_into')
-            kw = dict(shared_frames=shared_frames_capacity(shared, n, v.K, has_tgt), shared_targets='target_rgb' if has_tgt else None)
-          feeds[tag, k] = WindowFeed(v, arena, (tag, k), **kw)
-        elif isinstance(v, np.ndarray) and v.nbytes <= self._ARENA_MAX_BYTES:
-          arena.reserve((tag, k), v.shape, v.dtype)
-        else:                                   # device tensors (synthetic inputs), dense host windows: a buffer and a copy of their own
-          feeds[tag, k] = torch.as_tensor(v).to(dev).contiguous()
-    arena.seal()
-    def to_dev(tag, d):
-      if d is None:
-        return None
-      return _FeedDict(arena, tag, {k: feeds[tag, k] if (tag, k) in feeds else arena.view((tag, k)) for k in d})
-    fbuf, lbuf = to_dev('features', feats), to_dev('labels', labels)
+    fbuf, lbuf = feed.build_slots(self._device(), feats, labels,
+                                  (lambda K, goal: shared_frames_capacity(shared, n, K, goal)) if shared else None)
     params = dict(self.params)
     params['_variable_store'] = self._store
     params.setdefault('use_hipgraph', self.config.use_hipgraph)
@@ -429,13 +400,7 @@ class Estimator:
       self._store = spec.model.store
       self._store.initialize(seed=self.config.init_seed)
     self._restore_once()
-    # only the buffers the model adopted are fed per batch
-    used = {id(v) for v in spec.model.inputs.values()}
-    fbuf = _FeedDict(arena, 'features', {k: v for k, v in fbuf.items() if id(v) in used or
-                                         (getattr(v, 'buffer', None) is not None and id(v.buffer) in used) or
-                                         getattr(v, 'feeds_frame_table', False)})
-    lbuf = _FeedDict(arena, 'labels', {k: v for k, v in (lbuf or {}).items() if id(v) in used})
-    self._specs[key] = (spec, fbuf, lbuf)
+    self._specs[key] = (spec,) + feed.adopted_slots(fbuf, lbuf, spec.model.inputs)
     return self._specs[key]
 
   def _restore_once(self):
@@ -448,50 +413,7 @@ class Estimator:
       print('INFO: restored parameters from %s' % ckpt)
     gdist.broadcast_variables(self._store)
 
-  _ARENA_MAX_BYTES = 1 << 20      # host arrays up to this size share the arena's one copy; larger ones (dense windows) go alone
-
-  @staticmethod
-  def _feed(bufs, batch):
-    """One dict of a batch into its static buffers; on its own, or inside a ``_feed_step`` that shares the arena's copy."""
-    if batch is None:
-      return
-    alone = not bufs.arena.is_open
-    if alone:
-      bufs.arena.begin()
-    for k, buf in bufs.items():
-      src = batch[k]
-      if hasattr(buf, 'feed'):                 # input_fn.WindowFeed: repoint the address / frame tables or gather into the dense buffer
-        buf.feed(src, batch)
-      elif bufs.arena.has((bufs.tag, k)):
-        bufs.arena.write((bufs.tag, k), src.detach().cpu().numpy() if torch.is_tensor(src) else src)
-      elif hasattr(src, 'materialize_into'):
-        src.materialize_into(buf.view((len(src), src.K) + src.frame_shape))
-      else:
-        buf.copy_(torch.as_tensor(src), non_blocking=True)
-    if alone:
-      bufs.arena.flush()
-      Estimator._after_flush(bufs)
-
-  @staticmethod
-  def _after_flush(bufs):
-    """What a feed slot queues BEHIND the arena's copy and in front of the replay (input_fn.WindowFeed.after_flush: the
-    by-address fill of dense windows reads its window table from the arena on the device)."""
-    for buf in (bufs or {}).values():
-      if hasattr(buf, 'after_flush'):
-        buf.after_flush()
-
-  @classmethod
-  def _feed_step(cls, fbuf, lbuf, feats, labels):
-    """Features and labels of one step: every host array through the arena's ONE staging block and copy."""
-    fbuf.arena.begin()
-    try:
-      cls._feed(fbuf, feats)
-      if lbuf is not None and labels is not None:
-        cls._feed(lbuf, labels)
-    finally:
-      fbuf.arena.flush()
-    cls._after_flush(fbuf)
-    cls._after_flush(lbuf)
+  _feed_step = staticmethod(feed.feed_step)      # (fbuf, lbuf, feats, labels): one step's batch into the slots of _get_spec
 
   # -- public API --------------------------------------------------------------------------------
   def latest_checkpoint(self):

@@ -703,7 +703,7 @@ class _ModelBase:
     ops.window_states_bwd_into(self.enc.dfeatures[0], d.dstates, d.D, inp['frame_index'], self.enc.features[0], mode, F, N, K,
                                _CELLS, ch, self.cfg.dim_jnt_state, tgt_idx=inp.get('target_index'))
 
-  # image inputs this model can read as uint8 frames behind window addresses (input_fn.WindowFeed.pointers()) instead of dense
+  # image inputs this model can read as uint8 frames behind window addresses (feed.WindowFeed.pointers()) instead of dense
   # float32 windows; () = none
   u8_window_keys = ()
 
@@ -1086,7 +1086,7 @@ class E2EVMC(_ModelBase):
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None):
     """``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
-    'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (input_fn.DeviceWindows.frame_table); the encoder
+    'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
     super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames)

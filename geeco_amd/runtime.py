@@ -27,7 +27,7 @@ from . import dist as gdist
 
 # hipGraph capture in the default ("global") mode is invalidated by a hipMalloc / synchronous copy issued by ANOTHER
 # thread during the capture window (the input prefetcher uploads episodes in a background thread): both sides take
-# this lock (geeco_amd/input_fn.py: episode_to_device).
+# this lock (geeco_amd/device_windows.py: episode_to_device).
 CAPTURE_LOCK = threading.RLock()
 # 'thread_local': HIP calls of OTHER threads (the RCCL watchdog polling its events, a prefetch upload that slipped past
 # the lock) neither fail nor invalidate the capture; only this thread's stream work is recorded.

@@ -5,33 +5,8 @@ import numpy as np
 import pytest
 import torch
 
-from geeco_amd.input_fn import DeviceWindows
+from _fake_frames import FE, K, FakeFrames, windows as _windows
 from oracle import geeco_oracle as O
-
-SHAPE = (4, 6, 3)
-FE = int(np.prod(SHAPE))
-K = 3
-
-
-class FakeFrames:
-  """Stands in for an episode's resident frame tensor [T, frame_elems]: an address, a length, a dtype, a device."""
-
-  def __init__(self, base, T, dtype=torch.uint8, device='cuda:0'):
-    self.base, self.shape, self.dtype, self.device = base, (T, FE), dtype, torch.device(device)
-
-  def data_ptr(self):
-    return self.base
-
-  def is_contiguous(self):
-    return True
-
-
-def _windows(segments, k=K, squeeze=False):
-  dw = DeviceWindows(k, SHAPE, 255.0, squeeze_k=squeeze)
-  for frames, starts, div in segments:
-    dw.add(frames, np.asarray(starts, np.int32), div)
-  return dw
-
 
 def _expect(segments, k=K):
   """address of every frame of every window, straight from the definition"""

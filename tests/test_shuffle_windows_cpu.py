@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from _fake_frames import FE, SHAPE, FakeFrames, RecordingArena as _RecordingArena, windows as _windows
 from geeco_amd import input_fn as I
 from geeco_amd.input_fn import DeviceWindows, shuffle_stream
 
@@ -209,30 +210,6 @@ def test_synthetic_inputs_ignore_the_option():
 # ================================================================================================
 # DeviceWindows.window_table
 # ================================================================================================
-SHAPE = (4, 6, 3)
-FE = int(np.prod(SHAPE))
-
-
-class FakeFrames:
-  """Stands in for an episode's resident frame tensor [T, frame_elems]: an address, a length, a dtype, a device."""
-
-  def __init__(self, base, T, dtype=torch.uint8, device='cuda:0'):
-    self.base, self.shape, self.dtype, self.device = base, (T, FE), dtype, torch.device(device)
-
-  def data_ptr(self):
-    return self.base
-
-  def is_contiguous(self):
-    return True
-
-
-def _windows(segments, k=K, squeeze=False):
-  dw = DeviceWindows(k, SHAPE, 255.0, squeeze_k=squeeze)
-  for frames, starts, div in segments:
-    dw.add(frames, np.asarray(starts, np.int32), div)
-  return dw
-
-
 def _expect(segments):
   """(address, kind) of every window, straight from the definition"""
   addr, kind = [], []
@@ -327,34 +304,6 @@ def test_assembler_builds_segments_from_runs_and_marks_them():
 # ================================================================================================
 # WindowFeed: the by-address fill is queued behind the arena's copy
 # ================================================================================================
-class _RecordingArena:
-  """The FeedArena calls WindowFeed makes, on the host, with a log of their order."""
-
-  def __init__(self, log):
-    self.device, self.log, self.layout, self.values, self.block = torch.device('cpu'), log, {}, {}, None
-
-  def reserve(self, key, shape, dtype):
-    self.layout[key] = (tuple(shape), np.dtype(dtype))
-
-  def has(self, key):
-    return key in self.layout
-
-  def seal(self):
-    self.block = True
-
-  def write(self, key, values):
-    shape, dt = self.layout[key]
-    assert np.asarray(values).shape == shape and np.asarray(values).dtype == dt, key
-    self.values[key] = np.array(values)
-    self.log.append(('write', key[-1]))
-
-  def view(self, key):
-    return ('view',) + key
-
-  def flush(self):
-    self.log.append(('flush',))
-
-
 def test_window_feed_writes_the_table_then_gathers_after_the_flush(monkeypatch):
   from geeco_amd import ops
   log = []
