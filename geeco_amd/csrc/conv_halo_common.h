@@ -19,6 +19,7 @@
 // pixel) so every lane owns 4 consecutive NHWC channels of one pixel.
 #pragma once
 #include "geeco_common.h"
+#include "conv_wgrad_plan.h"
 
 // Workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains the
 // vector-memory counter (vmcnt(0)), which would expose the latency of the epilogue's global stores
@@ -84,28 +85,10 @@ static inline unsigned long long* geeco_arm_halo_stamps() { return nullptr; }
 // slices per encoder.  The entry points' `reserved_cus` argument k leaves k CUs free for a collective that runs beside them (data parallel:
 // the early gradient bucket is reduced while these two kernels run; a grid that occupies every CU would make the
 // collective's workgroups wait for - or delay - the persistent blocks).  The workspace is sized for k = 0.
-struct BottomSlices {
-  int S0, per, S, blocks;
-};
-// S0 = CUs / groups regular blocks per encoder.  When that leaves CUs over (three encoders on 256 CUs: one) and the tiles
-// the regular blocks leave over (T mod S0 per encoder) fit ONE more block of the same length, that block takes them:
-// bench shape, fused bottom: 85 x 49 tiles with the last two blocks short or empty and the 256th CU idle becomes
-// 85 x 48 + 1 x (3 x 16); conv2's filter gradient 97 -> 96 tiles per block.  Otherwise ceil(T / S0) tiles per block.
+// conv_wgrad_plan.h holds the slicing itself (BottomSlices, bottom_slices_on: plain C++ that the host tests evaluate); here only
+// the CU count of the call being served.
 static BottomSlices bottom_slices(int groups, long long T, bool for_ws = false) {
-  const int cus = 256 - (for_ws ? 0 : geeco_call_reserved_cus());
-  BottomSlices b;
-  b.S0 = cus / groups < 1 ? 1 : cus / groups;
-  const long long fl = T / b.S0, rem = T - fl * b.S0;
-  if (for_ws) {                       // upper bound over all T
-    b.per = 0; b.S = b.S0 + 1; b.blocks = b.S0 * groups + 1;
-    return b;
-  }
-  if (rem > 0 && fl >= 1 && cus - b.S0 * groups >= 1 && rem * groups <= fl) {
-    b.per = (int)fl; b.S = b.S0 + 1; b.blocks = b.S0 * groups + 1;
-  } else {
-    b.per = (int)((T + b.S0 - 1) / b.S0); b.S = b.S0; b.blocks = b.S0 * groups;
-  }
-  return b;
+  return bottom_slices_on(WGRAD_CUS - (for_ws ? 0 : geeco_call_reserved_cus()), groups, T, for_ws);
 }
 
 // tile grid of one encoder and its slicing over the persistent blocks (HaloWgradParams, FusedBottomParams)

@@ -380,13 +380,8 @@ __global__ __launch_bounds__(256) void conv1_halo_wgrad_kernel(const Conv1WgradP
   }
 }
 
-static int conv1_wgrad_S(int groups) {
-  int S = 768 / groups;
-  return S < 1 ? 1 : S;
-}
-
 int64_t geeco_conv1_wgrad_ws_bytes(int groups, int Cin, int Cout, int stride) {
-  if (stride == 1 && Cin == 4 && Cout == 32) return (int64_t)groups * conv1_wgrad_S(groups) * (9 * 4 * 32 + 32) * 4;
+  if (conv1_wgrad_handles(Cin, Cout, stride)) return (int64_t)groups * conv1_wgrad_S(groups) * (9 * 4 * 32 + 32) * 4;
   return 0;
 }
 
@@ -394,10 +389,10 @@ int geeco_try_conv1_wgrad(const float* x, const float* dz, float* dw, float* db,
                           int64_t gs_dz, int64_t gs_dw, int64_t gs_db, int N, int H, int W, int Cin, int Cout,
                           int stride, void* ws, hipStream_t stream, int* handled) {
   *handled = 0;
-  if (!(stride == 1 && Cin == 4 && Cout == 32)) return 0;
+  if (!conv1_wgrad_handles(Cin, Cout, stride)) return 0;
   Conv1WgradParams p = {};
   p.x = x; p.dz = dz; p.part = (float*)ws; p.gs_x = gs_x; p.gs_dz = gs_dz;
-  p.N = N; p.H = H; p.W = W; p.tiles_x = cdiv(W, 16); p.tiles_y = cdiv(H, 4);
+  p.N = N; p.H = H; p.W = W; p.tiles_x = cdiv(W, CONV1_WGRAD_TW); p.tiles_y = cdiv(H, CONV1_WGRAD_TH);
   p.tiles_per_group = N * p.tiles_x * p.tiles_y;
   p.S = conv1_wgrad_S(groups);
   geeco_note_kernel("conv1_halo_wgrad_kernel");

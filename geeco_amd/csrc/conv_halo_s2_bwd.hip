@@ -271,7 +271,7 @@ __global__ __launch_bounds__(512) void conv_s2_halo_wgrad_kernel(const HaloWgrad
 }
 
 int64_t geeco_halo_wgrad_ws_bytes(int groups, int N, int H, int W, int Cin, int Cout, int stride) {
-  if (stride == 2 && Cin == 32 && Cout == 48 && H % 2 == 0 && W % 2 == 0)
+  if (halo_wgrad_handles(H, W, Cin, Cout, stride))
     return (int64_t)groups * bottom_slices(groups, 0, true).S * (9ll * Cin * Cout + Cout) * 4;
   return 0;
 }
@@ -280,10 +280,10 @@ int geeco_try_halo_wgrad(const float* x, const float* dz, float* dw, float* db, 
                          int64_t gs_dz, int64_t gs_dw, int64_t gs_db, int N, int H, int W, int Cin, int Cout,
                          int stride, void* ws, hipStream_t stream, int* handled) {
   *handled = 0;
-  if (stride == 2 && Cin == 32 && Cout == 48 && (H % 2 == 0) && (W % 2 == 0)) {
+  if (halo_wgrad_handles(H, W, Cin, Cout, stride)) {
     HaloWgradParams p = {};
     p.x = x; p.dz = dz; p.part = (float*)ws; p.gs_x = gs_x; p.gs_dz = gs_dz;
-    const BottomSlices bs = fill_bottom_geometry(p, groups, N, H, W, cdiv(W / 2, 16), cdiv(H / 2, 4));
+    const BottomSlices bs = fill_bottom_geometry(p, groups, N, H, W, cdiv(W / 2, HALO_WGRAD_TW), cdiv(H / 2, HALO_WGRAD_TH));
     p.stamps = geeco_arm_halo_stamps();
     constexpr int HALO_F4 = ((9 * 17 * 16 + 63) / 64) * 64;
     const size_t lds = (size_t)(2 * HALO_F4 + 2 * 4 * 16 * 12) * 16;

@@ -19,6 +19,7 @@
 #include <stdlib.h>
 #include "conv_wgrad_body.h"
 #include "conv_internal.h"
+#include "conv_wgrad_plan.h"
 
 template <int BR, int BC, int MK>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
@@ -86,11 +87,6 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
   wgrad_reduce_body<SPLIT>(part, dw, db, gs_dw, gs_db, S, KC, Cout, blockIdx.y, blockIdx.x, sred);
 }
 
-// few float4 columns and many slabs: split the slabs over the waves to get enough parallelism
-static bool reduce_splits_slabs(int S, long long KC, int Cout, int groups) {
-  return S >= 16 && (KC + Cout) / 4 * groups < 64 * 1024;
-}
-
 // Several pending slab sums in one launch (geeco_slab_reduce_batch): block -> (item, group, column block) through the
 // prefix table; every item is summed exactly as its own wgrad_reduce_kernel launch would.
 struct SlabReduceBatch {
@@ -149,11 +145,11 @@ void geeco_launch_wgrad_reduce(const float* part, float* dw, float* db, long lon
   }
   const long long n4 = (KC + Cout) / 4;
   if (reduce_splits_slabs(S, KC, Cout, groups)) {
-    dim3 rgrid((unsigned)cdiv64(n4, 64), (unsigned)groups);
+    dim3 rgrid((unsigned)cdiv64(n4, reduce_block_span(true)), (unsigned)groups);
     geeco_note_kernel("wgrad_reduce_kernel<true>");
     hipLaunchKernelGGL(wgrad_reduce_kernel<true>, rgrid, dim3(256), 0, s, part, dw, db, gs_dw, gs_db, S, KC, Cout);
   } else {
-    dim3 rgrid((unsigned)cdiv64(n4, 256), (unsigned)groups);
+    dim3 rgrid((unsigned)cdiv64(n4, reduce_block_span(false)), (unsigned)groups);
     geeco_note_kernel("wgrad_reduce_kernel<false>");
     hipLaunchKernelGGL(wgrad_reduce_kernel<false>, rgrid, dim3(256), 0, s, part, dw, db, gs_dw, gs_db, S, KC, Cout);
   }
@@ -187,7 +183,7 @@ static int slab_reduce_batch_impl(const geeco_slab_reduce* items, int n, int64_t
     const int k = b.n++;
     b.it[k] = r;
     b.split[k] = reduce_splits_slabs(r.S, r.KC, r.Cout, r.groups) ? 1 : 0;
-    b.bpg[k] = (int)cdiv64((r.KC + r.Cout) / 4, b.split[k] ? 64 : 256);
+    b.bpg[k] = (int)cdiv64((r.KC + r.Cout) / 4, reduce_block_span(b.split[k] != 0));
     b.first[k] = (int)blocks;
     blocks += (long long)b.bpg[k] * r.groups;
   }
@@ -202,32 +198,18 @@ static int slab_reduce_batch_impl(const geeco_slab_reduce* items, int n, int64_t
   return 0;
 }
 
+// the generic kernel's plan (conv_wgrad_plan.h: wgrad_tile_plan) as the kernel's arguments
 void geeco_wgrad_plan(int groups, int N, int H, int W, int Cin, int Cout, int stride, WgradParams* p, int* bc) {
-  int Ho, Wo, pt, pl;
-  same_pad(H, 3, stride, &Ho, &pt);
-  same_pad(W, 3, stride, &Wo, &pl);
-  p->N = N; p->H = H; p->W = W; p->Cin = Cin; p->Ho = Ho; p->Wo = Wo; p->Cout = Cout;
-  p->stride = stride; p->pt = pt; p->pl = pl;
-  p->M = (long long)N * Ho * Wo;
-  p->Krows = 9 * Cin;
-  // 64-row tiles and at most 64 columns: 128-row / 128-column tiles halve the dz traffic per MFMA but measured on MI355X
-  // ~1.5 % of the step slower (occupancy beats traffic here)
-  const int BC = (Cout % 64 == 0) ? 64 : (Cout % 48 == 0) ? 48 : (Cout % 32 == 0) ? 32 : 16;
-  constexpr int BR = 64;
-  *bc = BC + 1000 * BR;
-  p->row_tiles = cdiv(p->Krows, BR);
-  p->col_tiles = cdiv(Cout, BC);
-  long long tiles = (long long)groups * p->row_tiles * p->col_tiles;
-  long long S = 1024 / tiles;
-  if (S < 1) S = 1;
-  long long maxS = p->M / 512;          // at least 512 pixels per slice
-  if (maxS < 1) maxS = 1;
-  if (S > maxS) S = maxS;
-  long long mps = cdiv64(p->M, S);
-  mps = cdiv64(mps, 64) * 64;   // multiple of every MK
-  S = cdiv64(p->M, mps);
-  p->S = (int)S;
-  p->m_per_split = mps;
+  const WgradTilePlan t = wgrad_tile_plan(groups, N, H, W, Cin, Cout, stride);
+  p->N = N; p->H = H; p->W = W; p->Cin = Cin; p->Ho = t.Ho; p->Wo = t.Wo; p->Cout = Cout;
+  p->stride = stride; p->pt = t.pt; p->pl = t.pl;
+  p->M = t.M;
+  p->Krows = t.Krows;
+  *bc = t.BC + 1000 * t.BR;
+  p->row_tiles = t.row_tiles;
+  p->col_tiles = t.col_tiles;
+  p->S = t.S;
+  p->m_per_split = t.m_per_split;
 }
 
 extern "C" int64_t geeco_conv3x3_wgrad_ws_bytes(int groups, int N, int H, int W, int Cin, int Cout, int stride) {
@@ -250,17 +232,27 @@ extern "C" int geeco_conv3x3_wgrad(const float* x, const float* dz, float* dw, f
   GEECO_CHECK_ARG(groups >= 1 && N >= 1 && H >= 1 && W >= 1, "conv3x3_wgrad: bad dims");
   GEECO_CHECK_ARG(Cin % 4 == 0 && Cin >= 4, "conv3x3_wgrad: Cin=%d must be a multiple of 4", Cin);
   GEECO_CHECK_ARG(Cout % 16 == 0, "conv3x3_wgrad: Cout=%d must be a multiple of 16", Cout);
-  {
+  const WgradFamily family = wgrad_family(groups, N, H, W, Cin, Cout, stride);      // the dispatch order: conv_wgrad_plan.h
+  if (family != WGRAD_FAMILY_GENERIC) {
     int handled = 0;
-    int rc = geeco_try_halo_wgrad(x, dz, dw, db, groups, gs_x, gs_dz, gs_dw, gs_db, N, H, W, Cin, Cout, stride, ws,
+    int rc = 0;
+    switch (family) {
+      case WGRAD_FAMILY_HALO:
+        rc = geeco_try_halo_wgrad(x, dz, dw, db, groups, gs_x, gs_dz, gs_dw, gs_db, N, H, W, Cin, Cout, stride, ws,
                                   (hipStream_t)stream, &handled);
-    if (rc || handled) return rc;
-    rc = geeco_try_conv1_wgrad(x, dz, dw, db, groups, gs_x, gs_dz, gs_dw, gs_db, N, H, W, Cin, Cout, stride, ws,
-                               (hipStream_t)stream, &handled);
-    if (rc || handled) return rc;
-    rc = geeco_try_wgrad_lds(x, dz, dw, db, groups, gs_x, gs_dz, gs_dw, gs_db, N, H, W, Cin, Cout, stride, ws,
-                             (hipStream_t)stream, &handled);
-    if (rc || handled) return rc;
+        break;
+      case WGRAD_FAMILY_CONV1:
+        rc = geeco_try_conv1_wgrad(x, dz, dw, db, groups, gs_x, gs_dz, gs_dw, gs_db, N, H, W, Cin, Cout, stride, ws,
+                                   (hipStream_t)stream, &handled);
+        break;
+      default:
+        rc = geeco_try_wgrad_lds(x, dz, dw, db, groups, gs_x, gs_dz, gs_dw, gs_db, N, H, W, Cin, Cout, stride, ws,
+                                 (hipStream_t)stream, &handled);
+        break;
+    }
+    if (rc) return rc;
+    GEECO_CHECK_ARG(handled, "conv3x3_wgrad: kernel family %d did not take the shape its plan gave it", (int)family);
+    return 0;
   }
   WgradParams p = {};
   int BC;

@@ -28,6 +28,7 @@
 //   dz  [pixel][16 granules], granule index XOR-ed by (pixel & 1) << 2 (A fragment: 16 channels x 4 pixels).
 #include "conv_halo_common.h"      // g_zero_page also feeds the DMA lanes on pad granules here
 #include "conv_internal.h"
+#include "conv_wgrad_plan.h"      // wgrad_halo_plan: variant, tile, ci / co blocks, slices, block count
 #include <stdlib.h>
 
 struct WgradHaloParams {
@@ -280,59 +281,6 @@ __global__ __launch_bounds__(64 * NCI * NCO, MINW) void conv_s2_wgrad_lds_kernel
 // ------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------
-struct WgradHaloPlan {
-  int variant;       // 0 = not handled; 1 = CIB 48 (conv3 type), TW 16; 4 = CIB 48, TW 8; 2 = CIB 64, TW 16; 3 = CIB 64, TW 8;
-                     // 5 = CIB 32 x COB 128, TW 8
-  int TH, TW, n_cib, n_cob, S;
-};
-
-static WgradHaloPlan wgrad_halo_plan(int groups, int N, int H, int W, int Cin, int Cout, int stride) {
-  WgradHaloPlan pl = {};
-  if (stride != 2 || (H & 1) || (W & 1) || Cout % 64 != 0) return pl;
-  const int Ho = H / 2, Wo = W / 2;
-  if (Wo < 8 || Ho < 2) return pl;                        // the tiny top layers stay with the gather kernel
-  // tile shape: 2 x 16 or 4 x 8 output pixels (same LDS); the squarer one has 7 % less halo ((9 x 17) / (8 x 16) = 1.20
-  // input pixels fetched per input pixel used, against (5 x 33) / (4 x 32) = 1.29)
-  // (measured, bench shapes: conv3 209.8 -> 203.5 us, conv4 142.3 -> 139.0, conv5 116.5 -> 113.9)
-  const bool wide = Wo >= 16 && Ho < 4;
-  if (Cin == 48 && Wo >= 16) {
-    pl.variant = wide ? 1 : 4; pl.TH = wide ? 2 : 4; pl.TW = wide ? 16 : 8; pl.n_cib = 1;
-  } else if (Cin % 64 == 0) {
-    pl.variant = wide ? 2 : 3;
-    pl.TH = wide ? 2 : 4; pl.TW = wide ? 16 : 8;
-    pl.n_cib = Cin / 64;
-  } else {
-    return pl;
-  }
-  pl.n_cob = Cout / 64;
-  const long long tiles = (long long)N * cdiv(Ho, pl.TH) * cdiv(Wo, pl.TW);
-  if (tiles >= (1ll << 30) || (long long)H * W * Cin >= (1ll << 31) || (long long)Ho * Wo * Cout >= (1ll << 31)) {
-    pl.variant = 0;                                       // 32-bit tile counters / in-frame offsets
-    return pl;
-  }
-  // One block per CU (its LDS images take > 80 KB).  Blocks are dealt round-robin to the 8 XCDs and the n_cob co
-  // blocks of a slice sit on one XCD: a launch must not put more than 32 blocks on any XCD, or that XCD runs two
-  // rounds while the others idle (measured on conv5: 33 blocks on four XCDs took 200 us instead of 100).
-  // 32 x 128 blocks of dw instead of 64 x 64 (same slab bytes): 35.6 KB of DMA per tile instead of 47 KB for the same
-  // MFMA work - the 64 x 64 blocks sit at the CU's ingest limit (5.1 B/clk next to MFMA waves)
-  if (pl.variant == 3 && Cout % 128 == 0) {
-    pl.variant = 5;
-    pl.n_cib = Cin / 32;
-    pl.n_cob = Cout / 128;
-  }
-  // 64 x 96 blocks where 128 does not divide Cout (conv5: 192 = 2 x 96): 256 blocks instead of 240 and 27 MFMAs per 12
-  // fragment reads instead of 18 per 11, against 1.5x the slab bytes: 114.4 -> 111.6 us, the step -2.5 us
-  if (pl.variant == 3 && Cout % 96 == 0) {
-    pl.variant = 6;
-    pl.n_cob = Cout / 96;
-  }
-  int S = (8 * (32 / pl.n_cob)) / (groups * pl.n_cib);
-  if (S < 1) S = 1;
-  if (S > tiles) S = (int)tiles;
-  pl.S = S;
-  return pl;
-}
-
 int64_t geeco_wgrad_lds_ws_bytes(int groups, int N, int H, int W, int Cin, int Cout, int stride) {
   const WgradHaloPlan pl = wgrad_halo_plan(groups, N, H, W, Cin, Cout, stride);
   if (!pl.variant) return 0;
@@ -378,8 +326,8 @@ int geeco_try_wgrad_lds(const float* x, const float* dz, float* dw, float* db, i
   p.tiles_x = cdiv(p.Wo, pl.TW); p.tiles_y = cdiv(p.Ho, pl.TH);
   p.tiles_per_group = N * p.tiles_x * p.tiles_y;
   p.S = pl.S; p.n_cib = pl.n_cib; p.n_cob = pl.n_cob;
-  p.n_sigma = groups * pl.n_cib * pl.S;
-  const int blocks = 8 * cdiv(p.n_sigma, 8) * pl.n_cob;
+  p.n_sigma = pl.n_sigma;
+  const int blocks = pl.blocks;
   int rc = 0;
   switch (pl.variant) {
     case 1: rc = launch_wgrad_lds<3, 4, 1, 2, 16, 14, false, 2, 3>(p, blocks, stream); break;

@@ -1,6 +1,8 @@
 """fp64 references, rounding bounds, seeded inputs and the case list for the gather GEMM (geeco_amd/csrc/conv_gemm.hip):
 tests/test_conv_gemm_variants_gpu.py holds the device side, tests/test_conv_refs_cpu.py shows that the bounds reject wrong kernels,
 tests/test_conv_cover_cpu.py that the case list (tests/native/conv_gemm_cases.txt) runs every launch variant the model reaches.
+The same four parts for the filter gradient (geeco_conv3x3_wgrad) are at the end of this file: tests/native/conv_wgrad_cases.txt,
+tests/test_conv_wgrad_variants_gpu.py, tests/test_conv_wgrad_refs_cpu.py, tests/test_conv_wgrad_cover_cpu.py.
 
 Everything here is written from the definition of tf.layers.conv2d(kernel_size=3, padding='SAME') on NHWC tensors with an HWIO
 kernel, not from the kernels: the padded input is built explicitly, the output is the sum over the nine taps of a strided window
@@ -10,6 +12,7 @@ float64 throughout, on the float32 values the device is given.  comparison helpe
 import collections
 import math
 import os
+import re
 
 import numpy as np
 import torch
@@ -224,3 +227,119 @@ def case_expect(c):
       _, mag, pre = conv_dgrad_ref(inp['dz'][g], inp['w'][g], (c.H, c.W), c.stride, None)
       out.append(conv_expect(pre, mag, dgrad_terms((c.H, c.W), c.stride, c.Cout), c.S, mask=m) + (pre, mag))
   return (inp,) + tuple(np.stack([o[i] for o in out]) for i in range(5))
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# filter gradient (geeco_conv3x3_wgrad): reference, bound, case list
+# --------------------------------------------------------------------------------------------------------------------------
+def _wgrad(x, dz, stride):
+  N, H, W, Cin = x.shape
+  _, Ho, Wo, Cout = dz.shape
+  ho, pt, pb = same_pad(H, stride)
+  wo, pl, pr = same_pad(W, stride)
+  assert (ho, wo) == (Ho, Wo), (x.shape, dz.shape, stride)
+  xp = np.zeros((N, H + pt + pb, W + pl + pr, Cin))
+  xp[:, pt:pt + H, pl:pl + W] = x
+  flat = dz.reshape(N * Ho * Wo, Cout)
+  dw = np.zeros((3, 3, Cin, Cout))
+  for ky in range(3):
+    for kx in range(3):
+      # y[i][j] = sum xp[s i + ky][s j + kx] . w[ky][kx], so w[ky][kx][ci][co] receives xp[s i + ky][s j + kx][ci] dz[i][j][co]
+      win = xp[:, ky:ky + (Ho - 1) * stride + 1:stride, kx:kx + (Wo - 1) * stride + 1:stride]
+      dw[ky, kx] = _mm(win.reshape(N * Ho * Wo, Cin).T, flat)
+  return dw, flat.sum(0)
+
+
+def conv_wgrad_ref(x, dz, stride):
+  """x [N][H][W][Cin], dz [N][Ho][Wo][Cout] -> (dw [3][3][Cin][Cout], db [Cout], mag_dw, mag_db): the gradients of
+  sum(conv(x, w) + b) . dz with respect to w and b, and the same sums over |x|, |dz|: per element, the sum of the magnitudes of
+  its terms."""
+  x, dz = np.asarray(x, np.float64), np.asarray(dz, np.float64)
+  dw, db = _wgrad(x, dz, stride)
+  mag_dw, mag_db = _wgrad(np.abs(x), np.abs(dz), stride)
+  return dw, db, mag_dw, mag_db
+
+
+def wgrad_bound(mag, slice_px, S):
+  """(slice_px + S + 8) U mag per element, U = 2**-24, for an element of dw or db: a sum over all output pixels, computed in
+  float32 in S slices of at most ``slice_px`` pixels each (one slab per slice) and a slab sum.
+    products: each is rounded once, alone or inside a fused multiply-add (db: none)           -> U mag in all;
+    inside a slice: a sum of n <= slice_px terms takes n - 1 additions in whatever order (MFMA accumulation chains, the order
+         of the tiles); each moves the result by at most U times a partial sum of magnitudes    -> (slice_px - 1) U mag;
+    the kernels that keep four waves' partial tiles of one slice (conv1's, the 32 -> 48 halo kernel) combine them through LDS:
+         at most 3 further additions                                                            -> 3 U mag;
+    slab sum: S - 1 additions of partial sums, in whatever grouping (the split form adds four waves' shares)  -> (S - 1) U mag;
+    in all (slice_px + S + 3) U mag to first order.  The remaining 5 U mag hold the second-order terms,
+    (1 + U)^n - 1 - n U < n^2 U^2: 0.05 U at n = 128 + 768 + 3, the longest chain of the case list.
+  The bound is worst case; a real float32 sum uses about 1 / sqrt(terms) of it.  It cannot see one dropped pixel once
+  slice_px + S passes a few thousand -- for that the device test has its exact pass (small integers: any order of float32
+  additions gives the float64 result) and keeps this one for what integers cannot show: a product path of reduced precision."""
+  return (float(slice_px) + S + 8.0) * U * mag
+
+
+WGRAD_CASES_TXT = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'native', 'conv_wgrad_cases.txt')
+
+WgradCase = collections.namedtuple('WgradCase', 'index G N H W Cin Cout stride flags text plan family inst S reduce slice_px remainder '
+                                   'unreached')
+_WGRAD_PLAN = re.compile(r'^(halo|conv1|lds|generic) (.+) S=(\d+) reduce=(split|plain|none) slice_px=(\d+)( remainder)?( unreached)?$')
+
+
+def load_wgrad_cases():
+  """The cases of tests/native/conv_wgrad_cases.txt with the plan recorded beside each (tests/test_conv_wgrad_cover_cpu.py holds
+  that text against what geeco_amd/csrc/conv_wgrad_plan.h gives)."""
+  cases = []
+  for line in open(WGRAD_CASES_TXT):
+    line = line.strip()
+    if not line or line.startswith('#'):
+      continue
+    text, plan = (s.strip() for s in line.split('|'))
+    f = text.split()
+    m = _WGRAD_PLAN.match(plan)
+    assert m and set(f[7:]) <= {'nodb'}, line
+    cases.append(WgradCase(len(cases), *(int(v) for v in f[:7]), frozenset(f[7:]), text, plan, m.group(1), m.group(2),
+                           int(m.group(3)), m.group(4), int(m.group(5)), bool(m.group(6)), bool(m.group(7))))
+  return cases
+
+
+def wgrad_key(c):
+  """The key tests/native/conv_wgrad_cover.cpp prints for the sweep's launches."""
+  return '%s %s reduce=%s %s %s' % (c.family, c.inst, c.reduce, 'S>1' if c.S > 1 else 'S=1', 'remainder' if c.remainder else 'regular')
+
+
+def wgrad_kernel_names(c):
+  """What ops.kernel_trace records for the case: the instantiation, and the slab-sum kernel unless the kernel wrote dw itself."""
+  return [c.inst] + ({'split': ['wgrad_reduce_kernel<true>'], 'plain': ['wgrad_reduce_kernel<false>'], 'none': []}[c.reduce])
+
+
+def wgrad_out_hw(c):
+  return same_pad(c.H, c.stride)[0], same_pad(c.W, c.stride)[0]
+
+
+def wgrad_pixels(c):
+  """M: output pixels per group, the number of terms of every element of dw and db."""
+  Ho, Wo = wgrad_out_hw(c)
+  return c.N * Ho * Wo
+
+
+def wgrad_case_inputs(c, exact):
+  """Seeded float32 x [G][N][H][W][Cin] and dz [G][N][Ho][Wo][Cout].  exact: integers in [-2, 2] -- every product and every
+  partial sum of at most M of them is an integer of magnitude <= 4 M < 2**24, which float32 holds exactly, so any order of
+  float32 additions, through any MFMA, slab split or slab-sum order, gives exactly the float64 result.  Otherwise N(0, 1)."""
+  r = np.random.default_rng(2000 + 2 * c.index + (1 if exact else 0))
+  Ho, Wo = wgrad_out_hw(c)
+  sx, sz = (c.G, c.N, c.H, c.W, c.Cin), (c.G, c.N, Ho, Wo, c.Cout)
+  if exact:
+    assert 4 * wgrad_pixels(c) < 2 ** 24
+    return r.integers(-2, 3, sx).astype(np.float32), r.integers(-2, 3, sz).astype(np.float32)
+  return r.standard_normal(sx).astype(np.float32), r.standard_normal(sz).astype(np.float32)
+
+
+def wgrad_case_expect(c, exact):
+  """(x, dz, dw, db, bound_dw, bound_db): the inputs and, per group, the float64 gradients and their bounds (zero in the exact
+  pass: the comparison is equality)."""
+  x, dz = wgrad_case_inputs(c, exact)
+  out = [conv_wgrad_ref(x[g], dz[g], c.stride) for g in range(c.G)]
+  dw, db, mw, mb = (np.stack([o[i] for o in out]) for i in range(4))
+  if exact:
+    return x, dz, dw, db, np.zeros_like(dw), np.zeros_like(db)
+  return x, dz, dw, db, wgrad_bound(mw, c.slice_px, c.S), wgrad_bound(mb, c.slice_px, c.S)

@@ -88,15 +88,17 @@ def test_conv3x3_dgrad(dev, N, H, W, Cin, Cout, stride):
   _close(dx, ref, 2e-5, 2e-5, 'conv dgrad')
 
 
-# LDS-staged filter gradient of the middle layers (conv_wgrad_halo.hip): every tile variant, ragged tile rows / columns,
-# several ci / co blocks, more slices than tiles
+# LDS-staged filter gradient of the middle layers (conv_wgrad_halo.hip) at larger shapes: ragged tile rows / columns, several
+# ci / co blocks, more slices than tiles.  The variant named beside a case is what wgrad_halo_plan (conv_wgrad_plan.h) gives it
+# today; nothing here pins it.  tests/native/conv_wgrad_cases.txt holds one small case per variant with the variant recorded and
+# checked (tests/test_conv_wgrad_cover_cpu.py, tests/test_conv_wgrad_variants_gpu.py): variant 1 (CIB 48, 2 x 16 tiles) runs only there.
 WGRAD_LDS_CASES = [
-    (2, 64, 64, 48, 64, 2),     # conv3 type (CIB 48, 2x16 tiles), exact tiles
-    (3, 36, 72, 48, 64, 2),     # conv3 type, Ho = 18, Wo = 36: ragged last tile column
-    (5, 20, 24, 64, 64, 2),     # CIB 64, 4x8 tiles: Ho = 10, Wo = 12 ragged in both directions
-    (4, 16, 16, 192, 256, 2),   # conv6 type: 3 ci blocks x 4 co blocks, 4x8 tiles
-    (1, 4, 32, 64, 128, 2),     # 2x16 tiles with fewer tiles (1) than slices
-    (2, 34, 66, 128, 64, 2),    # Ho = 17 (odd): last tile row half empty; Wo = 33
+    (2, 64, 64, 48, 64, 2),     # conv3 type: variant 4 (CIB 48, 4 x 8 tiles), exact tiles
+    (3, 36, 72, 48, 64, 2),     # conv3 type: variant 4, Ho = 18, Wo = 36: ragged last tile row and column
+    (5, 20, 24, 64, 64, 2),     # variant 3 (CIB 64, 4 x 8 tiles): Ho = 10, Wo = 12 ragged in both directions
+    (4, 16, 16, 192, 256, 2),   # conv6 type: variant 5 (32 x 128 blocks: 6 ci blocks x 2 co blocks), 4 x 8 tiles
+    (1, 4, 32, 64, 128, 2),     # variant 2 (CIB 64, 2 x 16 tiles) with fewer tiles (1) than slices
+    (2, 34, 66, 128, 64, 2),    # variant 3, two ci blocks: Ho = 17 (odd): last tile row mostly empty; Wo = 33
 ]
 
 
