@@ -268,30 +268,45 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 3 : (NCIT == 4 ? 2 : 4)) void co
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-template <int PR, int PC, int FR, int NCIT, int NW = 8>
-static int launch_dgrad_lds(const DgradLdsParams& p, int blocks, hipStream_t stream) {
-  constexpr int IR = (NW / FR) * PR + 1, IC = PC + 1;
-  constexpr int ZP_F4 = (4 * ((FR * IR * IC + 15) / 16 * 16) + 63) / 64 * 64;
-  constexpr size_t lds = (size_t)(2 * 9 * NCIT * 64 + 2 * ZP_F4) * 16;
+template <int PR, int PC, int FR, int NCIT, int NW>
+static int launch_dgrad_lds(const DgradLdsParams& p, const DgradLdsPlan& pl, hipStream_t stream) {
+  constexpr size_t lds = dgrad_lds_lds_bytes(PR, PC, FR, NCIT, NW);
   static_assert(lds * (NW == 4 ? 3 : (NCIT == 4 ? 1 : 2)) <= 160 * 1024, "LDS budget");
+  if (pl.PR != PR || pl.PC != PC || pl.FR != FR || pl.NCIT != NCIT || pl.NW != NW || pl.lds != lds) {
+    geeco_set_error("conv3x3_dgrad: the plan names another instantiation of the LDS-staged kernel");
+    return GEECO_EINVAL;
+  }
   if (int rc = geeco_lds_opt_in<&conv_s2_dgrad_lds_kernel<PR, PC, FR, NCIT, NW>>(lds)) return rc;
   geeco_note_kernel("conv_s2_dgrad_lds_kernel<%d, %d, %d, %d, %d>", PR, PC, FR, NCIT, NW);
-  hipLaunchKernelGGL((conv_s2_dgrad_lds_kernel<PR, PC, FR, NCIT, NW>), dim3((unsigned)blocks), dim3(64 * NW), lds, stream, p);
+  hipLaunchKernelGGL((conv_s2_dgrad_lds_kernel<PR, PC, FR, NCIT, NW>), dim3((unsigned)pl.blocks), dim3(64 * NW), lds, stream, p);
   return 0;
 }
 
-// does the dispatcher below take this shape (given the HWIO kernel)?  Such layers never read the transposed copy.
-int geeco_dgrad_lds_handles(int H, int W, int Cin, int Cout, int stride) {
-  if (stride != 2 || (H & 1) || (W & 1) || Cin % 64 != 0 || Cout % 16 != 0 || Cout < 32) return 0;
-  const int Ho = H / 2, Wo = W / 2;
-  if (!((Ho % 8 == 0 && Wo % 16 == 0) || (Ho == 8 && Wo == 8))) return 0;
-  if ((long long)H * W * Cin >= (1ll << 31) || (long long)Ho * Wo * Cout >= (1ll << 31) || 9ll * Cin * Cout >= (1ll << 30)) return 0;      // (weight granules are addressed by 32-bit BYTE offsets)
-  return 1;
-}
-
+// The whole choice (shape condition, 32-bit limits, variant, 64- or 32-channel items, tile grid, item and block counts) is
+// dgrad_lds_plan's (conv_halo_plan.h); geeco_dgrad_lds_handles there asks the same shape condition.  Layers it takes never read
+// the transposed copy.
 static int dgrad_lds_impl(const float* dz, const float* w_hwio, const float* ymask, const unsigned char* fields,
                           int64_t gs_fields, float* dx, int groups, int64_t gs_dz, int64_t gs_w, int64_t gs_dx, int N, int H,
-                          int W, int Cin, int Cout, int stride, hipStream_t stream, int* handled);
+                          int W, int Cin, int Cout, int stride, hipStream_t stream, int* handled) {
+  *handled = 0;
+  if (!w_hwio) return 0;
+  const DgradLdsPlan pl = dgrad_lds_plan(groups, N, H, W, Cin, Cout, stride);
+  if (pl.variant == DGRAD_LDS_NONE) return 0;
+  DgradLdsParams p = {};
+  p.dz = dz; p.w = w_hwio; p.mask = ymask; p.fields = fields; p.gs_fields = gs_fields; p.dx = dx; p.gs_dz = gs_dz; p.gs_w = gs_w; p.gs_dx = gs_dx;
+  p.N = N; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2; p.Cin = Cin; p.Cout = Cout;
+  p.stagger = 1;
+  p.tiles_y = pl.tiles_y; p.tiles_x = pl.tiles_x; p.tiles_per_group = pl.tiles_per_group;
+  p.n_cib = pl.n_cib; p.items = pl.items;
+  int rc;
+  if (pl.variant == DGRAD_LDS_FRAME) rc = launch_dgrad_lds<2, 8, 1, 2, 4>(p, pl, stream);
+  else if (pl.variant == DGRAD_LDS_32) rc = launch_dgrad_lds<1, 16, 1, 2, 8>(p, pl, stream);
+  else rc = launch_dgrad_lds<1, 16, 1, 4, 8>(p, pl, stream);
+  if (rc) return rc;
+  GEECO_LAUNCH_CHECK();
+  *handled = 1;
+  return 0;
+}
 
 int geeco_try_dgrad_lds(const float* dz, const float* w_hwio, const float* ymask, float* dx, int groups, int64_t gs_dz,
                         int64_t gs_w, int64_t gs_dx, int N, int H, int W, int Cin, int Cout, int stride,
@@ -317,62 +332,5 @@ extern "C" int geeco_conv3x3_dgrad_relu_fields(const float* dz, const float* w, 
   if (rc) return rc;
   GEECO_CHECK_ARG(handled, "conv3x3_dgrad_relu_fields: shape %dx%d, %d -> %d channels, stride %d is not served by the "
                            "LDS-staged input-gradient kernel", H, W, Cin, Cout, stride);
-  return 0;
-}
-
-static int dgrad_lds_impl(const float* dz, const float* w_hwio, const float* ymask, const unsigned char* fields,
-                          int64_t gs_fields, float* dx, int groups, int64_t gs_dz, int64_t gs_w, int64_t gs_dx, int N, int H,
-                          int W, int Cin, int Cout, int stride, hipStream_t stream, int* handled) {
-  *handled = 0;
-  if (!w_hwio || stride != 2 || (H & 1) || (W & 1) || Cin % 64 != 0 || Cout % 16 != 0 || Cout < 32) return 0;
-  const int Ho = H / 2, Wo = W / 2;
-  int variant = 0;
-  if (Ho % 8 == 0 && Wo % 16 == 0) variant = 1;          // 8 groups of 1 x 16 class pixels: a 16 x 32 input-pixel tile
-  else if (Ho == 8 && Wo == 8) variant = 2;               // 8 x 8 class pixels per frame: one-frame tiles
-  if (!variant) return 0;
-  if ((long long)H * W * Cin >= (1ll << 31) || (long long)Ho * Wo * Cout >= (1ll << 31) || 9ll * Cin * Cout >= (1ll << 30)) return 0;      // (weight granules are addressed by 32-bit BYTE offsets)
-  DgradLdsParams p = {};
-  p.dz = dz; p.w = w_hwio; p.mask = ymask; p.fields = fields; p.gs_fields = gs_fields; p.dx = dx; p.gs_dz = gs_dz; p.gs_w = gs_w; p.gs_dx = gs_dx;
-  p.N = N; p.H = H; p.W = W; p.Ho = Ho; p.Wo = Wo; p.Cin = Cin; p.Cout = Cout;
-  p.stagger = 1;
-  if (variant == 2) {
-    // 8 x 8 class pixels per frame: one-frame tiles of 4 groups, 32-channel items, 256-thread blocks, three per CU.  The
-    // two-frame / 8-wave form has only groups * (Cin / 64) * N / 2 items (conv6 of the bench: 144 for 256 CUs).
-    p.tiles_y = 1; p.tiles_x = 1;
-    p.tiles_per_group = N;
-    p.n_cib = Cin / 32;
-    const long long items = (long long)groups * p.n_cib * N;
-    if (items >= (1ll << 30)) return 0;
-    p.items = (int)items;
-    const int blocks = p.items < 768 ? p.items : 768;
-    int rcs = launch_dgrad_lds<2, 8, 1, 2, 4>(p, blocks, stream);
-    if (rcs) return rcs;
-    GEECO_LAUNCH_CHECK();
-    *handled = 1;
-    return 0;
-  }
-  p.tiles_y = Ho / 8; p.tiles_x = Wo / 16;
-  const long long tiles = (long long)N * p.tiles_y * p.tiles_x;
-  p.tiles_per_group = (int)tiles;
-  // 64-channel items (one block per CU) or 32-channel items (two blocks per CU): whichever spreads the launch more evenly
-  // over the 256 CUs; cost of an item in CU-time: 1 resp. 1/2.  Ties go to the 64-channel form (more reuse per staged byte).
-  const long long items64 = (long long)groups * (Cin / 64) * tiles;
-  if (items64 * 2 >= (1ll << 30)) return 0;
-  const double span64 = (double)((items64 + 255) / 256), span32 = 0.5 * (double)((2 * items64 + 255) / 256);
-  int rc;
-  if (span32 < span64) {
-    p.n_cib = Cin / 32;
-    p.items = (int)(2 * items64);
-    const int blocks = p.items < 512 ? p.items : 512;
-    rc = launch_dgrad_lds<1, 16, 1, 2>(p, blocks, stream);
-  } else {
-    p.n_cib = Cin / 64;
-    p.items = (int)items64;
-    const int blocks = p.items < 256 ? p.items : 256;
-    rc = launch_dgrad_lds<1, 16, 1, 4>(p, blocks, stream);
-  }
-  if (rc) return rc;
-  GEECO_LAUNCH_CHECK();
-  *handled = 1;
   return 0;
 }

@@ -601,20 +601,8 @@ static int launch_conv_gemm(ConvGemmParams& p, int groups, void* ws, hipStream_t
 
 // Which kernel family serves a layer, once per direction: every entry point below asks here, so a layer runs the same kernel
 // on every path (the bitwise statements of the tests rest on it).  Forward: LDS-halo, conv1's, else this file's gather GEMM.
-enum ConvFamily { CONV_HALO, CONV_CONV1, CONV_DGRAD_LDS, CONV_GATHER_GEMM };
-
-static ConvFamily conv_fwd_family(int H, int W, int Cin, int Cout, int stride) {
-  if (geeco_halo_fwd_handles(H, W, Cin, Cout, stride)) return CONV_HALO;
-  if (geeco_conv1_fwd_handles(Cin, Cout, stride)) return CONV_CONV1;
-  return CONV_GATHER_GEMM;
-}
-
-// Input gradient: LDS-halo, LDS-staged, else the gather GEMM.
-static ConvFamily conv_dgrad_family(int H, int W, int Cin, int Cout, int stride) {
-  if (geeco_halo_dgrad_handles(H, W, Cin, Cout, stride)) return CONV_HALO;
-  if (geeco_dgrad_lds_handles(H, W, Cin, Cout, stride)) return CONV_DGRAD_LDS;
-  return CONV_GATHER_GEMM;
-}
+// Input gradient: LDS-halo, LDS-staged, else the gather GEMM.  conv_fwd_family and conv_dgrad_family: conv_halo_plan.h (through
+// conv_internal.h), plain C++ that the host tests evaluate.
 
 extern "C" int64_t geeco_conv3x3_fwd_ws_bytes(int groups, int N, int H, int W, int Cin, int Cout, int stride) {
   ConvGemmParams p = {};

@@ -177,21 +177,16 @@ static int launch_conv1_fwd(const float* x, const float* w, const float* b, floa
   p.w_cin = w_cin;
   p.x = x; p.w = w; p.bias = b; p.y = y; p.gs_x = gs_x; p.gs_w = gs_w; p.gs_b = gs_b; p.gs_y = gs_y;
   p.bits = bits; p.gs_bits = gs_bits; p.Wp = (int)geeco_relu_bits_pitch(W); p.Hp = (int)geeco_relu_bits_rows(H);
-  p.N = N; p.H = H; p.W = W; p.tiles_x = cdiv(W, 32); p.tiles_y = cdiv(H, 8); p.relu = relu;
-  const int ntiles = N * p.tiles_x * p.tiles_y;
-  constexpr int bpg = 768;   // blocks per encoder (256..2048 within 5 %)
-  dim3 grid((unsigned)(ntiles < bpg ? ntiles : bpg), (unsigned)groups);
-  geeco_note_kernel("conv1_halo_fwd_kernel");
+  const HaloTileGrid tg = conv1_fwd_grid(groups, N, H, W);      // 8 x 32 tiles, 768 blocks per encoder: conv_halo_plan.h
+  p.N = N; p.H = H; p.W = W; p.tiles_x = tg.tiles_x; p.tiles_y = tg.tiles_y; p.relu = relu;
+  dim3 grid((unsigned)tg.blocks, (unsigned)tg.grid_y);
+  geeco_note_kernel("conv1_halo_fwd_kernel<%s>", w_cin == 3 ? "true" : "false");
   if (w_cin == 3)
     hipLaunchKernelGGL(conv1_halo_fwd_kernel<true>, grid, dim3(256), 0, stream, p);
   else
     hipLaunchKernelGGL(conv1_halo_fwd_kernel<false>, grid, dim3(256), 0, stream, p);
   GEECO_LAUNCH_CHECK();
   return 0;
-}
-
-int geeco_conv1_fwd_handles(int Cin, int Cout, int stride) {
-  return stride == 1 && Cin == 4 && Cout == 32;
 }
 
 int geeco_try_conv1_fwd(const float* x, const float* w, const float* b, float* y, int groups, int64_t gs_x,

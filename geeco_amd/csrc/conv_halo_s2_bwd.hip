@@ -767,11 +767,10 @@ __global__ __launch_bounds__(512) void conv_s2_halo_dgrad_chunked_kernel(const H
 
 template <int CIN, int COUT, bool FIELDS = false>
 static int launch_dgrad_chunked(HaloDgradParams& p, hipStream_t stream) {
-  constexpr int BUF_F4 = ((5 * 33 * 4 + 63) / 64) * 64;
-  const size_t lds = (size_t)(9 * CIN * (COUT / 4 + 2) + 2 * BUF_F4) * 16;
+  const size_t lds = halo_dgrad_chunked_lds_bytes(CIN, COUT);
   if (int rc = geeco_lds_opt_in<&conv_s2_halo_dgrad_chunked_kernel<CIN, COUT, FIELDS>>(lds)) return rc;
-  const long long cus = 256 - geeco_call_reserved_cus();     // data parallel: CUs left to the collective that runs beside part 2
-  long long blocks = p.ntiles < cus ? p.ntiles : cus;
+  // data parallel: the reserved CUs are left to the collective that runs beside part 2
+  const int blocks = halo_blocks(p.ntiles, 256 - geeco_call_reserved_cus());
   geeco_note_kernel("conv_s2_halo_dgrad_chunked_kernel<%d, %d, %s>", CIN, COUT, FIELDS ? "true" : "false");
   hipLaunchKernelGGL((conv_s2_halo_dgrad_chunked_kernel<CIN, COUT, FIELDS>), dim3((unsigned)blocks), dim3(512), lds, stream, p);
   return 0;
@@ -784,18 +783,15 @@ static HaloDgradParams halo_dgrad_params(const float* dz, const float* w_hwio, c
   p.dz = dz; p.w = w_hwio; p.mask = ymask; p.dx = dx;
   p.gs_dz = gs_dz; p.gs_w = gs_w; p.gs_dx = gs_dx;
   p.N = N; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2;
-  p.tiles_x = cdiv(W, 64); p.tiles_y = cdiv(H, 8);
-  p.tiles_per_group = N * p.tiles_x * p.tiles_y;
-  p.ntiles = (long long)groups * p.tiles_per_group;
+  const HaloTileGrid tg = halo_dgrad_grid(groups, N, H, W, 0);      // 8 x 64 input-pixel tiles: conv_halo_plan.h
+  p.tiles_x = tg.tiles_x; p.tiles_y = tg.tiles_y;
+  p.tiles_per_group = tg.tiles_per_group;
+  p.ntiles = tg.ntiles;
   return p;
 }
 
-// does the dispatcher below take this shape (given the HWIO kernel)?  Such layers never read the transposed copy.
-int geeco_halo_dgrad_handles(int H, int W, int Cin, int Cout, int stride) {
-  if (stride != 2 || (H % 2) || (W % 2)) return 0;
-  return (Cin == 48 && Cout == 64) || (Cin == 32 && Cout == 48);
-}
-
+// geeco_halo_dgrad_handles (conv_halo_plan.h): does the dispatcher below take this shape (given the HWIO kernel)?  Such layers
+// never read the transposed copy.
 int geeco_try_halo_dgrad(const float* dz, const float* w_hwio, const float* ymask, float* dx, int groups,
                          int64_t gs_dz, int64_t gs_w, int64_t gs_dx, int N, int H, int W, int Cin, int Cout,
                          int stride, hipStream_t stream, int* handled) {
@@ -806,9 +802,9 @@ int geeco_try_halo_dgrad(const float* dz, const float* w_hwio, const float* ymas
     int rc = launch_dgrad_chunked<48, 64>(p, stream);
     if (rc) return rc;
   } else {                // conv2
-    const size_t lds = (size_t)(9 * 32 * 15 + 2 * 12 * 165) * 16;
+    const size_t lds = halo_dgrad_lds_bytes(32, 48);
     if (int rc = geeco_lds_opt_in<&conv_s2_halo_dgrad_kernel<32, 48>>(lds)) return rc;
-    long long blocks = p.ntiles < 256 ? p.ntiles : 256;
+    const int blocks = halo_blocks(p.ntiles, 256);
     geeco_note_kernel("conv_s2_halo_dgrad_kernel<32, 48>");
     hipLaunchKernelGGL((conv_s2_halo_dgrad_kernel<32, 48>), dim3((unsigned)blocks), dim3(512), lds, stream, p);
   }

@@ -310,11 +310,10 @@ __global__ __launch_bounds__(512 + 64 * LW) void conv_s2_halo_fwd_ws_kernel(cons
 
 template <int CIN, int COUT, int LW>
 static int launch_s2_halo_fwd_ws(HaloFwdParams& p, hipStream_t s) {
-  constexpr int HALO_F4 = ((9 * 17 * 16 + 63) / 64) * 64;
-  const size_t lds = (size_t)(3 * HALO_F4 + 2 * 4 * (COUT / 16) * 64 + 4 * 16 * (COUT / 4 + 1)) * 16;
+  const size_t lds = halo_fwd_ws_lds_bytes(COUT);
   if (int rc = geeco_lds_opt_in<&conv_s2_halo_fwd_ws_kernel<CIN, COUT, LW>>(lds)) return rc;
   p.stamps = geeco_arm_halo_stamps();
-  long long blocks = p.ntiles < 256 ? p.ntiles : 256;
+  const int blocks = halo_blocks(p.ntiles, HALO_FWD_CUS);
   geeco_note_kernel("conv_s2_halo_fwd_ws_kernel<%d, %d, %d>", CIN, COUT, LW);
   hipLaunchKernelGGL((conv_s2_halo_fwd_ws_kernel<CIN, COUT, LW>), dim3((unsigned)blocks), dim3(512 + 64 * LW), lds, s, p);
   GEECO_LAUNCH_CHECK();
@@ -532,10 +531,9 @@ __global__ __launch_bounds__(512) void conv_s2_halo_fwd_chunked_kernel(const Hal
 
 template <int CIN, int COUT>
 static int launch_s2_halo_fwd_chunked(HaloFwdParams& p, hipStream_t s) {
-  constexpr int BUF_F4 = ((9 * 17 * 8 + 63) / 64) * 64;
-  const size_t lds = (size_t)(9 * (CIN / 4) * COUT + 2 * BUF_F4) * 16;
+  const size_t lds = halo_fwd_chunked_lds_bytes(CIN, COUT);
   if (int rc = geeco_lds_opt_in<&conv_s2_halo_fwd_chunked_kernel<CIN, COUT>>(lds)) return rc;
-  long long blocks = p.ntiles < 256 ? p.ntiles : 256;
+  const int blocks = halo_blocks(p.ntiles, HALO_FWD_CUS);
   geeco_note_kernel("conv_s2_halo_fwd_chunked_kernel<%d, %d>", CIN, COUT);
   hipLaunchKernelGGL((conv_s2_halo_fwd_chunked_kernel<CIN, COUT>), dim3((unsigned)blocks), dim3(512), lds, s, p);
   GEECO_LAUNCH_CHECK();
@@ -549,20 +547,16 @@ static HaloFwdParams halo_fwd_params(const float* x, const float* w, const float
   p.x = x; p.w = w; p.bias = b; p.y = y;
   p.gs_x = gs_x; p.gs_w = gs_w; p.gs_b = gs_b; p.gs_y = gs_y;
   p.N = N; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2;
-  p.tiles_x = cdiv(p.Wo, 16); p.tiles_y = cdiv(p.Ho, 4);
-  p.tiles_per_group = N * p.tiles_x * p.tiles_y;
-  p.ntiles = (long long)groups * p.tiles_per_group;
+  const HaloTileGrid tg = halo_fwd_grid(groups, N, H, W);      // 4 x 16 output-pixel tiles, at most 256 blocks: conv_halo_plan.h
+  p.tiles_x = tg.tiles_x; p.tiles_y = tg.tiles_y;
+  p.tiles_per_group = tg.tiles_per_group;
+  p.ntiles = tg.ntiles;
   p.relu = relu;
   return p;
 }
 
-// does the dispatcher below take this shape?  (geeco_conv3x3_fwd_state asks: a layer these kernels serve must not go through
-// the gather GEMM there while every other path runs it through them)
-int geeco_halo_fwd_handles(int H, int W, int Cin, int Cout, int stride) {
-  if (stride != 2 || (H % 2) || (W % 2)) return 0;
-  return (Cin == 32 && Cout == 48) || (Cin == 48 && Cout == 64);
-}
-
+// geeco_halo_fwd_handles (conv_halo_plan.h): does the dispatcher below take this shape?  (geeco_conv3x3_fwd_state asks: a layer
+// these kernels serve must not go through the gather GEMM there while every other path runs it through them)
 // Returns 1 if handled, 0 if the shape is not covered (caller falls back to the gather-GEMM),
 // or an error code < 0 / hipError.
 int geeco_try_halo_fwd(const float* x, const float* w, const float* b, float* y, int groups, int64_t gs_x,

@@ -2,7 +2,9 @@
 tests/test_conv_gemm_variants_gpu.py holds the device side, tests/test_conv_refs_cpu.py shows that the bounds reject wrong kernels,
 tests/test_conv_cover_cpu.py that the case list (tests/native/conv_gemm_cases.txt) runs every launch variant the model reaches.
 The same four parts for the filter gradient (geeco_conv3x3_wgrad) are at the end of this file: tests/native/conv_wgrad_cases.txt,
-tests/test_conv_wgrad_variants_gpu.py, tests/test_conv_wgrad_refs_cpu.py, tests/test_conv_wgrad_cover_cpu.py.
+tests/test_conv_wgrad_variants_gpu.py, tests/test_conv_wgrad_refs_cpu.py, tests/test_conv_wgrad_cover_cpu.py.  Behind them the same
+four parts for the LDS-halo and LDS-staged forwards and input gradients: tests/native/conv_halo_cases.txt,
+tests/test_conv_halo_variants_gpu.py, tests/test_conv_halo_refs_cpu.py, tests/test_conv_halo_cover_cpu.py.
 
 Everything here is written from the definition of tf.layers.conv2d(kernel_size=3, padding='SAME') on NHWC tensors with an HWIO
 kernel, not from the kernels: the padded input is built explicitly, the output is the sum over the nine taps of a strided window
@@ -10,6 +12,7 @@ times that tap's [Cin][Cout] matrix, and the input gradient scatters dz times th
 float64 throughout, on the float32 values the device is given.  comparison helpers: tests/_primitive_refs.py.
 """
 import collections
+import functools
 import math
 import os
 import re
@@ -343,3 +346,206 @@ def wgrad_case_expect(c, exact):
   if exact:
     return x, dz, dw, db, np.zeros_like(dw), np.zeros_like(db)
   return x, dz, dw, db, wgrad_bound(mw, c.slice_px, c.S), wgrad_bound(mb, c.slice_px, c.S)
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# LDS-halo and LDS-staged forwards and input gradients: case list, sign-field packers, seeded inputs, expectations
+# --------------------------------------------------------------------------------------------------------------------------
+HALO_CASES_TXT = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'native', 'conv_halo_cases.txt')
+
+HaloCase = collections.namedtuple('HaloCase', 'index dir G N H W Cin Cout stride flags reserved text plan family inst items blocks '
+                                  'rounds cross empty')
+_HALO_PLAN = re.compile(r'^(lds|halo|conv1) (.+) items=(\d+) blocks=(\d+) rounds=(\d+) cross=(\S+) empty=(\d+)$')
+_HALO_FLAGS = {'dgrad': {'mask', 'fields', 'hostonly'}, 'fwd': {'relu', 'bias', 'fields', 'bits', 'rgb', 'hostonly'}}
+
+
+def load_halo_cases(device_only=False):
+  """The cases of tests/native/conv_halo_cases.txt with the plan recorded beside each (tests/test_conv_halo_cover_cpu.py holds that
+  text against what geeco_amd/csrc/conv_halo_plan.h gives).  device_only: without the lines the cover alone holds."""
+  cases = []
+  for line in open(HALO_CASES_TXT):
+    line = line.strip()
+    if not line or line.startswith('#'):
+      continue
+    text, plan = (s.strip() for s in line.split('|'))
+    f = text.split()
+    flags = frozenset(t for t in f[8:] if not t.startswith('reserved='))
+    reserved = [int(t.split('=')[1]) for t in f[8:] if t.startswith('reserved=')]
+    assert f[0] in _HALO_FLAGS and flags <= _HALO_FLAGS[f[0]] and len(reserved) <= 1 and not {'fields', 'mask'} <= flags, line
+    m = _HALO_PLAN.match(plan)
+    assert m or plan == 'gemm', line
+    fam = (m.group(1), m.group(2), int(m.group(3)), int(m.group(4)), int(m.group(5)), frozenset(m.group(6).split('+')) - {'none'},
+           int(m.group(7))) if m else ('gemm', '', 0, 0, 0, frozenset(), 0)
+    c = HaloCase(len(cases), f[0], *(int(v) for v in f[1:8]), flags, reserved[0] if reserved else 0, text, plan, *fam)
+    assert (c.family == 'gemm') <= ('hostonly' in flags), line      # a declined shape is the gather GEMM's: not a case of the device list
+    cases.append(c)
+  return [c for c in cases if not (device_only and 'hostonly' in c.flags)]
+
+
+def halo_form(c):
+  """The mask form of a case: none / mask / fields for a gradient, plain / fields / bits for a forward."""
+  if c.dir == 'dgrad':
+    return 'fields' if 'fields' in c.flags else 'mask' if 'mask' in c.flags else 'none'
+  return 'fields' if 'fields' in c.flags else 'bits' if 'bits' in c.flags else 'plain'
+
+
+def halo_key(c):
+  """The key tests/native/conv_halo_cover.cpp prints for the sweep's launches."""
+  return '%s %s %s %s' % (c.family, c.inst, 'several' if c.rounds > 1 else 'one', halo_form(c))
+
+
+def halo_out_hw(c):
+  return same_pad(c.H, c.stride)[0], same_pad(c.W, c.stride)[0]
+
+
+def halo_terms(c):
+  """Products per output element: forward 9 Cin (27 through the RGB kernel variable: the pad channel has no kernel rows); input
+  gradient: dgrad_terms."""
+  if c.dir == 'fwd':
+    return 27.0 if 'rgb' in c.flags else 9.0 * c.Cin
+  return dgrad_terms((c.H, c.W), c.stride, c.Cout)
+
+
+# ---- sign fields and words, packed from the definitions in include/geeco_hip.h ---------------------------------------------
+def pack_fields16(pos):
+  """pos [..., C] bool, C = 16 n <= 64 -> uint16 [..., 4]: field q, bit 4 i + j set iff channel 16 i + 4 q + j is positive."""
+  C = pos.shape[-1]
+  assert C % 16 == 0 and C <= 64
+  out = np.zeros(pos.shape[:-1] + (4,), np.uint16)
+  for ch in range(C):
+    i, q, j = ch // 16, (ch % 16) // 4, ch % 4
+    out[..., q] |= pos[..., ch].astype(np.uint16) << np.uint16(4 * i + j)
+  return out
+
+
+def pack_fields8(pos):
+  """pos [..., C] bool, C = 32 n -> uint8 [..., C / 8]: byte (T >> 1) * 4 + q, bit 4 (T & 1) + j set iff channel 16 T + 4 q + j is
+  positive (T = 16-channel tile, q = channel quad inside it)."""
+  C = pos.shape[-1]
+  assert C % 32 == 0
+  out = np.zeros(pos.shape[:-1] + (C // 8,), np.uint8)
+  for ch in range(C):
+    T, q, j = ch // 16, (ch % 16) // 4, ch % 4
+    out[..., (T >> 1) * 4 + q] |= pos[..., ch].astype(np.uint8) << np.uint8(4 * (T & 1) + j)
+  return out
+
+
+def pack_bits32(pos):
+  """pos [..., 32] bool -> uint32 [...]: bit (c & 3) * 8 + (c >> 2) set iff channel c is positive (conv1's ReLU sign words)."""
+  assert pos.shape[-1] == 32
+  out = np.zeros(pos.shape[:-1], np.uint32)
+  for ch in range(32):
+    out |= pos[..., ch].astype(np.uint32) << np.uint32((ch & 3) * 8 + (ch >> 2))
+  return out
+
+
+def pad_planes(a, Hp, Wp, fill):
+  """a [G][N][H][W][...] -> [G][N][Hp][Wp][...] with ``fill`` outside the image (the padded planes of the uint16 fields and of
+  conv1's words: whole 8 x 64 tiles)."""
+  out = np.full(a.shape[:2] + (Hp, Wp) + a.shape[4:], fill, a.dtype)
+  out[:, :, :a.shape[2], :a.shape[3]] = a
+  return out
+
+
+def tiles_8x64(H, W):
+  return (H + 7) // 8 * 8, (W + 63) // 64 * 64
+
+
+# ---- seeded inputs and the float64 expectation -----------------------------------------------------------------------------
+def _halo_shape_key(c):
+  return (c.dir, c.G, c.N, c.H, c.W, c.Cin, c.Cout, c.stride, 'rgb' in c.flags)
+
+
+def _halo_seed(key, exact):
+  return [3000 + (1 if exact else 0)] + [int(v) for v in key[1:]] + [0 if key[0] == 'fwd' else 1]
+
+
+@functools.lru_cache(maxsize=1)
+def _halo_shape_expect(key, exact):
+  """Inputs, pre and mag of a shape: shared by the cases of the list that differ only in their mask form (one is kept: the
+  largest holds some hundred megabytes in float64).  Callers leave the arrays unchanged."""
+  d, G, N, H, W, Cin, Cout, s, rgb = key
+  r = np.random.default_rng(_halo_seed(key, exact))
+  Ho, Wo = same_pad(H, s)[0], same_pad(W, s)[0]
+  f = lambda a: a.astype(np.float32)
+  ints = lambda lo, hi, shape: f(r.integers(lo, hi + 1, shape))
+  if d == 'fwd':
+    wc = 3 if rgb else Cin
+    if exact:
+      x, w, b = ints(-2, 2, (G, N, H, W, Cin)), ints(-2, 2, (G, 3, 3, wc, Cout)), ints(-3, 3, (G, Cout))
+    else:
+      x = f(r.standard_normal((G, N, H, W, Cin)))
+      w = f(r.standard_normal((G, 3, 3, wc, Cout)) / math.sqrt(9 * wc))
+      b = f(np.sign(r.standard_normal((G, Cout))) * r.uniform(2.0, 4.0, (G, Cout)))
+    out = [conv_fwd_ref(x[g][..., :wc], w[g], b[g], s, False) for g in range(G)]
+    inp = dict(x=x, w=w, b=b)
+  else:
+    if exact:
+      dz, w = ints(-2, 2, (G, N, Ho, Wo, Cout)), ints(-2, 2, (G, 3, 3, Cin, Cout))
+      mask = ints(-1, 1, (G, N, H, W, Cin))
+    else:
+      dz = f(r.standard_normal((G, N, Ho, Wo, Cout)))
+      w = f(r.standard_normal((G, 3, 3, Cin, Cout)) / math.sqrt(9 * Cout))
+      mask = r.standard_normal((G, N, H, W, Cin), dtype=np.float32)
+      mask[r.random(mask.shape, dtype=np.float32) < 0.3] = 0.0
+    out = [conv_dgrad_ref(dz[g], w[g], (H, W), s, None) for g in range(G)]
+    inp = dict(dz=dz, w=w, mask=mask)
+  pre, mag = np.stack([o[2] for o in out]), np.stack([o[1] for o in out])
+  for a in (pre, mag):      # (the operands go to torch.from_numpy, which wants them writable: the device test checks them unchanged)
+    a.setflags(write=False)
+  return inp, pre, mag
+
+
+def halo_case_expect(c, exact):
+  """-> (inputs, ref, bound, keep) of a case, the last three [G][...].
+  exact: integers (operands in [-2, 2], bias in [-3, 3], mask in {-1, 0, 1}): every partial sum is an integer of magnitude at most
+  16 Cout + 3 (gradient: at most four taps reach a pixel) or 36 Cin + 3 (forward), far below 2**24, so float32 in any order gives the
+  float64 result: bound 0 everywhere, nothing left out.
+  Otherwise case_inputs' distributions under conv_bound(mag, halo_terms, S = 1).
+  The gradient's inputs always hold the float mask; the case's form decides what the launch is given (halo_form)."""
+  inp, pre, mag = _halo_shape_expect(_halo_shape_key(c), bool(exact))
+  if c.dir == 'fwd':
+    relu = 'relu' in c.flags
+    if exact:
+      ref = np.maximum(pre, 0.0) if relu else pre
+      return inp, ref, np.zeros_like(ref), np.ones(ref.shape, bool)
+    return (inp,) + conv_expect(pre, mag, halo_terms(c), 1, relu=relu)
+  mask = inp['mask'] if halo_form(c) != 'none' else None
+  if exact:
+    ref = pre if mask is None else np.where(mask > 0, pre, 0.0)
+    return inp, ref, np.zeros_like(ref), np.ones(ref.shape, bool)
+  return (inp,) + conv_expect(pre, mag, halo_terms(c)[None, None], 1, mask=mask)
+
+
+def halo_compare(c, exact, got, inp, ref, bound, keep):
+  """The comparisons of one pass of tests/test_conv_halo_variants_gpu.py on an output ``got`` [G][...] float32 -> (worst share of
+  the rounding bound, problems): what the device test asserts empty and tests/test_conv_halo_refs_cpu.py holds against emulated
+  kernels with one mistake each.
+    no NaN; exact pass: equality with the float64 result; rounding pass: assert_within's test, and equality where the bound is 0
+    (cut by the ReLU, masked off); a masked gradient: the elements masked off are +0.0 bit for bit."""
+  problems, worst = [], 0.0
+  if np.isnan(got).any():
+    problems.append('NaN in %d elements' % int(np.isnan(got).sum()))
+  g64 = got.astype(np.float64)
+  if exact:
+    bad = ~(g64 == ref)
+    if bad.any():
+      problems.append('exact: %d of %d elements differ from the float64 result, the first at %s' % (
+          int(bad.sum()), bad.size, tuple(np.argwhere(bad)[0])))
+  else:
+    err = np.abs(g64 - ref)
+    bad = ~(err <= bound) & keep
+    live = keep & (bound > 0)
+    if live.any():
+      with np.errstate(invalid='ignore'):
+        worst = float(np.nanmax(err[live] / bound[live]))
+    if bad.any():
+      at = tuple(np.argwhere(bad)[0])
+      problems.append('rounding: %d of %d elements out of bound, the first at %s: got %.9g, reference %.9g (bound %.3e)' % (
+          int(bad.sum()), bad.size, at, got[at], ref[at], bound[at]))
+  if c.dir == 'dgrad' and halo_form(c) != 'none':
+    off = ~(inp['mask'] > 0)
+    n = int(np.count_nonzero(np.ascontiguousarray(got).view(np.uint32)[off]))
+    if n:
+      problems.append('bits: %d masked elements are not +0.0' % n)
+  return worst, problems

@@ -48,6 +48,35 @@ class Slab:
     return self.buf.view(torch.int32)
 
 
+class IntSlab:
+  """Slab for sign fields and sign words (uint8 as torch.uint8, uint16 as torch.int16, uint32 as torch.int32): [G] tensors of
+  ``size`` elements each at group stride size + gap.  There is no NaN for integers: the slack, and every element a launch has not
+  written, is the byte pattern 0xA5."""
+  FILL = 0xA5
+
+  def __init__(self, dev, G, size, dtype, values=None, gap=12):
+    self.G, self.size, self.gs = G, size, size + gap
+    self.buf = torch.empty(LEAD + G * self.gs - gap + TAIL, dtype=dtype, device=dev)
+    self.buf.view(torch.uint8).fill_(self.FILL)
+    self.fill = int(self.buf[0])      # the pattern as one element of dtype
+    self.first = self.buf[LEAD:]
+    self.inside = torch.zeros(self.buf.numel(), dtype=torch.bool, device=dev)
+    for g in range(G):
+      self.inside[LEAD + g * self.gs:LEAD + g * self.gs + size] = True
+      if values is not None:
+        v = np.ascontiguousarray(values[g]).reshape(-1)
+        self.group(g).copy_(torch.from_numpy(v.view({1: np.uint8, 2: np.int16, 4: np.int32}[v.itemsize])))
+
+  def group(self, g):
+    return self.buf[LEAD + g * self.gs:LEAD + g * self.gs + self.size]
+
+  def slack_untouched(self):
+    return bool((self.buf[~self.inside] == self.fill).all())
+
+  def bits(self):
+    return self.buf
+
+
 def _launch(c, dev, inp):
   """One launch of the case into fresh NaN-filled buffers -> (kernel names, output slab, every slab, workspace bytes asked for)."""
   from geeco_amd import ops

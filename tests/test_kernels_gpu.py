@@ -59,7 +59,9 @@ def test_conv3x3_fwd(dev, N, H, W, Cin, Cout, stride):
 
 
 # LDS-staged input gradient of the middle layers (conv_dgrad_lds.hip): both tile variants, several ci blocks, odd frame
-# counts for the two-frame tiles, more items than one round of blocks
+# counts for the two-frame tiles, more items than one round of blocks.  Nothing here pins the instantiation a case runs or makes a
+# block take a second item: tests/native/conv_halo_cases.txt holds one small case per instantiation, mask form and edge with the
+# plan recorded and checked (tests/test_conv_halo_cover_cpu.py, tests/test_conv_halo_variants_gpu.py, against float64 inside NaN slack).
 DGRAD_LDS_CASES = [
     (3, 32, 64, 64, 128, 2),    # 1x16 groups: Ho = 16, Wo = 32 -> 2 x 2 tiles per frame
     (2, 16, 32, 128, 64, 2),    # two ci blocks, one tile per frame
@@ -396,6 +398,8 @@ def test_derive_conv_weights(dev):
 # Grouped launches (G encoders at a stride, as the training step issues them) of the persistent LDS-halo
 # kernels, sized so that some block's tile range CROSSES an encoder boundary: that block has to swap the
 # kernel it keeps resident in LDS mid-flight.  (The single-group cases above never take that path.)
+# (Exact and ragged tiles, ranges across frames and encoders, empty blocks, every mask form, under derived bounds:
+# tests/native/conv_halo_cases.txt, tests/test_conv_halo_variants_gpu.py.)
 @pytest.mark.parametrize('Cin,Cout,Nf,Nd', [(32, 48, 7, 5), (48, 64, 7, 5)])
 def test_conv3x3_grouped_halo_kernels(dev, Cin, Cout, Nf, Nd):
   from geeco_amd import ops
@@ -535,6 +539,8 @@ def test_conv1_relu_bits_and_fused_bits(dev, G, N, H, W, C):
   assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
 
 
+# (The uint16 fields against host-packed signs of a float64 reference, padded planes, reserved CUs: tests/native/conv_halo_cases.txt,
+# tests/test_conv_halo_variants_gpu.py.)
 @pytest.mark.parametrize('G,N,H,W', [(1, 2, 16, 64), (3, 2, 24, 72)])
 def test_conv2_relu_fields_and_conv3_dgrad_fields(dev, G, N, H, W):
   """conv2's forward with the sign-field side output (uint16 per (pixel, quad q): bit 4 i + j <-> channel 16 i + 4 q + j)
@@ -558,7 +564,7 @@ def test_conv2_relu_fields_and_conv3_dgrad_fields(dev, G, N, H, W):
   names = ops.kernel_trace(lambda: ops.conv2_fwd_relu_fields_into(y, fields, x, w2, b2, G, x[0].numel(), w2[0].numel(), 48,
                                                                   y[0].numel(), ne, N, H, W))
   torch.cuda.synchronize()
-  assert names[0].startswith('conv_s2_halo_fwd_ws_kernel'), names
+  assert names == ['conv_s2_halo_fwd_ws_kernel<32, 48, 4>'], names      # (the name conv_halo_plan.h's cover records)
   assert torch.equal(y, y_plain)
   pos = (y.cpu().numpy() > 0).reshape(G, N, H2, W2, 3, 4, 4)          # [.., i, q, j]
   want = np.zeros([G, N, H2, W2, 4], np.uint16)
@@ -782,6 +788,8 @@ def test_goal_dynimgs_from_resident_u8_frames(dev, N, K, H, W, C):
     ops.goal_dynimgs_u8_into(got[0], got[1], got[2], win.int(), tpt, K, N, HW, ws2, **kw)
 
 
+# (The byte fields against host-packed signs of a float64 reference, all three LDS-staged instantiations:
+# tests/native/conv_halo_cases.txt, tests/test_conv_halo_variants_gpu.py.)
 @pytest.mark.parametrize('G,N,H,W', [(1, 2, 32, 64), (3, 2, 64, 64)])
 def test_conv3_relu_fields_and_conv4_dgrad_fields(dev, G, N, H, W):
   """conv3's forward with the byte sign fields of its output (byte (T >> 1) * 4 + q, bit 4 (T & 1) + j <-> channel
@@ -802,7 +810,7 @@ def test_conv3_relu_fields_and_conv4_dgrad_fields(dev, G, N, H, W):
   names = ops.kernel_trace(lambda: ops.conv3_fwd_relu_fields_into(y, fields, x, w3, b3, G, x[0].numel(), w3[0].numel(), 64,
                                                                   y[0].numel(), fields[0].numel(), N, H, W))
   torch.cuda.synchronize()
-  assert names[0].startswith('conv_s2_halo_fwd_chunked_kernel'), names
+  assert names == ['conv_s2_halo_fwd_chunked_kernel<48, 64>'], names
   assert torch.equal(y, y_plain)
   pos = (y.cpu().numpy() > 0).reshape(G, N, H3, W3, 4, 4, 4)          # [.., T, q, j]
   want = np.zeros([G, N, H3, W3, 8], np.uint8)
@@ -824,7 +832,7 @@ def test_conv3_relu_fields_and_conv4_dgrad_fields(dev, G, N, H, W):
   n1 = ops.kernel_trace(lambda: ops.conv3x3_dgrad_relu_fields_into(dx, dz4, w4, fields, G, dz4[0].numel(), w4[0].numel(),
                                                                    fields[0].numel(), dx[0].numel(), N, H3, W3, 64, 128, 2))
   torch.cuda.synchronize()
-  assert n0 == n1 and n1[0].startswith('conv_s2_dgrad_lds_kernel'), (n0, n1)
+  assert n0 == n1 == ['conv_s2_dgrad_lds_kernel<1, 16, 1, 2, 8>'], (n0, n1)      # 32-channel items at both shapes (dgrad_lds_plan)
   assert not torch.isnan(dx).any() and torch.equal(dx, dx_ref)
 
 
@@ -908,6 +916,8 @@ def test_conv3x3_wgrad_grouped_lds(dev, Cin, Cout, H, W):
   assert torch.isnan(dw[:, 9 * Cin * Cout:]).all() and torch.isnan(db[:, Cout:]).all()     # pads untouched
 
 
+# (Blocks that take a second item across ci-block and encoder boundaries, <1, 16, 1, 4, 8>, Cout = 32: tests/native/conv_halo_cases.txt,
+# tests/test_conv_halo_variants_gpu.py.)
 @pytest.mark.parametrize('Cin,Cout,H,W,Nd', [(64, 128, 32, 32, 5), (128, 192, 16, 32, 4), (192, 256, 16, 16, 7)])
 def test_conv3x3_dgrad_grouped_lds(dev, Cin, Cout, H, W, Nd):
   """Grouped launch (G encoders, padded arena strides) of the LDS-staged input gradient with the fused ReluGrad mask and
@@ -931,7 +941,8 @@ def test_conv3x3_dgrad_grouped_lds(dev, Cin, Cout, H, W, Nd):
     names = ops.kernel_trace(lambda: ops.conv3x3_dgrad_into(dx, dzd, wt, md if use_mask else None, G, dzd[0].numel(), wt[0].numel(),
                                                             dx[0].numel(), Nd, H, W, Cin, Cout, stride, ws=dws, w=warena, gs_w=gs_w))
     torch.cuda.synchronize()
-    assert names and names[0].startswith('conv_s2_dgrad_lds_kernel'), names
+    # dgrad_lds_plan (conv_halo_plan.h): 32-channel items at the two wide shapes, one-frame tiles at 16 x 16
+    assert names == ['conv_s2_dgrad_lds_kernel<2, 8, 1, 2, 4>' if (H, W) == (16, 16) else 'conv_s2_dgrad_lds_kernel<1, 16, 1, 2, 8>'], names
     for g in range(G):
       xg = torch.zeros(Nd, H, W, Cin, dtype=torch.float64, requires_grad=True)
       yy = O.conv2d_same(xg, torch.tensor(w[g], dtype=torch.float64), torch.zeros(Cout, dtype=torch.float64), stride, relu=False)
