@@ -132,3 +132,118 @@ extern "C" int geeco_gather_windows_by_address(const int64_t* addr, const int* k
   GEECO_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- augmented window builder: the by-address builder with a per-window shift and colour transform ----------------------------
+// Training-time image augmentation (input_fn.pickplace_input_fn(augment=...)) where the frames already are: the
+// same table as above plus, per window, shift[n] = (dy, dx) in whole pixels and, for colour streams, colour[n] = gain[C], bias[C].
+// out[n][k][y][x][c] = tint(conv(frame k of window n at (y - dy, x - dx), channel c)), exactly 0.0f where that source pixel lies
+// outside the frame;  tint(v) = min(max(v * gain[c] + bias[c], 0), 1), the identity without `colour`.  One draw serves all K
+// frames of a window.  blockIdx = (unit, k, n) and 256 threads x 4 output elements as above.  A row holds RW = W * C elements and
+// a shift by whole pixels moves a row's elements by dx * C, so the channel of an element is kept and "inside the frame" is
+// 0 <= y - dy < H  and  0 <= r - dx * C < RW  for row offset r: both are tested BEFORE any address is formed, in 64-bit, so no
+// shift value reads outside [frame, frame + H * W * C).  RW % 4 == 0: a thread's four elements share a row and are stored as one
+// 16-byte word; four sources inside the row are read as one 16-byte (float32) / 4-byte (uint8) non-temporal load when their
+// address is aligned for it, else narrower: float32 as four words; uint8 as the two aligned words around them and a byte-align
+// when both lie inside the frame, else as bytes.  A group that crosses the left or right edge goes per element.  RW % 4 != 0
+// (groups straddle rows, frames are not 16-byte multiples): one element at a time, loads and stores.  HBM streaming: no LDS, no
+// atomics, nothing waits for another block.
+// tint of channel c; gains / biases as scalars by value (an indexed private array would be promoted to LDS)
+__device__ __forceinline__ float aug_tint(float v, unsigned c, bool on, float g0, float g1, float g2, float b0, float b1, float b2) {
+  if (!on) return v;
+  const float gain = c == 0 ? g0 : (c == 1 ? g1 : g2), bias = c == 0 ? b0 : (c == 1 ? b1 : b2);
+  return fminf(fmaxf(v * gain + bias, 0.f), 1.f);
+}
+
+__device__ __forceinline__ float aug_load(unsigned long long frame, bool f32, long long e) {
+  return f32 ? reinterpret_cast<const float*>(frame)[e] : (float)reinterpret_cast<const unsigned char*>(frame)[e] / 255.0f;
+}
+
+__global__ __launch_bounds__(256) void gather_windows_augmented_kernel(const long long* __restrict__ addr,
+                                                                       const int* __restrict__ kind,
+                                                                       const int* __restrict__ shift,
+                                                                       const float* __restrict__ colour, int K, int H, int W,
+                                                                       int C, float* __restrict__ out) {
+  const int n = blockIdx.z, k = blockIdx.y;
+  const unsigned RW = (unsigned)W * (unsigned)C, fe = RW * (unsigned)H;      // (the entry point checked H * W * C < 2^31)
+  const unsigned i4 = (blockIdx.x * 256u + threadIdx.x) * 4u;
+  if (i4 >= fe) return;
+  const bool f32 = kind[n] == 1;
+  const long long dy = shift[2 * n], dxe = (long long)shift[2 * n + 1] * C;   // the column shift in ELEMENTS of a row
+  const unsigned long long frame = (unsigned long long)addr[n] + (unsigned long long)k * fe * (f32 ? 4u : 1u);
+  float* o = out + ((long long)n * K + k) * fe + i4;
+  const bool on = colour != nullptr;
+  float g0 = 1.f, g1 = 1.f, g2 = 1.f, b0 = 0.f, b1 = 0.f, b2 = 0.f;
+  if (on) {
+    const float* col = colour + (long long)n * 2 * C;       // gain[C], bias[C]
+    g0 = col[0], b0 = col[C];
+    if (C == 3) g1 = col[1], g2 = col[2], b1 = col[4], b2 = col[5];
+  }
+  auto tint = [=](float v, unsigned c) { return aug_tint(v, c, on, g0, g1, g2, b0, b1, b2); };
+  if (RW % 4u != 0) {       // one element at a time
+    for (unsigned j = 0; j < 4 && i4 + j < fe; ++j) {
+      const unsigned y = (i4 + j) / RW, r = (i4 + j) - y * RW;
+      const long long sy = (long long)y - dy, sr = (long long)r - dxe;
+      const bool inside = sy >= 0 && sy < H && sr >= 0 && sr < (long long)RW;
+      o[j] = inside ? tint(aug_load(frame, f32, sy * RW + sr), C == 3 ? r % 3u : 0u) : 0.f;
+    }
+    return;
+  }
+  const unsigned y = i4 / RW, r = i4 - y * RW;      // r % 4 == 0 and r + 3 < RW: the group lies in row y
+  const long long sy = (long long)y - dy, sr = (long long)r - dxe;
+  const unsigned c0 = C == 3 ? r % 3u : 0u;
+  float e[4] = {0.f, 0.f, 0.f, 0.f};
+  if (sy >= 0 && sy < H && sr + 3 >= 0 && sr < (long long)RW) {      // at least one source inside the frame
+    const long long s0 = sy * RW + sr;
+    if (sr >= 0 && sr + 3 < (long long)RW) {                         // all four
+      if (f32) {
+        const unsigned long long a = frame + (unsigned long long)s0 * 4;
+        if ((a & 15u) == 0) {
+          const f32x4 x = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a));
+          e[0] = x.x, e[1] = x.y, e[2] = x.z, e[3] = x.w;
+        } else {
+          const float* s = reinterpret_cast<const float*>(a);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) e[j] = s[j];
+        }
+      } else {
+        const unsigned long long a = frame + (unsigned long long)s0, wa = a & ~3ull;
+        if (wa == a || (wa >= frame && wa + 8 <= frame + fe)) {
+          unsigned x = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(wa));
+          if (wa != a) x = __builtin_amdgcn_alignbyte(__builtin_nontemporal_load(reinterpret_cast<const unsigned*>(wa + 4)), x, (unsigned)(a & 3u));
+#pragma unroll
+          for (int j = 0; j < 4; ++j) e[j] = (float)((x >> (8 * j)) & 255u) / 255.0f;
+        } else {
+          const unsigned char* s = reinterpret_cast<const unsigned char*>(a);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) e[j] = (float)s[j] / 255.0f;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) e[j] = tint(e[j], C == 3 ? (c0 + j) % 3u : 0u);
+    } else {                                                         // the group crosses the left or right edge of the image
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (sr + j >= 0 && sr + j < (long long)RW) e[j] = tint(aug_load(frame, f32, s0 + j), C == 3 ? (c0 + j) % 3u : 0u);
+    }
+  }
+  *reinterpret_cast<f32x4*>(o) = f32x4{e[0], e[1], e[2], e[3]};
+}
+
+extern "C" int geeco_gather_windows_augmented(const int64_t* addr, const int32_t* kind, const int32_t* shift, const float* colour,
+                                              int N, int K, int H, int W, int C, float* out, void* stream) {
+  GEECO_CHECK_ARG(addr && kind && shift && out, "gather_windows_augmented: null pointer");
+  GEECO_CHECK_ARG(N >= 1 && N <= 65535 && K >= 1 && K <= 65535, "gather_windows_augmented: N=%d, K=%d outside 1..65535", N, K);
+  GEECO_CHECK_ARG(H >= 1 && W >= 1, "gather_windows_augmented: H=%d, W=%d must be >= 1", H, W);
+  GEECO_CHECK_ARG(C == 1 || C == 3, "gather_windows_augmented: C=%d must be 1 or 3", C);
+  const int64_t frame_elems = (int64_t)H * W * C;
+  GEECO_CHECK_ARG(frame_elems <= 0x7fffffffLL, "gather_windows_augmented: a frame of %lld elements is too large", (long long)frame_elems);
+  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "gather_windows_augmented: out must be 16-byte aligned");
+  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(addr) & 7) == 0 && (reinterpret_cast<uintptr_t>(kind) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(shift) & 3) == 0 && (reinterpret_cast<uintptr_t>(colour) & 3) == 0,
+                  "gather_windows_augmented: the tables must be aligned for their element types");
+  dim3 grid((unsigned)cdiv64(frame_elems, 1024), (unsigned)K, (unsigned)N);
+  hipLaunchKernelGGL(gather_windows_augmented_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)addr, kind, shift,
+                     colour, K, H, W, C, out);
+  GEECO_LAUNCH_CHECK();
+  return 0;
+}

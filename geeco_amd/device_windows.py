@@ -18,6 +18,22 @@ def resolve_device(device):
   return d
 
 
+class WindowAugment:
+  """The per-window augmentation draws of ONE batch (pickplace_input_fn(augment=...)): ``shift`` int32 [n][2] =
+  (dy, dx) in whole pixels, ``colour`` float32 [n][6] = gain[3], bias[3] of the RGB channels.  One object is referenced by every
+  DeviceWindows stream of the batch (``DeviceWindows.augment``): window i of 'rgb', 'target_rgb', 'depth' and 'target_depth'
+  moves by the same shift[i], the RGB streams are tinted by the same colour[i], depth streams are only moved."""
+
+  def __init__(self, shift, colour):
+    self.shift = np.ascontiguousarray(shift, np.int32).reshape(-1, 2)
+    self.colour = np.ascontiguousarray(colour, np.float32).reshape(-1, 6)
+    if len(self.shift) != len(self.colour):
+      raise ValueError('WindowAugment: %d shifts for %d colour rows' % (len(self.shift), len(self.colour)))
+
+  def __len__(self):
+    return len(self.shift)
+
+
 class DeviceWindows:
   """A batch of K-frame windows that lives in HBM as (episode frames, start indices) segments.
 
@@ -30,6 +46,7 @@ class DeviceWindows:
     self.segments = []      # (device tensor [T, frame_elems], np.int32 starts, divisor of THIS segment's frames)
     self.n = 0
     self.scattered = False  # built by the shuffling assembler (shuffle_windows): about one episode per window, see window_table
+    self.augment = None     # a WindowAugment shared with the other streams of the batch: the windows are these, transformed
 
   def add(self, frames_dev, starts, divisor=None):
     """``divisor``: what the gather divides this segment's frames by (default: the constructor's).  One batch can hold
@@ -42,6 +59,18 @@ class DeviceWindows:
   @property
   def shape(self):
     return (self.n,) + (() if self.squeeze_k else (self.K,)) + self.frame_shape
+
+  augmented = property(lambda self: self.augment is not None)
+
+  def augment_tables(self):
+    """(shift int32 [n][2], colour float32 [n][6] or None) for ops.gather_windows_augmented_into: colour for RGB frames only
+    (a one-channel stream is moved, never tinted)."""
+    aug = self.augment
+    if len(aug) != self.n:
+      raise ValueError('DeviceWindows: augmentation draws for %d windows on a batch of %d' % (len(aug), self.n))
+    if self.frame_shape[-1] not in (1, 3) or len(self.frame_shape) != 3:
+      raise ValueError('DeviceWindows: augmented frames must be [H, W, 3] or [H, W, 1], got %s' % (self.frame_shape,))
+    return aug.shift, (aug.colour if self.frame_shape[-1] == 3 else None)
 
   def __len__(self):
     return self.n
@@ -57,6 +86,8 @@ class DeviceWindows:
       out.segments += b.segments
       out.n += b.n
       out.scattered = out.scattered or b.scattered
+      if b.augment is not None:
+        raise ValueError('DeviceWindows.concat: augmented windows (the draws belong to one emitted batch)')
     return out
 
   def is_u8(self):
@@ -103,6 +134,9 @@ class DeviceWindows:
   def addresses(self, device):
     """int64 address of each window's first frame (WindowFeed.pointers(): the input kernel that follows them reads uint8 frames,
     so any other segment raises)."""
+    if self.augment is not None:
+      raise ValueError('DeviceWindows.addresses: augmented windows exist only as dense windows (the kernel that follows these '
+                       'addresses reads the frames as recorded)')
     addr, kinds, _ = self._window_addresses(resolve_device(device), 'addresses')
     if kinds.any():
       raise ValueError('DeviceWindows.addresses: float32 frames, the kernel that follows these addresses reads the uint8 (255) form')
@@ -126,6 +160,8 @@ class DeviceWindows:
     if device is not None:
       device = resolve_device(device)
     streams = [self] if targets is None else [self, targets]
+    if any(dw.augment is not None for dw in streams):
+      raise ValueError('DeviceWindows.frame_table: augmented windows share no frames (each window is transformed by its own draw)')
     if targets is not None and (targets.n, targets.K, targets.frame_shape) != (self.n, 1, self.frame_shape):
       raise ValueError('DeviceWindows.frame_table: targets must be %d single frames of shape %s' % (self.n, self.frame_shape))
     devices = {f.device for dw in streams for f, _, _ in dw.segments if f is not None}
@@ -154,10 +190,18 @@ class DeviceWindows:
 
   def materialize_into(self, out):
     """out [n][K][*frame_shape] <- the windows, one geeco_gather_windows launch per segment.  Every segment is checked on the
-    host (residency, device, bounds) before the first launch is queued: an out-of-range gather is a GPU fault."""
+    host (residency, device, bounds) before the first launch is queued: an out-of-range gather is a GPU fault.  Augmented
+    windows: ONE geeco_gather_windows_augmented launch behind four small copies of its tables (the feed's 'dense_augmented'
+    form sends them in the step's one block instead)."""
     import torch
     from . import ops
     fe = int(np.prod(self.frame_shape))
+    if self.augment is not None:
+      shift, colour = self.augment_tables()
+      addr, kinds = self.window_table(out.device)
+      up = lambda a: None if a is None else torch.from_numpy(a).to(out.device, non_blocking=True)
+      ops.gather_windows_augmented_into(out, up(addr), up(kinds), up(shift), up(colour), self.n, self.K, *self.frame_shape)
+      return
     off = 0
     for frames_dev, starts, divisor, _, _ in list(self._checked_segments(out.device)):
       n = len(starts)

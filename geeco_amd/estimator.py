@@ -382,12 +382,20 @@ class Estimator:
     scattered = any(isinstance(v, DeviceWindows) and v.scattered for v in feats.values())
     if scattered:
       key += ('scattered',)
+    # ... and so do batches of an augmenting input (pickplace_input_fn(augment=...)): their dense windows are filled by the
+    # augmented gather, and no slot of theirs offers window addresses
+    augmented = any(isinstance(v, DeviceWindows) and v.augmented for v in feats.values())
+    if augmented:
+      key += ('augmented',)
     if key in self._specs:
       return self._specs[key]
     shared = self.params.get('shared_frames')
     if shared and scattered:
       raise ValueError("params['shared_frames'] with a shuffling input (pickplace_input_fn(shuffle_windows=True)): a shuffled batch "
                        "of N windows holds about N * K distinct frames, so there is nothing to share; drop one of the two options")
+    if shared and augmented:
+      raise ValueError("params['shared_frames'] with an augmenting input (pickplace_input_fn(augment=...)): every window is "
+                       "transformed by its own draw, so no two windows share a frame; drop one of the two options")
     fbuf, lbuf = feed.build_slots(self._device(), feats, labels,
                                   (lambda K, goal: shared_frames_capacity(shared, n, K, goal)) if shared else None)
     params = dict(self.params)

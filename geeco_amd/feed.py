@@ -104,6 +104,10 @@ class WindowFeed:
     * 'dense_by_address' (``dense()`` of a slot whose first batch came from a shuffling input, ``DeviceWindows.scattered``: about
       one segment per window): that buffer filled by ONE geeco_gather_windows_by_address launch that follows a window table riding
       in the arena.  The table reaches the device with the arena's copy, so ``after_flush()`` queues the launch, behind the flush.
+    * 'dense_augmented' (``dense()`` of a slot whose first batch came from an augmenting input, ``DeviceWindows.augmented``):
+      that buffer filled by ONE geeco_gather_windows_augmented launch; the window table, the batch's shifts and, for an RGB
+      stream, its colour gains and biases ride in the arena, and ``after_flush()`` queues the launch as for 'dense_by_address'.
+      Such a slot is never ``u8``: augmented windows exist only as dense windows.
     * 'frame_table' (``frame_table()``, models built with shared_frames=F): the batch's distinct frames, see there."""
 
   def __init__(self, windows, arena, key, shared_frames=None, shared_targets=None):
@@ -112,9 +116,11 @@ class WindowFeed:
     batch), target index [n] -- see ``frame_table``."""
     self.n, self.K, self.frame_shape, self.squeeze_k = windows.n, windows.K, windows.frame_shape, windows.squeeze_k
     self.arena, self.key, self.device = arena, key, arena.device
-    self.u8, self.scattered = windows.is_u8(), bool(getattr(windows, 'scattered', False))
+    self.scattered, self.augmented = bool(getattr(windows, 'scattered', False)), getattr(windows, 'augment', None) is not None
+    self.u8 = windows.is_u8() and not self.augmented       # the slot can offer ``pointers()``
     self.shape = tuple(windows.shape)
-    self.form = None                              # 'pointers', 'dense', 'dense_by_address' or 'frame_table' once the model chose
+    # 'pointers', 'dense', 'dense_by_address', 'dense_augmented' or 'frame_table' once the model chose
+    self.form = None
     self.table = self.buffer = None
     # frame-table slots reserved in the arena (None: built without shared_frames) / in use (``frame_table()`` may take fewer)
     self.shared_reserved = self.shared = shared_frames
@@ -132,9 +138,14 @@ class WindowFeed:
     self._live = collections.deque(maxlen=FeedArena.SLOTS + 1)
     if self.u8:
       arena.reserve(key, (self.n,), np.int64)
-    if self.scattered:
+    if self.scattered or self.augmented:
       arena.reserve(key + ('window_addr',), (self.n,), np.int64)
       arena.reserve(key + ('window_kind',), (self.n,), np.int32)
+    if self.augmented:
+      windows.augment_tables()                      # (raises on frames that are not [H, W, 3] / [H, W, 1])
+      arena.reserve(key + ('aug_shift',), (self.n, 2), np.int32)
+      if self.frame_shape[-1] == 3:
+        arena.reserve(key + ('aug_colour',), (self.n, 6), np.float32)
 
   adopted = property(lambda self: self.form is not None)      # the model took this slot as an input: it chose a form
   feeds_frame_table = property(lambda self: self.form == 'frame_table')
@@ -173,7 +184,7 @@ class WindowFeed:
 
   def dense(self):
     import torch
-    self._choose('dense_by_address' if self.scattered else 'dense')
+    self._choose('dense_augmented' if self.augmented else 'dense_by_address' if self.scattered else 'dense')
     if self.buffer is None:
       self.buffer = torch.empty(self.shape, dtype=torch.float32, device=self.device)
     return self.buffer
@@ -183,6 +194,9 @@ class WindowFeed:
     adopted feeds nothing."""
     if (windows.n, windows.K, windows.frame_shape) != (self.n, self.K, self.frame_shape):
       raise ValueError('WindowFeed: batch of %s windows does not fit the slot %s' % (tuple(windows.shape), self.shape))
+    if (getattr(windows, 'augment', None) is not None) != self.augmented:
+      raise RuntimeError('WindowFeed: %s windows in a slot built for %s ones (the Estimator keys its models by the batch being '
+                         'augmented)' % (('plain', 'augmented') if self.augmented else ('augmented', 'plain')))
     self._gather_pending = False
     if self.form is not None:
       getattr(self, '_feed_' + self.form)(windows, batch)
@@ -204,6 +218,13 @@ class WindowFeed:
     self._live.append(windows)
     self._gather_pending = True       # the launch itself: after_flush()
 
+  def _feed_dense_augmented(self, windows, batch):
+    shift, colour = windows.augment_tables()
+    self._feed_dense_by_address(windows, batch)
+    self.arena.write(self.key + ('aug_shift',), shift)
+    if colour is not None:
+      self.arena.write(self.key + ('aug_colour',), colour)
+
   def _feed_frame_table(self, windows, batch):
     targets = None
     if self._with_targets:
@@ -221,16 +242,20 @@ class WindowFeed:
     self._live.append((windows, targets))
 
   def after_flush(self):
-    """The by-address fill of the dense buffer, queued behind the arena's copy (which carries this batch's window table) and in
-    front of the replay.  Does nothing for the other forms."""
+    """The by-address or augmented fill of the dense buffer, queued behind the arena's copy (which carries this batch's window
+    table and augmentation draws) and in front of the replay.  Does nothing for the other forms."""
     if not self._gather_pending:
       return
     from . import ops
     self._gather_pending = False
     if self._window_tables is None:       # static views of the sealed arena
-      self._window_tables = (self.arena.view(self.key + ('window_addr',)), self.arena.view(self.key + ('window_kind',)))
-    ops.gather_windows_by_address_into(self.buffer, self._window_tables[0], self._window_tables[1], self.n, self.K,
-                                       int(np.prod(self.frame_shape)))
+      view = lambda name: self.arena.view(self.key + (name,)) if self.arena.has(self.key + (name,)) else None
+      self._window_tables = tuple(view(name) for name in ('window_addr', 'window_kind', 'aug_shift', 'aug_colour'))
+    addr, kind, shift, colour = self._window_tables
+    if self.form == 'dense_augmented':
+      ops.gather_windows_augmented_into(self.buffer, addr, kind, shift, colour, self.n, self.K, *self.frame_shape)
+    else:
+      ops.gather_windows_by_address_into(self.buffer, addr, kind, self.n, self.K, int(np.prod(self.frame_shape)))
 
 
 # ---- the slots of one model (Estimator._get_spec) and the feed of one step ------------------------------------------------

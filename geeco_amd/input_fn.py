@@ -25,7 +25,7 @@ import numpy as np
 
 from . import tfrecord
 # what is not the reader keeps resolving from here (none of these modules imports this one when it loads)
-from .device_windows import DeviceWindows, EPISODE_CACHE, EpisodeCache, _PINNED, _PinnedPool, episode_to_device, resolve_device  # noqa: F401
+from .device_windows import DeviceWindows, EPISODE_CACHE, EpisodeCache, WindowAugment, _PINNED, _PinnedPool, episode_to_device, resolve_device  # noqa: F401
 from .feed import FeedArena, WindowFeed  # noqa: F401
 from .synthetic import synthetic_batches, synthetic_from_spec, synthetic_scene_frames, write_episode, write_synthetic_dataset  # noqa: F401
 
@@ -311,6 +311,48 @@ def _assemble_picks(picks, K):
   return feats, labels
 
 
+AUGMENT_STREAM = 0x617567      # third word of the augmentation generator's seed: a stream apart from the file order's and the shuffle's
+
+
+def check_augment(augment, hw=None):
+  """``pickplace_input_fn(augment=...)`` validated: None (off: ``augment`` is None or every value is 0) or (S, g, b).  ``hw`` =
+  (H, W) of the frames, when known: the shift must leave a part of the image in view."""
+  if augment is None:
+    return None
+  if not isinstance(augment, dict):
+    raise ValueError('augment must be None or dict(shift=S, gain=g, bias=b), got %r' % (augment,))
+  for k in augment:
+    if k not in ('shift', 'gain', 'bias'):
+      raise ValueError("augment: unknown key %r (the keys are 'shift', 'gain' and 'bias')" % (k,))
+  S, g, b = augment.get('shift', 0), augment.get('gain', 0.0), augment.get('bias', 0.0)
+  if isinstance(S, (bool, np.bool_)) or not isinstance(S, (int, np.integer)) or S < 0:
+    raise ValueError("augment['shift'] must be an integer >= 0 (whole pixels), got %r" % (S,))
+  if hw is not None and S >= min(hw):
+    raise ValueError("augment['shift'] must be smaller than the frames (%d x %d), got %r" % (hw[0], hw[1], S))
+  for k, v, hi in (('gain', g, 1.0), ('bias', b, float('inf'))):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= v < hi:
+      raise ValueError("augment[%r] must be a number in [0, %s), got %r" % (k, '1' if k == 'gain' else 'inf', v))
+  return None if (S == 0 and g == 0 and b == 0) else (int(S), float(g), float(b))
+
+
+def draw_augment(rng, n, S, g, b):
+  """The draws of one emitted batch of ``n`` windows, in this order: dy, dx ~ integers U[-S, S] ([n][2]), gain_c ~ U[1 - g, 1 + g]
+  ([n][3]), bias_c ~ U[-b, b] ([n][3])."""
+  shift = rng.integers(-S, S + 1, size=(n, 2))
+  gain = rng.uniform(1.0 - g, 1.0 + g, size=(n, 3))
+  bias = rng.uniform(-b, b, size=(n, 3))
+  return WindowAugment(shift, np.concatenate([gain, bias], axis=1))
+
+
+def _augment_batch(feats, rng, aug):
+  """Marks every DeviceWindows stream of an emitted batch with ONE WindowAugment drawn for it."""
+  draws = draw_augment(rng, len(feats['step']), *aug)
+  for v in feats.values():
+    if isinstance(v, DeviceWindows):
+      v.augment = draws
+  return feats
+
+
 class _Prefetcher:
   """Runs an iterator factory in a background thread (tf.data's prefetch); the episode readers it draws from are a
   thread pool of their own (``_EpisodeSource``)."""
@@ -494,7 +536,7 @@ def default_reader_threads(world=1):
 
 def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size=4, fetch_target=False,
                        shuffle_buffer=128, batch_size=1, num_epochs=1, num_threads=4, prefetch_size=4, seed=None,
-                       shard=None, device=None, device_keys=None, cache=True, shuffle_windows=False):
+                       shard=None, device=None, device_keys=None, cache=True, shuffle_windows=False, augment=None):
   """Same signature as the reference's pickplace_input_fn (geeco_gym.py:234-279).  Returns an iterable of
   (features, labels) numpy batches.  ``num_threads`` episodes are read in parallel, in order (num_parallel_reads /
   num_parallel_calls of :442-473; None = ``default_reader_threads``: this rank's share of the host cores); ``prefetch_size`` batches are prepared ahead of the consumer (:473).
@@ -511,9 +553,18 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
   ``default_rng([seed, rank])`` (rank 0 unless sharded; a fresh one for ``seed`` None).  The buffer holds (episode, start) pairs,
   never pixels: a batch is built from its picks when it is emitted, and on the ``device`` path an episode's resident frames stay
   referenced while one of its windows waits.  ``dp_schedule`` is the unshuffled one (it depends on counts only).  Without the
-  option ``shuffle_buffer`` is accepted and unused, as before."""
+  option ``shuffle_buffer`` is accepted and unused, as before.
+  ``augment`` = None | dict(shift=S, gain=g, bias=b) ('train' mode of an on-disk dataset on the ``device`` path only; off by
+  default and when all three are 0; the reference has no augmentation): every emitted window is moved by a whole-pixel shift
+  dy, dx ~ U{-S..S} (zeros move in; 0 <= S < min(H, W)) and its RGB channels become clip(v * gain_c + bias_c, 0, 1) with
+  gain_c ~ U[1 - g, 1 + g] (0 <= g < 1) and bias_c ~ U[-b, b] (b >= 0).  One draw per window serves its K frames and its
+  'target_rgb'; 'depth' / 'target_depth' take the same shift and no colour.  The host only draws (``draw_augment``, per emitted
+  batch, generator ``default_rng([seed, rank, AUGMENT_STREAM])``: file order and shuffle picks are those without the option); the
+  pixels are transformed on the device by the gather that builds the dense windows (DeviceWindows.augment).  Without
+  ``device`` it raises; other modes and ``synthetic:`` inputs ignore it."""
   if shuffle_windows and int(shuffle_buffer) < 1:
     raise ValueError('shuffle_windows needs shuffle_buffer >= 1, got %r' % (shuffle_buffer,))
+  check_augment(augment)
   if encoding != 'v4':
     # v1-v3 are dead code in the reference (undefined PickAndPlaceEncodingV1/2/3 -> NameError)
     raise KeyError(encoding)
@@ -540,6 +591,10 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
     steps = max(-(-w // batch_size) for w in per_rank) if per_rank else 0
     dp_schedule = [tuple(max(0, min(batch_size, w - s * batch_size)) for w in per_rank) for s in range(steps)]
     paths = paths[rank::world]
+  aug = check_augment(augment, (meta.img_height, meta.img_width)) if mode == 'train' else None      # train-only, as the shuffles
+  if aug is not None and device is None:
+    raise ValueError("augment needs device= (e.g. 'cuda'): the windows are transformed on the device, where the resident frames "
+                     "are; the host path has no augmentation")
   if device is not None:
     device = resolve_device(device)
   image_keys = _IMAGE_KEYS if device_keys is None else tuple(device_keys)
@@ -549,6 +604,13 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
   if device is not None and device.type == 'cuda' and cache:
     ep_cache = cache if isinstance(cache, EpisodeCache) else EPISODE_CACHE
   print('[pickplace_input_fn_v4] #tfrecords: %d' % len(paths))
+
+  def emitter():
+    """What a finished batch passes through on its way out: the augmentation draws, in emission order."""
+    if aug is None:
+      return lambda f, l: (f, l)
+    rng = np.random.default_rng(None if seed is None else [seed, shard[0] if shard is not None else 0, AUGMENT_STREAM])
+    return lambda f, l: (_augment_batch(f, rng, aug), l)
 
   def shuffled_batches():
     import itertools
@@ -563,20 +625,22 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
           yield ep, start
 
     picks = []      # the batch being filled; only the batch that straddles an epoch boundary mixes epochs, as without the shuffle
+    emit = emitter()
     try:
       for _ in range(num_epochs):
         for pick in shuffle_stream(windows(itertools.islice(source, len(paths))), int(shuffle_buffer), rng):
           picks.append(pick)
           if len(picks) == batch_size:
-            yield _assemble_picks(picks, K)
+            yield emit(*_assemble_picks(picks, K))
             picks = []
       if picks:     # ragged final batch
-        yield _assemble_picks(picks, K)
+        yield emit(*_assemble_picks(picks, K))
     finally:
       source.close()    # (a generator: runs _EpisodeSource's clean-up now, not when it is collected)
 
   def batches():
     carry_f, carry_l = None, None   # windows left over from the previous episode (batch() spans episodes)
+    emit = emitter()
     source = _EpisodeSource(paths * num_epochs, meta, fetch_target, num_threads, device, image_keys, ep_cache)
     for ex, dev in source:
       T = ex['step'].shape[0]
@@ -593,11 +657,11 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
           l = {k: np.concatenate([carry_l[k], l[k]], axis=0) for k in l}
           carry_f = carry_l = None
         if len(f['step']) == batch_size:
-          yield f, l
+          yield emit(f, l)
         else:
           carry_f, carry_l = f, l
     if carry_f is not None:   # ragged final batch (dataset.batch without drop_remainder, :471)
-      yield carry_f, carry_l
+      yield emit(carry_f, carry_l)
 
   it = _Prefetcher(shuffled_batches if shuffle_windows else batches, prefetch_size, device)
   it.dp_schedule = dp_schedule

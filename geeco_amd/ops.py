@@ -174,6 +174,23 @@ def gather_windows_by_address_into(out, addr, kind, N, K, frame_elems):
         'geeco_gather_windows_by_address')
 
 
+def gather_windows_augmented_into(out, addr, kind, shift, colour, N, K, H, W, C):
+  """gather_windows_by_address_into with a per-window augmentation: out[n][k][y][x][c] <- pixel (y - dy, x - dx) of frame k of
+  the window at addr[n], (dy, dx) = shift[n] (int32 [N][2] device table), times gain[c] plus bias[c] clamped to [0, 1] when
+  ``colour`` (float32 [N][2 * C] = gain[C], bias[C]; None: values unchanged); exactly 0 where the source pixel is outside the
+  frame.  ONE launch; any shift is safe (include/geeco_hip.h: geeco_gather_windows_augmented)."""
+  tables = ((addr, torch.int64, N), (kind, torch.int32, N), (shift, torch.int32, 2 * N)) + (
+      () if colour is None else ((colour, torch.float32, 2 * C * N),))
+  for t, dt, size in tables:
+    if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= size and t.device == out.device):
+      raise ValueError('gather_windows_augmented: the tables must be contiguous int64 addresses [N], int32 kinds [N], int32 shifts '
+                       '[N][2] and float32 colour [N][%d] for N=%d on %s' % (2 * C, N, out.device))
+  if out.numel() < N * K * H * W * C:
+    raise ValueError('gather_windows_augmented: output of %d floats for %d x %d frames of %d x %d x %d' % (out.numel(), N, K, H, W, C))
+  check(_lib().geeco_gather_windows_augmented(_p(addr), _p(kind), _p(shift), _p(colour), N, K, H, W, C, _p(out), _stream()),
+        'geeco_gather_windows_augmented')
+
+
 # -- batched predictor I/O (csrc/predict_io.hip; geeco_amd/batched_predictor.py) --------------------------------------------
 def predict_range_check_into(ctl, frames, B, HW, C, lo, hi):
   """ctl[b] = ctl[B] = 1 when channels 0..2 of env b's float32 frame leave [lo, hi] (or hold a NaN); never clears them."""

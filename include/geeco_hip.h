@@ -26,7 +26,8 @@ extern "C" {
 
 #define GEECO_ABI_VERSION 7  /* = the build round that last changed the entry points or their calling conventions */
 /* added within 7 (additive: no existing entry point or convention changed): geeco_lstm_seq_heads_fwd,
- * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd, geeco_gather_windows_by_address */
+ * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd, geeco_gather_windows_by_address,
+ * geeco_gather_windows_augmented */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -125,6 +126,18 @@ int geeco_gather_windows(const void* src, int src_is_u8, const int* starts_dev, 
  * loads (4 bytes uint8, 16 float32; float32 frames are 4-byte aligned in any case) goes one element at a time. */
 int geeco_gather_windows_by_address(const int64_t* addr, const int* kind, int N, int K, int64_t frame_elems, float* out,
                                     void* stream);
+/* The by-address builder with a per-window image augmentation (input_fn.pickplace_input_fn(augment=...); the
+ * reference has none).  addr / kind as above; frames are [H][W][C], C = 3 (RGB) or 1 (depth); shift [N][2] int32 = (dy, dx) in
+ * whole pixels; colour [N][2 * C] float32 = gain[C], bias[C], or NULL.  All four tables live on the device and are read when
+ * the kernel RUNS.  For every frame of window n:  out[n][k][y][x][c] = tint(v), v = conv(source pixel (y - dy, x - dx), channel
+ * c) as geeco_gather_windows_by_address converts it, tint(v) = min(max(v * gain[c] + bias[c], 0), 1) (the multiply-add may be
+ * fused), tint = identity when colour is NULL;  exactly 0.0f where the source pixel lies outside [0, H) x [0, W) (not tinted).
+ * Any int32 shift is valid: every source index is tested against the frame before it is read, |dy| >= H or |dx| >= W gives
+ * zeros.  Shift (0, 0) without colour is bitwise geeco_gather_windows_by_address.  H * W * C < 2^31, out 16-byte aligned,
+ * N and K <= 65535.  W * C % 4 == 0: 16-byte stores, loads as wide as the shifted source's address allows; else one element at
+ * a time. */
+int geeco_gather_windows_augmented(const int64_t* addr, const int32_t* kind, const int32_t* shift, const float* colour, int N,
+                                   int K, int H, int W, int C, float* out, void* stream);
 
 /* ---- batched predictor I/O: B control loops per call (reference predictor.py:127-209 per env) ----------------------
  * The ingest and output stages of one replayed graph (geeco_amd/batched_predictor.py): range check -> window push ->

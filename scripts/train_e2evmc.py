@@ -86,6 +86,14 @@ ARGPARSER.add_argument('--shuffle_windows', default=False, action='store_true',
                        help='Sample-level shuffle of the training windows through a buffer of --shuffle_buffer windows (the '
                             "reference's dataset.shuffle, live in its v1-v3 pipelines); without it a batch holds consecutive windows "
                             'of one episode.  Not with --shared_frames: a shuffled batch has no frames to share.')
+ARGPARSER.add_argument('--augment_shift', type=int, default=0,
+                       help='Training-time augmentation, on the device: move every window (its K frames and its target frame alike) '
+                            'by a random whole-pixel shift of up to this many pixels in y and in x; zeros move in.  0 = off.')
+ARGPARSER.add_argument('--augment_gain', type=float, default=0.0,
+                       help='... and scale each RGB channel of a window by a random gain in [1 - g, 1 + g] (0 <= g < 1).  0 = off.')
+ARGPARSER.add_argument('--augment_bias', type=float, default=0.0,
+                       help='... and add a random bias in [-b, b] to each RGB channel (values are clipped to [0, 1]).  0 = off.  '
+                            'None of the three with --shared_frames: augmented windows share no frames.')
 ARGPARSER.add_argument('--shared_frames', default=False, action='store_true',
                        help="Per-frame controllers (e2e_vmc; goal 'sequence' x 'constant' / 'residual'), one GPU, RGB: encode every "
                             'distinct frame of a batch once instead of once per window that holds it (same loss and gradients).  Needs '
@@ -142,6 +150,9 @@ def main(args):
     # (before anything is written or initialised)
     raise SystemExit('--shuffle_windows and --shared_frames exclude each other: a shuffled batch of N windows holds about N x K '
                      'distinct frames, so there is nothing for --shared_frames to share')
+  if (args.augment_shift or args.augment_gain or args.augment_bias) and args.shared_frames:
+    raise SystemExit('--augment_shift / --augment_gain / --augment_bias and --shared_frames exclude each other: every augmented '
+                     'window is transformed by its own draw, so no two windows share a frame')
   gdist.init_from_env()
   rank, world = gdist.rank(), gdist.world_size()
   os.makedirs(name=args.model_dir, exist_ok=True)
@@ -203,6 +214,7 @@ def main(args):
         window_size=e2evmc_config.window_size, fetch_target=(args.goal_condition == 'target'),
         shuffle_buffer=args.shuffle_buffer, num_epochs=1, num_threads=reader_threads,
         prefetch_size=args.prefetch_size, shuffle_windows=args.shuffle_windows,
+        augment=dict(shift=args.augment_shift, gain=args.augment_gain, bias=args.augment_bias),
         # episodes are uploaded once (to THIS rank's GPU), stay there across epochs (input_fn.EPISODE_CACHE) and windows are
         # gathered in HBM; an RGB model never reads the depth stream
         device=dev,
