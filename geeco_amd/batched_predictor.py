@@ -14,7 +14,7 @@ windows live in HBM: dense fp32 windows shifted in place, or -- uint8 frames on 
 (geeco-f RGB) -- a mirrored uint8 ring per env whose window start the graph itself advances.
 
 ``incremental=True`` (the per-frame controllers: e2e_vmc, goal_e2evmc 'sequence' x 'constant' / 'residual') keeps no frame window
-at all: per env a ring of the last K encoder FEATURE vectors and joint states (graph.E2EVMCStep / GoalE2EVMCStep).  A call
+at all: per env a ring of the last K encoder FEATURE vectors and joint states (step_models.E2EVMCStep / GoalE2EVMCStep).  A call
 encodes only the B new frames; the graph is range check, newest-frame pack, encoder at N = B, feature push + state gather,
 decoder, output pack.  Same methods, errors and returned dict.
 """
@@ -68,7 +68,7 @@ class _Layout:
 
 class _AddressTable:
   """What ``feed.WindowFeed.pointers()`` hands a model: ``pointers`` marks the input as window addresses and ``table`` is the
-  int64 device table of per-env addresses its input kernel reads when it runs (graph.GoalE2EVMC.forward)."""
+  int64 device table of per-env addresses its input kernel reads when it runs (graph.GoalE2EVMC._encode)."""
 
   def __init__(self, table, shape):
     self.table, self.shape = table, tuple(shape)

@@ -17,6 +17,7 @@ import torch
 
 ENC_FILTERS = (32, 48, 64, 128, 192, 256, 256)      # conv1..conv7 (graph.py:76-110); conv8 = dim_out
 ENC_STRIDES = (1, 2, 2, 2, 2, 2, 2, 2)
+_CELLS = 4   # the reference hard-codes the 2x2 tiling of the joint state (graph.py:139,163,188)
 
 
 def encoder_shapes(scope, cin, dim_out):
@@ -48,6 +49,39 @@ def decoder_shapes(scope, dim_in, cfg):
   for name, n in heads:
     s['%s/%s/kernel' % (scope, name)] = (cfg.dim_h_fc, n)
     s['%s/%s/bias' % (scope, name)] = (n,)
+  return s
+
+
+def model_variable_shapes(cfg, goal: bool):
+  """Variable creation order of ``e2e_vmc`` (graph.py:268-319) / ``goal_e2evmc`` (graph.py:321-416)."""
+  C, jn = cfg.img_channels, cfg.dim_jnt_state
+  if C not in (3, 4):
+    raise ValueError("Unsupported number of channels for input frame: %d!" % C)
+  s = collections.OrderedDict()
+  if not goal:
+    s.update(encoder_shapes('VMC/ConvEncoder', C, 256))
+    s.update(decoder_shapes('VMC/LSTMDecoder', _CELLS * (256 + jn), cfg))
+    return s
+  root = 'GoalVMC'
+  if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
+    raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
+  if cfg.proc_obs == 'sequence':
+    s.update(encoder_shapes(root + '/ConvEncoder', C, cfg.dim_s_obs))
+    if cfg.proc_tgt == 'constant':
+      din = _CELLS * (cfg.dim_s_obs + jn + cfg.dim_s_obs)
+    elif cfg.proc_tgt == 'residual':
+      din = _CELLS * (cfg.dim_s_obs + jn)
+    else:
+      s.update(encoder_shapes(root + '/DynDiffEncoder', C, cfg.dim_s_diff))
+      din = _CELLS * (cfg.dim_s_obs + jn + cfg.dim_s_diff)
+  elif cfg.proc_obs == 'dynimg':
+    s.update(encoder_shapes(root + '/ConvEncoder', C, cfg.dim_s_obs))
+    s.update(encoder_shapes(root + '/DynBuffEncoder', C, cfg.dim_s_dyn))
+    s.update(encoder_shapes(root + '/DynDiffEncoder', C, cfg.dim_s_diff))
+    din = _CELLS * (cfg.dim_s_obs + cfg.dim_s_dyn + jn + cfg.dim_s_diff)
+  else:
+    raise ValueError("Unknown processing mode for frame buffer: %s!" % (cfg.proc_obs,))
+  s.update(decoder_shapes(root + '/LSTMDecoder', din, cfg))
   return s
 
 
@@ -87,6 +121,7 @@ class VariableStore:
     self.adam_v = torch.zeros(self.size, dtype=torch.float32, device=self.device)
     self.global_step = torch.zeros(1, dtype=torch.int64, device=self.device)
     self.version = 0      # bumped whenever the parameters are (re)written from the host side
+    self.primary_stack = None     # the first training ConvEncoderStack built on this store (encoder.py: lazy_refresh)
 
   # -- views ------------------------------------------------------------------------------
   def _view(self, arena, name):

@@ -111,7 +111,7 @@ class _FakeModel:
     self.applied = None
     self.staging = None
     self.pieces = []
-    if can_redirect:      # like graph.ConvEncoderStack.redirect_late_gradients: the bottom part writes the staging buffer
+    if can_redirect:      # like encoder.ConvEncoderStack.redirect_late_gradients: the bottom part writes the staging buffer
       self.redirect_late_gradients = self._redirect
     if split:             # like graph._ModelBase.apply_gradients_of: the optimiser step in pieces (runtime: two, around the late bucket)
       self.apply_gradients_of = self._apply_of

@@ -597,3 +597,23 @@ def test_target_frame_loaders_round_trip(tmp_path):
   assert len(got) == 3 and all(np.array_equal(x, y) for x, y in zip(got, frames))
   with pytest.raises(FileNotFoundError):
     I.load_target_frame(root, 'episode_0099.tfrecord.zlib')
+
+
+def test_graph_reexports_what_moved_as_the_same_objects():
+  from geeco_amd import decoder, encoder, graph, step_models, variables
+  moved = {variables: ['model_variable_shapes'], encoder: ['ConvEncoderStack'], decoder: ['head_table', 'LSTMDecoder'],
+           step_models: ['E2EVMCStep', 'GoalE2EVMCStep']}
+  for module, names in moved.items():
+    for name in names:
+      assert getattr(graph, name) is getattr(module, name), name
+  for name in ('_ModelBase', 'GoalE2EVMC', 'E2EVMC'):
+    assert getattr(graph, name).__module__ == 'geeco_amd.graph', name
+
+
+@pytest.mark.parametrize('module', ['geeco_amd.encoder', 'geeco_amd.decoder'])
+def test_encoder_and_decoder_import_neither_graph_nor_each_other(module):
+  import subprocess
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  other = 'geeco_amd.decoder' if module.endswith('encoder') else 'geeco_amd.encoder'
+  code = "import sys, %s; sys.exit(int('geeco_amd.graph' in sys.modules or %r in sys.modules))" % (module, other)
+  assert subprocess.run([sys.executable, '-c', code], cwd=root).returncode == 0

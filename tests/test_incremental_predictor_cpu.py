@@ -1,4 +1,4 @@
-"""Incremental predictor (batched_predictor.py incremental=True, graph.E2EVMCStep / GoalE2EVMCStep, csrc/predict_io.hip) without a
+"""Incremental predictor (batched_predictor.py incremental=True, step_models.E2EVMCStep / GoalE2EVMCStep, csrc/predict_io.hip) without a
 GPU: the C ABI of its two entries and their host-side argument checks, the feature-ring specification its kernel is held to on
 the GPU (FeatureRingModel below; tests/test_incremental_predictor_gpu.py compares the kernel against it bitwise), and the premise
 that makes caching legitimate: in the oracle a window's state_t is a function of frame t alone."""
