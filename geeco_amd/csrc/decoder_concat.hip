@@ -41,6 +41,7 @@ __global__ __launch_bounds__(256) void concat_bwd_kernel(const ConcatParams p) {
   p.dfeats[f][i] = p.accumulate ? p.dfeats[f][i] + d : d;
 }
 
+// (the general form; state_layout.h holds its three-mode special case for the window kernels)
 int fill_concat(ConcatParams* p, const int* feat_ch, int nfeat, int jnt_pos, int J) {
   int off = 0;
   for (int i = 0; i < nfeat; ++i) {

@@ -1,22 +1,8 @@
 // The goal model's one-pass input stage: the buffer image, the pair image and the current frame's padded copy in one launch
-// (the plain dynamic image: dynimg.hip).
+// (the plain dynamic image: dynimg.hip).  From frame_ingest.h: u8x4_unit, the Newton form of the uint8 conversion.
 #include "dynimg_internal.h"
+#include "frame_ingest.h"
 #include <vector>
-
-// float(u8) / 255.0f (_parse_v4, geeco_gym.py:312) without the division sequence: one Newton correction of a * (1/255) is the
-// correctly rounded quotient for every a in 0..255 (tests/test_kernels_gpu.py::test_goal_dynimgs_from_resident_u8_frames plants
-// all 256 byte values and compares bitwise against the division of geeco_gather_windows, frame_pack.hip).
-__device__ __forceinline__ float u8_unit(float a) {
-  const float r = 1.0f / 255.0f;
-  const float q = a * r;
-  const float e = __builtin_fmaf(-255.0f, q, a);
-  return __builtin_fmaf(e, r, q);
-}
-
-__device__ __forceinline__ f32x4 u8x4_unit(unsigned int b) {
-  return f32x4{u8_unit((float)(b & 255u)), u8_unit((float)((b >> 8) & 255u)), u8_unit((float)((b >> 16) & 255u)),
-               u8_unit((float)(b >> 24))};
-}
 
 // 4 pixels = 12 bytes = three dwords of a uint8 RGB frame -> the three float4 the fp32 path loads
 __device__ __forceinline__ void load_u8_unit(const unsigned char* frame, long long u, f32x4& v0, f32x4& v1, f32x4& v2) {

@@ -1,5 +1,6 @@
-// Frame plumbing of the data path: channel packing and the on-device window builder.
-#include "geeco_common.h"
+// Frame plumbing of the data path: channel packing and the on-device window builders.  uint8 frames become floats through
+// frame_ingest.h: u8_unit_div per element, u8x4_unit_div per loaded word.
+#include "frame_ingest.h"
 
 // ---- pixel packing: [n][HW][C1] (+ [n][HW][C2]) -> [n][HW][Cpad] ---------------------------------
 __global__ __launch_bounds__(256) void pack_pixels_kernel(const float* src, long long s1, const float* src2,
@@ -38,7 +39,8 @@ extern "C" int geeco_pack_pixels(const float* src, int64_t src_sample_stride, co
 // src/data/geeco_gym.py:615-631) and feeds 12.6 MB per sample over PCIe.  Here an episode's frames
 // are uploaded ONCE (RGB as the uint8 values the recorder stored, data_recorder / tfrecord.py:73-74)
 // and each batch's windows are gathered in HBM:  out[n][k][:] = conv(src[starts[n] + k][:]),
-// conv(u8) = float(u8) / 255.0f  (the division of _parse_v4, geeco_gym.py:312, bit-exact).
+// conv = a division by `divisor`; uint8 frames with divisor 255 give u8_unit_div's values (the division of _parse_v4,
+// geeco_gym.py:312, bit-exact), the divisor being a run-time argument here.
 template <typename T>
 __global__ __launch_bounds__(256) void gather_windows_kernel(const T* __restrict__ src, const int* __restrict__ starts,
                                                              int K, long long frame_elems, float divisor,
@@ -77,9 +79,8 @@ extern "C" int geeco_gather_windows(const void* src, int src_is_u8, const int* s
 // ---- window builder by address: one launch for windows of any episode, order or frame kind ----------------------------------
 // A batch of SHUFFLED windows (input_fn.pickplace_input_fn(shuffle_windows=True)) holds about one episode per window; the
 // builder above takes one episode per launch.  Here the host hands a table instead:  out[n][k][:] = conv(frame k of the K
-// consecutive frames at addr[n]),  kind[n] = 0: uint8 frames, conv(u8) = float(u8) / 255.0f (bitwise the `divisor 255`
-// conversion above);  kind[n] = 1: float32 frames, a copy.  blockIdx = (unit, k, n): a block serves one frame of one window,
-// so it never straddles kinds, and takes the vector path when ITS window's address is aligned for it (4 bytes for a uint8
+// consecutive frames at addr[n]),  kind[n] = 0: uint8 frames, conv = u8_unit_div;  kind[n] = 1: float32 frames, a copy.
+// blockIdx = (unit, k, n): a block serves one frame of one window, so it never straddles kinds, and takes the vector path when ITS window's address is aligned for it (4 bytes for a uint8
 // word, 16 for a float4; frame_elems % 4 == 0 keeps every frame of an aligned window aligned), else one element at a time.
 // HBM streaming: 4- / 16-byte non-temporal loads on the vector path (as pack_frames_kernel, shared_frames.hip), 16-byte stores.
 __global__ __launch_bounds__(256) void gather_windows_by_address_kernel(const long long* __restrict__ addr,
@@ -105,12 +106,11 @@ __global__ __launch_bounds__(256) void gather_windows_by_address_kernel(const lo
     const unsigned long long a = base + (unsigned long long)k * frame_elems + i4;
     if ((base & 3u) == 0) {
       const unsigned x = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(a));
-#pragma unroll
-      for (int j = 0; j < 4; ++j) e[j] = (float)((x >> (8 * j)) & 255u) / 255.0f;
+      u8x4_unit_div(x, e);
     } else {
       const unsigned char* s = reinterpret_cast<const unsigned char*>(a);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) e[j] = (float)s[j] / 255.0f;
+      for (int j = 0; j < 4; ++j) e[j] = u8_unit_div(s[j]);
     }
   }
   *reinterpret_cast<f32x4*>(o) = f32x4{e[0], e[1], e[2], e[3]};
@@ -155,7 +155,7 @@ __device__ __forceinline__ float aug_tint(float v, unsigned c, bool on, float g0
 }
 
 __device__ __forceinline__ float aug_load(unsigned long long frame, bool f32, long long e) {
-  return f32 ? reinterpret_cast<const float*>(frame)[e] : (float)reinterpret_cast<const unsigned char*>(frame)[e] / 255.0f;
+  return f32 ? reinterpret_cast<const float*>(frame)[e] : u8_unit_div(reinterpret_cast<const unsigned char*>(frame)[e]);
 }
 
 __global__ __launch_bounds__(256) void gather_windows_augmented_kernel(const long long* __restrict__ addr,
@@ -210,12 +210,11 @@ __global__ __launch_bounds__(256) void gather_windows_augmented_kernel(const lon
         if (wa == a || (wa >= frame && wa + 8 <= frame + fe)) {
           unsigned x = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(wa));
           if (wa != a) x = __builtin_amdgcn_alignbyte(__builtin_nontemporal_load(reinterpret_cast<const unsigned*>(wa + 4)), x, (unsigned)(a & 3u));
-#pragma unroll
-          for (int j = 0; j < 4; ++j) e[j] = (float)((x >> (8 * j)) & 255u) / 255.0f;
+          u8x4_unit_div(x, e);
         } else {
           const unsigned char* s = reinterpret_cast<const unsigned char*>(a);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) e[j] = (float)s[j] / 255.0f;
+          for (int j = 0; j < 4; ++j) e[j] = u8_unit_div(s[j]);
         }
       }
 #pragma unroll

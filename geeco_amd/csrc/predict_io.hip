@@ -7,13 +7,15 @@
 //
 // The control words `ctl` [B + 1] int32: ctl[b] = 1 when env b's frame failed the range check, ctl[B] = 1 when any did.  The
 // range check only ever sets them; the output pack copies them out and zeroes them again, so every call starts from zeros.
-#include "dynimg_internal.h"
+//
+// From frame_ingest.h: u8_unit_div, load_rgb4 (the uint8 / float32 frame loads of load_new) and ld_vec; from state_layout.h: the
+// state columns and check_state_layout of the feature push.
+#include "dynimg_internal.h"      // DYN_MAXK
+#include "frame_ingest.h"
+#include "state_layout.h"
 
 #define PIO_MAXK DYN_MAXK       // the window lengths the input kernels of the models take
 #define GEECO_PREDICT_FEAT_THREADS 1024      // one block per env in the feature push + gather
-
-// float(u8) / 255.0f with the IEEE division: bitwise the `divisor 255` conversion of geeco_gather_windows (frame_pack.hip)
-__device__ __forceinline__ float pio_u8(unsigned v) { return (float)v / 255.0f; }
 
 // ---- 1. frame range check ---------------------------------------------------------------------------------------------
 // channels 0..2 of every env's new float frame inside [lo, hi]; a NaN fails (NaN compares false, as np.amin turns NaN)
@@ -100,21 +102,19 @@ __device__ __forceinline__ void load_new(const void* frames, int b, long long HW
                                          float (&dp)[PIX]) {
   if (U8) {        // C == 3
     const unsigned char* f = reinterpret_cast<const unsigned char*>(frames) + (long long)b * HW * 3 + u * PIX * 3;
-    if (PIX == 4) {
-      const unsigned* w = reinterpret_cast<const unsigned*>(f);
-#pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const unsigned x = w[q];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) px[q * 4 + k] = pio_u8((x >> (8 * k)) & 255u);
-      }
+    if constexpr (PIX == 4) {
+      load_rgb4(reinterpret_cast<const unsigned*>(f), px);
     } else {
 #pragma unroll
-      for (int k = 0; k < PIX * 3; ++k) px[k] = pio_u8(f[k]);
+      for (int k = 0; k < PIX * 3; ++k) px[k] = u8_unit_div(f[k]);
     }
     return;
   }
   const float* f = reinterpret_cast<const float*>(frames) + (long long)b * HW * C + u * PIX * C;
+  if constexpr (PIX == 4 && C == 3) {
+    load_rgb4(reinterpret_cast<const f32x4*>(f), px);
+    return;
+  }
   float v[PIX * C];
   if (PIX == 4) {
 #pragma unroll
@@ -367,23 +367,9 @@ extern "C" int geeco_predict_pack_newest(const void* frames, int frames_u8, int 
 // p = heads[b] (into every slot where reset[b]: first-frame padding), writes the decoder's states[t][b] for t = 0..K-1 from
 // slots p + 1, .., p + K - 1, p (mod K; oldest first) and moves the head on.  The new values are taken from the inputs, the
 // K - 1 older ones from slots this launch does not write, so no thread reads what another one writes; the head is read by
-// every thread before the block's barrier and written by one thread after it.  Column layout of a cell, the one
-// geeco_state_concat_fwd gives: plain [feat | jnt], constant [feat | jnt | tgt], residual [tgt - feat | jnt].
+// every thread before the block's barrier and written by one thread after it.  Column layout of a cell: state_layout.h.
 // V = floats per load of the feature sources (4: ch % 4 == 0 and 16-byte aligned bases).  The state rows are stored one float
 // per lane: with J = 7 a cell's columns start at odd offsets, a 16-byte store has nowhere aligned to go.
-template <int V>
-__device__ __forceinline__ void ld_feat(const float* p, float (&v)[V]) {
-  if (V == 4) {
-    const f32x4 x = *reinterpret_cast<const f32x4*>(p);
-    v[0] = x.x;
-    v[1] = x.y;
-    v[2] = x.z;
-    v[3] = x.w;
-  } else {
-    v[0] = *p;
-  }
-}
-
 template <int V>
 __global__ __launch_bounds__(GEECO_PREDICT_FEAT_THREADS) void push_features_kernel(
     const float* __restrict__ feat, const float* __restrict__ jnt, const int* __restrict__ reset, const int* __restrict__ any_bad,
@@ -395,8 +381,7 @@ __global__ __launch_bounds__(GEECO_PREDICT_FEAT_THREADS) void push_features_kern
   int p = heads[b];
   if ((unsigned)p >= (unsigned)K) p = 0;     // heads come zero-filled and only this kernel moves them; never index past a ring
   const int FE = cells * ch;                 // floats of one feature vector
-  const int Ctot = ch + J + (mode == GEECO_PREDICT_FEAT_CONSTANT ? ch : 0);
-  const int jnt_off = ch;
+  const StateLayout<int> L = state_layout(mode, ch, J);
   const float* fnew = feat + (long long)b * FE;
   const float* tg = mode == GEECO_PREDICT_FEAT_PLAIN ? nullptr : tgt + (long long)b * FE;
   float* fr = feat_ring + (long long)b * K * FE;
@@ -407,7 +392,7 @@ __global__ __launch_bounds__(GEECO_PREDICT_FEAT_THREADS) void push_features_kern
   for (int i = threadIdx.x; i < ns * nq; i += blockDim.x) {
     const int s = i / nq, q = i - s * nq;
     float v[V];
-    ld_feat<V>(fnew + q * V, v);
+    ld_vec<V>(fnew + q * V, v);
     float* o = fr + (long long)(s0 + s) * FE + q * V;
     if (V == 4) *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
     else o[0] = v[0];
@@ -423,20 +408,20 @@ __global__ __launch_bounds__(GEECO_PREDICT_FEAT_THREADS) void push_features_kern
     if (slot >= K) slot -= K;
     const bool fresh = rs || slot == p;
     float v[V];
-    ld_feat<V>(fresh ? fnew + q * V : fr + (long long)slot * FE + q * V, v);
+    ld_vec<V>(fresh ? fnew + q * V : fr + (long long)slot * FE + q * V, v);
     const int cell = (q * V) / ch, c = q * V - cell * ch;
-    float* o = states + ((long long)t * B + b) * state_stride + cell * Ctot + c;
+    float* o = states + ((long long)t * B + b) * state_stride + cell * L.Ctot + c;
     if (mode == GEECO_PREDICT_FEAT_PLAIN) {
 #pragma unroll
       for (int k = 0; k < V; ++k) o[k] = v[k];
     } else {
       float g[V];
-      ld_feat<V>(tg + q * V, g);
+      ld_vec<V>(tg + q * V, g);
       if (mode == GEECO_PREDICT_FEAT_CONSTANT) {
 #pragma unroll
         for (int k = 0; k < V; ++k) {
           o[k] = v[k];
-          o[ch + J + k] = g[k];
+          o[L.jnt_off + J + k] = g[k];      // (= L.tgt_off, without its select)
         }
       } else {
 #pragma unroll
@@ -451,7 +436,7 @@ __global__ __launch_bounds__(GEECO_PREDICT_FEAT_THREADS) void push_features_kern
     int slot = p + 1 + t;
     if (slot >= K) slot -= K;
     const bool fresh = rs || slot == p;
-    states[((long long)t * B + b) * state_stride + cell * Ctot + jnt_off + j] = fresh ? jnt[(long long)b * J + j] : jr[slot * J + j];
+    states[((long long)t * B + b) * state_stride + cell * L.Ctot + L.jnt_off + j] = fresh ? jnt[(long long)b * J + j] : jr[slot * J + j];
   }
   // 3. the head moves on: every thread of the block has read it before this barrier
   __syncthreads();
@@ -464,16 +449,10 @@ extern "C" int geeco_predict_push_features(const float* feat, const float* jnt, 
                                            void* stream) {
   GEECO_CHECK_ARG(feat && jnt && reset && any_bad && feat_ring && jnt_ring && heads && states,
                   "predict_push_features: null pointer");
-  GEECO_CHECK_ARG(mode == GEECO_PREDICT_FEAT_PLAIN || mode == GEECO_PREDICT_FEAT_CONSTANT || mode == GEECO_PREDICT_FEAT_RESIDUAL,
-                  "predict_push_features: mode=%d must be 0 (plain), 1 (constant) or 2 (residual)", mode);
+  if (int rc = check_state_layout("predict_push_features", mode, cells, ch, J, state_stride)) return rc;
   GEECO_CHECK_ARG(mode == GEECO_PREDICT_FEAT_PLAIN || tgt_feat, "predict_push_features: null pointer (tgt_feat, mode %d)", mode);
   GEECO_CHECK_ARG(B >= 1, "predict_push_features: B=%d must be >= 1", B);
   GEECO_CHECK_ARG(K >= 1 && K <= PIO_MAXK, "predict_push_features: K=%d outside 1..%d", K, PIO_MAXK);
-  GEECO_CHECK_ARG(cells >= 1 && ch >= 1 && J >= 1 && (int64_t)cells * ch <= (1 << 24), "predict_push_features: cells=%d ch=%d J=%d",
-                  cells, ch, J);
-  const int64_t Ctot = (int64_t)ch + J + (mode == GEECO_PREDICT_FEAT_CONSTANT ? ch : 0);
-  GEECO_CHECK_ARG(state_stride >= cells * Ctot, "predict_push_features: state_stride=%lld below cells * %lld columns",
-                  (long long)state_stride, (long long)Ctot);
   const uintptr_t al = reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(tgt_feat) |
                        reinterpret_cast<uintptr_t>(feat_ring);
   const bool vec = ch % 4 == 0 && (al & 15) == 0;

@@ -5,17 +5,17 @@
 // feature gradient is the sum over those windows.  The step then encodes a table of F frame SLOTS once:
 //   1. pack_frames_by_address: the table's resident frames (uint8 or float32 RGB) -> the encoder input x_in [F][HW][4];
 //   2. window_states_fwd:      feat [F][cells][ch] + idx [N][K] (+ tgt_idx [N]) -> the decoder's states [K][N][D], ONE launch
-//                              with the columns the K geeco_state_concat_fwd launches of the dense step give;
+//                              (columns: state_layout.h);
 //   3. window_states_bwd:      its adjoint, d(states) -> dfeat [F][cells][ch], one block per slot, a fixed summation order.
 // All three are HBM streaming (or tiny): 16-byte accesses where the layout allows, one float otherwise.  No atomics.
-#include "geeco_common.h"
+//
+// From frame_ingest.h: u8_unit_div, load_rgb4 (the 4-pixel path of the frame pack) and ld_vec; from state_layout.h: the state
+// columns and check_state_layout.
+#include "frame_ingest.h"
+#include "state_layout.h"
 
 #define SF_THREADS 256
 #define SF_MAX_POSITIONS 1024      // N * K of one launch: the backward's per-slot position list lives in LDS
-
-// float(u8) / 255.0f with the IEEE division: bitwise the `divisor 255` conversion of geeco_gather_windows (frame_pack.hip) and
-// of geeco_predict_pack_newest (predict_io.hip)
-__device__ __forceinline__ float sf_u8(unsigned v) { return (float)v / 255.0f; }
 
 // ---- 1. frame pack by address ---------------------------------------------------------------------------------------------
 // blockIdx.y = slot.  A block takes the 4-pixel path when HW % 4 == 0 and ITS frame's address is aligned for it (4 bytes for
@@ -36,25 +36,8 @@ __global__ __launch_bounds__(SF_THREADS) void pack_frames_kernel(const long long
   if (vec) {
     for (long long u = first; u < HW / 4; u += step) {
       float px[12];
-      if (U8) {
-        const unsigned* w = reinterpret_cast<const unsigned*>(addr) + u * 3;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          const unsigned x = w[q];
-#pragma unroll
-          for (int k = 0; k < 4; ++k) px[q * 4 + k] = sf_u8((x >> (8 * k)) & 255u);
-        }
-      } else {
-        const f32x4* w = reinterpret_cast<const f32x4*>(addr) + u * 3;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-          const f32x4 x = __builtin_nontemporal_load(w + q);
-          px[q * 4 + 0] = x.x;
-          px[q * 4 + 1] = x.y;
-          px[q * 4 + 2] = x.z;
-          px[q * 4 + 3] = x.w;
-        }
-      }
+      if (U8) load_rgb4(reinterpret_cast<const unsigned*>(addr) + u * 3, px);
+      else load_rgb4(reinterpret_cast<const f32x4*>(addr) + u * 3, px);
 #pragma unroll
       for (int p = 0; p < 4; ++p) o[u * 4 + p] = f32x4{px[p * 3 + 0], px[p * 3 + 1], px[p * 3 + 2], 0.f};
     }
@@ -65,7 +48,7 @@ __global__ __launch_bounds__(SF_THREADS) void pack_frames_kernel(const long long
     if (U8) {
       const unsigned char* s = reinterpret_cast<const unsigned char*>(addr) + px * 3;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) e[c] = sf_u8(s[c]);
+      for (int c = 0; c < 3; ++c) e[c] = u8_unit_div(s[c]);
     } else {
       const float* s = reinterpret_cast<const float*>(addr) + px * 3;
 #pragma unroll
@@ -98,27 +81,14 @@ extern "C" int geeco_pack_frames_by_address(const int64_t* table, int F, int fra
 // aligned base).  The state rows are stored one float per lane: with J = 7 a cell's columns start at odd offsets.  A slot index
 // outside [0, F) (the host never builds one) reads nothing and gives zeros.
 template <int V>
-__device__ __forceinline__ void sf_ld(const float* p, float (&v)[V]) {
-  if (V == 4) {
-    const f32x4 x = *reinterpret_cast<const f32x4*>(p);
-    v[0] = x.x;
-    v[1] = x.y;
-    v[2] = x.z;
-    v[3] = x.w;
-  } else {
-    v[0] = *p;
-  }
-}
-
-template <int V>
 __global__ __launch_bounds__(SF_THREADS) void window_states_fwd_kernel(const float* __restrict__ feat, const int* __restrict__ idx,
                                                                        const float* __restrict__ jnt, const int* __restrict__ tgt_idx,
                                                                        int mode, int F, int N, int K, int cells, int ch, int J,
                                                                        float* __restrict__ states, long long state_stride) {
   const int n = blockIdx.x, t = blockIdx.y;
   const int FE = cells * ch;
-  const int Ctot = ch + J + (mode == GEECO_PREDICT_FEAT_CONSTANT ? ch : 0);
   const int slot = idx[n * K + t];
+  const StateLayout<int> L = state_layout(mode, ch, J);
   const int tslot = mode == GEECO_PREDICT_FEAT_PLAIN ? -1 : tgt_idx[n];
   const float* fs = (unsigned)slot < (unsigned)F ? feat + (long long)slot * FE : nullptr;
   const float* tg = (unsigned)tslot < (unsigned)F ? feat + (long long)tslot * FE : nullptr;
@@ -128,10 +98,10 @@ __global__ __launch_bounds__(SF_THREADS) void window_states_fwd_kernel(const flo
     float v[V], g[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) v[k] = g[k] = 0.f;
-    if (fs) sf_ld<V>(fs + q * V, v);
-    if (tg) sf_ld<V>(tg + q * V, g);
+    if (fs) ld_vec<V>(fs + q * V, v);
+    if (tg) ld_vec<V>(tg + q * V, g);
     const int cell = (q * V) / ch, c = q * V - cell * ch;
-    float* o = row + cell * Ctot + c;
+    float* o = row + cell * L.Ctot + c;
     if (mode == GEECO_PREDICT_FEAT_PLAIN) {
 #pragma unroll
       for (int k = 0; k < V; ++k) o[k] = v[k];
@@ -139,7 +109,7 @@ __global__ __launch_bounds__(SF_THREADS) void window_states_fwd_kernel(const flo
 #pragma unroll
       for (int k = 0; k < V; ++k) {
         o[k] = v[k];
-        o[ch + J + k] = g[k];
+        o[L.jnt_off + J + k] = g[k];      // (= L.tgt_off, without its select)
       }
     } else {
 #pragma unroll
@@ -149,20 +119,15 @@ __global__ __launch_bounds__(SF_THREADS) void window_states_fwd_kernel(const flo
   const float* jn = jnt + ((long long)n * K + t) * J;
   for (int i = threadIdx.x; i < cells * J; i += SF_THREADS) {
     const int cell = i / J, j = i - cell * J;
-    row[cell * Ctot + ch + j] = jn[j];
+    row[cell * L.Ctot + L.jnt_off + j] = jn[j];
   }
 }
 
 static int sf_check_states(const char* what, int mode, int F, int N, int K, int cells, int ch, int J, int64_t state_stride) {
-  GEECO_CHECK_ARG(mode == GEECO_PREDICT_FEAT_PLAIN || mode == GEECO_PREDICT_FEAT_CONSTANT || mode == GEECO_PREDICT_FEAT_RESIDUAL,
-                  "%s: mode=%d must be 0 (plain), 1 (constant) or 2 (residual)", what, mode);
+  if (int rc = check_state_layout(what, mode, cells, ch, J, state_stride)) return rc;
   GEECO_CHECK_ARG(F >= 1 && F <= 65535, "%s: F=%d outside 1..65535", what, F);
   GEECO_CHECK_ARG(N >= 1 && K >= 1 && K <= 65535 && (int64_t)N * K <= SF_MAX_POSITIONS, "%s: N=%d K=%d (N * K within 1..%d)", what, N, K,
                   SF_MAX_POSITIONS);
-  GEECO_CHECK_ARG(cells >= 1 && ch >= 1 && J >= 1 && (int64_t)cells * ch <= (1 << 24), "%s: cells=%d ch=%d J=%d", what, cells, ch, J);
-  const int64_t Ctot = (int64_t)ch + J + (mode == GEECO_PREDICT_FEAT_CONSTANT ? ch : 0);
-  GEECO_CHECK_ARG(state_stride >= cells * Ctot, "%s: state_stride=%lld below cells * %lld columns", what, (long long)state_stride,
-                  (long long)Ctot);
   return 0;
 }
 
@@ -231,13 +196,11 @@ __global__ __launch_bounds__(SF_THREADS) void window_states_bwd_kernel(const flo
   __syncthreads();
   const int cnt = s_cnt[0], tcnt = s_cnt[1];
   const int FE = cells * ch;
-  const int Ctot = ch + J + (mode == GEECO_PREDICT_FEAT_CONSTANT ? ch : 0);
-  const int toff = mode == GEECO_PREDICT_FEAT_CONSTANT ? ch + J : 0;
-  const float sign = mode == GEECO_PREDICT_FEAT_RESIDUAL ? -1.f : 1.f;
+  const StateLayout<int> L = state_layout(mode, ch, J);
   const int nq = FE / V;
   for (int q = threadIdx.x; q < nq; q += SF_THREADS) {
     const int cell = (q * V) / ch, c = q * V - cell * ch;
-    const long long col = (long long)cell * Ctot + c;
+    const long long col = (long long)cell * L.Ctot + c;
     float acc[V];
 #pragma unroll
     for (int k = 0; k < V; ++k) acc[k] = 0.f;
@@ -246,19 +209,19 @@ __global__ __launch_bounds__(SF_THREADS) void window_states_bwd_kernel(const flo
       const int n = e / K, t = e - n * K;
       const float* d = dstates + ((long long)t * N + n) * state_stride + col;
 #pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] += d[k] * sign;
+      for (int k = 0; k < V; ++k) acc[k] += d[k] * L.feat_sign;
     }
     for (int i = 0; i < tcnt; ++i) {
       const int n = s_tgt[i];
       for (int t = 0; t < K; ++t) {
-        const float* d = dstates + ((long long)t * N + n) * state_stride + col + toff;
+        const float* d = dstates + ((long long)t * N + n) * state_stride + col + L.tgt_off;
 #pragma unroll
         for (int k = 0; k < V; ++k) acc[k] += d[k];
       }
     }
     const long long at = (long long)f * FE + q * V;
     float v[V];
-    sf_ld<V>(feat + at, v);
+    ld_vec<V>(feat + at, v);
 #pragma unroll
     for (int k = 0; k < V; ++k) acc[k] = v[k] > 0.f ? acc[k] : 0.f;
     if (V == 4) *reinterpret_cast<f32x4*>(dfeat + at) = f32x4{acc[0], acc[1], acc[2], acc[3]};

@@ -43,6 +43,14 @@ def _iarr(vals):
   return arr
 
 
+def _check_tables(tables, device, message, exact=False):
+  """ValueError(message) unless every (tensor, dtype, n) of ``tables`` is a contiguous table of that dtype with at least (``exact``:
+  exactly) n entries on ``device``."""
+  for t, dt, n in tables:
+    if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and (t.numel() == n if exact else t.numel() >= n) and t.device == device):
+      raise ValueError(message)
+
+
 def same_out(size: int, stride: int) -> int:
   return -(-size // stride)
 
@@ -50,12 +58,6 @@ def same_out(size: int, stride: int) -> int:
 # --------------------------------------------------------------------------------------------
 # dynamic image
 # --------------------------------------------------------------------------------------------
-def dynimg_alpha(K: int):
-  buf = (ctypes.c_float * K)()
-  _lib().geeco_dynimg_alpha(K, ctypes.cast(buf, ctypes.c_void_p))
-  return [float(v) for v in buf]
-
-
 _ALPHA_CACHE = {}
 
 
@@ -65,6 +67,10 @@ def _alpha_buf(K):
     _lib().geeco_dynimg_alpha(K, ctypes.cast(buf, ctypes.c_void_p))
     _ALPHA_CACHE[K] = buf
   return _ALPHA_CACHE[K]
+
+
+def dynimg_alpha(K: int):
+  return [float(v) for v in _alpha_buf(K)]
 
 
 def dynimg_ws(N, hwc, device):
@@ -108,9 +114,8 @@ def goal_dynimgs_u8_into(cur_out, buf_out, diff_out, win_ptrs, tgt_ptrs, K, N, H
   """goal_dynimgs_into fed from resident uint8 frames: win_ptrs / tgt_ptrs are int64 DEVICE tensors of N addresses (window n =
   K consecutive [HW][3] uint8 frames; its target frame).  Bitwise the images of gather_windows_into(divisor 255) +
   goal_dynimgs_into, without the fp32 window tensor in between."""
-  for t in (win_ptrs, tgt_ptrs):
-    if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == N and t.device == buf_out.device):
-      raise ValueError('goal_dynimgs_u8: address tables must be contiguous int64 tensors of N=%d entries on %s' % (N, buf_out.device))
+  _check_tables(((win_ptrs, torch.int64, N), (tgt_ptrs, torch.int64, N)), buf_out.device, exact=True, message=(
+      'goal_dynimgs_u8: address tables must be contiguous int64 tensors of N=%d entries on %s' % (N, buf_out.device)))
   check(_lib().geeco_goal_dynimgs_u8_fwd(ctypes.c_void_p(win_ptrs.data_ptr()), ctypes.c_void_p(tgt_ptrs.data_ptr()), _p(depth),
                                          dsample_stride, dframe_stride, _p(tgt_depth), ctypes.cast(_alpha_buf(K), ctypes.c_void_p),
                                          ctypes.cast(_alpha_buf(2), ctypes.c_void_p), N, K, HW, _p(cur_out), _p(buf_out),
@@ -164,10 +169,8 @@ def gather_windows_into(out, src, starts_dev, N, K, frame_elems, divisor=1.0):
 def gather_windows_by_address_into(out, addr, kind, N, K, frame_elems):
   """out[n][k] <- frame k of the window at addr[n] (int64 device table; kind[n] int32: 0 = uint8 frames / 255, 1 = float32
   frames copied), ONE launch whatever the windows' order, episodes or kinds; bitwise gather_windows_into per window."""
-  for t, dt in ((addr, torch.int64), (kind, torch.int32)):
-    if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= N and t.device == out.device):
-      raise ValueError('gather_windows_by_address: the tables must be contiguous int64 / int32 tensors of N=%d entries on %s' %
-                       (N, out.device))
+  _check_tables(((addr, torch.int64, N), (kind, torch.int32, N)), out.device,
+                'gather_windows_by_address: the tables must be contiguous int64 / int32 tensors of N=%d entries on %s' % (N, out.device))
   if out.numel() < N * K * frame_elems:
     raise ValueError('gather_windows_by_address: output of %d floats for %d x %d frames of %d' % (out.numel(), N, K, frame_elems))
   check(_lib().geeco_gather_windows_by_address(_p(addr), _p(kind), N, K, frame_elems, _p(out), _stream()),
@@ -181,10 +184,8 @@ def gather_windows_augmented_into(out, addr, kind, shift, colour, N, K, H, W, C)
   frame.  ONE launch; any shift is safe (include/geeco_hip.h: geeco_gather_windows_augmented)."""
   tables = ((addr, torch.int64, N), (kind, torch.int32, N), (shift, torch.int32, 2 * N)) + (
       () if colour is None else ((colour, torch.float32, 2 * C * N),))
-  for t, dt, size in tables:
-    if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and t.numel() >= size and t.device == out.device):
-      raise ValueError('gather_windows_augmented: the tables must be contiguous int64 addresses [N], int32 kinds [N], int32 shifts '
-                       '[N][2] and float32 colour [N][%d] for N=%d on %s' % (2 * C, N, out.device))
+  _check_tables(tables, out.device, 'gather_windows_augmented: the tables must be contiguous int64 addresses [N], int32 kinds [N], '
+                'int32 shifts [N][2] and float32 colour [N][%d] for N=%d on %s' % (2 * C, N, out.device))
   if out.numel() < N * K * H * W * C:
     raise ValueError('gather_windows_augmented: output of %d floats for %d x %d frames of %d x %d x %d' % (out.numel(), N, K, H, W, C))
   check(_lib().geeco_gather_windows_augmented(_p(addr), _p(kind), _p(shift), _p(colour), N, K, H, W, C, _p(out), _stream()),
@@ -613,17 +614,22 @@ def heads_ws_bytes(N, H, Hfc):
   return int(_lib().geeco_heads_ws_bytes(N, H, Hfc))
 
 
+def _head_arrays(heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride):
+  """The heads' parallel arrays as both heads entry points take them, in argument order: nheads, weights, biases, sizes, kinds,
+  loss weights, targets, target strides."""
+  nh = len(heads_w)
+  return (nh, _parr(heads_w), _parr(heads_b), _iarr(head_size), _iarr(head_kind), (ctypes.c_float * nh)(*[float(v) for v in head_weight]),
+          _parr(targets), (ctypes.c_int64 * nh)(*[int(v) for v in target_stride]))
+
+
 def heads_loss_into(preds, losses, h, fc1_w, fc1_b, heads_w, heads_b, head_size, head_kind, head_weight, targets,
                     target_stride, loss_scale, N, H, Hfc, ws, dh=None, d_fc1_w=None, d_fc1_b=None, d_heads_w=None,
                     d_heads_b=None):
   """fc1 + heads + losses (+ their gradients when ``dh`` is given); see include/geeco_hip.h."""
   backward = dh is not None
-  nh = len(heads_w)
-  farr = (ctypes.c_float * nh)(*[float(v) for v in head_weight])
-  larr = (ctypes.c_int64 * nh)(*[int(v) for v in target_stride])
   check(_lib().geeco_heads_loss_fwd_bwd(
-      _p(h), _p(fc1_w), _p(fc1_b), nh, _parr(heads_w), _parr(heads_b), _iarr(head_size), _iarr(head_kind), farr,
-      _parr(targets), larr, loss_scale, N, H, Hfc, _p(preds), _p(losses), 1 if backward else 0, _p(dh),
+      _p(h), _p(fc1_w), _p(fc1_b), *_head_arrays(heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride),
+      loss_scale, N, H, Hfc, _p(preds), _p(losses), 1 if backward else 0, _p(dh),
       _p(d_fc1_w), _p(d_fc1_b), _parr(d_heads_w) if backward else None, _parr(d_heads_b) if backward else None,
       _p(ws), _stream()), 'geeco_heads_loss_fwd_bwd')
 
@@ -636,12 +642,9 @@ def lstm_step_heads_into(z, c, h, gates, x, wx, bias, N, H, D, ldx, ldw, gemm_ws
   lstm_step_bwd_into(pending=...); None: they run here.  Returns False (nothing launched) for shapes the per-sample kernel does
   not serve: the caller then runs lstm_input_step_fwd_into + heads_loss_into (+ lstm_gates_bwd_into)."""
   backward = dz is not None
-  nh = len(heads_w)
-  farr = (ctypes.c_float * nh)(*[float(v) for v in head_weight])
-  larr = (ctypes.c_int64 * nh)(*[int(v) for v in target_stride])
   rc = _lib().geeco_lstm_step_heads_fwd_bwd(
-      _p(x), ldx, _p(wx), ldw, _p(bias), _p(z), _p(c), _p(h), _p(gates), N, H, D, _p(gemm_ws), _p(fc1_w), _p(fc1_b), nh,
-      _parr(heads_w), _parr(heads_b), _iarr(head_size), _iarr(head_kind), farr, _parr(targets), larr, loss_scale, Hfc, _p(preds),
+      _p(x), ldx, _p(wx), ldw, _p(bias), _p(z), _p(c), _p(h), _p(gates), N, H, D, _p(gemm_ws), _p(fc1_w), _p(fc1_b),
+      *_head_arrays(heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride), loss_scale, Hfc, _p(preds),
       _p(losses), 1 if backward else 0, _p(dz), _p(d_fc1_w), _p(d_fc1_b), _parr(d_heads_w) if backward else None,
       _parr(d_heads_b) if backward else None, _p(heads_ws), ctypes.byref(pending) if pending is not None else None, _stream())
   if rc == _native.GEECO_ENOSUP:

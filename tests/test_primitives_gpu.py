@@ -489,3 +489,63 @@ def test_gather_windows(dev, u8, E):
   assert ref.dtype == np.float32
   np.testing.assert_array_equal(_np(out[:N * K * E]).reshape(N, K, E).view(np.uint32), ref.view(np.uint32))
   assert _all_nan(out[N * K * E:])
+
+
+def test_every_u8_ingest_path_is_the_one_conversion(dev):
+  """Every entry point that turns resident uint8 frames into floats gives numpy.float32(v) / numpy.float32(255) BITWISE for all 256
+  byte values: the division form of csrc/frame_ingest.h in the gathers, the frame pack and the predictor's pack and push, at
+  8 x 12 (their 4-byte / 4-pixel paths) and at 5 x 5 (one element or pixel at a time), and the Newton form in the one-pass input
+  stage's copy of the current frame.  The frames start with arange(256)."""
+  from geeco_amd import ops
+
+  def same(got, want, what):
+    np.testing.assert_array_equal(_np(got).reshape(-1).view(np.uint32), np.ascontiguousarray(want, np.float32).reshape(-1).view(np.uint32), what)
+
+  def i32(a):
+    return torch.tensor(a, dtype=torch.int32, device=dev)
+
+  r, K, J = np.random.default_rng(255), 2, 3
+  for H, W, F in ((8, 12, 2), (5, 5, 4)):
+    HW, fe, what = H * W, H * W * 3, '%d x %d' % (H, W)
+    f = r.integers(0, 256, size=F * fe, dtype=np.uint8)
+    f[:256] = np.arange(256, dtype=np.uint8)
+    want = (f.astype(np.float32) / np.float32(255)).reshape(F, H, W, 3)
+    N = F // K                                   # windows of K consecutive frames: together every byte of f
+    buf = torch.zeros(F * fe + 1, dtype=torch.uint8, device=dev)
+    buf[1:] = torch.from_numpy(f)
+    src, off1 = buf[1:].clone(), buf[1:]         # the same frames 4-byte aligned (a fresh allocation) and 1 byte past alignment
+    assert src.data_ptr() % 4 == 0 and off1.data_ptr() % 4 == 1
+    addr = lambda t: torch.tensor([t.data_ptr() + n * K * fe for n in range(N)], dtype=torch.int64, device=dev)
+    kind = i32([0] * N)
+    if fe % 4 == 0:
+      out = _nan(dev, N * K * fe)
+      ops.gather_windows_into(out, src, i32([n * K for n in range(N)]), N, K, fe, 255.0)
+      same(out, want, what + ' gather_windows')
+      for t, name in ((src, 'aligned'), (off1, 'offset by 1 byte')):
+        out = _nan(dev, N * K * fe)
+        ops.gather_windows_by_address_into(out, addr(t), kind, N, K, fe)
+        same(out, want, what + ' gather_windows_by_address, ' + name)
+    for dx in (0, 1):
+      out = _nan(dev, N * K * fe)
+      ops.gather_windows_augmented_into(out, addr(src), kind, i32([[0, dx]] * N), None, N, K, H, W, 3)
+      shifted = np.zeros_like(want)
+      shifted[:, :, dx:] = want[:, :, :W - dx]
+      same(out, shifted, what + ' gather_windows_augmented, dx = %d' % dx)
+    padded = np.zeros((F, H, W, 4), np.float32)
+    padded[..., :3] = want
+    frames = src.view(F, HW, 3)
+    x_in = _nan(dev, F, HW, 4)
+    ops.pack_frames_by_address_into(x_in, torch.tensor([src.data_ptr() + i * fe for i in range(F)], dtype=torch.int64, device=dev), F, HW, True)
+    same(x_in, padded, what + ' pack_frames_by_address')
+    x_in = _nan(dev, F, HW, 4)
+    ops.predict_pack_newest_into(x_in, frames, F, HW, 3)
+    same(x_in, padded, what + ' predict_pack_newest')
+    rgb, jw = _nan(dev, F, K, HW, 3), _nan(dev, F, K, J)
+    ops.predict_push_dense_into(rgb, None, jw, frames, torch.zeros(F, J, device=dev), i32([1] * F), i32([0] * (F + 1)), F, K, HW, 3, J)
+    same(rgb, np.repeat(want[:, None], K, axis=1), what + ' predict_push_dense')
+    if HW % 4 == 0:                              # the window's LAST frame is the current one: the arange frame goes there
+      win = torch.cat([src[fe:2 * fe], src[:fe]])
+      imgs = [_nan(dev, 1, H, W, 4) for _ in range(3)]
+      ptr = torch.tensor([win.data_ptr()], dtype=torch.int64, device=dev)
+      ops.goal_dynimgs_u8_into(imgs[0], imgs[1], imgs[2], ptr, ptr, K, 1, HW, ops.goal_dynimgs_ws(1, HW, dev))
+      same(imgs[0], padded[:1], what + ' goal_dynimgs_u8 cur_out')
