@@ -17,12 +17,17 @@ def check_image_size(H, W):
 class ConvEncoderStack:
   """``conv_encoder`` for G weight sets with identical shapes, Nf frames each."""
 
+  # The data-parallel runner cuts the backward here: 'upper' = conv8 .. conv(SPLIT+1) down to that layer's filter gradient, 'bottom'
+  # opens with its INPUT gradient and runs conv(SPLIT) .. conv1 (round 4 cut after it: every gradient of the early bucket exists once
+  # that filter gradient does, so the bucket leaves a launch earlier)
+  SPLIT = 2
+
   def __init__(self, store: VariableStore, scopes, Nf, H, W, Cin, dim_out, training):
     """``dim_out``: conv8's output channels, one int or one per encoder (dim_s_obs / dim_s_dyn / dim_s_diff,
     graph.py:390,394,402).  With unequal values conv1..conv7 still run as grouped launches and conv8 (the only layer
     whose shape differs) runs once per encoder (``split_top``)."""
     self.store, self.scopes, self.G, self.Nf = store, list(scopes), len(scopes), Nf
-    self.H, self.W, self.Cin = H, W, Cin
+    self.Cin = Cin
     self.late = None       # (staging buffer, per-encoder length): see redirect_late_gradients
     # CUs the two persistent bottom-of-the-backward launches leave to a collective running beside them: a launch argument
     # (runtime.TrainStepRunner sets it around its own part 2, so every runner captures the grids it was built for)
@@ -59,9 +64,7 @@ class ConvEncoderStack:
             b = store.offsets['%s/conv%d/%s' % (self.scopes[0], l, kind)]
             if a - b != g * gs:
               raise ValueError('encoders are not uniformly strided in the arena')
-      self.gs_p = gs
-    else:
-      self.gs_p = 0
+    self.gs_p = gs if G > 1 else 0
     # layer geometry
     self.layers = []
     h, w, c = H, W, self.Cpad
@@ -82,6 +85,10 @@ class ConvEncoderStack:
     self.pad1_copy = self.pad1      # the channel-padded copy of conv1's kernel is kept up to date (see below)
     if self.pad1:
       self.w1p = torch.zeros(G, 3, 3, self.Cpad, self.layers[0]['Cout'], **f32)
+    # what only a training stack can have: False / empty / None on every other one
+    self.fused_bottom = self.relu_bits = self.relu_fields = self.relu_fields3 = False
+    self.bits1 = self.fields2 = self.fields3 = None      # the signs of conv1's / conv2's / conv3's outputs, for the backward
+    self.needs_wt, self.needs_wt7, self.sides = [False] * 8, [], []      # (needs_wt7: conv8 per encoder, split_top)
     if training:
       # encoder bottom fused backward (conv2 dgrad + conv1 wgrad): the reference encoder's shapes, even sizes
       L0, L1 = self.layers[0], self.layers[1]
@@ -130,7 +137,6 @@ class ConvEncoderStack:
       # read conv3..conv8's workspaces while conv2's filter gradient writes its own
       self.ws_l = [torch.empty(ops.conv3x3_wgrad_ws_bytes(G, Nf, L['H'], L['W'], L['Cin'], L['Cout'], L['stride']) // 4 + 4,
                                **f32) for L in self.layers]
-      self.ws = self.ws_l[0]
       dsb = max(ops.conv3x3_dgrad_ws_bytes(G, Nf, L['H'], L['W'], L['Cin'], L['Cout'], L['stride'])
                 for L in self.layers[1:])
       self.dws = torch.empty(dsb // 4 + 4, **f32)
@@ -144,6 +150,19 @@ class ConvEncoderStack:
         self.fws_fused = torch.empty(ops.conv2_dgrad_conv1_wgrad_ws_bytes(G) // 4 + 4, **f32)
     fsb = max(ops.conv3x3_fwd_ws_bytes(G, Nf, L['H'], L['W'], L['Cin'], L['Cout'], L['stride']) for L in self.layers)
     self.fws = torch.empty(fsb // 4 + 4, **f32)
+    # The launch plan: which kernel runs each layer, decided here once (launch_fwd / launch_dgrad dispatch on it).  Forward: 'plain',
+    # or the variant that also leaves the signs of its output for the backward -- conv1 one bit per value ('bits_rgb': straight from
+    # the RGB variable, no padded kernel copy), conv2 16-bit fields, conv3 byte fields -- or conv8 per encoder.  Input gradient of
+    # layer l (into dz[l-1]): 'plain', conv2's fused with conv1's filter gradient, conv3's from the 16-bit fields, conv4's LDS-staged
+    # from the byte fields, conv8's per encoder.
+    pick = lambda flag, variant: variant if flag else 'plain'
+    top = pick(self.split_top, 'per_encoder')
+    self.fwd_plan = [pick(self.relu_bits, 'bits' if self.pad1_copy or not self.pad1 else 'bits_rgb'), pick(self.relu_fields, 'fields16'),
+                     pick(self.relu_fields3, 'fields8'), 'plain', 'plain', 'plain', 'plain', top]
+    self.dgrad_plan = [None, pick(self.fused_bottom, 'fused_bottom'), pick(self.relu_fields, 'fields16'),
+                       pick(self.relu_fields3, 'fields8'), 'plain', 'plain', 'plain', top]
+    # conv7's input gradient and conv7's / conv8's filter gradients need only conv8's input gradient: one grid for the three
+    self.top_one_grid = not self.split_top and self.layers[6]['stride'] == self.layers[7]['stride'] == 2
 
   def _w(self, l, g=0):
     return self.store.var('%s/conv%d/kernel' % (self.scopes[g], l + 1))
@@ -153,15 +172,12 @@ class ConvEncoderStack:
 
   def _grad_view(self, l, g, kind):
     name = '%s/conv%d/%s' % (self.scopes[g], l + 1, kind)
-    if self.late is None or l >= ConvEncoderStack.SPLIT:
-      return self.store.grad(name)
-    staging, stride = self.late
-    shp = self.store.shapes[name]
+    grad = self.store.grad(name)
+    if self.late is None or l >= self.SPLIT:
+      return grad
+    staging, stride = self.late      # the same view, of encoder g's block of the staging buffer
     o = self.store.offsets[name] - self.store.offsets[self.scopes[g] + '/conv1/kernel'] + g * stride
-    n = 1
-    for d in shp:
-      n *= int(d)
-    return staging[o:o + n].view(*shp)
+    return staging[o:o + grad.numel()].view_as(grad)
 
   def _dw(self, l, g=0):
     return self._grad_view(l, g, 'kernel')
@@ -171,7 +187,7 @@ class ConvEncoderStack:
 
   def _gs_g(self, l):
     """Group stride of layer l's gradient views (the arena's, or the late staging buffer's for conv1 / conv2)."""
-    return self.late[1] if (self.late is not None and l < ConvEncoderStack.SPLIT) else self.gs_p
+    return self.late[1] if (self.late is not None and l < self.SPLIT) else self.gs_p
 
   def redirect_late_gradients(self, staging, late_ranges):
     """Data parallel (runtime.TrainStepRunner): the gradients of conv1 / conv2 -- the LATE bucket, written by the last
@@ -184,7 +200,7 @@ class ConvEncoderStack:
       return False
     off = self.store.offsets
     lo0 = off[self.scopes[0] + '/conv1/kernel']
-    length = off[self.scopes[0] + '/conv%d/kernel' % (ConvEncoderStack.SPLIT + 1)] - lo0
+    length = off[self.scopes[0] + '/conv%d/kernel' % (self.SPLIT + 1)] - lo0
     want = [(lo0 + g * self.gs_p, length) for g in range(self.G)]
     if [tuple(r) for r in late_ranges] != want or staging.numel() != self.G * length or not self.training:
       return False
@@ -206,12 +222,10 @@ class ConvEncoderStack:
     Adam hipGraph), so the forward / backward graphs contain no pad or transpose launches."""
     G = self.G
     # only the layers whose input-gradient kernel reads the transposed copy (the LDS-staged ones read the HWIO kernel)
-    ls = [l for l in range(1, 7 if self.split_top else 8) if self.needs_wt[l]] if self.training else []
-    if self.training and self.split_top:
-      L7 = self.layers[7]
-      for g in range(G):
-        if self.wt[7][g] is not None:
-          ops.derive_conv_weights([self._w(7, g)], [self.wt[7][g].unsqueeze(0)], [L7['Cin']], [self.dim_outs[g]], 1, 0)
+    ls = [l for l in range(1, 7 if self.split_top else 8) if self.needs_wt[l]]
+    for g, needed in enumerate(self.needs_wt7):
+      if needed:
+        ops.derive_conv_weights([self._w(7, g)], [self.wt[7][g].unsqueeze(0)], [self.layers[7]['Cin']], [self.dim_outs[g]], 1, 0)
     pad = dict(pad_src=self._w(0), pad_dst=self.w1p, pad_cin=self.Cin, pad_cin_padded=self.Cpad,
                pad_cout=self.layers[0]['Cout']) if self.pad1_copy else {}
     if ls or pad:
@@ -220,70 +234,73 @@ class ConvEncoderStack:
     self.derived_version = self.store.version
 
   # -- single launches (also timed one by one by bench.py's per-layer table) ---------------------------
+  # One helper per direction gives layer l's arguments as (tensors, (groups, group strides ...), (N, H, W, Cin, Cout, stride)).
+  # ``g``: encoder g alone -- conv8 under split_top, whose outputs, gradients and kernel copies are one tensor per encoder: buf[g] is
+  # encoder g's part of a grouped buffer and of such a list alike, and a single group has no strides.
+
+  def _shape(self, l, g=None):
+    L = self.layers[l]
+    return (self.Nf, L['H'], L['W'], L['Cin'], L['Cout'] if g is None else self.dim_outs[g], L['stride'])
+
+  def _fwd_operands(self, l, g=None):
+    """(y, x, w, b), (G, gs_x, gs_w, gs_b, gs_y), shape."""
+    x, y = self.x_in if l == 0 else self.acts[l - 1], self.acts[l]
+    if g is not None:
+      return (y[g], x[g], self._w(l, g), self._b(l, g)), (1, 0, 0, 0, 0), self._shape(l, g)
+    w, gs_w = (self.w1p, self.w1p[0].numel()) if (l == 0 and self.pad1_copy) else (self._w(l), self.gs_p)
+    return (y, x, w, self._b(l)), (self.G, x[0].numel(), gs_w, self.gs_p, y[0].numel()), self._shape(l)
+
+  def _dgrad_operands(self, l, g=None):
+    """(dx, dz, wt, x, w), (G, gs_dz, gs_wt, gs_dx, gs_w), shape; x = the layer's input, whose sign is the ReluGrad mask."""
+    dx, dz, wt, x = self.dz[l - 1], self.dz[l], self.wt[l], self.acts[l - 1]
+    if g is not None:
+      return (dx[g], dz[g], wt[g], x[g], self._w(l, g)), (1, 0, 0, 0, 0), self._shape(l, g)
+    return ((dx, dz, wt, x, self._w(l)), (self.G, dz[0].numel(), wt[0].numel() if wt is not None else 0, dx[0].numel(), self.gs_p),
+            self._shape(l))
+
+  def _wgrad_operands(self, l, g=None):
+    """(dw, db, x, dz), (G, gs_x, gs_dz, gs_dw, gs_db), shape; conv1's filter gradient in the channel-padded layout where that exists."""
+    x, dz = self.x_in if l == 0 else self.acts[l - 1], self.dz[l]
+    if g is not None:
+      return (self._dw(l, g), self._db(l, g), x[g], dz[g]), (1, 0, 0, 0, 0), self._shape(l, g)
+    dw, gs_dw = (self.dw1p, self.dw1p[0].numel()) if (l == 0 and self.pad1) else (self._dw(l), self._gs_g(l))
+    return (dw, self._db(l), x, dz), (self.G, x[0].numel(), dz[0].numel(), gs_dw, self._gs_g(l)), self._shape(l)
 
   def launch_fwd(self, l):
-    G, Nf, L = self.G, self.Nf, self.layers[l]
-    if l == 7 and self.split_top:
-      for g in range(G):
-        ops.conv3x3_fwd_into(self.acts[7][g], self.acts[6][g], self._w(7, g), self._b(7, g), 1, 0, 0, 0, 0, Nf, L['H'], L['W'],
-                             L['Cin'], self.dim_outs[g], L['stride'], relu=True, ws=self.fws)
+    plan = self.fwd_plan[l]
+    if plan in ('plain', 'per_encoder'):
+      for g in range(self.G) if plan == 'per_encoder' else (None,):
+        tensors, groups, shape = self._fwd_operands(l, g)
+        ops.conv3x3_fwd_into(*tensors, *groups, *shape, relu=True, ws=self.fws)
       return
-    x = self.x_in if l == 0 else self.acts[l - 1]
-    y = self.acts[l]
-    if l == 0 and self.pad1:
-      w, gs_w = self.w1p, self.w1p[0].numel()
-    else:
-      w, gs_w = self._w(l), self.gs_p
-    if l == 2 and self.training and self.relu_fields3:
-      ops.conv3_fwd_relu_fields_into(y, self.fields3, x, w, self._b(2), G, x[0].numel(), gs_w, self.gs_p, y[0].numel(),
-                                     self.fields3[0].numel(), Nf, L['H'], L['W'])
-      return
-    if l == 1 and self.training and self.relu_fields:
-      ops.conv2_fwd_relu_fields_into(y, self.fields2, x, w, self._b(1), G, x[0].numel(), gs_w, self.gs_p, y[0].numel(),
-                                     self.fields2[0].numel(), Nf, L['H'], L['W'])
-      return
-    if l == 0 and self.training and self.relu_bits and self.pad1 and not self.pad1_copy:
-      ops.conv1_fwd_relu_bits_rgb_into(y, self.bits1, x, self._w(0), self._b(0), G, x[0].numel(), self.gs_p, self.gs_p, y[0].numel(),
-                                       self.bits1[0].numel(), Nf, L['H'], L['W'])
-      return
-    if l == 0 and self.training and self.relu_bits:
-      ops.conv1_fwd_relu_bits_into(y, self.bits1, x, w, self._b(0), G, x[0].numel(), gs_w, self.gs_p, y[0].numel(),
-                                   self.bits1[0].numel(), Nf, L['H'], L['W'])
-      return
-    ops.conv3x3_fwd_into(y, x, w, self._b(l), G, x[0].numel(), gs_w, self.gs_p, y[0].numel(), Nf, L['H'], L['W'],
-                         L['Cin'], L['Cout'], L['stride'], relu=True, ws=self.fws)
+    fwd = {'bits': ops.conv1_fwd_relu_bits_into, 'bits_rgb': ops.conv1_fwd_relu_bits_rgb_into,
+           'fields16': ops.conv2_fwd_relu_fields_into, 'fields8': ops.conv3_fwd_relu_fields_into}[plan]
+    (y, x, w, b), groups, shape = self._fwd_operands(l)
+    signs = (self.bits1, self.fields2, self.fields3)[l]
+    fwd(y, signs, x, w, b, *groups, signs[0].numel(), *shape[:3])
 
   def launch_wgrad(self, l, pending=None):
     """Filter + bias gradient of layer l (skipped for conv1 when the encoder bottom is fused: launch_dgrad(1) does it).
     ``pending`` (a list): the kernel's final slab sum is deferred to ``ops.slab_reduce_batch(pending)``."""
-    G, Nf, L = self.G, self.Nf, self.layers[l]
     if l == 0 and self.fused_bottom:
       return
     if l == 7 and self.split_top:
-      for g in range(G):
-        ops.conv3x3_wgrad_into(self._dw(7, g), self._db(7, g), self.acts[6][g], self.dz[7][g], 1, 0, 0, 0, 0, Nf, L['H'],
-                               L['W'], L['Cin'], self.dim_outs[g], L['stride'], self.ws_l[7])
+      for g in range(self.G):
+        tensors, groups, shape = self._wgrad_operands(l, g)
+        ops.conv3x3_wgrad_into(*tensors, *groups, *shape, self.ws_l[l])
       return
-    x = self.x_in if l == 0 else self.acts[l - 1]
-    dz = self.dz[l]
-    if l == 0 and self.pad1:
-      dw, gs_dw = self.dw1p, self.dw1p[0].numel()
-    else:
-      dw, gs_dw = self._dw(l), self._gs_g(l)
-    if l == 0 and self.pad1:
-      pending = None     # the padded gradient is repacked right below
-    ops.conv3x3_wgrad_into(dw, self._db(l), x, dz, G, x[0].numel(), dz[0].numel(), gs_dw, self._gs_g(l), Nf, L['H'],
-                           L['W'], L['Cin'], L['Cout'], L['stride'], self.ws_l[l], pending=pending,
+    repack = l == 0 and self.pad1     # the padded gradient is repacked right below: its slab sum is not deferred
+    tensors, groups, shape = self._wgrad_operands(l)
+    ops.conv3x3_wgrad_into(*tensors, *groups, *shape, self.ws_l[l], pending=None if repack else pending,
                            reserved_cus=self.reserved_cus if (l == 1 and pending is not None) else 0)
-    if l == 0 and self.pad1:
-      for g in range(G):
-        ops.pad_mid_into(self._dw(0, g), self.dw1p[g], 9, self.Cpad, self.Cin, L['Cout'])
+    if repack:
+      for g in range(self.G):
+        ops.pad_mid_into(self._dw(0, g), self.dw1p[g], 9, self.Cpad, self.Cin, shape[4])
 
   def _wgrad_args(self, l):
-    L = self.layers[l]
-    x, dz = self.acts[l - 1], self.dz[l]
-    return dict(dw=self._dw(l), db=self._db(l), x=x, dz=dz, gs_x=x[0].numel(), gs_dz=dz[0].numel(), gs_dw=self._gs_g(l),
-                gs_db=self._gs_g(l), N=self.Nf, H=L['H'], W=L['W'], Cin=L['Cin'], Cout=L['Cout'], ws=self.ws_l[l])
+    (dw, db, x, dz), (_, gs_x, gs_dz, gs_dw, gs_db), (N, H, W, Cin, Cout, _) = self._wgrad_operands(l)
+    return dict(dw=dw, db=db, x=x, dz=dz, gs_x=gs_x, gs_dz=gs_dz, gs_dw=gs_dw, gs_db=gs_db, N=N, H=H, W=W, Cin=Cin, Cout=Cout,
+                ws=self.ws_l[l])
 
   def launch_wgrad_top_pair(self, pending=None):
     """conv7's and conv8's filter gradients as ONE launch (both are ready once conv8's input gradient exists; each alone is
@@ -293,46 +310,35 @@ class ConvEncoderStack:
   def launch_top_bwd(self, l, wgrads, pending=None):
     """Layer l's input gradient AND the filter gradients of layers ``wgrads`` as one heterogeneous launch (independent work
     that needs only dz[l]): l = 6 with (6, 7)."""
-    L = self.layers[l]
-    wt = self.wt[l]
-    d = dict(dx=self.dz[l - 1], dz=self.dz[l], wt=wt, ymask=self.acts[l - 1], w=self._w(l), gs_dz=self.dz[l][0].numel(),
-             gs_w=self.gs_p, gs_wt=wt[0].numel() if wt is not None else 0, gs_dx=self.dz[l - 1][0].numel(), N=self.Nf, H=L['H'],
-             W=L['W'], Cin=L['Cin'], Cout=L['Cout'], ws=self.dws)
-    return ops.conv_top_bwd_into(d, self._wgrad_args(wgrads[0]), self._wgrad_args(wgrads[1]) if len(wgrads) > 1 else None, self.G,
-                                 L['stride'], pending=pending)
+    (dx, dz, wt, x, w), (G, gs_dz, gs_wt, gs_dx, gs_w), (N, H, W, Cin, Cout, stride) = self._dgrad_operands(l)
+    d = dict(dx=dx, dz=dz, wt=wt, ymask=x, w=w, gs_dz=gs_dz, gs_w=gs_w, gs_wt=gs_wt, gs_dx=gs_dx, N=N, H=H, W=W, Cin=Cin, Cout=Cout,
+             ws=self.dws)
+    return ops.conv_top_bwd_into(d, self._wgrad_args(wgrads[0]), self._wgrad_args(wgrads[1]) if len(wgrads) > 1 else None, G,
+                                 stride, pending=pending)
 
   def launch_dgrad(self, l, pending=None):
     """Input gradient of layer l >= 1 into dz[l-1] (ReluGrad of the layer below fused).  With the fused encoder
     bottom, l == 1 also produces conv1's filter / bias gradient: dz1 has no other consumer and stays on chip
     (805 MB less written and read again per step, one big launch less)."""
-    G, Nf, L = self.G, self.Nf, self.layers[l]
-    if l == 7 and self.split_top:
-      for g in range(G):
-        ops.conv3x3_dgrad_into(self.dz[6][g], self.dz[7][g], self.wt[7][g], self.acts[6][g], 1, 0, 0, 0, Nf, L['H'], L['W'],
-                               L['Cin'], self.dim_outs[g], L['stride'], ws=self.dws, w=self._w(7, g), gs_w=0)
-      return
-    x = self.acts[l - 1]
-    dz = self.dz[l]
-    if l == 1 and self.fused_bottom:
+    plan = self.dgrad_plan[l]
+    if plan == 'fused_bottom':
       # the kernel writes conv1's gradient in the variable's own [3][3][Cin][32] layout (no padded copy to repack) and reads
       # the sign bits of conv1's output (relu_bits) for its ReluGrad
-      ops.conv2_dgrad_conv1_wgrad_bits_into(self._dw(0), self._db(0), dz, self._w(1), self.bits1, self.x_in, G,
+      dz, (N, H, W, _, _, _) = self.dz[l], self._shape(l)
+      ops.conv2_dgrad_conv1_wgrad_bits_into(self._dw(0), self._db(0), dz, self._w(1), self.bits1, self.x_in, self.G,
                                             dz[0].numel(), self.gs_p, self.bits1[0].numel(), self.x_in[0].numel(),
-                                            self._gs_g(0), self._gs_g(0), Nf, L['H'], L['W'], self.fws_fused,
+                                            self._gs_g(0), self._gs_g(0), N, H, W, self.fws_fused,
                                             real_channels=self.Cin, pending=pending, reserved_cus=self.reserved_cus)
       return
-    wt = self.wt[l]
-    dx = self.dz[l - 1]
-    if l == 3 and self.relu_fields3:
-      ops.conv3x3_dgrad_relu_fields_into(dx, dz, self._w(3), self.fields3, G, dz[0].numel(), self.gs_p, self.fields3[0].numel(),
-                                         dx[0].numel(), Nf, L['H'], L['W'], L['Cin'], L['Cout'], L['stride'])
-      return
-    if l == 2 and self.relu_fields:
-      ops.conv3_dgrad_relu_fields_into(dx, dz, self._w(2), self.fields2, G, dz[0].numel(), self.gs_p, self.fields2[0].numel(),
-                                       dx[0].numel(), Nf, L['H'], L['W'], reserved_cus=self.reserved_cus)
-      return
-    ops.conv3x3_dgrad_into(dx, dz, wt, x, G, dz[0].numel(), wt[0].numel() if wt is not None else 0, dx[0].numel(), Nf, L['H'],
-                           L['W'], L['Cin'], L['Cout'], L['stride'], ws=self.dws, w=self._w(l), gs_w=self.gs_p)
+    for g in range(self.G) if plan == 'per_encoder' else (None,):
+      (dx, dz, wt, x, w), (G, gs_dz, gs_wt, gs_dx, gs_w), shape = self._dgrad_operands(l, g)
+      if plan in ('plain', 'per_encoder'):
+        ops.conv3x3_dgrad_into(dx, dz, wt, x, G, gs_dz, gs_wt, gs_dx, *shape, ws=self.dws, w=w, gs_w=gs_w)
+      elif plan == 'fields8':
+        ops.conv3x3_dgrad_relu_fields_into(dx, dz, w, self.fields3, G, gs_dz, gs_w, self.fields3[0].numel(), gs_dx, *shape)
+      else:
+        ops.conv3_dgrad_relu_fields_into(dx, dz, w, self.fields2, G, gs_dz, gs_w, self.fields2[0].numel(), gs_dx, *shape[:3],
+                                         reserved_cus=self.reserved_cus)
 
   def forward(self, state=None):
     """``state`` (one-step decoders): dict(state, state_stride, feat_off, Ctot, jnt, jnt_stride, jnt_off, J) of the state
@@ -345,55 +351,39 @@ class ConvEncoderStack:
       self.launch_fwd(l)
     # the state concat of a one-step decoder rides in conv8's split-K epilogue
     if state is not None and not self.split_top:
-      G, Nf, L = self.G, self.Nf, self.layers[top]
-      x, y = self.acts[top - 1], self.acts[top]
-      if ops.conv3x3_fwd_state_into(y, x, self._w(top), self._b(top), G, x[0].numel(), self.gs_p, self.gs_p, y[0].numel(), Nf,
-                                    L['H'], L['W'], L['Cin'], L['Cout'], L['stride'], self.fws, **state):
+      tensors, groups, shape = self._fwd_operands(top)
+      if ops.conv3x3_fwd_state_into(*tensors, *groups, *shape, self.fws, **state):
         return True
     self.launch_fwd(top)
     return False
 
-  def backward(self, hi=7, lo=0, prepare=None, defer_dgrad=False, lead_dgrad=None, defer_sums=None, before_bottom=None):
-    """Expects ``self.dz[7]`` = d(loss)/d(pre-activation of conv8) (ReluGrad already applied).  Runs layers
-    hi..lo (the data-parallel runner splits the chain at conv3 / conv2 to start the gradient exchange early).
-    ``prepare`` = (global_step, lr, scal): the optimiser's per-step scalars ride in this part's slab-sum launch.
-    ``defer_dgrad``: layer lo's INPUT gradient is left to the next part, which opens with it (``lead_dgrad=lo``): every
-    gradient of the early bucket exists once layer lo's filter gradient does, so the bucket leaves a launch earlier.
-    ``defer_sums`` (a list): this part's pending slab sums are handed to the caller instead of launched (``prepare`` must be None).
-    ``before_bottom``: called right before the LAST launch of the chain, conv2's input gradient (+ conv1's filter gradient when
-    the bottom is fused) -- graph._ModelBase.backward_and_apply releases the optimiser's early piece onto a second stream there."""
-    assert defer_sums is None or prepare is None
-    pending = []   # slab sums of all layers of this part: one launch at the end
-    # conv7's input gradient and conv7's / conv8's filter gradients need only conv8's input gradient: one grid for the three
-    pair_top = (hi == 7 and lo <= 6 and not self.split_top
-                and self.layers[6]['stride'] == self.layers[7]['stride'] == 2)
-    if lead_dgrad is not None:
-      self.launch_dgrad(lead_dgrad, pending)
-    for l in range(hi, lo - 1, -1):
-      if pair_top and l == 7:
-        self.launch_dgrad(7, pending)
-        continue
-      if pair_top and l == 6:
-        if self.launch_top_bwd(6, (6, 7), pending):
-          continue
+  # -- the backward in two halves: every launch appends its deferred slab sum to ``pending``, graph._ModelBase.backward launches them
+
+  def backward_upper(self, pending):
+    """Expects ``self.dz[7]`` = d(loss)/d(pre-activation of conv8) (ReluGrad already applied).  conv8 .. conv(SPLIT+1), the last
+    one's input gradient left to ``backward_bottom``."""
+    first = 7
+    if self.top_one_grid:
+      self.launch_dgrad(7, pending)
+      if not self.launch_top_bwd(6, (6, 7), pending):
         if not self.launch_wgrad_top_pair(pending):
           self.launch_wgrad(7, pending)
           self.launch_wgrad(6, pending)
         self.launch_dgrad(6, pending)
-        continue
+      first = 5
+    for l in range(first, self.SPLIT, -1):
       self.launch_wgrad(l, pending)
-      if l == 0 or (l == lo and defer_dgrad):
-        break   # conv1's input is data: no dgrad / the next part opens with this layer's
+      self.launch_dgrad(l, pending)
+    self.launch_wgrad(self.SPLIT, pending)
+
+  def backward_bottom(self, pending, before_bottom=None):
+    """conv(SPLIT+1)'s input gradient, then conv(SPLIT) .. conv1 (whose input is data: no input gradient).  ``before_bottom(pending)``
+    is called right in front of the LAST big launch of the chain, conv2's input gradient (+ conv1's filter gradient when the bottom
+    is fused) -- graph.BesideBottom releases side work there."""
+    self.launch_dgrad(self.SPLIT, pending)
+    for l in range(self.SPLIT - 1, 0, -1):
+      self.launch_wgrad(l, pending)
       if l == 1 and before_bottom is not None:
         before_bottom(pending)
       self.launch_dgrad(l, pending)
-      if l == 1 and self.fused_bottom:
-        break
-    if defer_sums is not None:
-      defer_sums.extend(pending)
-      return
-    if pending or prepare is not None:
-      ops.slab_reduce_batch(pending, prepare)
-
-  # backward(part='upper') = layers 7..SPLIT, 'bottom' = SPLIT-1..0, which opens with layer SPLIT's INPUT gradient (round 4 cut after it)
-  SPLIT = 2
+    self.launch_wgrad(0, pending)

@@ -19,6 +19,8 @@ predictors' ``E2EVMCStep`` / ``GoalE2EVMCStep`` in step_models.py.
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 
 from . import ops
@@ -26,6 +28,46 @@ from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
 from .variables import _CELLS, VariableStore, model_variable_shapes
+
+
+class BesideBottom:
+  """The hand-off in front of the fused encoder bottom, the last and longest launch of the backward, which leaves room on every CU for
+  streaming work (finding 38; numbers: ``_ModelBase.backward_and_apply``).  Use: ``run_bottom(bottom)``, the side work under ``with
+  side_work():`` (the model's optimiser stream), ``join()``.  ``run_bottom`` calls ``bottom(before_bottom)`` and records an event on
+  the main stream when conv2's filter gradient has been launched: everything before it, conv3's input gradient too (the last reader
+  of a variable of the optimiser's early piece, conv3's kernel), precedes the event; released any earlier the side work could not
+  co-reside (conv2's filter gradient and conv3's input gradient fill the register file) but would start first and delay them.  With
+  ``sums`` (a list) the pending slab sum of that filter gradient moves there, to run with the side work: only conv1's stays behind
+  the bottom.  A bottom without such a launch marks behind its chain (nothing to hide behind).
+  The side work is launched BEHIND the fused bottom (and waits for the event, recorded in front of it): the bottom's packet is the
+  older one, its 256 persistent blocks take their CUs first, and the streaming blocks then fill what those leave, one per CU at a
+  time.  Issued in front of it (hipGraph replays nodes in creation order) the streaming blocks take the wave slots first, the
+  bottom's block cannot become resident on a CU until they have drained, and the bottom ends 35-45 us late (measured)."""
+
+  def __init__(self, model, sums=None):
+    self.side, self.main = model.optimizer_stream(), torch.cuda.current_stream()
+    self.sums, self.event, self.marked = sums, torch.cuda.Event(), False
+
+  def _mark(self, pending=None):
+    self.event.record(self.main)
+    if pending and self.sums is not None:
+      self.sums.extend(pending)
+      del pending[:]
+    self.marked = True
+
+  def run_bottom(self, bottom):
+    bottom(self._mark)
+    if not self.marked:
+      self._mark()
+
+  @contextlib.contextmanager
+  def side_work(self):
+    self.side.wait_event(self.event)
+    with torch.cuda.stream(self.side):
+      yield
+
+  def join(self):
+    self.main.wait_stream(self.side)
 
 
 class _ModelBase:
@@ -194,18 +236,26 @@ class _ModelBase:
     """part None = whole backward; 'upper' / 'bottom' = the two halves the data-parallel runner captures
     separately (runtime.py): everything down to conv3, then the encoder bottom (conv2 / conv1).  ``adam_prepare``: see
     _prepare_args (the optimiser's scalars ride in the slab-sum launch of the part it is passed to -- once per step).
-    ``defer_sums`` (part 'upper') / ``before_bottom`` (part 'bottom'): ConvEncoderStack.backward, used by backward_and_apply."""
-    S = ConvEncoderStack.SPLIT
-    if part == 'bottom':
-      self.enc.backward(hi=S - 1, lo=0, prepare=self._prepare_args(adam_prepare), lead_dgrad=S, before_bottom=before_bottom)
-      return
-    if self.shared_frames is not None:
-      self.decoder.backward()
-      self._scatter_shared()
-    else:
-      self._decoder_backward()      # ... down to the encoders' feature gradients
-    self.enc.backward(hi=7, lo=S if part == 'upper' else 0, defer_dgrad=part == 'upper',
-                      prepare=self._prepare_args(adam_prepare and defer_sums is None), defer_sums=defer_sums if part == 'upper' else None)
+    ``defer_sums`` (a list, part 'upper'): the part's pending slab sums are handed to the caller instead of launched (no
+    ``adam_prepare`` then); ``before_bottom`` (part 'bottom'): ConvEncoderStack.backward_bottom.  Both are BesideBottom's."""
+    pending = []      # the slab sums of every layer of this call: ONE launch at the end
+    if part != 'bottom':
+      if self.shared_frames is not None:
+        self.decoder.backward()
+        self._scatter_shared()
+      else:
+        self._decoder_backward()      # ... down to the encoders' feature gradients
+      self.enc.backward_upper(pending)
+      if defer_sums is not None:
+        if part == 'upper':
+          defer_sums.extend(pending)
+          return
+        adam_prepare = False
+    if part != 'upper':
+      self.enc.backward_bottom(pending, before_bottom if part == 'bottom' else None)
+    prepare = self._prepare_args(adam_prepare)
+    if pending or prepare is not None:
+      ops.slab_reduce_batch(pending, prepare)
 
   def _bind_labels(self):
     K, inp = self.K, self.inputs
@@ -264,9 +314,11 @@ class _ModelBase:
     """The second stream of backward_and_apply: the first of the training encoder's two streams (a process gets 4 hardware queues
     by default; a stream more would share one with another stream -- RCCL's, perhaps)."""
     if self._opt_stream is None:
-      sides = getattr(self.enc, 'sides', None)
-      self._opt_stream = sides[0] if sides else torch.cuda.Stream(device=self.store.params.device)
+      self._opt_stream = self.enc.sides[0] if self.enc.sides else torch.cuda.Stream(device=self.store.params.device)
     return self._opt_stream
+
+  def bottom_handoff(self, sums=None):
+    return BesideBottom(self, sums)
 
   def backward_and_apply(self, early, late):
     """Backward + optimiser step of a single-GPU training step with the optimiser's HBM-streaming work hidden beside the fused
@@ -280,38 +332,18 @@ class _ModelBase:
     The fused bottom holds two 209-VGPR waves per SIMD and 151 KB of LDS: 80 registers per lane and 9 KB of LDS stay free on every
     CU, room for one block of the slab sums (55 VGPRs, 4 KB) or of Adam (51 VGPRs) at a time, and the bottom moves 1.1 TB/s of the
     8 the HBM has.  Beside it the 35 + 33 us of streaming work take 190 + 155 us and end long before its 455 us are over, which
-    stay 455.  Order matters twice: released any earlier the side work could not co-reside (conv2's filter gradient and conv3's
-    input gradient fill the register file) but would start first and delay them -- and `*` is behind conv3's input gradient, the
-    last reader of a variable of the early piece (conv3's kernel); and the side launches are issued BEHIND the bottom's (see
-    below).  Element by element the arithmetic of backward(adam_prepare=True) + apply_gradients(): bitwise the same parameters,
-    slots and gradients (tests/test_model_gpu.py)."""
-    side = self.optimizer_stream()
-    main = torch.cuda.current_stream()
-    sums = []
+    stay 455.  Where `*` sits and that the side launches are issued behind the bottom's: BesideBottom.  Element by element the
+    arithmetic of backward(adam_prepare=True) + apply_gradients(): bitwise the same parameters, slots and gradients
+    (tests/test_model_gpu.py)."""
+    g, sums = self.store.grads, []
+    h = self.bottom_handoff(sums)
     self.backward(part='upper', defer_sums=sums)
     prepare = self._prepare_args(True)
-    g = self.store.grads
-    ev = torch.cuda.Event()
-    marked = []
-
-    def mark(pending=None):      # conv2's filter gradient has been launched: everything before it (conv3's input gradient too) precedes `ev`
-      ev.record(main)
-      if pending:                # ... and its slab sum joins the ones that run beside the bottom: only conv1's stays behind it
-        sums.extend(pending)
-        del pending[:]
-      marked.append(True)
-    self.backward(part='bottom', before_bottom=mark)
-    if not marked:       # (an encoder whose chain has no conv2 input gradient: nothing to hide behind)
-      mark()
-    # The side work is launched BEHIND the fused bottom (and waits for `ev`, recorded in front of it): the bottom's packet is the
-    # older one, its 256 persistent blocks take their CUs first, and the streaming blocks then fill what those leave, one per CU
-    # at a time.  Issued in front of it (hipGraph replays nodes in creation order) the streaming blocks take the wave slots first,
-    # the bottom's block cannot become resident on a CU until they have drained, and the bottom ends 35-45 us late (measured).
-    side.wait_event(ev)
-    with torch.cuda.stream(side):
+    h.run_bottom(lambda mark: self.backward(part='bottom', before_bottom=mark))
+    with h.side_work():
       ops.slab_reduce_batch(sums, prepare)
       self.apply_gradients_of([(g[off:off + n], off, n) for off, n in early], last=False)
-    main.wait_stream(side)
+    h.join()
     self.apply_gradients_of([(g[off:off + n], off, n) for off, n in late], last=True)
 
   def _refresh_after_update(self):

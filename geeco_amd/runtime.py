@@ -18,6 +18,7 @@ The Adam step counter and lr_t live in device memory, so replays advance them co
 """
 from __future__ import annotations
 
+import contextlib
 import re
 import threading
 
@@ -58,6 +59,18 @@ def gradient_buckets(store):
   if store.size > pos:
     early.append((pos, store.size - pos))
   return early, [(lo, hi - lo) for lo, hi in late]
+
+
+def capture_graphs(parts):
+  """Each callable of ``parts`` captured into a hipGraph of its own; returns the graphs' ``replay`` methods.  (Capture does not execute.)"""
+  replays = []
+  with CAPTURE_LOCK:
+    for fn in parts:
+      g = torch.cuda.CUDAGraph()
+      with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
+        fn()
+      replays.append(g.replay)
+  return replays
 
 
 class CaptureFailed(RuntimeError):
@@ -105,7 +118,7 @@ class TrainStepRunner:
     if self.dp and self.late:
       store = model.store
       # one staging buffer per variable store: models built for other batch sizes (ragged last batch) share it
-      if getattr(store, 'late_staging', None) is None:
+      if store.late_staging is None:
         store.late_staging = torch.zeros(sum(n for _, n in self.late), dtype=torch.float32, device=store.grads.device)
       self.staging = store.late_staging
       # The bottom of the backward writes the conv1 / conv2 gradients STRAIGHT into the staging buffer (no pack copies),
@@ -163,21 +176,23 @@ class TrainStepRunner:
       self.model.redirect_late_gradients(self.staging, self.late)
     if enc is not None and self.reserved_cus:
       enc.reserved_cus = self.reserved_cus
-    try:
-      if before_bottom is None:
-        self.model.backward(part='bottom', adam_prepare=prepare)
-      else:
-        self.model.backward(part='bottom', adam_prepare=prepare, before_bottom=before_bottom)
+    try:      # (before_bottom: only a model that has bottom_handoff is ever passed one)
+      self.model.backward(part='bottom', adam_prepare=prepare, **({} if before_bottom is None else dict(before_bottom=before_bottom)))
     finally:
       if enc is not None:
         enc.reserved_cus = 0
       if self.redirected:
         self.model.redirect_late_gradients(None, None)
-    if self.redirected or self.staging is None:
-      return
-    g, pos = self.model.store.grads, 0
+    if not self.redirected and self.staging is not None:      # (a model that cannot redirect: pack copies)
+      g = self.model.store.grads
+      for packed, off, n in self._late_staged():
+        packed.copy_(g[off:off + n])
+
+  def _late_staged(self):
+    """(staging slice, arena offset, length) of every late range: the staging buffer holds the ranges back to back."""
+    pos = 0
     for off, n in self.late:
-      self.staging[pos:pos + n].copy_(g[off:off + n])
+      yield self.staging[pos:pos + n], off, n
       pos += n
 
   def _part3_early(self):
@@ -185,18 +200,13 @@ class TrainStepRunner:
     self.model.apply_gradients_of([(g[off:off + n], off, n) for off, n in self.early], last=False)
 
   def _part3_late(self):
-    segs, pos = [], 0
-    for off, n in self.late:
-      segs.append((self.staging[pos:pos + n], off, n))
-      pos += n
-    self.model.apply_gradients_of(segs, g_out=self.model.store.grads, last=True)     # (the gradient arena gets them too)
+    self.model.apply_gradients_of(list(self._late_staged()), g_out=self.model.store.grads, last=True)     # (the gradient arena gets them too)
 
   def _part3(self):
     if self.dp and self.staging is not None:
-      g, pos = self.model.store.grads, 0
-      for off, n in self.late:
-        g[off:off + n].copy_(self.staging[pos:pos + n])
-        pos += n
+      g = self.model.store.grads
+      for packed, off, n in self._late_staged():
+        g[off:off + n].copy_(packed)
     self.model.apply_gradients()
 
   def _whole_step(self):
@@ -226,29 +236,26 @@ class TrainStepRunner:
     optimiser's scalars ride in the slab-sum launch of part 1 (they must exist before the early piece).  If the bucket is late the
     early piece simply runs when it arrives -- behind the bottom at worst, where it used to be."""
     m = self.model
-    main = torch.cuda.current_stream()
-    side = m.optimizer_stream()
+    h = m.bottom_handoff()
     m.forward(backward_too=True)
     m.backward(part='upper', adam_prepare=True)
     works = self._exchange_early()
-    ev = torch.cuda.Event()
-    marked = []
-
-    def mark(pending=None):
-      ev.record(main)
-      marked.append(True)
-    self._part2(prepare=False, before_bottom=mark)
-    if not marked:
-      mark()
+    h.run_bottom(lambda mark: self._part2(prepare=False, before_bottom=mark))
     late = self._exchange_late()           # (issued before the side work: its launch is on the critical path, the early piece is not)
-    side.wait_event(ev)                    # behind conv3's input gradient (reads conv3's kernel) and behind the bottom's launch packet
-    with torch.cuda.stream(side):
+    self._apply_as_they_arrive(works, late, h)
+
+  def _apply_as_they_arrive(self, works, late, handoff=None):
+    """The optimiser step in two pieces: wait for the early bucket (the compute stream waits; the host does not -- RCCL), apply the
+    early piece, 99 % of the update, beside the late bucket's all-reduce; wait for that, apply the late piece.  ``handoff``
+    (graph.BesideBottom): the early half is the side work beside the backward's bottom."""
+    with handoff.side_work() if handoff is not None else contextlib.nullcontext():
       for w in works:
         w.wait()
       self._part3_early()
     for w in late:
       w.wait()
-    main.wait_stream(side)
+    if handoff is not None:
+      handoff.join()
     self._part3_late()
 
   def _dp_step(self, run=None):
@@ -263,34 +270,15 @@ class TrainStepRunner:
     if not self.overlap:
       works = self._exchange_early()
     late = self._exchange_late()
-    if whole and self.split_adam:
-      for w in works:
-        w.wait()                           # the compute stream waits; the host does not (RCCL)
-      self._part3_early()                  # 99 % of the update, beside the late bucket's all-reduce
-      for w in late:
-        w.wait()
-      self._part3_late()
-      return
     if len(run) == 2:                      # two graphs + the optimiser's pieces launched eagerly (eager_adam)
       # part 2's graph carries the optimiser's per-step scalars (adam_prepare rides in its last slab-sum launch); a REPLAY runs no
       # python, so the flag that tells apply_gradients_of not to prepare again is set here
       self.model._prepared = True
-      for w in works:
-        w.wait()
-      self._part3_early()                  # beside the late bucket's all-reduce
-      for w in late:
-        w.wait()
-      self._part3_late()
-      return
+    if len(run) == 2 or (whole and self.split_adam):
+      return self._apply_as_they_arrive(works, late)
     for w in works + late:
       w.wait()
     run[2]()
-
-  def _part3_pieces(self):
-    """Part 3 of the three-graph form: the optimiser step as the same two pieces the one-pass forms use, back to back (both buckets have
-    arrived by then) -- conv1 / conv2 are updated from the staging buffer, so the three unpack copies of ``_part3`` are not launched."""
-    self._part3_early()
-    self._part3_late()
 
   def _parts(self):
     if not self.dp:
@@ -299,20 +287,13 @@ class TrainStepRunner:
       return [self._dp_step]
     if self.eager_adam and self.split_adam:
       return [self._part1, self._part2]
-    return [self._part1, self._part2, self._part3_pieces if self.split_adam else self._part3]
+    # part 3 of the three-graph form: the optimiser step as the same two pieces the one-pass forms use, back to back (both buckets have
+    # arrived by then) -- conv1 / conv2 are updated from the staging buffer, so the three unpack copies of ``_part3`` are not launched
+    return [self._part1, self._part2, (lambda: self._apply_as_they_arrive((), ())) if self.split_adam else self._part3]
 
   def _capture(self):
     # the warm-up steps before this call already ran eagerly
     # single process: the whole step is one graph (no inter-graph launch gap); data parallel: the exchange sits between
-    def capture(parts):
-      graphs = []
-      with CAPTURE_LOCK:
-        for fn in parts:
-          g = torch.cuda.CUDAGraph()
-          with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-            fn()
-          graphs.append(g.replay)
-      return graphs
     if self.dp and self.capture_exchange and gdist.group_active() and gdist.backend() != 'nccl':
       # Decided BEFORE anything is captured: only RCCL's launches are stream work a hipGraph can hold; any other backend's
       # collective on a device tensor (gloo: copies through the host, stream synchronisation) cannot be captured, and an attempt
@@ -333,7 +314,7 @@ class TrainStepRunner:
       # training script exits non-zero and is restarted with --dp_form three_graphs.  Nothing was executed by the attempt.
       orig = torch.cuda.current_stream()
       try:
-        self._graphs = capture(self._parts())
+        self._graphs = capture_graphs(self._parts())
       except RuntimeError as e:
         torch.cuda.set_stream(orig)
         self.model._prepared = False
@@ -341,7 +322,7 @@ class TrainStepRunner:
                             'leaves the streams of a failed capture in capture mode, so this process cannot capture or launch on '
                             'them again: restart with a three_graphs* form (three_graphs_reserve16 is the default)' % (type(e).__name__, str(e)[:300])) from e
       return
-    self._graphs = capture(self._parts())
+    self._graphs = capture_graphs(self._parts())
 
   def prepare(self):
     """Untimed set-up for benchmarks: run the eager warm-up steps and capture the graphs now, so that
@@ -459,13 +440,9 @@ class EvalStepRunner:
 
   def step(self):
     if self.use_graph and self._g is None and self._calls >= self._warm:
-      g = torch.cuda.CUDAGraph()
-      with CAPTURE_LOCK:
-        with torch.cuda.graph(g, capture_error_mode=_CAPTURE_MODE):
-          self.model.forward(backward_too=False)
-      self._g = g
+      self._g = capture_graphs([lambda: self.model.forward(backward_too=False)])[0]
     self._calls += 1
     if self._g is not None:
-      self._g.replay()
+      self._g()
     else:
       self.model.forward(backward_too=False)

@@ -122,6 +122,7 @@ class VariableStore:
     self.global_step = torch.zeros(1, dtype=torch.int64, device=self.device)
     self.version = 0      # bumped whenever the parameters are (re)written from the host side
     self.primary_stack = None     # the first training ConvEncoderStack built on this store (encoder.py: lazy_refresh)
+    self.late_staging = None      # data parallel: the conv1 / conv2 gradients on their way to the exchange (runtime.TrainStepRunner)
 
   # -- views ------------------------------------------------------------------------------
   def _view(self, arena, name):

@@ -617,3 +617,18 @@ def test_encoder_and_decoder_import_neither_graph_nor_each_other(module):
   other = 'geeco_amd.decoder' if module.endswith('encoder') else 'geeco_amd.encoder'
   code = "import sys, %s; sys.exit(int('geeco_amd.graph' in sys.modules or %r in sys.modules))" % (module, other)
   assert subprocess.run([sys.executable, '-c', code], cwd=root).returncode == 0
+
+
+def test_eval_encoder_stack_has_every_flag_false_or_empty():
+  """The training-only decisions of ConvEncoderStack exist on every stack, so no reader has to probe for them."""
+  from geeco_amd.encoder import ConvEncoderStack
+  from geeco_amd.params import create_e2evmc_config
+  from geeco_amd.variables import VariableStore, model_variable_shapes
+  assert ConvEncoderStack.SPLIT == 2
+  cfg = create_e2evmc_config(dict(window_size=2, img_height=130, img_width=130))
+  store = VariableStore(model_variable_shapes(cfg, False), 'cpu')
+  enc = ConvEncoderStack(store, ['VMC/ConvEncoder'], 1, 130, 130, 3, 256, training=False)
+  for flag in ('fused_bottom', 'relu_bits', 'relu_fields', 'relu_fields3'):
+    assert getattr(enc, flag) is False, flag
+  assert not any(enc.needs_wt) and enc.sides == [] and not enc.training and store.primary_stack is None
+  assert not hasattr(enc, 'ws')
