@@ -142,6 +142,8 @@ SIGNATURES = {
     'geeco_adam_prepare': (_I, [_P, _F, _F, _F, _P, _P]),
     'geeco_adam_tf': (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _P]),
     'geeco_adam_tf_segments': (_I, [_P, _P, _P, _P, _P, _I, _P, _F, _F, _F, _F, _F, _P]),
+    'geeco_adam_tf_ema': (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _F, _F, _F, _F, _F, _F, _P]),
+    'geeco_adam_tf_segments_ema': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _F, _F, _F, _P]),
     'geeco_sumsq': (_I, [_P, _L, _P, _P]),
 }
 

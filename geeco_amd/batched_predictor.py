@@ -81,7 +81,8 @@ class _BatchedPredictorBase:
   _goal = False
 
   def __init__(self, model_dir, num_envs, checkpoint_name=None, memcap=0.8, device=None, frame_dtype='float32',
-               debug_images=False, incremental=False):
+               debug_images=False, incremental=False, use_ema=False):
+    """``use_ema``: run the checkpoint's averaged weights (a training run with params['ema_decay']); KeyError if it holds none."""
     B = int(num_envs)
     if B < 1:
       raise ValueError('num_envs must be >= 1, got %d' % B)
@@ -122,7 +123,7 @@ class _BatchedPredictorBase:
     with torch.cuda.device(dev):
       # the per-frame controllers' K-step decoder as one launch (geeco-f runs T = 1: its decoder ignores the argument)
       m = self._model = ctor(cfg, B, dev, training=False, one_launch_decoder=True)
-      est.restore_for_inference(m.store, model_dir, checkpoint_name)
+      est.restore_for_inference(m.store, model_dir, checkpoint_name, use_ema=use_ema)
       # uint8 frames on a model whose input kernel reads uint8 windows: the mirrored ring (no fp32 window is ever written)
       self._ring = self._u8 and not self._incremental and 'rgb' in m.u8_window_keys
       self._make_staging_block()

@@ -72,11 +72,16 @@ def group_active() -> bool:
   return dist.is_available() and dist.is_initialized()
 
 
+def _replicated_arenas(store):
+  """What every replica holds bitwise alike: parameters, Adam slots and, where kept, the averaged weights."""
+  return [store.params, store.adam_m, store.adam_v] + ([store.ema] if getattr(store, 'ema', None) is not None else [])
+
+
 def broadcast_variables(store, src=0):
   """Every replica starts from rank 0's weights and optimiser state."""
   if world_size() == 1:
     return
-  for t in (store.params, store.adam_m, store.adam_v, store.global_step):
+  for t in _replicated_arenas(store) + [store.global_step]:
     dist.broadcast(t, src=src)
   store.version += 1
 
@@ -144,7 +149,7 @@ def replicas_identical(store) -> bool:
   independent, computed on the device), gathered over the ranks; one small collective."""
   if world_size() == 1:
     return True
-  sums = torch.stack([t.detach().view(torch.int32).sum(dtype=torch.int64) for t in (store.params, store.adam_m, store.adam_v)] +
+  sums = torch.stack([t.detach().view(torch.int32).sum(dtype=torch.int64) for t in _replicated_arenas(store)] +
                      [store.global_step.detach().reshape(-1)[0].to(torch.int64)])
   sums = sums.to(_coll_device(store.params.device))
   out = [torch.zeros_like(sums) for _ in range(world_size())]

@@ -28,6 +28,8 @@ from . import feed
 from . import graph
 from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
+from .tf_checkpoint import EMA_SUFFIX
+from .variables import check_ema_decay
 
 
 class ModeKeys:
@@ -135,18 +137,25 @@ def load_checkpoint(store, prefix):
     tf_checkpoint.import_checkpoint(store, prefix, load_optimizer=True)
 
 
-def restore_for_inference(store, model_dir, checkpoint_name=None):
+def restore_for_inference(store, model_dir, checkpoint_name=None, use_ema=False):
   """The predictors' restore (predictor.py:85-95): the named checkpoint, else the latest one of the directory -- a native
-  .pt file, or a TensorFlow-1.15 tensor bundle (e.g. the published geeco_models_icra21 weights).  Parameters only."""
+  .pt file, or a TensorFlow-1.15 tensor bundle (e.g. the published geeco_models_icra21 weights).  Parameters only.
+  ``use_ema``: the parameters are the checkpoint's averaged weights (params['ema_decay'] of the training run); KeyError naming the
+  first missing tensor if it holds none."""
   ckpt = os.path.join(model_dir, checkpoint_name) if checkpoint_name else latest_checkpoint(model_dir)
   if ckpt is None:
     raise FileNotFoundError('no checkpoint in %s' % model_dir)
-  if os.path.exists(ckpt + '.pt'):
+  if os.path.exists(ckpt + '.pt') and use_ema:
+    sd = torch.load(ckpt + '.pt', map_location='cpu')
+    if sd.get('ema') is None:
+      raise KeyError('%s%s: checkpoint %s.pt holds no averaged weights' % (list(sd['names'])[0], EMA_SUFFIX, ckpt))
+    store.load_state_dict(dict(sd, params=sd['ema']))
+  elif os.path.exists(ckpt + '.pt'):
     load_checkpoint(store, ckpt)
   else:
     from . import tf_checkpoint
-    tf_checkpoint.import_checkpoint(store, ckpt, load_optimizer=False)
-  print('>>> Restored model parameters from %s' % (ckpt,))
+    tf_checkpoint.import_checkpoint(store, ckpt, load_optimizer=False, use_ema=use_ema)
+  print('>>> Restored model parameters from %s%s' % (ckpt, ' (averaged weights)' if use_ema else ''))
 
 
 # ================================================================================================
@@ -206,6 +215,16 @@ def _model_fn(features, labels, mode, params, goal):
   N = int(rgb.shape[0])
   training = mode == ModeKeys.TRAIN
   ctor = graph.GoalE2EVMC if goal else graph.E2EVMC
+  # params['ema_decay']: the store carries the shadow arena, the training step keeps it, and every other mode's model
+  # is built on the store's shadow view -- its parameters ARE the averaged weights (an inference stack re-derives its weight
+  # copies from them on every forward)
+  decay = check_ema_decay(params.get('ema_decay'), "params['ema_decay']")
+  store = params.get('_variable_store')
+  if decay is not None:
+    store = store or graph.build_store(cfg, goal, rgb.device, ema=True)
+    if not training:
+      store = store.shadow_view()
+  ema = dict(ema_decay=decay) if training else {}
   shared = params.get('shared_frames')
   tables = {}
   if shared:
@@ -217,13 +236,13 @@ def _model_fn(features, labels, mode, params, goal):
       raise ValueError("params['shared_frames'] needs the windows as DeviceWindows (pickplace_input_fn(device='cuda')): "
                        "dense 'rgb' tensors hold every frame K times and no frame addresses")
     F = shared_frames_capacity(shared, N, cfg.window_size, goal)
-    model = ctor(cfg, N, rgb.device, training=training, store=params.get('_variable_store'), shared_frames=F)
+    model = ctor(cfg, N, rgb.device, training=training, store=store, shared_frames=F, **ema)
     tables = rgb.frame_table(F, with_targets=goal)
     model.frames_u8 = rgb.u8
     for k, v in tables.items():
       model.inputs[k] = v
   else:
-    model = ctor(cfg, N, rgb.device, training=training, store=params.get('_variable_store'))
+    model = ctor(cfg, N, rgb.device, training=training, store=store, **ema)
   # adopt the caller's static buffers as the model inputs (placeholders)
   source = lambda k: labels.get(k) if (labels is not None and k in model.label_keys) else features.get(k)
   # all of the model's image inputs that CAN come as window addresses must, or none does
@@ -313,6 +332,7 @@ class Estimator:
     self.model_dir = model_dir
     self.config = config or RunConfig()
     self.params = dict(params or {})
+    check_ema_decay(self.params.get('ema_decay'), "params['ema_decay']")
     self._specs = {}          # (mode, N) -> (spec, feature buffers, label buffers)
     self.last_train_stats = None
     self._store = None
@@ -405,7 +425,7 @@ class Estimator:
     spec = self._model_fn(fbuf, lbuf, mode, params)
     spec.model.decoder.loss_scale = float(loss_scale)
     if self._store is None:
-      self._store = spec.model.store
+      self._store = spec.model.store.base      # (an eval / predict model of a run with ema_decay sits on the shadow view)
       self._store.initialize(seed=self.config.init_seed)
     self._restore_once()
     self._specs[key] = (spec,) + feed.adopted_slots(fbuf, lbuf, spec.model.inputs)

@@ -27,7 +27,14 @@ from . import ops
 from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
-from .variables import _CELLS, VariableStore, model_variable_shapes
+from .variables import _CELLS, VariableStore, check_ema_decay, model_variable_shapes
+
+
+def build_store(cfg, goal, device, ema=False):
+  """The variable store of a model: TF's creation order, the encoders' blocks at a common stride; ``ema``: with the shadow arena."""
+  shapes = model_variable_shapes(cfg, goal)
+  encoder_scopes = sorted({n.split('/conv')[0] for n in shapes if '/conv' in n}, key=lambda sc: list(shapes).index(sc + '/conv1/kernel'))
+  return VariableStore(shapes, device, uniform_scopes=encoder_scopes, ema=ema)
 
 
 class BesideBottom:
@@ -73,16 +80,20 @@ class BesideBottom:
 class _ModelBase:
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
-  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None):
+  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
+    self.ema_decay = check_ema_decay(ema_decay)
     self.shared_frames = self._check_shared_frames(cfg, goal, shared_frames)
     self.device = torch.device(device)
     self.K = cfg.window_size
     self.H, self.W, self.C = cfg.img_height, cfg.img_width, cfg.img_channels
     check_image_size(self.H, self.W)
-    shapes = model_variable_shapes(cfg, goal)
-    encoder_scopes = sorted({n.split('/conv')[0] for n in shapes if '/conv' in n}, key=lambda sc: list(shapes).index(sc + '/conv1/kernel'))
-    self.store = store or VariableStore(shapes, self.device, uniform_scopes=encoder_scopes)
+    self.store = store or build_store(cfg, goal, self.device, ema=self.ema_decay is not None)
+    if training and (self.ema_decay is None) != (self.store.ema is None):
+      # the store decides which optimiser entry point runs (apply_gradients / apply_gradients_of): one that keeps averaged weights needs the
+      # decay, and a decay without the arena would silently average nothing
+      raise ValueError('ema_decay=%r, but the VariableStore %s (VariableStore(ema=True) goes with a decay in (0, 1))'
+                       % (ema_decay, 'keeps no averaged weights' if self.store.ema is None else 'keeps averaged weights'))
     f32 = dict(dtype=torch.float32, device=self.device)
     N, K, H, W = self.N, self.K, self.H, self.W
     F = self.shared_frames
@@ -292,18 +303,22 @@ class _ModelBase:
     """The optimiser step of SOME pieces of the arena (``ops.adam_tf_segments``; data parallel: everything that came with the early
     bucket first, the late bucket's variables when it has arrived).  ``last``: the pieces complete the step (weight copies are
     re-derived behind it)."""
-    s, cfg = self.store, self.cfg
+    s, kw = self.store, dict(g_out=g_out, grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
     self._prepare_unless_done(last)
-    ops.adam_tf_segments(s.params, s.adam_m, s.adam_v, segments, self.scal, g_out=g_out, grad_scale=1.0 / self.world,
-                         l2=float(cfg.l2_regularizer))
+    if s.ema is not None:      # the averaged weights follow in the same launch (DESIGN 5.15)
+      ops.adam_tf_segments_ema(s.params, s.adam_m, s.adam_v, s.ema, segments, self.scal, s.global_step, self.ema_decay, **kw)
+    else:
+      ops.adam_tf_segments(s.params, s.adam_m, s.adam_v, segments, self.scal, **kw)
     if last:
       self._refresh_after_update()
 
   def apply_gradients(self):
-    s, cfg = self.store, self.cfg
+    s, kw = self.store, dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
     self._prepare_unless_done()
-    ops.adam_tf(s.params, s.grads, s.adam_m, s.adam_v, s.size, self.scal, grad_scale=1.0 / self.world,
-                l2=float(cfg.l2_regularizer))
+    if s.ema is not None:
+      ops.adam_tf_ema(s.params, s.grads, s.adam_m, s.adam_v, s.ema, s.size, self.scal, s.global_step, self.ema_decay, **kw)
+    else:
+      ops.adam_tf(s.params, s.grads, s.adam_m, s.adam_v, s.size, self.scal, **kw)
     self._refresh_after_update()
 
   def can_apply_beside_bottom(self):
@@ -393,9 +408,9 @@ class _ModelBase:
 class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None):
-    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only): see E2EVMC."""
-    super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames)
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None):
+    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``: see E2EVMC."""
+    super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -525,12 +540,15 @@ class GoalE2EVMC(_ModelBase):
 class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None):
-    """``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None):
+    """``ema_decay`` (a float in (0, 1); None / 0 = off): the optimiser step also keeps an exponential moving average of the
+    parameters in ``store.ema`` (tf.train.ExponentialMovingAverage with num_updates = global_step); a store passed in
+    must have been built with the arena (``build_store(..., ema=True)``).
+    ``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
     'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
-    super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames)
+    super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     self.window_mode, self.feat_ch = 'plain', [256]
     # frames are processed time-major ([K][N]) so that step t's features are one dense block

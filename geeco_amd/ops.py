@@ -680,10 +680,13 @@ def adam_tf(p, g, m, v, n, scal, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.
         'geeco_adam_tf')
 
 
-def adam_tf_segments(p, m, v, segments, scal, g_out=None, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
-  """``geeco_adam_tf_segments``: the Adam update of up to 8 pieces of the arena, ``segments`` = [(gradient tensor of the piece, offset
-  in the arena, count)], offsets / counts in floats and multiples of 4; ``g_out``: the gradient arena that also receives the pieces'
-  gradients (a piece whose source IS its place in that arena needs none)."""
+def adam_tf_ema(p, g, m, v, ema, n, scal, global_step, decay, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
+  """``geeco_adam_tf_ema``: adam_tf, and the shadow arena ``ema`` follows the new parameters in the same pass."""
+  check(_lib().geeco_adam_tf_ema(_p(p), _p(g), _p(m), _p(v), _p(ema), n, _p(scal), _p(global_step), decay, beta1, beta2, eps, grad_scale,
+                                 l2, _stream()), 'geeco_adam_tf_ema')
+
+
+def _adam_segments(segments):
   if not 1 <= len(segments) <= _native.ADAM_SEGMENTS_MAX:
     raise ValueError('adam_tf_segments: 1..%d pieces, got %d' % (_native.ADAM_SEGMENTS_MAX, len(segments)))
   arr = (_native.AdamSegment * len(segments))()
@@ -691,8 +694,24 @@ def adam_tf_segments(p, m, v, segments, scal, g_out=None, beta1=0.9, beta2=0.999
     if g.numel() < n:
       raise ValueError('adam_tf_segments: a piece of %d floats with %d gradients' % (n, g.numel()))
     a.g, a.p_off, a.count = _p(g), int(off), int(n)
+  return arr
+
+
+def adam_tf_segments(p, m, v, segments, scal, g_out=None, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
+  """``geeco_adam_tf_segments``: the Adam update of up to 8 pieces of the arena, ``segments`` = [(gradient tensor of the piece, offset
+  in the arena, count)], offsets / counts in floats and multiples of 4; ``g_out``: the gradient arena that also receives the pieces'
+  gradients (a piece whose source IS its place in that arena needs none)."""
+  arr = _adam_segments(segments)
   check(_lib().geeco_adam_tf_segments(_p(p), _p(g_out), _p(m), _p(v), arr, len(segments), _p(scal), beta1, beta2, eps, grad_scale, l2,
                                       _stream()), 'geeco_adam_tf_segments')
+
+
+def adam_tf_segments_ema(p, m, v, ema, segments, scal, global_step, decay, g_out=None, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0,
+                         l2=0.0):
+  """``geeco_adam_tf_segments_ema``: adam_tf_segments, and the pieces' part of the shadow arena ``ema`` (indexed like ``p``) follows."""
+  arr = _adam_segments(segments)
+  check(_lib().geeco_adam_tf_segments_ema(_p(p), _p(g_out), _p(m), _p(v), _p(ema), arr, len(segments), _p(scal), _p(global_step), decay,
+                                          beta1, beta2, eps, grad_scale, l2, _stream()), 'geeco_adam_tf_segments_ema')
 
 
 def sumsq_into(out, p, n):

@@ -23,10 +23,10 @@ from .batched_predictor import TOL_FRAME_RANGE, BatchedE2EVMCPredictor, BatchedG
 class _PredictorBase:
   _core_cls = None
 
-  def __init__(self, model_dir, checkpoint_name=None, memcap=0.8, device=None, incremental=False):
+  def __init__(self, model_dir, checkpoint_name=None, memcap=0.8, device=None, incremental=False, use_ema=False):
     # one prediction at a time (predictor.py:56): cfg.batch_size == 1
     self._core = self._core_cls(model_dir, 1, checkpoint_name=checkpoint_name, memcap=memcap, device=device,
-                                frame_dtype='float32', debug_images=True, incremental=incremental)
+                                frame_dtype='float32', debug_images=True, incremental=incremental, use_ema=use_ema)
     self._model = self._core._model
 
   @property

@@ -16,7 +16,8 @@ Format [TF 1.15: core/util/tensor_bundle, core/lib/io/table (a LevelDB table)]:
   <prefix>.data-00000-of-00001   raw little-endian tensor bytes at (offset, size).
 Variable names: the model variables of SURVEY.md 8b, their Adam slots ``<var>/Adam`` (m) and
 ``<var>/Adam_1`` (v), ``beta1_power`` / ``beta2_power``, ``global_step`` (int64) and the unused
-``.../LSTMDecoder/lstm_memory`` (skipped on import exactly as predictor.py:87 does).
+``.../LSTMDecoder/lstm_memory`` (skipped on import exactly as predictor.py:87 does).  A store that keeps averaged weights
+writes each as ``<var>/ExponentialMovingAverage`` (tf.train.ExponentialMovingAverage's shadow-variable name) and reads them back.
 
 NOT VERIFIED AGAINST A TF-WRITTEN FILE: no TensorFlow and no checkpoint exist in this environment.  The tests cover
 writer -> reader round trips, a bundle assembled by hand from the documented table / proto layouts with an independent
@@ -31,6 +32,7 @@ import numpy as np
 
 from .tfrecord import _enc_varint, _fields, _varint, masked_crc32c
 
+EMA_SUFFIX = '/ExponentialMovingAverage'      # tf.train.ExponentialMovingAverage's name of a variable's shadow
 _MAGIC = 0xdb4775248b80fb57
 _BLOCK_SIZE = 4096
 _RESTART_INTERVAL = 16
@@ -213,17 +215,25 @@ def write_checkpoint(prefix, tensors: dict):
 # ------------------------------------------------------------------------------------------------
 # mapping to / from the variable store
 # ------------------------------------------------------------------------------------------------
-def import_checkpoint(store, prefix, load_optimizer=True):
-  """Fills ``store`` (parameters, and Adam slots / global_step when present) from a TF checkpoint."""
+def import_checkpoint(store, prefix, load_optimizer=True, use_ema=False):
+  """Fills ``store`` (parameters, and Adam slots / global_step when present) from a TF checkpoint.  The averaged weights
+  (``<var>/ExponentialMovingAverage``) go into a store that keeps them; a bundle without them leaves the shadow arena equal to the
+  parameters.  ``use_ema``: the PARAMETERS are filled from the averaged weights (KeyError naming the first missing tensor)."""
   import torch
   t = read_checkpoint(prefix)
+  if use_ema:
+    for n in store.shapes:
+      if n + EMA_SUFFIX not in t:
+        raise KeyError('%s: checkpoint %s holds no averaged weights' % (n + EMA_SUFFIX, prefix))
+    t.update({n: t[n + EMA_SUFFIX] for n in store.shapes})
   missing = [n for n in store.shapes if n not in t]
   if missing:
     raise KeyError('checkpoint %s lacks variables: %s' % (prefix, missing[:5]))
   for name, shp in store.shapes.items():
     if tuple(t[name].shape) != tuple(shp):
       raise ValueError('%s: checkpoint shape %s != model shape %s' % (name, t[name].shape, tuple(shp)))
-  store.load_numpy({n: t[n] for n in store.shapes})
+  shadows = {n: t[n + EMA_SUFFIX] for n in store.shapes if n + EMA_SUFFIX in t}
+  store.load_numpy({n: t[n] for n in store.shapes}, ema_values=shadows if len(shadows) == len(store.shapes) else None)
   if load_optimizer:
     for arena, suffix in ((store.adam_m, '/Adam'), (store.adam_v, '/Adam_1')):
       for name, shp in store.shapes.items():
@@ -242,6 +252,9 @@ def export_checkpoint(store, prefix, lstm_memory_name=None, batch_size=None, bet
   for name in store.shapes:
     tensors[name + '/Adam'] = m[name]
     tensors[name + '/Adam_1'] = v[name]
+  if store.ema is not None:
+    for name, val in store.to_numpy('ema').items():
+      tensors[name + EMA_SUFFIX] = val
   step = int(store.global_step.item())
   tensors['global_step'] = np.asarray(step, np.int64)
   tensors['beta1_power'] = np.asarray(beta1 ** (step + 1), np.float32)     # AdamOptimizer keeps beta^(t+1) after t updates

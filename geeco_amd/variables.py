@@ -3,7 +3,8 @@
 The reference keeps 60 ``tf.Variable``s (+ Adam slots) created by ``tf.layers`` under the scopes
 listed in SURVEY.md 8b.  Here all trainable variables live in ONE contiguous fp32 buffer in HBM
 (creation order = TF's), with three same-shaped siblings (gradient, Adam m, Adam v), so the
-optimiser is a single fused pass and data-parallel training all-reduces a single bucket.
+optimiser is a single fused pass and data-parallel training all-reduces a single bucket.  A fourth
+sibling is opt-in: ``ema``, the exponential moving average of the parameters the same pass keeps.
 Each variable starts on a 16-byte boundary (float4 loads in the conv kernels); the few pad floats
 are zero and stay zero under Adam (g = 0).
 """
@@ -11,6 +12,7 @@ from __future__ import annotations
 
 import collections
 import math
+import numbers
 
 import numpy as np
 import torch
@@ -85,13 +87,30 @@ def model_variable_shapes(cfg, goal: bool):
   return s
 
 
+def check_ema_decay(value, key='ema_decay'):
+  """The decay of the shadow weights: None or 0 = off (returns None), else a float in (0, 1); anything else raises ValueError
+  naming ``key``."""
+  if value is None or (isinstance(value, numbers.Real) and value == 0):
+    return None
+  if isinstance(value, bool) or not isinstance(value, numbers.Real) or not 0.0 < float(value) < 1.0:
+    raise ValueError('%s=%r: the decay of the averaged weights must lie in (0, 1) (None or 0 = off)' % (key, value))
+  return float(value)
+
+
+def ema_decay_at(decay, t):
+  """d_t = min(decay, (1 + t) / (10 + t)) in float32, as the Adam kernels compute it from the device's step counter."""
+  t = np.float32(t)
+  return min(np.float32(decay), (np.float32(1) + t) / (np.float32(10) + t))
+
+
 class VariableStore:
   """Named views into flat param / grad / Adam arenas."""
 
   ALIGN = 4   # floats
 
-  def __init__(self, shapes, device, uniform_scopes=None):
-    """``uniform_scopes``: scope prefixes (the encoders of one model) whose variable blocks must start at a COMMON
+  def __init__(self, shapes, device, uniform_scopes=None, ema=False):
+    """``ema``: also hold the shadow arena ``ema`` (same size, alignment and device), the exponential moving average of the
+    parameters that the optimiser's EMA entry points keep; it starts equal to the parameters.  ``uniform_scopes``: scope prefixes (the encoders of one model) whose variable blocks must start at a COMMON
     stride, so that one grouped launch can address encoder g at base + g * stride.  Blocks of equal size (the default
     dim_s_obs == dim_s_dyn == dim_s_diff) already do; a shorter block (smaller conv8) is followed by zero pad floats."""
     self.shapes = collections.OrderedDict(shapes)
@@ -119,6 +138,9 @@ class VariableStore:
     self.grads = torch.zeros(self.size, dtype=torch.float32, device=self.device)
     self.adam_m = torch.zeros(self.size, dtype=torch.float32, device=self.device)
     self.adam_v = torch.zeros(self.size, dtype=torch.float32, device=self.device)
+    self.ema = torch.zeros(self.size, dtype=torch.float32, device=self.device) if ema else None
+    self._shadow = None           # shadow_view()
+    self.base = self              # ... and, on such a view, the store it was taken from
     self.global_step = torch.zeros(1, dtype=torch.int64, device=self.device)
     self.version = 0      # bumped whenever the parameters are (re)written from the host side
     self.primary_stack = None     # the first training ConvEncoderStack built on this store (encoder.py: lazy_refresh)
@@ -135,6 +157,28 @@ class VariableStore:
 
   def grad(self, name):
     return self._view(self.grads, name)
+
+  def ema_var(self, name):
+    return self._view(self.ema, name)
+
+  def shadow_view(self):
+    """This store with the shadow arena in the parameters' place: what an evaluation / prediction model is built on to run on the
+    averaged weights.  Shares every arena (nothing is copied; the view follows training) and has no shadow arena of its own.  For
+    inference models only -- they re-derive their weight copies on every forward, so the view carries no version of its own."""
+    if self.ema is None:
+      raise ValueError('this VariableStore keeps no averaged weights (VariableStore(ema=True))')
+    if self._shadow is None:
+      view = object.__new__(VariableStore)
+      view.__dict__.update(self.__dict__)
+      view.params, view.ema, view._shadow, view.primary_stack, view.base = self.ema, None, None, None, self
+      self._shadow = view
+    return self._shadow
+
+  def _params_rewritten(self):
+    """The parameters were (re)written from the host side: the shadow arena restarts from them."""
+    if self.ema is not None:
+      self.ema.copy_(self.params)
+    self.version += 1
 
   def count_parameters(self) -> int:
     """models/e2evmc/utils.py:10-14."""
@@ -155,15 +199,21 @@ class VariableStore:
         lim = math.sqrt(6.0 / (fan_in + fan_out))
         val = rng.uniform(-lim, lim, size=shp).astype(np.float32)
       self.var(name).copy_(torch.from_numpy(val))
-    self.version += 1
+    self._params_rewritten()
 
-  def load_numpy(self, values: dict):
+  def load_numpy(self, values: dict, ema_values=None):
+    """``ema_values`` ({name: array}, a store with the shadow arena): the shadow tensors; None = they restart from the parameters."""
     for name in self.shapes:
       self.var(name).copy_(torch.from_numpy(np.ascontiguousarray(values[name], dtype=np.float32)))
-    self.version += 1
+    self._params_rewritten()
+    if ema_values is not None and self.ema is not None:
+      for name in self.shapes:
+        self.ema_var(name).copy_(torch.from_numpy(np.ascontiguousarray(ema_values[name], dtype=np.float32)))
 
   def to_numpy(self, which='params'):
-    arena = {'params': self.params, 'grads': self.grads, 'adam_m': self.adam_m, 'adam_v': self.adam_v}[which]
+    arena = {'params': self.params, 'grads': self.grads, 'adam_m': self.adam_m, 'adam_v': self.adam_v, 'ema': self.ema}[which]
+    if arena is None:
+      raise ValueError('this VariableStore keeps no averaged weights (VariableStore(ema=True))')
     host = arena.detach().cpu().numpy()
     out = collections.OrderedDict()
     for name, shp in self.shapes.items():
@@ -172,10 +222,13 @@ class VariableStore:
     return out
 
   def state_dict(self):
-    return {'params': self.params.detach().cpu(), 'adam_m': self.adam_m.detach().cpu(),
-            'adam_v': self.adam_v.detach().cpu(), 'global_step': self.global_step.detach().cpu(),
-            'names': list(self.shapes.keys()), 'shapes': [tuple(s) for s in self.shapes.values()],
-            'offsets': list(self.offsets.values())}
+    sd = {'params': self.params.detach().cpu(), 'adam_m': self.adam_m.detach().cpu(),
+          'adam_v': self.adam_v.detach().cpu(), 'global_step': self.global_step.detach().cpu(),
+          'names': list(self.shapes.keys()), 'shapes': [tuple(s) for s in self.shapes.values()],
+          'offsets': list(self.offsets.values())}
+    if self.ema is not None:
+      sd['ema'] = self.ema.detach().cpu()
+    return sd
 
   def load_state_dict(self, sd):
     if list(sd['names']) != list(self.shapes.keys()) or [tuple(s) for s in sd['shapes']] != \
@@ -185,4 +238,6 @@ class VariableStore:
     self.adam_m.copy_(sd['adam_m'])
     self.adam_v.copy_(sd['adam_v'])
     self.global_step.copy_(sd['global_step'])
-    self.version += 1
+    self._params_rewritten()       # (a checkpoint without shadow weights: they restart from its parameters)
+    if self.ema is not None and sd.get('ema') is not None:
+      self.ema.copy_(sd['ema'])

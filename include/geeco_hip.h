@@ -27,7 +27,7 @@ extern "C" {
 #define GEECO_ABI_VERSION 7  /* = the build round that last changed the entry points or their calling conventions */
 /* added within 7 (additive: no existing entry point or convention changed): geeco_lstm_seq_heads_fwd,
  * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd, geeco_gather_windows_by_address,
- * geeco_gather_windows_augmented */
+ * geeco_gather_windows_augmented, geeco_adam_tf_ema, geeco_adam_tf_segments_ema */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -549,6 +549,21 @@ typedef struct geeco_adam_segment {
 int geeco_adam_tf_segments(float* p, float* g_out, float* m, float* v, const geeco_adam_segment* segs, int nseg,
                            const float* lr_t_dev, float beta1, float beta2, float eps, float grad_scale, float l2,
                            void* stream);
+/* The two updates above with an exponential moving average of the parameters kept by the same pass (opt-in; semantics of
+ * tf.train.ExponentialMovingAverage with zero_debias=False and num_updates=global_step): p, m, v come out bit for bit as
+ * geeco_adam_tf / geeco_adam_tf_segments leave them, and every updated element of the shadow arena `ema` (indexed like p, 16-byte
+ * aligned) follows, in float32,
+ *   d_t = min(decay, (1 + t) / (10 + t));   ema -= (ema - p') (1 - d_t),      p' = the parameter just written,
+ * t = *global_step_dev as the prepare work of this step left it (geeco_adam_prepare or the last launch of
+ * geeco_slab_reduce_batch_prepare, earlier on the stream): the t of lr_t.  No second read of p and no extra launch; any
+ * partition of the arena gives bitwise the one-pass shadow arena too.  GEECO_EINVAL (nothing launched): ema or global_step_dev
+ * NULL, ema misaligned, decay outside (0, 1). */
+int geeco_adam_tf_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* lr_t_dev,
+                      const int64_t* global_step_dev, float decay, float beta1, float beta2, float eps, float grad_scale,
+                      float l2, void* stream);
+int geeco_adam_tf_segments_ema(float* p, float* g_out, float* m, float* v, float* ema, const geeco_adam_segment* segs, int nseg,
+                               const float* lr_t_dev, const int64_t* global_step_dev, float decay, float beta1, float beta2,
+                               float eps, float grad_scale, float l2, void* stream);
 /* sum of squares of an arena (for the L2 regularisation loss term); out[0] overwritten. */
 int geeco_sumsq(const float* p, int64_t n, float* out, void* stream);
 

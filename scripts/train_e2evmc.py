@@ -98,6 +98,11 @@ ARGPARSER.add_argument('--shared_frames', default=False, action='store_true',
                        help="Per-frame controllers (e2e_vmc; goal 'sequence' x 'constant' / 'residual'), one GPU, RGB: encode every "
                             'distinct frame of a batch once instead of once per window that holds it (same loss and gradients).  Needs '
                             '--batch_size <= the windows of an episode.')
+ARGPARSER.add_argument('--ema_decay', type=float, default=0.0,
+                       help='Keep an exponential moving average of the weights (tf.train.ExponentialMovingAverage with '
+                            'num_updates = global_step: d_t = min(decay, (1 + t) / (10 + t))), updated inside the optimiser pass; '
+                            'evaluation, snapshots and predictors with use_ema=True run the averaged weights.  A value in (0, 1), '
+                            'e.g. 0.999; 0 = off.  Not part of the model config (e2evmc_config.json stays as the reference writes it).')
 
 _OBSERVATION_FORMAT_TO_CHANNELS = {'rgb': 3, 'rgbd': 4}                      # train_e2evmc.py:129-132
 _GOAL_CONDITION_TO_MODEL = {'none': (e2evmc_model_fn, 'VMC'),               # train_e2evmc.py:134-137
@@ -145,6 +150,16 @@ def _export_snapshot(model_dir, eval_results, num_best_ckpt):
   return ckpt_dir
 
 
+def estimator_params(args, e2evmc_config):
+  """The Estimator's ``params`` of a command line: the model config, and the opt-ins that are not part of it."""
+  params = {'e2evmc_config': e2evmc_config, 'log_steps': args.log_steps, 'debug': args.debug}
+  if args.shared_frames:
+    params['shared_frames'] = True
+  if args.ema_decay:
+    params['ema_decay'] = args.ema_decay
+  return params
+
+
 def main(args):
   if args.shuffle_windows and args.shared_frames:
     # (before anything is written or initialised)
@@ -183,11 +198,9 @@ def main(args):
   if world > 1:
     import torch.distributed as dist
     dist.barrier()
-  estimator_params = {'e2evmc_config': e2evmc_config, 'log_steps': args.log_steps, 'debug': args.debug}
-  if args.shared_frames:
-    estimator_params['shared_frames'] = True
   model_fn, _scope = _GOAL_CONDITION_TO_MODEL[args.goal_condition]
-  estimator = est.Estimator(model_fn=model_fn, model_dir=args.model_dir, config=run_config, params=estimator_params)
+  estimator = est.Estimator(model_fn=model_fn, model_dir=args.model_dir, config=run_config,
+                            params=estimator_params(args, e2evmc_config))
 
   local_rank = int(os.environ.get('LOCAL_RANK', '0'))
   synthetic = args.dataset_dir.startswith('synthetic:')
