@@ -144,6 +144,10 @@ SIGNATURES = {
     'geeco_adam_tf_segments': (_I, [_P, _P, _P, _P, _P, _I, _P, _F, _F, _F, _F, _F, _P]),
     'geeco_adam_tf_ema': (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _F, _F, _F, _F, _F, _F, _P]),
     'geeco_adam_tf_segments_ema': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _F, _F, _F, _F, _F, _P]),
+    'geeco_clip_ws_floats': (_L, [_L]),
+    'geeco_grad_sumsq_segments': (_I, [_P, _P, _I, _L, _F, _F, _P, _P]),
+    'geeco_clip_scale': (_I, [_P, _L, _F, _P, _P]),
+    'geeco_adam_tf_segments_clip': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _P, _F, _F, _F, _F, _F, _P]),
     'geeco_sumsq': (_I, [_P, _L, _P, _P]),
 }
 

@@ -29,7 +29,7 @@ from . import graph
 from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
 from .tf_checkpoint import EMA_SUFFIX
-from .variables import check_ema_decay
+from .variables import check_clip_norm, check_ema_decay
 
 
 class ModeKeys:
@@ -183,6 +183,8 @@ class _SummarySaverHook:
       return
     self.model.check_device_errors()        # (the loss read-out below waits for the device anyway)
     parts = {k: float(v) for k, v in self.model.loss_parts().items()}
+    if getattr(self.model, 'clip_out', None) is not None:      # params['clip_norm']: the norm of this step's gradient before clipping
+      parts['grad_norm'] = float(self.model.clip_out[1])
     parts['global_step'] = step
     parts['wall_time'] = time.time()
     if model_dir:
@@ -225,6 +227,10 @@ def _model_fn(features, labels, mode, params, goal):
     if not training:
       store = store.shadow_view()
   ema = dict(ema_decay=decay) if training else {}
+  # params['clip_norm']: the training step clips the gradient by its global norm, on the device
+  clip = check_clip_norm(params.get('clip_norm'), "params['clip_norm']")
+  if training and clip is not None:
+    ema['clip_norm'] = clip
   shared = params.get('shared_frames')
   tables = {}
   if shared:
@@ -333,6 +339,7 @@ class Estimator:
     self.config = config or RunConfig()
     self.params = dict(params or {})
     check_ema_decay(self.params.get('ema_decay'), "params['ema_decay']")
+    check_clip_norm(self.params.get('clip_norm'), "params['clip_norm']")
     self._specs = {}          # (mode, N) -> (spec, feature buffers, label buffers)
     self.last_train_stats = None
     self._store = None

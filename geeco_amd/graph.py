@@ -27,7 +27,7 @@ from . import ops
 from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
-from .variables import _CELLS, VariableStore, check_ema_decay, model_variable_shapes
+from .variables import _CELLS, VariableStore, check_clip_norm, check_ema_decay, model_variable_shapes
 
 
 def build_store(cfg, goal, device, ema=False):
@@ -80,9 +80,10 @@ class BesideBottom:
 class _ModelBase:
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
-  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None):
+  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
     self.ema_decay = check_ema_decay(ema_decay)
+    self.clip_norm = check_clip_norm(clip_norm)
     self.shared_frames = self._check_shared_frames(cfg, goal, shared_frames)
     self.device = torch.device(device)
     self.K = cfg.window_size
@@ -132,6 +133,13 @@ class _ModelBase:
     self.world = 1
     self._prepared = False      # this step's backward has done adam_prepare's work (_prepare_args; runtime.py sets it too)
     self._opt_stream = None     # optimizer_stream()
+    # clip_norm: the sums of squares of the arena's chunks, [s, norm] of the last optimiser step, and the pieces of
+    # the arena whose update waits for the norm of all of them (apply_gradients_of); a model without the option has none of it
+    self.clip_ws = self.clip_out = None
+    self._clip_calls = []
+    if self.clip_norm is not None and training:
+      self.clip_ws = torch.zeros(ops.clip_ws_floats(self.store.size), **f32)
+      self.clip_out = torch.zeros(2, **f32)
     # GoalE2EVMC's branch and the control block of its one-pass input stage; the gather mode of a model that takes shared_frames
     self.mode = self.dyn_ws2 = self.window_mode = None
     # RGB-D: rgb || depth (estimator.py:36,169,172).  The dynimg branch of the goal model forms the concat inside its
@@ -235,6 +243,7 @@ class _ModelBase:
       # (an exception between the parts, a one-graph capture that failed after recording part 2, a caller that ran the backward
       # alone to look at gradients) must not make THIS step's apply_gradients skip its adam_prepare.
       self._prepared = False
+      del self._clip_calls[:]      # ... nor may the pieces it had handed to apply_gradients_of(last=False) join this step's
     if self.shared_frames is not None:
       self._encode_shared()
     else:
@@ -303,6 +312,8 @@ class _ModelBase:
     """The optimiser step of SOME pieces of the arena (``ops.adam_tf_segments``; data parallel: everything that came with the early
     bucket first, the late bucket's variables when it has arrived).  ``last``: the pieces complete the step (weight copies are
     re-derived behind it)."""
+    if self.clip_ws is not None:
+      return self._apply_clipped(segments, g_out, last)
     s, kw = self.store, dict(g_out=g_out, grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
     self._prepare_unless_done(last)
     if s.ema is not None:      # the averaged weights follow in the same launch (DESIGN 5.15)
@@ -312,7 +323,34 @@ class _ModelBase:
     if last:
       self._refresh_after_update()
 
+  def _apply_clipped(self, segments, g_out, last):
+    """apply_gradients_of under ``clip_norm``: no piece may move before the norm of ALL of them is known, so the pieces of a call that
+    does not complete the step are recorded and nothing is launched for them; the call that does runs, in order, the sum of squares
+    over every recorded piece and its own (ONE launch: the partial sums are then bitwise those of the undivided arena, whatever the
+    pieces), the scale, and the clipped Adam update call by call (each with its own ``g_out``).  Three launches for the whole arena,
+    four for the two pieces of the schedules in runtime.py -- constant per schedule, so the step stays one captured graph."""
+    self._clip_calls.append((list(segments), g_out))
+    if not last:
+      return
+    s, calls = self.store, self._clip_calls
+    self._clip_calls = []
+    pieces = [seg for segs, _ in calls for seg in segs]
+    if len(pieces) > ops._native.ADAM_SEGMENTS_MAX:
+      raise ValueError('clip_norm: the optimiser step came in %d pieces; the norm of the whole gradient is one launch over at most %d'
+                       % (len(pieces), ops._native.ADAM_SEGMENTS_MAX))
+    kw = dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
+    self._prepare_unless_done()
+    ops.grad_sumsq_segments(self.clip_ws, s.params, pieces, s.size, **kw)
+    ops.clip_scale(self.clip_out, self.clip_ws, self.clip_ws.numel(), self.clip_norm)
+    ema = dict(ema=s.ema, global_step=s.global_step, decay=self.ema_decay) if s.ema is not None else {}
+    for segs, out in calls:
+      ops.adam_tf_segments_clip(s.params, s.adam_m, s.adam_v, segs, self.scal, self.clip_out, g_out=out, **ema, **kw)
+    self._refresh_after_update()
+
   def apply_gradients(self):
+    if self.clip_ws is not None:      # the whole arena is the one-piece call
+      del self._clip_calls[:]
+      return self._apply_clipped([(self.store.grads, 0, self.store.size)], None, True)
     s, kw = self.store, dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
     self._prepare_unless_done()
     if s.ema is not None:
@@ -408,9 +446,10 @@ class _ModelBase:
 class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None):
-    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``: see E2EVMC."""
-    super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay)
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None):
+    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``: see E2EVMC."""
+    super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
+                     clip_norm=clip_norm)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -540,15 +579,18 @@ class GoalE2EVMC(_ModelBase):
 class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None):
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None):
     """``ema_decay`` (a float in (0, 1); None / 0 = off): the optimiser step also keeps an exponential moving average of the
     parameters in ``store.ema`` (tf.train.ExponentialMovingAverage with num_updates = global_step); a store passed in
     must have been built with the arena (``build_store(..., ema=True)``).
+    ``clip_norm`` (a finite number > 0; None / 0 = off): the optimiser step clips the total gradient g / world + l2 * p by its global norm
+    first (tf.clip_by_global_norm), on the device; ``clip_out`` then holds [scale, norm before clipping] of the last step.
     ``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
     'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
-    super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay)
+    super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
+                     clip_norm=clip_norm)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     self.window_mode, self.feat_ch = 'plain', [256]
     # frames are processed time-major ([K][N]) so that step t's features are one dense block

@@ -714,6 +714,38 @@ def adam_tf_segments_ema(p, m, v, ema, segments, scal, global_step, decay, g_out
                                           beta1, beta2, eps, grad_scale, l2, _stream()), 'geeco_adam_tf_segments_ema')
 
 
+def clip_ws_floats(n):
+  """Partial sums ``grad_sumsq_segments`` writes for an arena of ``n`` floats (one per fixed chunk)."""
+  return int(_lib().geeco_clip_ws_floats(int(n)))
+
+
+def grad_sumsq_segments(partials, p, segments, n, grad_scale=1.0, l2=0.0):
+  """``geeco_grad_sumsq_segments``: partials[k] = sum of (g * grad_scale + l2 * p)^2 over chunk k of the arena [0, n); the gradient of an
+  element comes from the piece of ``segments`` (as ``adam_tf_segments`` takes them, but any offset and count) that covers it, an
+  element no piece covers adds 0.  Any partition of the same elements gives bitwise the same partials.  ``p`` may be None when l2 == 0."""
+  if partials.numel() < clip_ws_floats(n):
+    raise ValueError('grad_sumsq_segments: %d partials for an arena of %d floats, %d needed' % (partials.numel(), n, clip_ws_floats(n)))
+  arr = _adam_segments(segments)
+  check(_lib().geeco_grad_sumsq_segments(_p(p), arr, len(segments), int(n), grad_scale, l2, _p(partials), _stream()),
+        'geeco_grad_sumsq_segments')
+
+
+def clip_scale(out2, partials, nchunks, clip):
+  """``geeco_clip_scale``: out2[0] = clip / max(norm, clip), out2[1] = norm = sqrt(sum of the first ``nchunks`` partials)."""
+  if out2.numel() < 2 or partials.numel() < nchunks:
+    raise ValueError('clip_scale: out2 holds 2 floats, partials at least nchunks = %d' % nchunks)
+  check(_lib().geeco_clip_scale(_p(partials), int(nchunks), clip, _p(out2), _stream()), 'geeco_clip_scale')
+
+
+def adam_tf_segments_clip(p, m, v, segments, scal, clip_dev, ema=None, global_step=None, decay=0.0, g_out=None, beta1=0.9, beta2=0.999,
+                          eps=1e-8, grad_scale=1.0, l2=0.0):
+  """``geeco_adam_tf_segments_clip``: adam_tf_segments (``ema`` None) or adam_tf_segments_ema on the total gradient times
+  ``clip_dev[0]`` (clip_scale's out2).  Offsets are multiples of 4 floats, counts any number >= 1: the whole arena is one piece."""
+  arr = _adam_segments(segments)
+  check(_lib().geeco_adam_tf_segments_clip(_p(p), _p(g_out), _p(m), _p(v), _p(ema), arr, len(segments), _p(scal), _p(global_step), decay,
+                                           _p(clip_dev), beta1, beta2, eps, grad_scale, l2, _stream()), 'geeco_adam_tf_segments_clip')
+
+
 def sumsq_into(out, p, n):
   check(_lib().geeco_sumsq(_p(p), n, _p(out), _stream()), 'geeco_sumsq')
 

@@ -97,6 +97,17 @@ def check_ema_decay(value, key='ema_decay'):
   return float(value)
 
 
+def check_clip_norm(value, key='clip_norm'):
+  """The global norm the gradient is clipped to: None or 0 = off (returns None), else a finite number > 0 that float32 holds;
+  anything else raises ValueError naming ``key``."""
+  if value is None or (isinstance(value, numbers.Real) and not isinstance(value, bool) and value == 0):
+    return None
+  f32 = np.finfo(np.float32)
+  if isinstance(value, bool) or not isinstance(value, numbers.Real) or not float(f32.tiny) <= float(value) <= float(f32.max):
+    raise ValueError('%s=%r: the norm to clip the gradient to must be a finite number > 0, a normal float32 (None or 0 = off)' % (key, value))
+  return float(value)
+
+
 def ema_decay_at(decay, t):
   """d_t = min(decay, (1 + t) / (10 + t)) in float32, as the Adam kernels compute it from the device's step counter."""
   t = np.float32(t)

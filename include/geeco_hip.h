@@ -27,7 +27,8 @@ extern "C" {
 #define GEECO_ABI_VERSION 7  /* = the build round that last changed the entry points or their calling conventions */
 /* added within 7 (additive: no existing entry point or convention changed): geeco_lstm_seq_heads_fwd,
  * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd, geeco_gather_windows_by_address,
- * geeco_gather_windows_augmented, geeco_adam_tf_ema, geeco_adam_tf_segments_ema */
+ * geeco_gather_windows_augmented, geeco_adam_tf_ema, geeco_adam_tf_segments_ema, geeco_clip_ws_floats,
+ * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -564,6 +565,25 @@ int geeco_adam_tf_ema(float* p, const float* g, float* m, float* v, float* ema, 
 int geeco_adam_tf_segments_ema(float* p, float* g_out, float* m, float* v, float* ema, const geeco_adam_segment* segs, int nseg,
                                const float* lr_t_dev, const int64_t* global_step_dev, float decay, float beta1, float beta2,
                                float eps, float grad_scale, float l2, void* stream);
+/* Opt-in clipping of the gradient by its global norm (tf.clip_by_global_norm in front of the optimiser), three launches, all on
+ * the device.  The total gradient of element i is the one Adam forms, G_i = g_i * grad_scale + l2 * p_i.
+ * geeco_grad_sumsq_segments: partials[k] = the sum of G_i^2 over the arena offsets [k * CH, (k + 1) * CH) below n, CH a constant
+ *   of the library, geeco_clip_ws_floats(n) partials in all.  The gradient of an element is found through the pieces (the table of
+ *   geeco_adam_tf_segments, but ANY offset and count >= 1 inside [0, n), sources 4-byte aligned, pieces disjoint); an element no
+ *   piece covers adds 0; p is read only when l2 != 0.  The summation order inside a chunk is fixed, so any partition of the same
+ *   elements into pieces gives bitwise the same partials.
+ * geeco_clip_scale: norm = sqrt(sum of the partials, one fixed order), out2[0] = s = clip / max(norm, clip) (exactly 1.0f whenever
+ *   norm <= clip), out2[1] = norm.  clip: finite, > 0.  A non-finite norm is not guarded: s and every update are then NaN.
+ * geeco_adam_tf_segments_clip: geeco_adam_tf_segments (ema_or_null == NULL) or geeco_adam_tf_segments_ema on G_i * clip_dev[0];
+ *   clip_dev[0] == 1.0f gives bitwise their p, m, v and shadow arena.  Offsets are multiples of 4 floats, counts any number >= 1
+ *   (a piece ends in a scalar tail), so the whole arena is the one-piece call. */
+int64_t geeco_clip_ws_floats(int64_t n);
+int geeco_grad_sumsq_segments(const float* p, const geeco_adam_segment* segs, int nseg, int64_t n, float grad_scale, float l2,
+                              float* partials, void* stream);
+int geeco_clip_scale(const float* partials, int64_t nchunks, float clip, float* out2, void* stream);
+int geeco_adam_tf_segments_clip(float* p, float* g_out, float* m, float* v, float* ema_or_null, const geeco_adam_segment* segs,
+                                int nseg, const float* lr_t_dev, const int64_t* global_step_dev, float decay, const float* clip_dev,
+                                float beta1, float beta2, float eps, float grad_scale, float l2, void* stream);
 /* sum of squares of an arena (for the L2 regularisation loss term); out[0] overwritten. */
 int geeco_sumsq(const float* p, int64_t n, float* out, void* stream);
 

@@ -103,6 +103,10 @@ ARGPARSER.add_argument('--ema_decay', type=float, default=0.0,
                             'num_updates = global_step: d_t = min(decay, (1 + t) / (10 + t))), updated inside the optimiser pass; '
                             'evaluation, snapshots and predictors with use_ema=True run the averaged weights.  A value in (0, 1), '
                             'e.g. 0.999; 0 = off.  Not part of the model config (e2evmc_config.json stays as the reference writes it).')
+ARGPARSER.add_argument('--clip_norm', type=float, default=0.0,
+                       help='Clip the gradient (L2 term included, as TF clips the gradient of the total loss) by its global norm before '
+                            'the optimiser step (tf.clip_by_global_norm), on the device; events.jsonl then carries grad_norm, the norm '
+                            'before clipping.  A finite number > 0, e.g. 5.0; 0 = off.  Not part of the model config.')
 
 _OBSERVATION_FORMAT_TO_CHANNELS = {'rgb': 3, 'rgbd': 4}                      # train_e2evmc.py:129-132
 _GOAL_CONDITION_TO_MODEL = {'none': (e2evmc_model_fn, 'VMC'),               # train_e2evmc.py:134-137
@@ -157,6 +161,8 @@ def estimator_params(args, e2evmc_config):
     params['shared_frames'] = True
   if args.ema_decay:
     params['ema_decay'] = args.ema_decay
+  if args.clip_norm:
+    params['clip_norm'] = args.clip_norm
   return params
 
 
