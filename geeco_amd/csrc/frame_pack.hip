@@ -246,3 +246,180 @@ extern "C" int geeco_gather_windows_augmented(const int64_t* addr, const int32_t
   GEECO_LAUNCH_CHECK();
   return 0;
 }
+
+// ---- scene builder: the augmented builder of RGB streams with occluders and per-element sensor noise behind the gather ---------
+// (input_fn.pickplace_input_fn(augment=dict(noise=, occlude=)))  Per element, in this order:  v1 = what the kernel
+// above writes (shift, zero fill, tint);  v2 = the colour component of the highest-numbered rectangle of window n that holds the
+// element's OUTPUT pixel, else v1;  out = min(max(fma(sigma, z, v2), 0), 1) with z ~ N(0, 1) from Philox4x32-10 under the counter
+// (e / 4, k, n, tag) for element offset e of the frame: z depends on (key, tag, n, k, e) alone, whatever path or thread made it.
+// sigma == 0 skips the noise step (no clamp: the output is v2 itself).  The gather is the one above, duplicated: moved into a
+// function shared by both kernels it changed the merged kernel's gfx950 code, so that kernel's source stays as it
+// is.  The rectangles and the key are uniform per block (scalar loads); no address is formed from a rectangle.  Grid, thread
+// ownership and stores as above; a thread's four elements are e = i4 .. i4 + 3 on either path, so ONE Philox call serves them.
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
+                                              unsigned x[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0, c1 = lo1, c2 = hi0 ^ c3 ^ k1, c3 = lo0;
+    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
+  }
+  x[0] = c0, x[1] = c1, x[2] = c2, x[3] = c3;
+}
+
+// Box-Muller on two words: ua = ((xa >> 8) + 0.5) 2^-24 in (0, 1), ub = (xb >> 8) 2^-24;  za, zb = sqrt(-2 ln ua) (cos, sin)(2 pi ub).
+// t = 2^25 ua is an odd integer below 2^25: float32 holds it exactly below 2^24 and rounds it to a neighbour above, which next
+// to ua = 1 would lose all of ln ua.  The rounding res = t - float(t) is an integer in {-1, 0, 1}, so
+// ln ua = ln(float(t) 2^-25) + res / float(t) up to res^2 / (2 t^2) < 2^-49.  2 ub is exact in float32.
+__device__ __forceinline__ void philox_normal_pair(unsigned xa, unsigned xb, float& za, float& zb) {
+  const unsigned t = ((xa >> 8) << 1) | 1u;
+  const float tf = (float)t;
+  const float res = (float)((int)t - (int)tf);
+  const float ln = logf(tf * 0x1p-25f) + res * __builtin_amdgcn_rcpf(tf);
+  const float r = sqrtf(-2.f * ln);
+  const float a = (float)(xb >> 8) * 0x1p-23f;
+  za = r * cospif(a), zb = r * sinpif(a);
+}
+
+// One rectangle slot of a window as scalars (an indexed private array would leave the registers): (y0, x0, h, w) and its colour;
+// h <= 0 or w <= 0: an empty slot.
+struct SceneRect {
+  int y0, x0, h, w;
+  float r, g, b;
+};
+
+__device__ __forceinline__ SceneRect scene_rect(const int* occ_rect, const float* occ_colour, int n, int j) {
+  if (!occ_rect) return SceneRect{0, 0, 0, 0, 0.f, 0.f, 0.f};
+  const int* rc = occ_rect + ((long long)n * 4 + j) * 4;
+  const float* cc = occ_colour + ((long long)n * 4 + j) * 3;
+  return SceneRect{rc[0], rc[1], rc[2], rc[3], cc[0], cc[1], cc[2]};
+}
+
+// v under one rectangle at output pixel (y, x), channel c.  y, x < 2^31: y >= y0 as int32, then y - y0 lies in [0, 2^32) and is
+// compared unsigned with h > 0 -- no overflow for any table content.
+__device__ __forceinline__ float scene_occlude(float v, const SceneRect q, unsigned y, unsigned x, unsigned c) {
+  const bool in = q.h > 0 && q.w > 0 && (int)y >= q.y0 && y - (unsigned)q.y0 < (unsigned)q.h && (int)x >= q.x0 &&
+                  x - (unsigned)q.x0 < (unsigned)q.w;
+  return in ? (c == 0 ? q.r : (c == 1 ? q.g : q.b)) : v;
+}
+
+__global__ __launch_bounds__(256) void gather_windows_scene_kernel(const long long* __restrict__ addr, const int* __restrict__ kind,
+                                                                   const int* __restrict__ shift, const float* __restrict__ colour,
+                                                                   const int* __restrict__ occ_rect,
+                                                                   const float* __restrict__ occ_colour,
+                                                                   const unsigned* __restrict__ noise_key, float sigma,
+                                                                   unsigned tag, int K, int H, int W, float* __restrict__ out) {
+  constexpr int C = 3;
+  const int n = blockIdx.z, k = blockIdx.y;
+  const unsigned RW = (unsigned)W * (unsigned)C, fe = RW * (unsigned)H;      // (the entry point checked H * W * C < 2^31)
+  const unsigned i4 = (blockIdx.x * 256u + threadIdx.x) * 4u;
+  if (i4 >= fe) return;
+  const bool f32 = kind[n] == 1;
+  const long long dy = shift[2 * n], dxe = (long long)shift[2 * n + 1] * C;   // the column shift in ELEMENTS of a row
+  const unsigned long long frame = (unsigned long long)addr[n] + (unsigned long long)k * fe * (f32 ? 4u : 1u);
+  float* o = out + ((long long)n * K + k) * fe + i4;
+  const bool on = colour != nullptr;
+  float g0 = 1.f, g1 = 1.f, g2 = 1.f, b0 = 0.f, b1 = 0.f, b2 = 0.f;
+  if (on) {
+    const float* col = colour + (long long)n * 2 * C;       // gain[C], bias[C]
+    g0 = col[0], g1 = col[1], g2 = col[2], b0 = col[3], b1 = col[4], b2 = col[5];
+  }
+  auto tint = [=](float v, unsigned c) { return aug_tint(v, c, on, g0, g1, g2, b0, b1, b2); };
+  const bool occluded = occ_rect != nullptr;
+  const SceneRect q0 = scene_rect(occ_rect, occ_colour, n, 0), q1 = scene_rect(occ_rect, occ_colour, n, 1),
+                  q2 = scene_rect(occ_rect, occ_colour, n, 2), q3 = scene_rect(occ_rect, occ_colour, n, 3);
+  float z[4] = {0.f, 0.f, 0.f, 0.f};
+  const bool noisy = sigma != 0.f;
+  if (noisy) {
+    unsigned x[4];
+    philox4x32_10(i4 >> 2, (unsigned)k, (unsigned)n, tag, noise_key[0], noise_key[1], x);
+    philox_normal_pair(x[0], x[1], z[0], z[1]);
+    philox_normal_pair(x[2], x[3], z[2], z[3]);
+  }
+  // v1 of element j of this thread at (row y, row offset r) -> the stored value
+  auto finish = [&](float v, unsigned y, unsigned r, int j) {
+    if (occluded) {       // the highest-numbered slot that holds the pixel wins
+      const unsigned x = r / 3u, c = r % 3u;
+      v = scene_occlude(scene_occlude(scene_occlude(scene_occlude(v, q0, y, x, c), q1, y, x, c), q2, y, x, c), q3, y, x, c);
+    }
+    return noisy ? fminf(fmaxf(fmaf(sigma, z[j], v), 0.f), 1.f) : v;
+  };
+  if (RW % 4u != 0) {       // one element at a time
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      if (i4 + j >= fe) break;
+      const unsigned y = (i4 + j) / RW, r = (i4 + j) - y * RW;
+      const long long sy = (long long)y - dy, sr = (long long)r - dxe;
+      const bool inside = sy >= 0 && sy < H && sr >= 0 && sr < (long long)RW;
+      o[j] = finish(inside ? tint(aug_load(frame, f32, sy * RW + sr), r % 3u) : 0.f, y, r, j);
+    }
+    return;
+  }
+  const unsigned y = i4 / RW, r = i4 - y * RW;      // r % 4 == 0 and r + 3 < RW: the group lies in row y
+  const long long sy = (long long)y - dy, sr = (long long)r - dxe;
+  const unsigned c0 = r % 3u;
+  float e[4] = {0.f, 0.f, 0.f, 0.f};
+  if (sy >= 0 && sy < H && sr + 3 >= 0 && sr < (long long)RW) {      // at least one source inside the frame
+    const long long s0 = sy * RW + sr;
+    if (sr >= 0 && sr + 3 < (long long)RW) {                         // all four
+      if (f32) {
+        const unsigned long long a = frame + (unsigned long long)s0 * 4;
+        if ((a & 15u) == 0) {
+          const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a));
+          e[0] = v.x, e[1] = v.y, e[2] = v.z, e[3] = v.w;
+        } else {
+          const float* s = reinterpret_cast<const float*>(a);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) e[j] = s[j];
+        }
+      } else {
+        const unsigned long long a = frame + (unsigned long long)s0, wa = a & ~3ull;
+        if (wa == a || (wa >= frame && wa + 8 <= frame + fe)) {
+          unsigned v = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(wa));
+          if (wa != a) v = __builtin_amdgcn_alignbyte(__builtin_nontemporal_load(reinterpret_cast<const unsigned*>(wa + 4)), v, (unsigned)(a & 3u));
+          u8x4_unit_div(v, e);
+        } else {
+          const unsigned char* s = reinterpret_cast<const unsigned char*>(a);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) e[j] = u8_unit_div(s[j]);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) e[j] = tint(e[j], (c0 + j) % 3u);
+    } else {                                                         // the group crosses the left or right edge of the image
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (sr + j >= 0 && sr + j < (long long)RW) e[j] = tint(aug_load(frame, f32, s0 + j), (c0 + j) % 3u);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) e[j] = finish(e[j], y, r + j, j);
+  *reinterpret_cast<f32x4*>(o) = f32x4{e[0], e[1], e[2], e[3]};
+}
+
+extern "C" int geeco_gather_windows_scene(const int64_t* addr, const int32_t* kind, const int32_t* shift, const float* colour,
+                                          const int32_t* occ_rect, const float* occ_colour, const uint32_t* noise_key, float sigma,
+                                          int tag, int N, int K, int H, int W, int C, float* out, void* stream) {
+  GEECO_CHECK_ARG(addr && kind && shift && out, "gather_windows_scene: null pointer");
+  GEECO_CHECK_ARG(N >= 1 && N <= 65535 && K >= 1 && K <= 65535, "gather_windows_scene: N=%d, K=%d outside 1..65535", N, K);
+  GEECO_CHECK_ARG(H >= 1 && W >= 1, "gather_windows_scene: H=%d, W=%d must be >= 1", H, W);
+  GEECO_CHECK_ARG(C == 3, "gather_windows_scene: C=%d must be 3 (occluders and noise are built for RGB streams)", C);
+  const int64_t frame_elems = (int64_t)H * W * C;
+  GEECO_CHECK_ARG(frame_elems <= 0x7fffffffLL, "gather_windows_scene: a frame of %lld elements is too large", (long long)frame_elems);
+  GEECO_CHECK_ARG(sigma >= 0.f && sigma < 1.f, "gather_windows_scene: sigma=%g outside [0, 1)", (double)sigma);
+  GEECO_CHECK_ARG(tag == 0 || tag == 1, "gather_windows_scene: tag=%d must be 0 (rgb) or 1 (target_rgb)", tag);
+  GEECO_CHECK_ARG((occ_rect == nullptr) == (occ_colour == nullptr), "gather_windows_scene: occ_rect and occ_colour must be null together");
+  GEECO_CHECK_ARG(noise_key || sigma == 0.f, "gather_windows_scene: sigma=%g needs a noise key", (double)sigma);
+  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "gather_windows_scene: out must be 16-byte aligned");
+  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(addr) & 7) == 0 && (reinterpret_cast<uintptr_t>(kind) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(shift) & 3) == 0 && (reinterpret_cast<uintptr_t>(colour) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(occ_rect) & 3) == 0 && (reinterpret_cast<uintptr_t>(occ_colour) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(noise_key) & 3) == 0,
+                  "gather_windows_scene: the tables must be aligned for their element types");
+  dim3 grid((unsigned)cdiv64(frame_elems, 1024), (unsigned)K, (unsigned)N);
+  hipLaunchKernelGGL(gather_windows_scene_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)addr, kind, shift,
+                     colour, occ_rect, occ_colour, noise_key, sigma, (unsigned)tag, K, H, W, out);
+  GEECO_LAUNCH_CHECK();
+  return 0;
+}

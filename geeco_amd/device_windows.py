@@ -22,16 +22,42 @@ class WindowAugment:
   """The per-window augmentation draws of ONE batch (pickplace_input_fn(augment=...)): ``shift`` int32 [n][2] =
   (dy, dx) in whole pixels, ``colour`` float32 [n][6] = gain[3], bias[3] of the RGB channels.  One object is referenced by every
   DeviceWindows stream of the batch (``DeviceWindows.augment``): window i of 'rgb', 'target_rgb', 'depth' and 'target_depth'
-  moves by the same shift[i], the RGB streams are tinted by the same colour[i], depth streams are only moved."""
+  moves by the same shift[i], the RGB streams are tinted by the same colour[i], depth streams are only moved.
+  The scene extras (RGB streams only, each optional): ``occ_rect`` int32 [n][4][4] = (y0, x0, h, w) of up to four
+  rectangles per window in output coordinates with ``occ_colour`` float32 [n][4][3] (an all-zero slot is empty), and the sensor
+  noise ``sigma`` in (0, 1) with ``noise_key``, the two uint32 words of the batch's Philox key."""
 
-  def __init__(self, shift, colour):
+  def __init__(self, shift, colour, occ_rect=None, occ_colour=None, noise_key=None, sigma=0.0):
     self.shift = np.ascontiguousarray(shift, np.int32).reshape(-1, 2)
     self.colour = np.ascontiguousarray(colour, np.float32).reshape(-1, 6)
     if len(self.shift) != len(self.colour):
       raise ValueError('WindowAugment: %d shifts for %d colour rows' % (len(self.shift), len(self.colour)))
+    if (occ_rect is None) != (occ_colour is None):
+      raise ValueError('WindowAugment: occ_rect and occ_colour come together')
+    self.occ_rect = self.occ_colour = self.noise_key = None
+    if occ_rect is not None:
+      self.occ_rect = np.ascontiguousarray(occ_rect, np.int32).reshape(-1, 4, 4)
+      self.occ_colour = np.ascontiguousarray(occ_colour, np.float32).reshape(-1, 4, 3)
+      if not len(self.occ_rect) == len(self.occ_colour) == len(self.shift):
+        raise ValueError('WindowAugment: %d / %d occluder rows for %d windows' % (len(self.occ_rect), len(self.occ_colour), len(self.shift)))
+    self.sigma = float(sigma)
+    if not 0.0 <= self.sigma < 1.0:
+      raise ValueError('WindowAugment: sigma must lie in [0, 1), got %r' % (sigma,))
+    if self.sigma > 0:
+      if noise_key is None:
+        raise ValueError('WindowAugment: sigma > 0 needs a noise key')
+      self.noise_key = np.ascontiguousarray(noise_key, np.uint32).reshape(2)
 
   def __len__(self):
     return len(self.shift)
+
+  @property
+  def scene(self):
+    """None, or which extras the draws carry: 'occlude', 'noise' or 'occlude+noise' (a feed slot is built for one of them)."""
+    return '+'.join(w for w, on in (('occlude', self.occ_rect is not None), ('noise', self.noise_key is not None)) if on) or None
+
+
+SCENE_TAGS = {'rgb': 0, 'target_rgb': 1}      # the noise generator's stream number of an RGB feature (counter word 3)
 
 
 class DeviceWindows:
@@ -47,6 +73,7 @@ class DeviceWindows:
     self.n = 0
     self.scattered = False  # built by the shuffling assembler (shuffle_windows): about one episode per window, see window_table
     self.augment = None     # a WindowAugment shared with the other streams of the batch: the windows are these, transformed
+    self.scene_tag = 0      # SCENE_TAGS of the feature this stream is (the sensor noise of 'rgb' and 'target_rgb' differs)
 
   def add(self, frames_dev, starts, divisor=None):
     """``divisor``: what the gather divides this segment's frames by (default: the constructor's).  One batch can hold
@@ -71,6 +98,16 @@ class DeviceWindows:
     if self.frame_shape[-1] not in (1, 3) or len(self.frame_shape) != 3:
       raise ValueError('DeviceWindows: augmented frames must be [H, W, 3] or [H, W, 1], got %s' % (self.frame_shape,))
     return aug.shift, (aug.colour if self.frame_shape[-1] == 3 else None)
+
+  def scene_tables(self):
+    """None (the draws carry no extras, or this is a one-channel stream: shift only, through the merged entry point), or
+    (occ_rect int32 [n][4][4] or None, occ_colour float32 [n][4][3] or None, noise_key int32 [2] or None, sigma, tag) for
+    ops.gather_windows_scene_into."""
+    aug = self.augment
+    if aug is None or aug.scene is None or self.frame_shape[-1] != 3:
+      return None
+    key = None if aug.noise_key is None else aug.noise_key.view(np.int32)
+    return aug.occ_rect, aug.occ_colour, key, aug.sigma, self.scene_tag
 
   def __len__(self):
     return self.n
@@ -192,7 +229,7 @@ class DeviceWindows:
     """out [n][K][*frame_shape] <- the windows, one geeco_gather_windows launch per segment.  Every segment is checked on the
     host (residency, device, bounds) before the first launch is queued: an out-of-range gather is a GPU fault.  Augmented
     windows: ONE geeco_gather_windows_augmented launch behind four small copies of its tables (the feed's 'dense_augmented'
-    form sends them in the step's one block instead)."""
+    form sends them in the step's one block instead); geeco_gather_windows_scene when ``scene_tables()`` has extras."""
     import torch
     from . import ops
     fe = int(np.prod(self.frame_shape))
@@ -200,7 +237,13 @@ class DeviceWindows:
       shift, colour = self.augment_tables()
       addr, kinds = self.window_table(out.device)
       up = lambda a: None if a is None else torch.from_numpy(a).to(out.device, non_blocking=True)
-      ops.gather_windows_augmented_into(out, up(addr), up(kinds), up(shift), up(colour), self.n, self.K, *self.frame_shape)
+      scene = self.scene_tables()
+      if scene is None:
+        ops.gather_windows_augmented_into(out, up(addr), up(kinds), up(shift), up(colour), self.n, self.K, *self.frame_shape)
+      else:
+        occ_rect, occ_colour, key, sigma, tag = scene
+        ops.gather_windows_scene_into(out, up(addr), up(kinds), up(shift), up(colour), up(occ_rect), up(occ_colour), up(key), sigma,
+                                      tag, self.n, self.K, *self.frame_shape)
       return
     off = 0
     for frames_dev, starts, divisor, _, _ in list(self._checked_segments(out.device)):

@@ -414,6 +414,10 @@ class Estimator:
     augmented = any(isinstance(v, DeviceWindows) and v.augmented for v in feats.values())
     if augmented:
       key += ('augmented',)
+      # ... and slots of their own per set of scene extras the draws carry (occluders, sensor noise: other arena entries, another fill)
+      scene = next((v.augment.scene for v in feats.values() if isinstance(v, DeviceWindows) and v.augmented), None)
+      if scene is not None:
+        key += ('scene:' + scene,)
     if key in self._specs:
       return self._specs[key]
     shared = self.params.get('shared_frames')

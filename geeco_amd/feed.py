@@ -107,7 +107,9 @@ class WindowFeed:
     * 'dense_augmented' (``dense()`` of a slot whose first batch came from an augmenting input, ``DeviceWindows.augmented``):
       that buffer filled by ONE geeco_gather_windows_augmented launch; the window table, the batch's shifts and, for an RGB
       stream, its colour gains and biases ride in the arena, and ``after_flush()`` queues the launch as for 'dense_by_address'.
-      Such a slot is never ``u8``: augmented windows exist only as dense windows.
+      Such a slot is never ``u8``: augmented windows exist only as dense windows.  An RGB stream whose draws carry scene extras
+      (``DeviceWindows.scene_tables()``: occluders, sensor noise) is filled by ONE geeco_gather_windows_scene launch
+      instead; the rectangles, their colours and the noise key ride in the arena too, sigma and the tag are launch arguments.
     * 'frame_table' (``frame_table()``, models built with shared_frames=F): the batch's distinct frames, see there."""
 
   def __init__(self, windows, arena, key, shared_frames=None, shared_targets=None):
@@ -126,6 +128,9 @@ class WindowFeed:
     self.shared_reserved = self.shared = shared_frames
     self.shared_targets, self._with_targets = shared_targets, False
     self._gather_pending, self._window_tables = False, None
+    scene = windows.scene_tables() if self.augmented else None
+    # which extras an augmented RGB slot carries ('occlude', 'noise', 'occlude+noise'; None: the merged augmented fill)
+    self.scene, self._scene_args = (windows.augment.scene if scene is not None else None), None
     if shared_frames is not None:
       arena.reserve(key + ('frame_table',), (int(shared_frames),), np.int64)
       arena.reserve(key + ('frame_index',), (self.n, self.K), np.int32)
@@ -146,6 +151,11 @@ class WindowFeed:
       arena.reserve(key + ('aug_shift',), (self.n, 2), np.int32)
       if self.frame_shape[-1] == 3:
         arena.reserve(key + ('aug_colour',), (self.n, 6), np.float32)
+      if scene is not None and scene[0] is not None:
+        arena.reserve(key + ('aug_occ_rect',), (self.n, 4, 4), np.int32)
+        arena.reserve(key + ('aug_occ_colour',), (self.n, 4, 3), np.float32)
+      if scene is not None and scene[2] is not None:
+        arena.reserve(key + ('aug_noise_key',), (2,), np.int32)
 
   adopted = property(lambda self: self.form is not None)      # the model took this slot as an input: it chose a form
   feeds_frame_table = property(lambda self: self.form == 'frame_table')
@@ -224,6 +234,18 @@ class WindowFeed:
     self.arena.write(self.key + ('aug_shift',), shift)
     if colour is not None:
       self.arena.write(self.key + ('aug_colour',), colour)
+    scene = windows.scene_tables()
+    if (windows.augment.scene if scene is not None else None) != self.scene:
+      raise RuntimeError('WindowFeed: a batch with the scene extras %r in a slot built for %r (the Estimator keys its models by '
+                         'them)' % (windows.augment.scene if scene is not None else None, self.scene))
+    if scene is not None:
+      occ_rect, occ_colour, noise_key, sigma, tag = scene
+      if occ_rect is not None:
+        self.arena.write(self.key + ('aug_occ_rect',), occ_rect)
+        self.arena.write(self.key + ('aug_occ_colour',), occ_colour)
+      if noise_key is not None:
+        self.arena.write(self.key + ('aug_noise_key',), noise_key)
+      self._scene_args = (sigma, tag)
 
   def _feed_frame_table(self, windows, batch):
     targets = None
@@ -250,9 +272,13 @@ class WindowFeed:
     self._gather_pending = False
     if self._window_tables is None:       # static views of the sealed arena
       view = lambda name: self.arena.view(self.key + (name,)) if self.arena.has(self.key + (name,)) else None
-      self._window_tables = tuple(view(name) for name in ('window_addr', 'window_kind', 'aug_shift', 'aug_colour'))
-    addr, kind, shift, colour = self._window_tables
-    if self.form == 'dense_augmented':
+      self._window_tables = tuple(view(name) for name in ('window_addr', 'window_kind', 'aug_shift', 'aug_colour', 'aug_occ_rect',
+                                                          'aug_occ_colour', 'aug_noise_key'))
+    addr, kind, shift, colour, occ_rect, occ_colour, noise_key = self._window_tables
+    if self.form == 'dense_augmented' and self.scene is not None:
+      ops.gather_windows_scene_into(self.buffer, addr, kind, shift, colour, occ_rect, occ_colour, noise_key, *self._scene_args,
+                                    self.n, self.K, *self.frame_shape)
+    elif self.form == 'dense_augmented':
       ops.gather_windows_augmented_into(self.buffer, addr, kind, shift, colour, self.n, self.K, *self.frame_shape)
     else:
       ops.gather_windows_by_address_into(self.buffer, addr, kind, self.n, self.K, int(np.prod(self.frame_shape)))

@@ -25,7 +25,7 @@ import numpy as np
 
 from . import tfrecord
 # what is not the reader keeps resolving from here (none of these modules imports this one when it loads)
-from .device_windows import DeviceWindows, EPISODE_CACHE, EpisodeCache, WindowAugment, _PINNED, _PinnedPool, episode_to_device, resolve_device  # noqa: F401
+from .device_windows import DeviceWindows, EPISODE_CACHE, EpisodeCache, SCENE_TAGS, WindowAugment, _PINNED, _PinnedPool, episode_to_device, resolve_device  # noqa: F401
 from .feed import FeedArena, WindowFeed  # noqa: F401
 from .synthetic import synthetic_batches, synthetic_from_spec, synthetic_scene_frames, write_episode, write_synthetic_dataset  # noqa: F401
 
@@ -312,6 +312,9 @@ def _assemble_picks(picks, K):
 
 
 AUGMENT_STREAM = 0x617567      # third word of the augmentation generator's seed: a stream apart from the file order's and the shuffle's
+AUGMENT_SCENE_STREAM = 0x7363656e      # ... and of the scene draws' generator (occluders, noise key): the shift / colour draws stay put
+AUGMENT_SCENE_KEYS = ('noise', 'occlude', 'occlude_size')      # validated by check_augment_scene
+OCCLUDE_MAX = 4      # rectangle slots per window (include/geeco_hip.h: geeco_gather_windows_scene)
 
 
 def check_augment(augment, hw=None):
@@ -322,8 +325,8 @@ def check_augment(augment, hw=None):
   if not isinstance(augment, dict):
     raise ValueError('augment must be None or dict(shift=S, gain=g, bias=b), got %r' % (augment,))
   for k in augment:
-    if k not in ('shift', 'gain', 'bias'):
-      raise ValueError("augment: unknown key %r (the keys are 'shift', 'gain' and 'bias')" % (k,))
+    if k not in ('shift', 'gain', 'bias') + AUGMENT_SCENE_KEYS:
+      raise ValueError("augment: unknown key %r (the keys are 'shift', 'gain', 'bias', 'noise', 'occlude' and 'occlude_size')" % (k,))
   S, g, b = augment.get('shift', 0), augment.get('gain', 0.0), augment.get('bias', 0.0)
   if isinstance(S, (bool, np.bool_)) or not isinstance(S, (int, np.integer)) or S < 0:
     raise ValueError("augment['shift'] must be an integer >= 0 (whole pixels), got %r" % (S,))
@@ -335,6 +338,25 @@ def check_augment(augment, hw=None):
   return None if (S == 0 and g == 0 and b == 0) else (int(S), float(g), float(b))
 
 
+def check_augment_scene(augment, hw=None):
+  """The scene keys of ``pickplace_input_fn(augment=...)`` validated: None (off: no dict, or ``noise`` and
+  ``occlude`` both 0) or (sigma, R, f) -- ``noise`` = sigma in [0, 1), ``occlude`` = R in 0..4 rectangles at most per window,
+  ``occlude_size`` = f in (0, 1], their largest side as a fraction of the frame's (default 0.25).  The other keys are
+  ``check_augment``'s, which also refuses unknown ones; ``hw`` is accepted for symmetry with it (no value depends on the frame)."""
+  if augment is None:
+    return None
+  check_augment({k: v for k, v in augment.items() if k not in AUGMENT_SCENE_KEYS} if isinstance(augment, dict) else augment, hw)
+  sigma, R, f = augment.get('noise', 0.0), augment.get('occlude', 0), augment.get('occlude_size', 0.25)
+  number = lambda v: not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, float, np.integer, np.floating))
+  if not number(sigma) or not 0 <= sigma < 1:
+    raise ValueError("augment['noise'] must be a number in [0, 1), got %r" % (sigma,))
+  if isinstance(R, (bool, np.bool_)) or not isinstance(R, (int, np.integer)) or not 0 <= R <= OCCLUDE_MAX:
+    raise ValueError("augment['occlude'] must be an integer in 0..%d (rectangles per window at most), got %r" % (OCCLUDE_MAX, R))
+  if not number(f) or not 0 < f <= 1:
+    raise ValueError("augment['occlude_size'] must be a number in (0, 1], got %r" % (f,))
+  return None if (sigma == 0 and R == 0) else (float(sigma), int(R), float(f))
+
+
 def draw_augment(rng, n, S, g, b):
   """The draws of one emitted batch of ``n`` windows, in this order: dy, dx ~ integers U[-S, S] ([n][2]), gain_c ~ U[1 - g, 1 + g]
   ([n][3]), bias_c ~ U[-b, b] ([n][3])."""
@@ -344,12 +366,36 @@ def draw_augment(rng, n, S, g, b):
   return WindowAugment(shift, np.concatenate([gain, bias], axis=1))
 
 
-def _augment_batch(feats, rng, aug):
-  """Marks every DeviceWindows stream of an emitted batch with ONE WindowAugment drawn for it."""
-  draws = draw_augment(rng, len(feats['step']), *aug)
-  for v in feats.values():
+def draw_augment_scene(rng, n, H, W, sigma, R, f):
+  """The scene draws of one emitted batch of ``n`` windows of H x W frames, in this order: the noise key, two uint32 words (drawn
+  whatever sigma is, so the rectangles do not depend on it); per window a count r ~ U{0..R}; per slot j < r: h ~ U{1..max(1,
+  floor(f H))}, w ~ U{1..max(1, floor(f W))}, y0 ~ U{0..H - h}, x0 ~ U{0..W - w} and a colour of three U[0, 1) values; slots
+  j >= r stay zero (empty).  Returns the keyword arguments WindowAugment takes: noise_key and sigma when sigma > 0, occ_rect
+  [n][4][4] and occ_colour [n][4][3] when R > 0."""
+  key = rng.integers(0, 1 << 32, size=2, dtype=np.uint64).astype(np.uint32)
+  out = dict(noise_key=key, sigma=sigma) if sigma > 0 else {}
+  if R > 0:
+    rect, colour = np.zeros((n, OCCLUDE_MAX, 4), np.int32), np.zeros((n, OCCLUDE_MAX, 3), np.float32)
+    hmax, wmax = max(1, int(np.floor(f * H))), max(1, int(np.floor(f * W)))
+    for i in range(n):
+      for j in range(int(rng.integers(0, R + 1))):
+        h, w = int(rng.integers(1, hmax + 1)), int(rng.integers(1, wmax + 1))
+        rect[i, j] = int(rng.integers(0, H - h + 1)), int(rng.integers(0, W - w + 1)), h, w
+        colour[i, j] = rng.random(3).astype(np.float32)
+    out.update(occ_rect=rect, occ_colour=colour)
+  return out
+
+
+def _augment_batch(feats, rng, aug, scene_rng=None, scene=None, hw=None):
+  """Marks every DeviceWindows stream of an emitted batch with ONE WindowAugment drawn for it (``scene``: with the scene extras,
+  from their own generator)."""
+  n = len(feats['step'])
+  extras = draw_augment_scene(scene_rng, n, hw[0], hw[1], *scene) if scene is not None else {}
+  draws = draw_augment(rng, n, *(aug or (0, 0.0, 0.0)))
+  draws = WindowAugment(draws.shift, draws.colour, **extras)
+  for k, v in feats.items():
     if isinstance(v, DeviceWindows):
-      v.augment = draws
+      v.augment, v.scene_tag = draws, SCENE_TAGS.get(k, 0)
   return feats
 
 
@@ -561,10 +607,18 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
   'target_rgb'; 'depth' / 'target_depth' take the same shift and no colour.  The host only draws (``draw_augment``, per emitted
   batch, generator ``default_rng([seed, rank, AUGMENT_STREAM])``: file order and shuffle picks are those without the option); the
   pixels are transformed on the device by the gather that builds the dense windows (DeviceWindows.augment).  Without
-  ``device`` it raises; other modes and ``synthetic:`` inputs ignore it."""
+  ``device`` it raises; other modes and ``synthetic:`` inputs ignore it.
+  Scene keys of the same dict (RGB streams only, depth keeps the shift alone; off by default, independent of the
+  three above): ``noise=sigma`` in [0, 1) adds sigma * z, z ~ N(0, 1) independent per window, frame, pixel and channel (and between
+  'rgb' and 'target_rgb'), then clips to [0, 1]; ``occlude=R`` in 0..4 paints up to R rectangles per window, one constant colour
+  each, the same in its K frames and its 'target_rgb' (a static distractor), with sides up to ``occlude_size`` (default 0.25) of
+  the frame's.  Order per element: shift / tint, rectangles, noise.  Their draws (``draw_augment_scene``) come from
+  ``default_rng([seed, rank, AUGMENT_SCENE_STREAM])``, so file order, shuffle picks and the shift / colour draws are those without
+  them."""
   if shuffle_windows and int(shuffle_buffer) < 1:
     raise ValueError('shuffle_windows needs shuffle_buffer >= 1, got %r' % (shuffle_buffer,))
   check_augment(augment)
+  check_augment_scene(augment)
   if encoding != 'v4':
     # v1-v3 are dead code in the reference (undefined PickAndPlaceEncodingV1/2/3 -> NameError)
     raise KeyError(encoding)
@@ -592,7 +646,8 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
     dp_schedule = [tuple(max(0, min(batch_size, w - s * batch_size)) for w in per_rank) for s in range(steps)]
     paths = paths[rank::world]
   aug = check_augment(augment, (meta.img_height, meta.img_width)) if mode == 'train' else None      # train-only, as the shuffles
-  if aug is not None and device is None:
+  scene = check_augment_scene(augment, (meta.img_height, meta.img_width)) if mode == 'train' else None
+  if (aug is not None or scene is not None) and device is None:
     raise ValueError("augment needs device= (e.g. 'cuda'): the windows are transformed on the device, where the resident frames "
                      "are; the host path has no augmentation")
   if device is not None:
@@ -607,10 +662,11 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
 
   def emitter():
     """What a finished batch passes through on its way out: the augmentation draws, in emission order."""
-    if aug is None:
+    if aug is None and scene is None:
       return lambda f, l: (f, l)
-    rng = np.random.default_rng(None if seed is None else [seed, shard[0] if shard is not None else 0, AUGMENT_STREAM])
-    return lambda f, l: (_augment_batch(f, rng, aug), l)
+    stream = lambda word: np.random.default_rng(None if seed is None else [seed, shard[0] if shard is not None else 0, word])
+    rng, scene_rng = stream(AUGMENT_STREAM), stream(AUGMENT_SCENE_STREAM)
+    return lambda f, l: (_augment_batch(f, rng, aug, scene_rng, scene, (meta.img_height, meta.img_width)), l)
 
   def shuffled_batches():
     import itertools

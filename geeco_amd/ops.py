@@ -192,6 +192,26 @@ def gather_windows_augmented_into(out, addr, kind, shift, colour, N, K, H, W, C)
         'geeco_gather_windows_augmented')
 
 
+def gather_windows_scene_into(out, addr, kind, shift, colour, occ_rect, occ_colour, noise_key, sigma, tag, N, K, H, W, C):
+  """gather_windows_augmented_into of an RGB stream (C == 3) with occluders and sensor noise behind the gather:
+  ``occ_rect`` int32 [N][4][4] = (y0, x0, h, w) per slot and ``occ_colour`` float32 [N][4][3], both None for no occluders;
+  ``noise_key`` int32 [2] (the two uint32 words of the Philox key, on the device; None only when ``sigma`` == 0); ``tag`` 0 for
+  'rgb', 1 for 'target_rgb'.  ONE launch (include/geeco_hip.h: geeco_gather_windows_scene)."""
+  if (occ_rect is None) != (occ_colour is None):
+    raise ValueError('gather_windows_scene: occ_rect and occ_colour come together')
+  tables = ((addr, torch.int64, N), (kind, torch.int32, N), (shift, torch.int32, 2 * N)) + (
+      () if colour is None else ((colour, torch.float32, 2 * C * N),)) + (
+      () if occ_rect is None else ((occ_rect, torch.int32, 16 * N), (occ_colour, torch.float32, 12 * N))) + (
+      () if noise_key is None else ((noise_key, torch.int32, 2),))
+  _check_tables(tables, out.device, 'gather_windows_scene: the tables must be contiguous int64 addresses [N], int32 kinds [N], '
+                'int32 shifts [N][2], float32 colour [N][%d], int32 rectangles [N][4][4], float32 rectangle colours [N][4][3] and '
+                'an int32 key [2] for N=%d on %s' % (2 * C, N, out.device))
+  if out.numel() < N * K * H * W * C:
+    raise ValueError('gather_windows_scene: output of %d floats for %d x %d frames of %d x %d x %d' % (out.numel(), N, K, H, W, C))
+  check(_lib().geeco_gather_windows_scene(_p(addr), _p(kind), _p(shift), _p(colour), _p(occ_rect), _p(occ_colour), _p(noise_key),
+                                          float(sigma), int(tag), N, K, H, W, C, _p(out), _stream()), 'geeco_gather_windows_scene')
+
+
 # -- batched predictor I/O (csrc/predict_io.hip; geeco_amd/batched_predictor.py) --------------------------------------------
 def predict_range_check_into(ctl, frames, B, HW, C, lo, hi):
   """ctl[b] = ctl[B] = 1 when channels 0..2 of env b's float32 frame leave [lo, hi] (or hold a NaN); never clears them."""

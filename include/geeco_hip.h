@@ -28,7 +28,7 @@ extern "C" {
 /* added within 7 (additive: no existing entry point or convention changed): geeco_lstm_seq_heads_fwd,
  * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd, geeco_gather_windows_by_address,
  * geeco_gather_windows_augmented, geeco_adam_tf_ema, geeco_adam_tf_segments_ema, geeco_clip_ws_floats,
- * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip */
+ * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip, geeco_gather_windows_scene */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -139,6 +139,21 @@ int geeco_gather_windows_by_address(const int64_t* addr, const int* kind, int N,
  * a time. */
 int geeco_gather_windows_augmented(const int64_t* addr, const int32_t* kind, const int32_t* shift, const float* colour, int N,
                                    int K, int H, int W, int C, float* out, void* stream);
+/* The augmented builder of an RGB stream (C must be 3) with occluders and sensor noise behind the gather
+ * (input_fn.pickplace_input_fn(augment=dict(noise=, occlude=))).  addr / kind / shift / colour, the argument checks and
+ * the launch shape as above.  Per element, in this order:  v1 = what geeco_gather_windows_augmented writes, bitwise;  v2 = the
+ * colour component of the highest-numbered rectangle of window n that holds the element's OUTPUT pixel (y, x), else v1:
+ * occ_rect [N][4][4] int32 = (y0, x0, h, w) per slot, a slot with h <= 0 or w <= 0 is empty, occ_colour [N][4][3] float32 = its
+ * RGB; both NULL: no occluders.  Any int32 content is valid (containment is overflow-free, no address is formed from it); the
+ * rectangles serve all K frames and paint over the zero border.  out = min(max(fma(sigma, z, v2), 0), 1), z standard normal from
+ * Philox4x32-10 under the key noise_key[0..1] (two uint32 words on the device, read when the kernel RUNS; may be NULL only when
+ * sigma == 0) and the counter (e / 4, k, n, tag), e = the element's offset in its frame: the four output words give the normals
+ * of elements 4g .. 4g + 3 by Box-Muller (words 0, 1 -> the first two, words 2, 3 -> the last two), so z depends on (key, tag,
+ * n, k, e) alone.  tag: 0 for 'rgb', 1 for 'target_rgb'.  0 <= sigma < 1; sigma == 0 skips the noise step (no clamp), and with
+ * NULL occluders too the output is bitwise geeco_gather_windows_augmented. */
+int geeco_gather_windows_scene(const int64_t* addr, const int32_t* kind, const int32_t* shift, const float* colour,
+                               const int32_t* occ_rect, const float* occ_colour, const uint32_t* noise_key, float sigma, int tag,
+                               int N, int K, int H, int W, int C, float* out, void* stream);
 
 /* ---- batched predictor I/O: B control loops per call (reference predictor.py:127-209 per env) ----------------------
  * The ingest and output stages of one replayed graph (geeco_amd/batched_predictor.py): range check -> window push ->

@@ -94,6 +94,15 @@ ARGPARSER.add_argument('--augment_gain', type=float, default=0.0,
 ARGPARSER.add_argument('--augment_bias', type=float, default=0.0,
                        help='... and add a random bias in [-b, b] to each RGB channel (values are clipped to [0, 1]).  0 = off.  '
                             'None of the three with --shared_frames: augmented windows share no frames.')
+ARGPARSER.add_argument('--augment_noise', type=float, default=0.0,
+                       help='... and add per-frame sensor noise sigma * N(0, 1) to every RGB value (0 <= sigma < 1), independent per '
+                            'window, frame, pixel and channel; values are clipped to [0, 1].  0 = off.')
+ARGPARSER.add_argument('--augment_occlude', type=int, default=0,
+                       help='... and paint up to this many (0..4) random one-colour rectangles over each window, the same in its K '
+                            'frames and its target frame (a static distractor).  0 = off.')
+ARGPARSER.add_argument('--augment_occlude_size', type=float, default=0.25,
+                       help="The largest side of such a rectangle as a fraction of the frame's, in (0, 1].  Not with --shared_frames "
+                            'either.')
 ARGPARSER.add_argument('--shared_frames', default=False, action='store_true',
                        help="Per-frame controllers (e2e_vmc; goal 'sequence' x 'constant' / 'residual'), one GPU, RGB: encode every "
                             'distinct frame of a batch once instead of once per window that holds it (same loss and gradients).  Needs '
@@ -171,8 +180,8 @@ def main(args):
     # (before anything is written or initialised)
     raise SystemExit('--shuffle_windows and --shared_frames exclude each other: a shuffled batch of N windows holds about N x K '
                      'distinct frames, so there is nothing for --shared_frames to share')
-  if (args.augment_shift or args.augment_gain or args.augment_bias) and args.shared_frames:
-    raise SystemExit('--augment_shift / --augment_gain / --augment_bias and --shared_frames exclude each other: every augmented '
+  if (args.augment_shift or args.augment_gain or args.augment_bias or args.augment_noise or args.augment_occlude) and args.shared_frames:
+    raise SystemExit('--augment_shift / _gain / _bias / _noise / _occlude and --shared_frames exclude each other: every augmented '
                      'window is transformed by its own draw, so no two windows share a frame')
   gdist.init_from_env()
   rank, world = gdist.rank(), gdist.world_size()
@@ -233,7 +242,8 @@ def main(args):
         window_size=e2evmc_config.window_size, fetch_target=(args.goal_condition == 'target'),
         shuffle_buffer=args.shuffle_buffer, num_epochs=1, num_threads=reader_threads,
         prefetch_size=args.prefetch_size, shuffle_windows=args.shuffle_windows,
-        augment=dict(shift=args.augment_shift, gain=args.augment_gain, bias=args.augment_bias),
+        augment=dict(shift=args.augment_shift, gain=args.augment_gain, bias=args.augment_bias, noise=args.augment_noise,
+                     occlude=args.augment_occlude, occlude_size=args.augment_occlude_size),
         # episodes are uploaded once (to THIS rank's GPU), stay there across epochs (input_fn.EPISODE_CACHE) and windows are
         # gathered in HBM; an RGB model never reads the depth stream
         device=dev,
