@@ -1,5 +1,6 @@
 // The fused bottom of the encoder's backward (family: conv_halo_common.h): conv2's input gradient and conv1's filter/bias
 // gradient in one kernel, conv2_dgrad_conv1_wgrad_kernel, and its entry points geeco_conv2_dgrad_conv1_wgrad*.
+// Every instantiation and launch form against float64 at small shapes: tests/native/conv_bottom_cases.txt.
 #define GEECO_ZERO_PAGE g_zero_page_bottom
 #include "conv_halo_common.h"
 #include "conv_internal.h"
@@ -450,7 +451,11 @@ static int fused_bottom_impl(const float* dz2, const float* w2, const float* y1,
   p.dz = dz2; p.w = w2; p.mask = y1; p.x = x; p.part = (float*)ws; p.dx = dz1;
   p.bits = y1_bits; p.gs_bits = gs_bits; p.Wp = (int)geeco_relu_bits_pitch(W); p.Hp = (int)geeco_relu_bits_rows(H);
   p.gs_dz = gs_dz2; p.gs_w = gs_w2; p.gs_y = gs_y1; p.gs_x = gs_x;
-  const BottomSlices bs = fill_bottom_geometry(p, groups, N, H, W, cdiv(W, 64), cdiv(H, 8));
+  // tile grid and slicing: conv_wgrad_plan.h (plain C++ the host tests evaluate), on the CUs this call may occupy
+  const FusedBottomLaunchPlan lp = fused_bottom_launch_plan(WGRAD_CUS - geeco_call_reserved_cus(), groups, N, H, W);
+  p.N = N; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2;
+  p.tiles_x = lp.tiles_x; p.tiles_y = lp.tiles_y; p.tiles_per_group = lp.tiles;
+  p.S = lp.S; p.S0 = lp.S0; p.per = lp.per; p.groups = groups;
   const size_t lds = FB_LDS_BYTES;
   // all four instantiations on the first call, as ever: none is left to opt in on a later call (inside a graph capture, say)
   int rc = geeco_lds_opt_in<&conv2_dgrad_conv1_wgrad_kernel<3, false>>(lds);
@@ -460,7 +465,7 @@ static int fused_bottom_impl(const float* dz2, const float* w2, const float* y1,
   if (rc) return rc;
   p.stamps = geeco_arm_halo_stamps();
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)bs.blocks);
+  const dim3 grid((unsigned)lp.blocks);
   const bool bits = y1_bits != nullptr;
   geeco_note_kernel("conv2_dgrad_conv1_wgrad_kernel<%d, %s>", real_channels == 3 ? 3 : 4, bits ? "true" : "false");
   if (real_channels == 3 && bits)

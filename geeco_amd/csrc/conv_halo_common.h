@@ -91,7 +91,8 @@ static BottomSlices bottom_slices(int groups, long long T, bool for_ws = false) 
   return bottom_slices_on(WGRAD_CUS - (for_ws ? 0 : geeco_call_reserved_cus()), groups, T, for_ws);
 }
 
-// tile grid of one encoder and its slicing over the persistent blocks (HaloWgradParams, FusedBottomParams)
+// tile grid of one encoder and its slicing over the persistent blocks (HaloWgradParams; the fused bottom takes its own from
+// fused_bottom_launch_plan)
 template <class P>
 static BottomSlices fill_bottom_geometry(P& p, int groups, int N, int H, int W, int tiles_x, int tiles_y) {
   p.N = N; p.H = H; p.W = W; p.Ho = H / 2; p.Wo = W / 2;

@@ -157,6 +157,31 @@ static inline bool halo_wgrad_handles(int H, int W, int Cin, int Cout, int strid
   return stride == 2 && Cin == 32 && Cout == 48 && H % 2 == 0 && W % 2 == 0;
 }
 
+// the fused conv2-dgrad + conv1-wgrad (conv_halo_bottom.hip): 8 x 64 input pixels per tile, walked by the same persistent blocks.
+// tests/native/conv_bottom_cover.cpp holds the plan of every case of tests/native/conv_bottom_cases.txt against the text recorded there.
+constexpr int FUSED_BOTTOM_TH = 8, FUSED_BOTTOM_TW = 64;
+
+struct FusedBottomLaunchPlan {
+  int tiles_x, tiles_y;      // per frame
+  int tiles;                 // per encoder: N * tiles_x * tiles_y
+  int S0, per, S, blocks;    // BottomSlices
+  long long slice_px;        // per * 8 * 64: the most pixels one slab accumulates (a ragged tile holds fewer; the remainder block
+                             // walks at most per / groups tiles per encoder)
+  bool remainder;            // the remainder-block form (S == S0 + 1): block S0 * groups walks what every encoder leaves over
+};
+
+static inline FusedBottomLaunchPlan fused_bottom_launch_plan(int cus, int groups, int N, int H, int W) {
+  FusedBottomLaunchPlan l = {};
+  l.tiles_x = cdiv(W, FUSED_BOTTOM_TW);
+  l.tiles_y = cdiv(H, FUSED_BOTTOM_TH);
+  l.tiles = N * l.tiles_x * l.tiles_y;
+  const BottomSlices bs = bottom_slices_on(cus, groups, l.tiles, false);
+  l.S0 = bs.S0; l.per = bs.per; l.S = bs.S; l.blocks = bs.blocks;
+  l.slice_px = (long long)bs.per * FUSED_BOTTOM_TH * FUSED_BOTTOM_TW;
+  l.remainder = bs.S == bs.S0 + 1;
+  return l;
+}
+
 // ---- the dispatch order of geeco_conv3x3_wgrad ----------------------------------------------------------------------------
 static inline WgradFamily wgrad_family(int groups, int N, int H, int W, int Cin, int Cout, int stride) {
   if (halo_wgrad_handles(H, W, Cin, Cout, stride)) return WGRAD_FAMILY_HALO;

@@ -4,7 +4,9 @@ tests/test_conv_cover_cpu.py that the case list (tests/native/conv_gemm_cases.tx
 The same four parts for the filter gradient (geeco_conv3x3_wgrad) are at the end of this file: tests/native/conv_wgrad_cases.txt,
 tests/test_conv_wgrad_variants_gpu.py, tests/test_conv_wgrad_refs_cpu.py, tests/test_conv_wgrad_cover_cpu.py.  Behind them the same
 four parts for the LDS-halo and LDS-staged forwards and input gradients: tests/native/conv_halo_cases.txt,
-tests/test_conv_halo_variants_gpu.py, tests/test_conv_halo_refs_cpu.py, tests/test_conv_halo_cover_cpu.py.
+tests/test_conv_halo_variants_gpu.py, tests/test_conv_halo_refs_cpu.py, tests/test_conv_halo_cover_cpu.py.  Last, for the fused
+encoder-bottom backward (conv2's input gradient + conv1's filter gradient in one kernel): tests/native/conv_bottom_cases.txt,
+tests/test_conv_bottom_variants_gpu.py, tests/test_conv_bottom_refs_cpu.py, tests/test_conv_bottom_cover_cpu.py.
 
 Everything here is written from the definition of tf.layers.conv2d(kernel_size=3, padding='SAME') on NHWC tensors with an HWIO
 kernel, not from the kernels: the padded input is built explicitly, the output is the sum over the nine taps of a strided window
@@ -548,4 +550,190 @@ def halo_compare(c, exact, got, inp, ref, bound, keep):
     n = int(np.count_nonzero(np.ascontiguousarray(got).view(np.uint32)[off]))
     if n:
       problems.append('bits: %d masked elements are not +0.0' % n)
+  return worst, problems
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# fused encoder-bottom backward (conv2_dgrad_conv1_wgrad_kernel<CREAL, BITS>): case list, reference, seeded inputs, bounds
+# --------------------------------------------------------------------------------------------------------------------------
+BOTTOM_CASES_TXT = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'native', 'conv_bottom_cases.txt')
+
+BottomCase = collections.namedtuple('BottomCase', 'index G N H W C flags reserved text plan inst tiles blocks S per slice_px remainder '
+                                    'cross empty')
+_BOTTOM_PLAN = re.compile(r'^(conv2_dgrad_conv1_wgrad_kernel<([34]), (true|false)>) tiles=(\d+) blocks=(\d+) S=(\d+) per=(\d+) '
+                          r'slice_px=(\d+) (remainder|regular) cross=(\S+) empty=(\d+)$')
+_BOTTOM_FLAGS = {'mask', 'bits', 'dz1', 'pending'}
+
+
+def load_bottom_cases():
+  """The cases of tests/native/conv_bottom_cases.txt with the plan recorded beside each (tests/test_conv_bottom_cover_cpu.py holds
+  that text against what fused_bottom_launch_plan of geeco_amd/csrc/conv_wgrad_plan.h gives)."""
+  cases = []
+  for line in open(BOTTOM_CASES_TXT):
+    line = line.strip()
+    if not line or line.startswith('#'):
+      continue
+    text, plan = (s.strip() for s in line.split('|'))
+    f = text.split()
+    flags = frozenset(t for t in f[5:] if not t.startswith('reserved='))
+    reserved = [int(t.split('=')[1]) for t in f[5:] if t.startswith('reserved=')]
+    m = _BOTTOM_PLAN.match(plan)
+    assert m and flags <= _BOTTOM_FLAGS and len(reserved) <= 1, line
+    c = BottomCase(len(cases), *(int(v) for v in f[:5]), flags, reserved[0] if reserved else 0, text, plan, m.group(1),
+                   *(int(m.group(i)) for i in range(4, 9)), m.group(9) == 'remainder', frozenset(m.group(10).split('+')) - {'none'},
+                   int(m.group(11)))
+    # one mask form, and it is the instantiation's; dz1 is stored by the float-mask forms only; reserved CUs need the deferred form
+    assert ('mask' in flags) != ('bits' in flags) and ('bits' in flags) == (m.group(3) == 'true') and int(m.group(2)) == c.C, line
+    assert not {'dz1', 'bits'} <= flags and (not c.reserved or 'pending' in flags), line
+    cases.append(c)
+  return cases
+
+
+def bottom_key(c):
+  """The key tests/native/conv_bottom_cover.cpp prints for the sweep's launches."""
+  return '%s %s cross=%s' % ('bits' if 'bits' in c.flags else 'mask', 'remainder' if c.remainder else 'regular',
+                             '+'.join(k for k in ('frame', 'enc') if k in c.cross) or 'none')
+
+
+def bottom_kernel_names(c):
+  """What ops.kernel_trace records for the entry point: the instantiation and the slab sum (85 or more slabs of 1184 floats: the
+  split form), unless that is deferred -- ops.slab_reduce_batch then launches wgrad_reduce_batch_kernel."""
+  return [c.inst] + ([] if 'pending' in c.flags else ['wgrad_reduce_kernel<true>'])
+
+
+def bottom_pixels(c):
+  return c.N * c.H * c.W
+
+
+def bottom_ranges(c):
+  """[(encoder, slab, first tile, end tile)] of every block (the remainder block: one entry per encoder), from the recorded plan:
+  regular block b of S0 = S - remainder per encoder walks [b per, min(b per + per, tiles)), the remainder block [S0 per, tiles)
+  of every encoder into slab S0."""
+  S0 = c.S - (1 if c.remainder else 0)
+  out = [(g, b, b * c.per, max(b * c.per, min(b * c.per + c.per, c.tiles))) for g in range(c.G) for b in range(S0)]
+  if c.remainder:
+    out += [(g, S0, S0 * c.per, c.tiles) for g in range(c.G)]
+  return out
+
+
+BOTTOM_EXACT_MAX = 4 * 48 * 2      # |dz1| in the exact pass: at most 4 taps reach a pixel, 48 channels, |dz2| <= 2, |w2| <= 1
+
+
+def bottom_slab_bound(mag, slice_px, S):
+  """wgrad_bound with the fused kernel's block reduction: its eight waves each keep partial tiles of the block's slice and are
+  summed through LDS in seven additions where wgrad_bound allows three -> (slice_px + S + 12) U mag.  The second-order terms,
+  n^2 U^2 at n = 6144 + 43 + 7, the longest chain of the case list, are 2.3 U: inside the 5 U wgrad_bound keeps for them."""
+  return wgrad_bound(mag, slice_px, S) + 4.0 * U * mag
+
+
+def _bottom_shape_key(c):
+  return (c.G, c.N, c.H, c.W, c.C)
+
+
+@functools.lru_cache(maxsize=2)
+def _bottom_shape_expect(key, exact):
+  """Inputs and the float64 results of a shape, shared by the cases that differ in mask form, entry point or CUs.
+  x [G][N][H][W][4] (C = 3: the pad channel holds data too -- it has no column in dw1 and must not reach it), w2 [G][3][3][32][48],
+  dz2 [G][N][H/2][W/2][48], mask [G][N][H][W][32]: about half of it is not > 0, with exact zeros and negative values.
+    exact: x, w2, mask in {-1, 0, 1} (mask: a quarter -1, a quarter 0), dz2 integers in [-2, 2];  otherwise N(0, 1), a tenth of
+    the mask set to exactly 0.
+  Per encoder, from the definitions (conv2: stride 2, conv1: stride 1, TF SAME):
+    dz1 = on * conv2_dgrad(dz2, w2), on = mask > 0 (data, not a computed sign);
+    dw1[tap][c][co] = sum_p x[p + tap][c] dz1[p][co] over the C real channels;   db1 = sum_p dz1[p].
+  e1: dz1's own rounding bound, conv_bound(mag, taps * 48, S = 1) where the mask is on and 0 where it is off (exact: 0);
+  ew, eb: what e1 can move dw1 / db1 by, sum_p |x| e1;  mw, mb: the magnitudes sum_p |x| (|dz1| + e1) of the filter gradient's terms.
+  Callers leave the arrays unchanged."""
+  G, N, H, W, C = key
+  r = np.random.default_rng([4000 + (1 if exact else 0), G, N, H, W, C])
+  f = lambda a: a.astype(np.float32)
+  sx, sw, sz, sm = (G, N, H, W, 4), (G, 3, 3, 32, 48), (G, N, H // 2, W // 2, 48), (G, N, H, W, 32)
+  if exact:
+    x, w2, dz2 = f(r.integers(-1, 2, sx)), f(r.integers(-1, 2, sw)), f(r.integers(-2, 3, sz))
+    mask = f(r.choice(np.array([-1, 0, 1, 1]), sm))
+  else:
+    x, w2, dz2 = f(r.standard_normal(sx)), f(r.standard_normal(sw)), f(r.standard_normal(sz))
+    mask = r.standard_normal(sm, dtype=np.float32)
+    mask[r.random(sm, dtype=np.float32) < 0.1] = 0.0
+  on = mask > 0
+  out = collections.defaultdict(list)
+  terms = dgrad_terms((H, W), 2, 48)[None]
+  for g in range(G):
+    z64, w64 = dz2[g].astype(np.float64), w2[g].astype(np.float64)
+    pre = _dgrad(z64, w64, (H, W), 2)
+    dz1 = np.where(on[g], pre, 0.0)
+    e1 = np.zeros_like(dz1) if exact else np.where(on[g], conv_bound(_dgrad(np.abs(z64), np.abs(w64), (H, W), 2), terms, 1), 0.0)
+    xr = x[g][..., :C].astype(np.float64)
+    dw, db = _wgrad(xr, dz1, 1)
+    ew, eb = _wgrad(np.abs(xr), e1, 1)
+    eb = e1.reshape(-1, 32).sum(0)
+    mw, _ = _wgrad(np.abs(xr), np.abs(dz1) + e1, 1)
+    mb = (np.abs(dz1) + e1).reshape(-1, 32).sum(0)
+    for k, v in dict(dz1=dz1, e1=e1, dw=dw, db=db, ew=ew, eb=eb, mw=mw, mb=mb).items():
+      out[k].append(v)
+  res = {k: np.stack(v) for k, v in out.items()}
+  for a in res.values():      # (the operands go to torch.from_numpy, which wants them writable: the device test checks them unchanged)
+    a.setflags(write=False)
+  res.update(x=x, w2=w2, dz2=dz2, mask=mask)
+  return res
+
+
+def bottom_case_expect(c, exact):
+  """-> dict: the inputs (x, w2, dz2, mask), the float64 results (dw [G][3][3][C][32], db [G][32], dz1 [G][N][H][W][32]) and their
+  bounds (bw, bb, e1).
+  exact: every dz1 is an integer of magnitude <= 384 and every partial sum of dw1 / db1 an integer of magnitude <= 384 N H W < 2**24
+  (asserted), which float32 holds exactly, so any order of float32 additions through any MFMA, tile walk, LDS reduction or slab
+  sum gives the float64 result: all bounds are 0 and the comparison is equality.
+  Otherwise dz1 is held under e1, and dw1 under
+      sum_p |x| e1  +  bottom_slab_bound(sum_p |x| (|dz1| + e1), slice_px, S)
+  -- the filter gradient of the float64 dz1 moved by dz1's own error, plus the rounding of a float32 filter gradient whose terms
+  are at most |x| (|dz1| + e1), in S slabs of at most slice_px pixels (the case's recorded plan) -- and db1 under the same with
+  |x| = 1.  No element is left out: where the mask is off, dz1 is 0 with bound 0."""
+  e = dict(_bottom_shape_expect(_bottom_shape_key(c), bool(exact)))
+  if exact:
+    assert BOTTOM_EXACT_MAX * bottom_pixels(c) < 2 ** 24, c.text
+    e['bw'], e['bb'] = np.zeros_like(e['dw']), np.zeros_like(e['db'])
+  else:
+    e['bw'] = e['ew'] + bottom_slab_bound(e['mw'], c.slice_px, c.S)
+    e['bb'] = e['eb'] + bottom_slab_bound(e['mb'], c.slice_px, c.S)
+  return e
+
+
+def bottom_bits_planes(c, mask):
+  """The signs of ``mask`` [G][N][H][W][32] as the sign-word entry point wants them, packed on the host: uint32 [G][N][Hp][Wp],
+  whole 8 x 64 tiles, zero outside the image (the entry point's contract)."""
+  return pad_planes(pack_bits32(np.asarray(mask) > 0), *tiles_8x64(c.H, c.W), np.uint32(0))
+
+
+def bottom_compare(c, exact, got, e):
+  """The comparisons of one pass of tests/test_conv_bottom_variants_gpu.py on ``got`` = dict(dw, db[, dz1]) float32 [G][...] against
+  bottom_case_expect's ``e`` -> (worst share of a rounding bound per output, problems): what the device test asserts empty and
+  tests/test_conv_bottom_refs_cpu.py holds against emulated kernels with one mistake each.  Every element of every output is
+  compared: none is NaN, exact pass: equality with the float64 result; rounding pass: within its bound (0 where the mask is off)."""
+  problems, worst = [], {}
+  for name, ref, bound in (('dw', e['dw'], e['bw']), ('db', e['db'], e['bb']), ('dz1', e['dz1'], e['e1'])):
+    if name not in got:
+      continue
+    worst[name] = 0.0
+    g64 = np.asarray(got[name]).astype(np.float64)
+    assert g64.shape == ref.shape == bound.shape and np.isfinite(bound).all(), (name, g64.shape, ref.shape)
+    if np.isnan(g64).any():
+      problems.append('nan %s: %d elements' % (name, int(np.isnan(g64).sum())))
+    if exact:
+      bad = ~(g64 == ref)
+      if bad.any():
+        at = tuple(np.argwhere(bad)[0])
+        problems.append('exact %s: %d of %d elements differ from the float64 result, the first at %s: got %.9g, reference %.9g' % (
+            name, int(bad.sum()), bad.size, at, g64[at], ref[at]))
+    else:
+      err = np.abs(g64 - ref)
+      bad = ~(err <= bound)
+      live = bound > 0
+      ratio = err[live] / bound[live]
+      ratio = ratio[~np.isnan(ratio)]
+      if ratio.size:
+        worst[name] = float(ratio.max())
+      if bad.any():
+        at = tuple(np.argwhere(bad)[0])
+        problems.append('rounding %s: %d of %d elements out of bound, the first at %s: got %.9g, reference %.9g (bound %.3e)' % (
+            name, int(bad.sum()), bad.size, at, g64[at], ref[at], bound[at]))
   return worst, problems

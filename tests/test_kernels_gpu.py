@@ -446,6 +446,8 @@ def test_conv3x3_grouped_halo_kernels(dev, Cin, Cout, Nf, Nd):
 # second one partial) and a block whose tile range crosses an image boundary.
 # (3, 8, 64, 256): 256 tiles per encoder = 85 blocks x 3 + 1: the launch takes the remainder-block form (one more block
 # walks the tile each encoder leaves over: three segments, three slabs)
+# (All four instantiations against a float64 reference with host-packed sign words, exact integers, guard values, ragged tiles with
+# dz1, every remainder form, reserved CUs: tests/native/conv_bottom_cases.txt, tests/test_conv_bottom_variants_gpu.py.)
 @pytest.mark.parametrize('G,N,H,W,C', [(1, 2, 16, 64, 3), (3, 3, 24, 72, 3), (2, 40, 32, 64, 3), (2, 3, 24, 72, 4),
                                        (3, 8, 64, 256, 3)])
 def test_conv2_dgrad_conv1_wgrad_fused(dev, G, N, H, W, C):
