@@ -56,6 +56,16 @@ class AdamSegment(Structure):
 
 ADAM_SEGMENTS_MAX = 8
 
+LR_KINDS = ('constant', 'exponential', 'cosine', 'piecewise')      # GEECO_LR_* of include/geeco_hip.h, in order
+LR_BOUNDARIES_MAX = 8
+
+
+class LrSchedule(Structure):
+  """geeco_lr_schedule (include/geeco_hip.h): a learning-rate schedule as the device holds it (float rates, int64 step counts)."""
+  _fields_ = [('kind', c_int32), ('base_lr', c_float), ('warmup_steps', c_int64), ('decay_steps', c_int64), ('decay_rate', c_float),
+              ('alpha', c_float), ('staircase', c_int32), ('n_boundaries', c_int32), ('boundaries', c_int64 * LR_BOUNDARIES_MAX),
+              ('values', c_float * (LR_BOUNDARIES_MAX + 1))]
+
 # symbol -> (restype, argtypes); mirrors include/geeco_hip.h one to one
 SIGNATURES = {
     'geeco_abi_version': (_I, []),
@@ -149,6 +159,9 @@ SIGNATURES = {
     'geeco_grad_sumsq_segments': (_I, [_P, _P, _I, _L, _F, _F, _P, _P]),
     'geeco_clip_scale': (_I, [_P, _L, _F, _P, _P]),
     'geeco_adam_tf_segments_clip': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _P, _F, _F, _F, _F, _F, _P]),
+    'geeco_adam_prepare_schedule': (_I, [_P, POINTER(LrSchedule), _F, _F, _P, _P]),
+    'geeco_slab_reduce_batch_prepare_schedule': (_I, [POINTER(SlabReduce), _I, _P, POINTER(LrSchedule), _F, _F, _P, _P]),
+    'geeco_lr_schedule_eval': (_I, [POINTER(LrSchedule), _L, POINTER(ctypes.c_double)]),
     'geeco_sumsq': (_I, [_P, _L, _P, _P]),
 }
 

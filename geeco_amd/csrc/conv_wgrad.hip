@@ -20,6 +20,7 @@
 #include "conv_wgrad_body.h"
 #include "conv_internal.h"
 #include "conv_wgrad_plan.h"
+#include "lr_schedule.h"
 
 template <int BR, int BC, int MK>
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
@@ -132,6 +133,34 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(const SlabReduc
     wgrad_reduce_body<false>(it.part, it.dw, it.db, it.gs_dw, it.gs_db, it.S, it.KC, it.Cout, g, bx, sred);
 }
 
+// ... and under a learning-rate schedule (geeco_slab_reduce_batch_prepare_schedule): the rider evaluates lr(s) at the
+// step it advances the counter to (lr_schedule.h) and also leaves it in scal[2].  A kernel of its own, so that the one above and its
+// argument block stay what they were.  The walk through the table is restated: as an inline function shared by the two it gave the
+// kernel above other code (the selects came out branch-free, two SGPRs fewer), which nobody has timed; every item is still summed
+// by wgrad_reduce_body, so the sums are bitwise the same (tests/test_lr_schedule_gpu.py).
+__global__ __launch_bounds__(256) void wgrad_reduce_batch_schedule_kernel(const SlabReduceBatch b, const geeco_lr_schedule sc) {
+  __shared__ f32x4 sred[4][64];
+  const int bid = blockIdx.x;
+  if (bid == b.prep_block) {
+    if (threadIdx.x == 0) adam_prepare_schedule_step(b.step, sc, b.b1, b.b2, b.scal);
+    return;
+  }
+  geeco_slab_reduce it = b.it[0];
+  int first = 0, bpg = b.bpg[0], split = b.split[0];
+#pragma unroll
+  for (int i = 1; i < GEECO_SLAB_REDUCE_MAX; ++i) {
+    if (i < b.n && bid >= b.first[i]) {
+      it = b.it[i]; first = b.first[i]; bpg = b.bpg[i]; split = b.split[i];
+    }
+  }
+  const int lb = bid - first;
+  const int g = lb / bpg, bx = lb - g * bpg;
+  if (split)
+    wgrad_reduce_body<true>(it.part, it.dw, it.db, it.gs_dw, it.gs_db, it.S, it.KC, it.Cout, g, bx, sred);
+  else
+    wgrad_reduce_body<false>(it.part, it.dw, it.db, it.gs_dw, it.gs_db, it.S, it.KC, it.Cout, g, bx, sred);
+}
+
 // while a *_partial entry point runs on this thread, the slab sum is recorded here instead of launched
 static thread_local geeco_slab_reduce* tl_pending = nullptr;
 void geeco_set_pending_reduce(geeco_slab_reduce* p) { tl_pending = p; }
@@ -156,7 +185,7 @@ void geeco_launch_wgrad_reduce(const float* part, float* dw, float* db, long lon
 }
 
 static int slab_reduce_batch_impl(const geeco_slab_reduce* items, int n, int64_t* step, float lr, float b1, float b2, float* scal,
-                                  void* stream);
+                                  void* stream, const geeco_lr_schedule* schedule = nullptr);
 
 extern "C" int geeco_slab_reduce_batch(const geeco_slab_reduce* items, int n, void* stream) {
   return slab_reduce_batch_impl(items, n, nullptr, 0.f, 0.f, 0.f, nullptr, stream);
@@ -168,8 +197,16 @@ extern "C" int geeco_slab_reduce_batch_prepare(const geeco_slab_reduce* items, i
   return slab_reduce_batch_impl(items, n, global_step_dev, lr, beta1, beta2, scal_dev, stream);
 }
 
+extern "C" int geeco_slab_reduce_batch_prepare_schedule(const geeco_slab_reduce* items, int n, int64_t* global_step_dev,
+                                                        const geeco_lr_schedule* schedule, float beta1, float beta2, float* scal_dev,
+                                                        void* stream) {
+  GEECO_CHECK_ARG(global_step_dev && scal_dev, "slab_reduce_batch_prepare_schedule: null pointer");
+  if (int rc = check_lr_schedule("slab_reduce_batch_prepare_schedule", schedule)) return rc;
+  return slab_reduce_batch_impl(items, n, global_step_dev, 0.f, beta1, beta2, scal_dev, stream, schedule);
+}
+
 static int slab_reduce_batch_impl(const geeco_slab_reduce* items, int n, int64_t* step, float lr, float b1, float b2, float* scal,
-                                  void* stream) {
+                                  void* stream, const geeco_lr_schedule* schedule) {
   GEECO_CHECK_ARG(n >= 0 && n <= GEECO_SLAB_REDUCE_MAX && (items || n == 0), "slab_reduce_batch: n = %d (0..%d)", n,
                   GEECO_SLAB_REDUCE_MAX);
   SlabReduceBatch b = {};
@@ -192,8 +229,13 @@ static int slab_reduce_batch_impl(const geeco_slab_reduce* items, int n, int64_t
     b.step = (long long*)step; b.scal = scal; b.lr = lr; b.b1 = b1; b.b2 = b2;
   }
   if (blocks == 0) return 0;
-  geeco_note_kernel("wgrad_reduce_batch_kernel");
-  hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, b);
+  if (schedule) {                       // (checked by the caller, and only ever given with `step`)
+    geeco_note_kernel("wgrad_reduce_batch_schedule_kernel");
+    hipLaunchKernelGGL(wgrad_reduce_batch_schedule_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, b, *schedule);
+  } else {
+    geeco_note_kernel("wgrad_reduce_batch_kernel");
+    hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, b);
+  }
   GEECO_LAUNCH_CHECK();
   return 0;
 }

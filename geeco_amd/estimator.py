@@ -29,7 +29,7 @@ from . import graph
 from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
 from .tf_checkpoint import EMA_SUFFIX
-from .variables import check_clip_norm, check_ema_decay
+from .variables import check_clip_norm, check_ema_decay, check_lr_schedule
 
 
 class ModeKeys:
@@ -185,12 +185,14 @@ class _SummarySaverHook:
     parts = {k: float(v) for k, v in self.model.loss_parts().items()}
     if getattr(self.model, 'clip_out', None) is not None:      # params['clip_norm']: the norm of this step's gradient before clipping
       parts['grad_norm'] = float(self.model.clip_out[1])
+    if getattr(self.model, 'lr_schedule', None) is not None:   # params['lr_schedule']: the rate this step was taken with, as the device formed it
+      parts['learning_rate'] = float(self.model.scal[2])
     parts['global_step'] = step
     parts['wall_time'] = time.time()
     if model_dir:
       with open(os.path.join(model_dir, 'events.jsonl'), 'a') as f:
         f.write(json.dumps(parts) + '\n')
-      self._writer(model_dir).add_scalars({k: v for k, v in parts.items() if k.startswith('loss')}, step, parts['wall_time'])
+      self._writer(model_dir).add_scalars({k: v for k, v in parts.items() if k.startswith('loss') or k == 'learning_rate'}, step, parts['wall_time'])
     print('INFO: loss = %.6f, step = %d' % (parts['loss'], step), flush=True)
 
 
@@ -231,6 +233,9 @@ def _model_fn(features, labels, mode, params, goal):
   clip = check_clip_norm(params.get('clip_norm'), "params['clip_norm']")
   if training and clip is not None:
     ema['clip_norm'] = clip
+  # params['lr_schedule']: the learning rate follows the device's step counter, from cfg.lr as the base rate
+  if training and check_lr_schedule(params.get('lr_schedule'), cfg.lr, "params['lr_schedule']") is not None:
+    ema['lr_schedule'] = params['lr_schedule']
   shared = params.get('shared_frames')
   tables = {}
   if shared:
@@ -340,6 +345,7 @@ class Estimator:
     self.params = dict(params or {})
     check_ema_decay(self.params.get('ema_decay'), "params['ema_decay']")
     check_clip_norm(self.params.get('clip_norm'), "params['clip_norm']")
+    check_lr_schedule(self.params.get('lr_schedule'), getattr(self.params.get('e2evmc_config'), 'lr', 0.0), "params['lr_schedule']")
     self._specs = {}          # (mode, N) -> (spec, feature buffers, label buffers)
     self.last_train_stats = None
     self._store = None

@@ -27,7 +27,7 @@ from . import ops
 from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
-from .variables import _CELLS, VariableStore, check_clip_norm, check_ema_decay, model_variable_shapes
+from .variables import _CELLS, VariableStore, check_clip_norm, check_ema_decay, check_lr_schedule, model_variable_shapes
 
 
 def build_store(cfg, goal, device, ema=False):
@@ -80,10 +80,14 @@ class BesideBottom:
 class _ModelBase:
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
-  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None):
+  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None, lr_schedule=None):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
     self.ema_decay = check_ema_decay(ema_decay)
     self.clip_norm = check_clip_norm(clip_norm)
+    # lr_schedule (DESIGN 5.18): the normalised schedule, and the struct the prepare work is handed in place of cfg.lr
+    # (_prepare_args, _prepare_unless_done); the device then leaves lr(s) of the step in scal[2].  None: cfg.lr, as ever.
+    self.lr_schedule = check_lr_schedule(lr_schedule, cfg.lr)
+    self._lr_arg = float(cfg.lr) if self.lr_schedule is None else ops.lr_schedule_struct(self.lr_schedule)
     self.shared_frames = self._check_shared_frames(cfg, goal, shared_frames)
     self.device = torch.device(device)
     self.K = cfg.window_size
@@ -129,7 +133,7 @@ class _ModelBase:
       self.inputs['target_rgb'] = torch.zeros(N, H, W, 3, **f32)
       if self.C == 4:
         self.inputs['target_depth'] = torch.zeros(N, H, W, 1, **f32)
-    self.scal = torch.zeros(4, **f32)          # [0] = Adam lr_t, [1] = sum of squares of the arena
+    self.scal = torch.zeros(4, **f32)          # [0] = Adam lr_t, [1] = sum of squares of the arena, [2] = lr(s) under lr_schedule
     self.world = 1
     self._prepared = False      # this step's backward has done adam_prepare's work (_prepare_args; runtime.py sets it too)
     self._opt_stream = None     # optimizer_stream()
@@ -300,12 +304,15 @@ class _ModelBase:
     if not adam_prepare:
       return None
     self._prepared = True
-    return (self.store.global_step, float(self.cfg.lr), self.scal)
+    return (self.store.global_step, self._lr_arg, self.scal)
 
   def _prepare_unless_done(self, last=True):
     """adam_prepare unless this step's backward carried it; ``last``: the optimiser step is complete behind this piece."""
     if not self._prepared:
-      ops.adam_prepare(self.store.global_step, float(self.cfg.lr), self.scal)
+      if self.lr_schedule is None:
+        ops.adam_prepare(self.store.global_step, self._lr_arg, self.scal)
+      else:
+        ops.adam_prepare_schedule(self.store.global_step, self._lr_arg, self.scal)
     self._prepared = not last
 
   def apply_gradients_of(self, segments, g_out=None, last=True):
@@ -446,10 +453,11 @@ class _ModelBase:
 class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None):
-    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``: see E2EVMC."""
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
+               lr_schedule=None):
+    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``, ``lr_schedule``: see E2EVMC."""
     super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm)
+                     clip_norm=clip_norm, lr_schedule=lr_schedule)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -579,18 +587,22 @@ class GoalE2EVMC(_ModelBase):
 class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None):
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
+               lr_schedule=None):
     """``ema_decay`` (a float in (0, 1); None / 0 = off): the optimiser step also keeps an exponential moving average of the
     parameters in ``store.ema`` (tf.train.ExponentialMovingAverage with num_updates = global_step); a store passed in
     must have been built with the arena (``build_store(..., ema=True)``).
     ``clip_norm`` (a finite number > 0; None / 0 = off): the optimiser step clips the total gradient g / world + l2 * p by its global norm
     first (tf.clip_by_global_norm), on the device; ``clip_out`` then holds [scale, norm before clipping] of the last step.
+    ``lr_schedule`` (``variables.check_lr_schedule``; None, or 'constant' without warm-up = off): the learning rate of every step is the
+    schedule's value at the device's step counter, with ``cfg.lr`` as its base rate, evaluated by the thread that forms Adam's lr_t
+    (DESIGN 5.18): a captured step follows it and a restored counter continues it; ``scal[2]`` then holds the rate of the last step.
     ``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
     'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
     super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm)
+                     clip_norm=clip_norm, lr_schedule=lr_schedule)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     self.window_mode, self.feat_ch = 'plain', [256]
     # frames are processed time-major ([K][N]) so that step t's features are one dense block

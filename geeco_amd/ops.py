@@ -404,15 +404,21 @@ def conv_top_bwd_into(d, a, b, G, stride, pending=None):
 
 def slab_reduce_batch(pending, prepare=None, beta1=0.9, beta2=0.999):
   """Finishes the deferred slab sums of ``pending`` (<= 8 per launch) and empties the list.  ``prepare`` = (global_step, lr,
-  scal): the last launch also does adam_prepare's work (one block more instead of a dependent launch)."""
+  scal): the last launch also does adam_prepare's work (one block more instead of a dependent launch); a learning-rate schedule
+  (``lr_schedule_struct``) in place of the float ``lr``: adam_prepare_schedule's."""
   MAX = 8
   chunks = [pending[i:i + MAX] for i in range(0, len(pending), MAX)] or ([[]] if prepare is not None else [])
   for j, chunk in enumerate(chunks):
     arr = (_native.SlabReduce * max(len(chunk), 1))(*chunk)
     if prepare is not None and j == len(chunks) - 1:
       step, lr, scal = prepare
-      check(_lib().geeco_slab_reduce_batch_prepare(arr, len(chunk), _p(step), float(lr), beta1, beta2, _p(scal), _stream()),
-            'geeco_slab_reduce_batch_prepare')
+      if isinstance(lr, (dict, _native.LrSchedule)):
+        _scal_holds_lr(scal)
+        check(_lib().geeco_slab_reduce_batch_prepare_schedule(arr, len(chunk), _p(step), ctypes.byref(lr_schedule_struct(lr)), beta1, beta2,
+                                                              _p(scal), _stream()), 'geeco_slab_reduce_batch_prepare_schedule')
+      else:
+        check(_lib().geeco_slab_reduce_batch_prepare(arr, len(chunk), _p(step), float(lr), beta1, beta2, _p(scal), _stream()),
+              'geeco_slab_reduce_batch_prepare')
     else:
       check(_lib().geeco_slab_reduce_batch(arr, len(chunk), _stream()), 'geeco_slab_reduce_batch')
   del pending[:]
@@ -693,6 +699,46 @@ def lstm_seq_heads_into(preds, zx, wh, bias, fc1_w, fc1_b, heads_w, heads_b, hea
 # --------------------------------------------------------------------------------------------
 def adam_prepare(global_step, lr, scal, beta1=0.9, beta2=0.999):
   check(_lib().geeco_adam_prepare(_p(global_step), lr, beta1, beta2, _p(scal), _stream()), 'geeco_adam_prepare')
+
+
+def lr_schedule_struct(schedule):
+  """``geeco_lr_schedule`` of a normalised schedule (the dictionary ``variables.check_lr_schedule`` returns); a struct is passed
+  through.  Rates and values are rounded to float32 here: the struct is what the device evaluates."""
+  if isinstance(schedule, _native.LrSchedule):
+    return schedule
+  st = _native.LrSchedule()
+  st.kind = _native.LR_KINDS.index(schedule['kind'])
+  st.base_lr, st.decay_rate, st.alpha = schedule['base_lr'], schedule['decay_rate'], schedule['alpha']
+  st.warmup_steps, st.decay_steps, st.staircase = schedule['warmup_steps'], schedule['decay_steps'], int(bool(schedule['staircase']))
+  boundaries, values = schedule['boundaries'], schedule['values']
+  if len(boundaries) > _native.LR_BOUNDARIES_MAX or (schedule['kind'] == 'piecewise' and len(values) != len(boundaries) + 1):
+    raise ValueError('lr_schedule_struct: %d boundaries (at most %d) need one value more, got %d'
+                     % (len(boundaries), _native.LR_BOUNDARIES_MAX, len(values)))
+  st.n_boundaries = len(boundaries)
+  for i, b in enumerate(boundaries):
+    st.boundaries[i] = b
+  for i, v in enumerate(values[:_native.LR_BOUNDARIES_MAX + 1]):
+    st.values[i] = v
+  return st
+
+
+def lr_schedule_eval(schedule, step):
+  """``geeco_lr_schedule_eval``: lr(step) of the schedule in float64, on the host, by the function the device evaluates."""
+  out = ctypes.c_double()
+  check(_lib().geeco_lr_schedule_eval(ctypes.byref(lr_schedule_struct(schedule)), int(step), ctypes.byref(out)), 'geeco_lr_schedule_eval')
+  return out.value
+
+
+def _scal_holds_lr(scal):
+  if scal.numel() < 3:
+    raise ValueError('a learning-rate schedule stores lr in scal[2]: scal holds %d floats' % scal.numel())
+
+
+def adam_prepare_schedule(global_step, schedule, scal, beta1=0.9, beta2=0.999):
+  """``geeco_adam_prepare_schedule``: adam_prepare with lr(s) of ``schedule`` at the step the counter is advanced to; scal[2] = lr(s)."""
+  _scal_holds_lr(scal)
+  check(_lib().geeco_adam_prepare_schedule(_p(global_step), ctypes.byref(lr_schedule_struct(schedule)), beta1, beta2, _p(scal), _stream()),
+        'geeco_adam_prepare_schedule')
 
 
 def adam_tf(p, g, m, v, n, scal, beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):

@@ -11,6 +11,7 @@ are zero and stay zero under Adam (g = 0).
 from __future__ import annotations
 
 import collections
+import collections.abc
 import math
 import numbers
 
@@ -106,6 +107,74 @@ def check_clip_norm(value, key='clip_norm'):
   if isinstance(value, bool) or not isinstance(value, numbers.Real) or not float(f32.tiny) <= float(value) <= float(f32.max):
     raise ValueError('%s=%r: the norm to clip the gradient to must be a finite number > 0, a normal float32 (None or 0 = off)' % (key, value))
   return float(value)
+
+
+LR_KINDS = ('constant', 'exponential', 'cosine', 'piecewise')
+LR_BOUNDARIES_MAX = 8       # GEECO_LR_BOUNDARIES_MAX of include/geeco_hip.h
+_LR_FIELDS = ('kind', 'warmup_steps', 'decay_steps', 'decay_rate', 'alpha', 'staircase', 'boundaries', 'values')
+
+
+def check_lr_schedule(value, base_lr, key='lr_schedule'):
+  """The learning-rate schedule the device evaluates from its step counter.  ``value``: None, or a mapping with 'kind'
+  ('constant', 'exponential', 'cosine', 'piecewise') and of 'warmup_steps', 'decay_steps', 'decay_rate', 'staircase', 'alpha',
+  'boundaries', 'values' those the kind uses; ``base_lr``: the constant rate it starts from (cfg.lr).  None, or 'constant' without
+  warm-up, is off and returns None; else the normalised schedule, a dictionary with every field (``ops.lr_schedule_struct`` takes
+  it).  Anything else raises ValueError naming ``key`` and the offending field."""
+  if value is None:
+    return None
+
+  def bad(field, why):
+    return ValueError('%s: %s=%r: %s' % (key, field, value.get(field) if isinstance(value, collections.abc.Mapping) else value, why))
+
+  def whole(field, least, default=None):
+    x = value.get(field, default)
+    if isinstance(x, bool) or not isinstance(x, numbers.Integral) or not least <= int(x) < 2 ** 62:
+      raise bad(field, 'must be a whole number >= %d' % least)
+    return int(x)
+
+  def rate(field, x, above_zero=False, most=float(np.finfo(np.float32).max)):
+    ok = not isinstance(x, bool) and isinstance(x, numbers.Real) and 0.0 <= float(x) <= most and not (above_zero and float(np.float32(x)) <= 0.0)
+    if not ok:
+      raise bad(field, 'must be a finite number %s that float32 holds' % ('> 0' if above_zero else ('in [0, 1]' if most == 1.0 else '>= 0')))
+    return float(x)
+
+  if not isinstance(value, collections.abc.Mapping):
+    raise bad('value', "must be None or a mapping with 'kind' and the fields the kind uses")
+  for field in value:
+    if field not in _LR_FIELDS:
+      raise ValueError('%s: unknown field %r (known: %s)' % (key, field, ', '.join(_LR_FIELDS)))
+  kind = value.get('kind')
+  if not isinstance(kind, str) or kind not in LR_KINDS:
+    raise bad('kind', 'must be one of %s' % ', '.join(LR_KINDS))
+  out = dict(kind=kind, base_lr=0.0, warmup_steps=whole('warmup_steps', 0, 0), decay_steps=1, decay_rate=1.0, alpha=0.0, staircase=False,
+             boundaries=(), values=())
+  if kind == 'piecewise':      # base_lr is ignored
+    boundaries, values = value.get('boundaries', ()), value.get('values')
+    if isinstance(boundaries, (str, bytes)) or not isinstance(boundaries, collections.abc.Sequence) or len(boundaries) > LR_BOUNDARIES_MAX:
+      raise bad('boundaries', 'must be a sequence of at most %d step counts' % LR_BOUNDARIES_MAX)
+    for i, b in enumerate(boundaries):
+      if isinstance(b, bool) or not isinstance(b, numbers.Integral) or abs(int(b)) >= 2 ** 62 or (i and int(b) <= int(boundaries[i - 1])):
+        raise bad('boundaries', 'must be whole numbers, strictly increasing (entry %d)' % i)
+    if isinstance(values, (str, bytes)) or not isinstance(values, collections.abc.Sequence) or len(values) != len(boundaries) + 1:
+      raise bad('values', 'must be a sequence of %d rates, one more than boundaries' % (len(boundaries) + 1))
+    out['boundaries'] = tuple(int(b) for b in boundaries)
+    out['values'] = tuple(rate('values', v) for v in values)
+    return out
+  if isinstance(base_lr, bool) or not isinstance(base_lr, numbers.Real) or not 0.0 <= float(base_lr) <= float(np.finfo(np.float32).max):
+    raise ValueError('%s: base_lr=%r (the configured lr) must be a finite number >= 0 that float32 holds' % (key, base_lr))
+  out['base_lr'] = float(base_lr)
+  if kind == 'constant':
+    return out if out['warmup_steps'] else None
+  out['decay_steps'] = whole('decay_steps', 1)
+  if kind == 'exponential':
+    out['decay_rate'] = rate('decay_rate', value.get('decay_rate'), above_zero=True)
+    staircase = value.get('staircase', False)
+    if not isinstance(staircase, (bool, np.bool_)):
+      raise bad('staircase', 'must be True or False')
+    out['staircase'] = bool(staircase)
+  else:
+    out['alpha'] = rate('alpha', value.get('alpha', 0.0), most=1.0)
+  return out
 
 
 def ema_decay_at(decay, t):

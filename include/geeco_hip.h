@@ -28,7 +28,8 @@ extern "C" {
 /* added within 7 (additive: no existing entry point or convention changed): geeco_lstm_seq_heads_fwd,
  * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd, geeco_gather_windows_by_address,
  * geeco_gather_windows_augmented, geeco_adam_tf_ema, geeco_adam_tf_segments_ema, geeco_clip_ws_floats,
- * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip, geeco_gather_windows_scene */
+ * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip, geeco_gather_windows_scene,
+ * geeco_adam_prepare_schedule, geeco_slab_reduce_batch_prepare_schedule, geeco_lr_schedule_eval */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -599,6 +600,42 @@ int geeco_clip_scale(const float* partials, int64_t nchunks, float clip, float* 
 int geeco_adam_tf_segments_clip(float* p, float* g_out, float* m, float* v, float* ema_or_null, const geeco_adam_segment* segs,
                                 int nseg, const float* lr_t_dev, const int64_t* global_step_dev, float decay, const float* clip_dev,
                                 float beta1, float beta2, float eps, float grad_scale, float l2, void* stream);
+/* Opt-in learning-rate schedules, evaluated on the device from the step counter by the thread that does the prepare work: no
+ * launch, no host synchronisation and no re-capture of a recorded step; a restored counter continues the schedule.
+ * With t the counter after the increment (the t of lr_t), s = t - 1 the updates completed (the global_step TF 1.15's
+ * tf.train.*_decay see), w = warmup_steps and u = s - w:
+ *   s <  w:  lr(s) = L0 (s + 1) / w,  L0 = the schedule's value at its own step 0 (base_lr; values[0] for PIECEWISE)
+ *   s >= w:  CONSTANT     base_lr
+ *            EXPONENTIAL  base_lr decay_rate^(u / decay_steps); staircase != 0: the exponent is floor(u / decay_steps)
+ *            COSINE       base_lr ((1 - alpha) 0.5 (1 + cos(pi min(u, decay_steps) / decay_steps)) + alpha)
+ *            PIECEWISE    values[i] for the first i with u <= boundaries[i], else values[n_boundaries]; base_lr is ignored
+ * (tf.train.exponential_decay, cosine_decay, piecewise_constant), all in double from the fields as declared, one rounding to float.
+ * geeco_adam_prepare_schedule / geeco_slab_reduce_batch_prepare_schedule: their constant-lr counterparts with lr(s) in place of
+ *   lr (slab sums bitwise geeco_slab_reduce_batch's); they also store lr(s) in scal_dev[2] (scal_dev[1] and [3] are not touched).
+ * geeco_lr_schedule_eval: *lr_out = lr(step) on the host; needs no GPU.
+ * All three return GEECO_EINVAL before any launch for: a null pointer, an unknown kind, warmup_steps < 0, decay_steps < 1
+ * (EXPONENTIAL, COSINE), n_boundaries outside 0..GEECO_LR_BOUNDARIES_MAX or boundaries not strictly increasing, a rate or value that
+ * is negative or not finite, decay_rate <= 0, alpha outside [0, 1]; geeco_lr_schedule_eval also for step < 0. */
+#define GEECO_LR_CONSTANT 0
+#define GEECO_LR_EXPONENTIAL 1
+#define GEECO_LR_COSINE 2
+#define GEECO_LR_PIECEWISE 3
+#define GEECO_LR_BOUNDARIES_MAX 8
+typedef struct geeco_lr_schedule {
+  int32_t kind;                                  /* GEECO_LR_* */
+  float base_lr;
+  int64_t warmup_steps, decay_steps;
+  float decay_rate, alpha;
+  int32_t staircase, n_boundaries;
+  int64_t boundaries[GEECO_LR_BOUNDARIES_MAX];   /* in steps after the warm-up (u) */
+  float values[GEECO_LR_BOUNDARIES_MAX + 1];
+} geeco_lr_schedule;
+int geeco_adam_prepare_schedule(int64_t* global_step_dev, const geeco_lr_schedule* schedule, float beta1, float beta2,
+                                float* scal_dev, void* stream);
+int geeco_slab_reduce_batch_prepare_schedule(const geeco_slab_reduce* items, int n, int64_t* global_step_dev,
+                                             const geeco_lr_schedule* schedule, float beta1, float beta2, float* scal_dev,
+                                             void* stream);
+int geeco_lr_schedule_eval(const geeco_lr_schedule* schedule, int64_t step, double* lr_out);
 /* sum of squares of an arena (for the L2 regularisation loss term); out[0] overwritten. */
 int geeco_sumsq(const float* p, int64_t n, float* out, void* stream);
 

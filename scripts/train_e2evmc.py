@@ -116,6 +116,23 @@ ARGPARSER.add_argument('--clip_norm', type=float, default=0.0,
                        help='Clip the gradient (L2 term included, as TF clips the gradient of the total loss) by its global norm before '
                             'the optimiser step (tf.clip_by_global_norm), on the device; events.jsonl then carries grad_norm, the norm '
                             'before clipping.  A finite number > 0, e.g. 5.0; 0 = off.  Not part of the model config.')
+ARGPARSER.add_argument('--lr_schedule', type=str, default=None, choices=['constant', 'exponential', 'cosine', 'piecewise'],
+                       help='Learning-rate schedule, evaluated on the device from its step counter (a resumed run continues it); '
+                            'events.jsonl then carries learning_rate.  After --lr_warmup_steps, with u the steps since: exponential = '
+                            'lr * rate^(u / decay_steps) (tf.train.exponential_decay), cosine = tf.train.cosine_decay down to alpha * lr '
+                            'at decay_steps, piecewise = --lr_values between --lr_boundaries (tf.train.piecewise_constant; --lr is '
+                            'ignored), constant = --lr (useful with a warm-up).  Default: the constant --lr.  Not part of the model config.')
+ARGPARSER.add_argument('--lr_warmup_steps', type=int, default=0,
+                       help='Linear warm-up in front of the schedule: step s < W runs lr0 * (s + 1) / W, lr0 the schedule\'s first value.')
+ARGPARSER.add_argument('--lr_decay_steps', type=int, default=None, help='decay_steps of the exponential and cosine schedules (>= 1).')
+ARGPARSER.add_argument('--lr_decay_rate', type=float, default=None, help='decay_rate of the exponential schedule (> 0).')
+ARGPARSER.add_argument('--lr_staircase', default=False, action='store_true',
+                       help='Exponential schedule: decay in steps, the exponent is floor(u / decay_steps).')
+ARGPARSER.add_argument('--lr_alpha', type=float, default=0.0, help='Cosine schedule: the rate ends at alpha * lr; in [0, 1].')
+ARGPARSER.add_argument('--lr_boundaries', type=str, default='',
+                       help='Piecewise schedule: at most 8 strictly increasing step counts (after the warm-up), comma-separated: a,b,..')
+ARGPARSER.add_argument('--lr_values', type=str, default='',
+                       help='Piecewise schedule: one rate more than boundaries, comma-separated: x,y,..; value i runs while u <= boundary i.')
 
 _OBSERVATION_FORMAT_TO_CHANNELS = {'rgb': 3, 'rgbd': 4}                      # train_e2evmc.py:129-132
 _GOAL_CONDITION_TO_MODEL = {'none': (e2evmc_model_fn, 'VMC'),               # train_e2evmc.py:134-137
@@ -172,7 +189,24 @@ def estimator_params(args, e2evmc_config):
     params['ema_decay'] = args.ema_decay
   if args.clip_norm:
     params['clip_norm'] = args.clip_norm
+  if args.lr_schedule:
+    params['lr_schedule'] = lr_schedule_of(args)
   return params
+
+
+def lr_schedule_of(args):
+  """params['lr_schedule'] from the --lr_* flags: the fields the chosen kind uses (the Estimator checks their values)."""
+  schedule = {'kind': args.lr_schedule, 'warmup_steps': args.lr_warmup_steps}
+  if args.lr_schedule in ('exponential', 'cosine'):
+    schedule['decay_steps'] = args.lr_decay_steps
+  if args.lr_schedule == 'exponential':
+    schedule.update(decay_rate=args.lr_decay_rate, staircase=args.lr_staircase)
+  if args.lr_schedule == 'cosine':
+    schedule['alpha'] = args.lr_alpha
+  if args.lr_schedule == 'piecewise':
+    schedule['boundaries'] = [int(x) for x in args.lr_boundaries.split(',') if x.strip()]
+    schedule['values'] = [float(x) for x in args.lr_values.split(',') if x.strip()]
+  return schedule
 
 
 def main(args):
