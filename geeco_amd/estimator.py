@@ -29,7 +29,7 @@ from . import graph
 from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
 from .tf_checkpoint import EMA_SUFFIX
-from .variables import check_clip_norm, check_ema_decay, check_lr_schedule
+from .variables import check_clip_norm, check_ema_decay, check_lr_schedule, check_skip_nonfinite
 
 
 class ModeKeys:
@@ -179,12 +179,20 @@ class _SummarySaverHook:
     return cls._writers[model_dir]
 
   def after_run(self, step, model_dir):
-    if step % self.every or gdist.rank() != 0:
+    if step % self.every:
+      return
+    if gdist.rank() != 0 and getattr(self.model, 'guard', None) is None:
       return
     self.model.check_device_errors()        # (the loss read-out below waits for the device anyway)
+    # params['skip_nonfinite']: the limit is checked on EVERY rank -- the replicas decide alike, so all of them stop together
+    skipped = check_skipped_steps(self.model)
+    if gdist.rank() != 0:
+      return
     parts = {k: float(v) for k, v in self.model.loss_parts().items()}
-    if getattr(self.model, 'clip_out', None) is not None:      # params['clip_norm']: the norm of this step's gradient before clipping
+    if getattr(self.model, 'clip_out', None) is not None:      # params['clip_norm'] / ['skip_nonfinite']: the norm of this step's gradient before clipping
       parts['grad_norm'] = float(self.model.clip_out[1])
+    if getattr(self.model, 'guard', None) is not None:         # params['skip_nonfinite']: steps this model has skipped so far (not checkpointed)
+      parts['skipped_steps'] = skipped
     if getattr(self.model, 'lr_schedule', None) is not None:   # params['lr_schedule']: the rate this step was taken with, as the device formed it
       parts['learning_rate'] = float(self.model.scal[2])
     parts['global_step'] = step
@@ -194,6 +202,20 @@ class _SummarySaverHook:
         f.write(json.dumps(parts) + '\n')
       self._writer(model_dir).add_scalars({k: v for k, v in parts.items() if k.startswith('loss') or k == 'learning_rate'}, step, parts['wall_time'])
     print('INFO: loss = %.6f, step = %d' % (parts['loss'], step), flush=True)
+
+
+def check_skipped_steps(model):
+  """params['skip_nonfinite']: the steps ``model`` has skipped in all (0 for a model without the option).  Raises
+  RuntimeError once as many in a row as the limit were skipped: the input, not one batch, is broken.  READS the device: called
+  where the host synchronises anyway."""
+  if getattr(model, 'guard', None) is None:
+    return 0
+  _, total, row = (int(x) for x in model.guard.tolist())
+  if row >= model.skip_limit:
+    raise RuntimeError('geeco_amd: the last %d optimiser steps in a row were skipped for a non-finite gradient (%d skipped in all; norm of the '
+                       "last one: %r; params['skip_nonfinite'] allows fewer than %d in a row); nothing was saved"
+                       % (row, total, float(model.clip_out[1]), model.skip_limit))
+  return total
 
 
 def shared_frames_capacity(shared, N, K, goal):
@@ -233,6 +255,10 @@ def _model_fn(features, labels, mode, params, goal):
   clip = check_clip_norm(params.get('clip_norm'), "params['clip_norm']")
   if training and clip is not None:
     ema['clip_norm'] = clip
+  # params['skip_nonfinite']: a step whose gradient is not finite updates nothing, decided on the device
+  skip = check_skip_nonfinite(params.get('skip_nonfinite'), "params['skip_nonfinite']")
+  if training and skip is not None:
+    ema['skip_nonfinite'] = skip
   # params['lr_schedule']: the learning rate follows the device's step counter, from cfg.lr as the base rate
   if training and check_lr_schedule(params.get('lr_schedule'), cfg.lr, "params['lr_schedule']") is not None:
     ema['lr_schedule'] = params['lr_schedule']
@@ -345,6 +371,7 @@ class Estimator:
     self.params = dict(params or {})
     check_ema_decay(self.params.get('ema_decay'), "params['ema_decay']")
     check_clip_norm(self.params.get('clip_norm'), "params['clip_norm']")
+    check_skip_nonfinite(self.params.get('skip_nonfinite'), "params['skip_nonfinite']")
     check_lr_schedule(self.params.get('lr_schedule'), getattr(self.params.get('e2evmc_config'), 'lr', 0.0), "params['lr_schedule']")
     self._specs = {}          # (mode, N) -> (spec, feature buffers, label buffers)
     self.last_train_stats = None
@@ -503,10 +530,12 @@ class Estimator:
         break
     if hasattr(source, 'close'):
       source.close()      # an epoch left early must not leave reader threads filling a queue nobody drains
+    skipped = 0
     if nsteps and torch.cuda.is_available():
       torch.cuda.synchronize()
       for sp, _, _ in self._specs.values():      # a device-side error of any model that ran this epoch (input-stage timeout)
         sp.model.check_device_errors()
+        skipped += check_skipped_steps(sp.model)      # ... or a run of skipped steps as long as params['skip_nonfinite'] allows
     if nsteps and world > 1 and not gdist.replicas_identical(self._store):
       # data parallel: summed gradients + a deterministic optimiser keep every replica bitwise equal; if they are not, the exchange
       # lost or raced something and rank 0's checkpoint would be one replica's opinion
@@ -514,6 +543,8 @@ class Estimator:
                          '(dp_form=%s); nothing was saved' % (nsteps, rank, getattr(self.config, 'dp_form', None) or 'three_graphs_reserve16'))
     # wall time of the input + step loop alone (the checkpoint written below is not part of the data path)
     self.last_train_stats = {'steps': nsteps, 'loop_seconds': time.time() - t0}
+    if check_skip_nonfinite(self.params.get('skip_nonfinite')) is not None:
+      self.last_train_stats['skipped_steps'] = skipped
     if nsteps and rank == 0 and self.model_dir:
       path = save_checkpoint(self._store, self.model_dir, self.config.keep_checkpoint_max, self.config.save_tf_bundle,
                           self.params['e2evmc_config'].batch_size if 'e2evmc_config' in self.params else None)

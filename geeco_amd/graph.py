@@ -27,7 +27,7 @@ from . import ops
 from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
-from .variables import _CELLS, VariableStore, check_clip_norm, check_ema_decay, check_lr_schedule, model_variable_shapes
+from .variables import _CELLS, VariableStore, check_clip_norm, check_ema_decay, check_lr_schedule, check_skip_nonfinite, model_variable_shapes
 
 
 def build_store(cfg, goal, device, ema=False):
@@ -80,10 +80,12 @@ class BesideBottom:
 class _ModelBase:
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
-  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None, lr_schedule=None):
+  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None, lr_schedule=None,
+               skip_nonfinite=None):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
     self.ema_decay = check_ema_decay(ema_decay)
     self.clip_norm = check_clip_norm(clip_norm)
+    self.skip_limit = check_skip_nonfinite(skip_nonfinite)      # consecutive skipped steps the caller tolerates (None: option off)
     # lr_schedule (DESIGN 5.18): the normalised schedule, and the struct the prepare work is handed in place of cfg.lr
     # (_prepare_args, _prepare_unless_done); the device then leaves lr(s) of the step in scal[2].  None: cfg.lr, as ever.
     self.lr_schedule = check_lr_schedule(lr_schedule, cfg.lr)
@@ -139,11 +141,15 @@ class _ModelBase:
     self._opt_stream = None     # optimizer_stream()
     # clip_norm: the sums of squares of the arena's chunks, [s, norm] of the last optimiser step, and the pieces of
     # the arena whose update waits for the norm of all of them (apply_gradients_of); a model without the option has none of it
-    self.clip_ws = self.clip_out = None
+    # skip_nonfinite shares them -- the norm decides whether the step is applied -- and adds ``guard``: int64 [verdict
+    # of the last step (1 applied, 0 skipped), skipped steps in all, skipped steps in a row]
+    self.clip_ws = self.clip_out = self.guard = None
     self._clip_calls = []
-    if self.clip_norm is not None and training:
+    if (self.clip_norm is not None or self.skip_limit is not None) and training:
       self.clip_ws = torch.zeros(ops.clip_ws_floats(self.store.size), **f32)
       self.clip_out = torch.zeros(2, **f32)
+      if self.skip_limit is not None:
+        self.guard = torch.zeros(3, dtype=torch.int64, device=self.device)
     # GoalE2EVMC's branch and the control block of its one-pass input stage; the gather mode of a model that takes shared_frames
     self.mode = self.dyn_ws2 = self.window_mode = None
     # RGB-D: rgb || depth (estimator.py:36,169,172).  The dynimg branch of the goal model forms the concat inside its
@@ -331,11 +337,13 @@ class _ModelBase:
       self._refresh_after_update()
 
   def _apply_clipped(self, segments, g_out, last):
-    """apply_gradients_of under ``clip_norm``: no piece may move before the norm of ALL of them is known, so the pieces of a call that
+    """apply_gradients_of under ``clip_norm`` and / or ``skip_nonfinite``: no piece may move before the norm of ALL of them is known, so the pieces of a call that
     does not complete the step are recorded and nothing is launched for them; the call that does runs, in order, the sum of squares
     over every recorded piece and its own (ONE launch: the partial sums are then bitwise those of the undivided arena, whatever the
     pieces), the scale, and the clipped Adam update call by call (each with its own ``g_out``).  Three launches for the whole arena,
-    four for the two pieces of the schedules in runtime.py -- constant per schedule, so the step stays one captured graph."""
+    four for the two pieces of the schedules in runtime.py -- constant per schedule, so the step stays one captured graph.
+    Under ``skip_nonfinite`` the scale comes from ``guard_decide`` (clip 0 = no clipping) with the verdict on the step, and the update
+    is the one that honours it: the same launches whether the step is applied or skipped."""
     self._clip_calls.append((list(segments), g_out))
     if not last:
       return
@@ -343,15 +351,20 @@ class _ModelBase:
     self._clip_calls = []
     pieces = [seg for segs, _ in calls for seg in segs]
     if len(pieces) > ops._native.ADAM_SEGMENTS_MAX:
-      raise ValueError('clip_norm: the optimiser step came in %d pieces; the norm of the whole gradient is one launch over at most %d'
+      raise ValueError('clip_norm / skip_nonfinite: the optimiser step came in %d pieces; the norm of the whole gradient is one launch over at most %d'
                        % (len(pieces), ops._native.ADAM_SEGMENTS_MAX))
     kw = dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
     self._prepare_unless_done()
     ops.grad_sumsq_segments(self.clip_ws, s.params, pieces, s.size, **kw)
-    ops.clip_scale(self.clip_out, self.clip_ws, self.clip_ws.numel(), self.clip_norm)
     ema = dict(ema=s.ema, global_step=s.global_step, decay=self.ema_decay) if s.ema is not None else {}
-    for segs, out in calls:
-      ops.adam_tf_segments_clip(s.params, s.adam_m, s.adam_v, segs, self.scal, self.clip_out, g_out=out, **ema, **kw)
+    if self.guard is not None:
+      ops.guard_decide(self.clip_out, self.guard, self.clip_ws, self.clip_ws.numel(), self.clip_norm or 0.0)
+      for segs, out in calls:
+        ops.adam_tf_segments_guard(s.params, s.adam_m, s.adam_v, segs, self.scal, self.clip_out, self.guard, g_out=out, **ema, **kw)
+    else:
+      ops.clip_scale(self.clip_out, self.clip_ws, self.clip_ws.numel(), self.clip_norm)
+      for segs, out in calls:
+        ops.adam_tf_segments_clip(s.params, s.adam_m, s.adam_v, segs, self.scal, self.clip_out, g_out=out, **ema, **kw)
     self._refresh_after_update()
 
   def apply_gradients(self):
@@ -454,10 +467,11 @@ class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None):
-    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``, ``lr_schedule``: see E2EVMC."""
+               lr_schedule=None, skip_nonfinite=None):
+    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``, ``lr_schedule``, ``skip_nonfinite``: see
+    E2EVMC."""
     super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm, lr_schedule=lr_schedule)
+                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -588,7 +602,7 @@ class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None):
+               lr_schedule=None, skip_nonfinite=None):
     """``ema_decay`` (a float in (0, 1); None / 0 = off): the optimiser step also keeps an exponential moving average of the
     parameters in ``store.ema`` (tf.train.ExponentialMovingAverage with num_updates = global_step); a store passed in
     must have been built with the arena (``build_store(..., ema=True)``).
@@ -597,12 +611,15 @@ class E2EVMC(_ModelBase):
     ``lr_schedule`` (``variables.check_lr_schedule``; None, or 'constant' without warm-up = off): the learning rate of every step is the
     schedule's value at the device's step counter, with ``cfg.lr`` as its base rate, evaluated by the thread that forms Adam's lr_t
     (DESIGN 5.18): a captured step follows it and a restored counter continues it; ``scal[2]`` then holds the rate of the last step.
+    ``skip_nonfinite`` (True, or the tolerated number of consecutive skipped steps, an integer >= 1; None / False = off): an optimiser
+    step whose gradient has a non-finite global norm leaves p, m, v and the shadow arena as they are -- the step counter still
+    advances; ``guard`` then holds [last verdict, skipped steps in all, in a row] and ``clip_out`` [scale, norm].
     ``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
     'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
     super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm, lr_schedule=lr_schedule)
+                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     self.window_mode, self.feat_ch = 'plain', [256]
     # frames are processed time-major ([K][N]) so that step t's features are one dense block

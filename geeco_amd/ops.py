@@ -812,6 +812,24 @@ def adam_tf_segments_clip(p, m, v, segments, scal, clip_dev, ema=None, global_st
                                            _p(clip_dev), beta1, beta2, eps, grad_scale, l2, _stream()), 'geeco_adam_tf_segments_clip')
 
 
+def guard_decide(out2, guard, partials, nchunks, clip=0.0):
+  """``geeco_guard_decide``: norm = sqrt(sum of the first ``nchunks`` partials) as ``clip_scale`` forms it.  Finite: out2 = [clip_scale's s
+  (``clip`` > 0) or 1.0 (``clip`` == 0), norm], guard = [1, total, 0]; not finite: out2 = [0, norm], guard = [0, total + 1, consecutive + 1].
+  ``guard``: three int64 on the device."""
+  if out2.numel() < 2 or partials.numel() < nchunks or guard.numel() < 3 or guard.dtype != torch.int64:
+    raise ValueError('guard_decide: out2 holds 2 floats, guard 3 int64, partials at least nchunks = %d' % nchunks)
+  check(_lib().geeco_guard_decide(_p(partials), int(nchunks), clip, _p(out2), _p(guard), _stream()), 'geeco_guard_decide')
+
+
+def adam_tf_segments_guard(p, m, v, segments, scal, clip_dev, guard, ema=None, global_step=None, decay=0.0, g_out=None, beta1=0.9, beta2=0.999,
+                           eps=1e-8, grad_scale=1.0, l2=0.0):
+  """``geeco_adam_tf_segments_guard``: ``adam_tf_segments_clip`` when ``guard[0]`` (guard_decide's verdict) is 1; when it is 0 only ``g_out``
+  is written and p, m, v and ``ema`` keep every bit."""
+  arr = _adam_segments(segments)
+  check(_lib().geeco_adam_tf_segments_guard(_p(p), _p(g_out), _p(m), _p(v), _p(ema), arr, len(segments), _p(scal), _p(global_step), decay,
+                                            _p(clip_dev), _p(guard), beta1, beta2, eps, grad_scale, l2, _stream()), 'geeco_adam_tf_segments_guard')
+
+
 def sumsq_into(out, p, n):
   check(_lib().geeco_sumsq(_p(p), n, _p(out), _stream()), 'geeco_sumsq')
 

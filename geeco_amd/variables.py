@@ -109,6 +109,23 @@ def check_clip_norm(value, key='clip_norm'):
   return float(value)
 
 
+SKIP_NONFINITE_DEFAULT_LIMIT = 100
+
+
+def check_skip_nonfinite(value, key='skip_nonfinite'):
+  """Skipping of optimiser steps whose gradient is not finite: None or False = off (returns None); True = on with the
+  default limit of 100 consecutive skipped steps; an integer L >= 1 = on with limit L.  Returns the limit; anything else raises
+  ValueError naming ``key``."""
+  if value is None or value is False:
+    return None
+  if value is True:
+    return SKIP_NONFINITE_DEFAULT_LIMIT
+  if isinstance(value, numbers.Integral) and value >= 1:
+    return int(value)
+  raise ValueError('%s=%r: True, or the number of consecutive skipped steps after which training stops, an integer >= 1 '
+                   '(None or False = off)' % (key, value))
+
+
 LR_KINDS = ('constant', 'exponential', 'cosine', 'piecewise')
 LR_BOUNDARIES_MAX = 8       # GEECO_LR_BOUNDARIES_MAX of include/geeco_hip.h
 _LR_FIELDS = ('kind', 'warmup_steps', 'decay_steps', 'decay_rate', 'alpha', 'staircase', 'boundaries', 'values')

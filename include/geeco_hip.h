@@ -29,7 +29,8 @@ extern "C" {
  * geeco_pack_frames_by_address, geeco_window_states_fwd, geeco_window_states_bwd, geeco_gather_windows_by_address,
  * geeco_gather_windows_augmented, geeco_adam_tf_ema, geeco_adam_tf_segments_ema, geeco_clip_ws_floats,
  * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip, geeco_gather_windows_scene,
- * geeco_adam_prepare_schedule, geeco_slab_reduce_batch_prepare_schedule, geeco_lr_schedule_eval */
+ * geeco_adam_prepare_schedule, geeco_slab_reduce_batch_prepare_schedule, geeco_lr_schedule_eval, geeco_guard_decide,
+ * geeco_adam_tf_segments_guard */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -589,7 +590,8 @@ int geeco_adam_tf_segments_ema(float* p, float* g_out, float* m, float* v, float
  *   piece covers adds 0; p is read only when l2 != 0.  The summation order inside a chunk is fixed, so any partition of the same
  *   elements into pieces gives bitwise the same partials.
  * geeco_clip_scale: norm = sqrt(sum of the partials, one fixed order), out2[0] = s = clip / max(norm, clip) (exactly 1.0f whenever
- *   norm <= clip), out2[1] = norm.  clip: finite, > 0.  A non-finite norm is not guarded: s and every update are then NaN.
+ *   norm <= clip), out2[1] = norm.  clip: finite, > 0.  A non-finite norm is not guarded: s and every update are then NaN
+ *   (the opt-in that skips such a step: geeco_guard_decide below).
  * geeco_adam_tf_segments_clip: geeco_adam_tf_segments (ema_or_null == NULL) or geeco_adam_tf_segments_ema on G_i * clip_dev[0];
  *   clip_dev[0] == 1.0f gives bitwise their p, m, v and shadow arena.  Offsets are multiples of 4 floats, counts any number >= 1
  *   (a piece ends in a scalar tail), so the whole arena is the one-piece call. */
@@ -600,6 +602,25 @@ int geeco_clip_scale(const float* partials, int64_t nchunks, float clip, float* 
 int geeco_adam_tf_segments_clip(float* p, float* g_out, float* m, float* v, float* ema_or_null, const geeco_adam_segment* segs,
                                 int nseg, const float* lr_t_dev, const int64_t* global_step_dev, float decay, const float* clip_dev,
                                 float beta1, float beta2, float eps, float grad_scale, float l2, void* stream);
+/* Opt-in skipping of optimiser steps whose gradient is not finite: geeco_grad_sumsq_segments, then the two entries below in place of
+ * geeco_clip_scale and geeco_adam_tf_segments_clip.  The step is APPLIED iff norm = sqrt(sum of the partials), formed in float32 in
+ * geeco_clip_scale's order, is finite.  A NaN or an infinity in any element a piece covers makes it non-finite, and so does a finite
+ * gradient whose squares overflow float32 (|G_i| beyond about 1.8e19).
+ * geeco_guard_decide: one 256-thread block.  clip: finite, >= 0; 0 = no clipping.  guard: int64[3] the caller zeroes once.
+ *   finite norm:      out2[0] = geeco_clip_scale's s, bitwise (clip > 0), or 1.0f (clip == 0); out2[1] = norm;
+ *                     guard[0] = 1, guard[1] (skipped steps in all) unchanged, guard[2] (skipped steps in a row) = 0
+ *   non-finite norm:  out2[0] = 0.0f; out2[1] = norm as computed (NaN or +inf); guard[0] = 0, guard[1] += 1, guard[2] += 1
+ * geeco_adam_tf_segments_guard: geeco_adam_tf_segments_clip behind one uniform test of guard_dev[0].  1: exactly that entry point's
+ *   work (clip_dev[0] == 1.0f: bitwise the unclipped kernels' p, m, v and shadow arena).  0: g_out, where non-null, receives the
+ *   pieces' gradients and p, m, v and the shadow arena are neither read nor written.  The step counter is not this kernel's: a
+ *   skipped step has advanced it (the prepare work runs before the norm exists) and is a step with no update.
+ * Both return GEECO_EINVAL before any launch for a null pointer (guard / guard_dev included), nchunks < 1, a clip that is negative or
+ * not finite, and whatever geeco_adam_tf_segments_clip refuses. */
+int geeco_guard_decide(const float* partials, int64_t nchunks, float clip, float* out2, int64_t* guard, void* stream);
+int geeco_adam_tf_segments_guard(float* p, float* g_out, float* m, float* v, float* ema_or_null, const geeco_adam_segment* segs,
+                                 int nseg, const float* lr_t_dev, const int64_t* global_step_dev, float decay, const float* clip_dev,
+                                 const int64_t* guard_dev, float beta1, float beta2, float eps, float grad_scale, float l2,
+                                 void* stream);
 /* Opt-in learning-rate schedules, evaluated on the device from the step counter by the thread that does the prepare work: no
  * launch, no host synchronisation and no re-capture of a recorded step; a restored counter continues the schedule.
  * With t the counter after the increment (the t of lr_t), s = t - 1 the updates completed (the global_step TF 1.15's

@@ -116,6 +116,14 @@ ARGPARSER.add_argument('--clip_norm', type=float, default=0.0,
                        help='Clip the gradient (L2 term included, as TF clips the gradient of the total loss) by its global norm before '
                             'the optimiser step (tf.clip_by_global_norm), on the device; events.jsonl then carries grad_norm, the norm '
                             'before clipping.  A finite number > 0, e.g. 5.0; 0 = off.  Not part of the model config.')
+ARGPARSER.add_argument('--skip_nonfinite', default=False, action='store_true',
+                       help='Skip an optimiser step whose gradient is not finite (a NaN or an infinity anywhere in it, or a norm that '
+                            'overflows float32) instead of writing NaN into every weight: weights, Adam moments and averaged weights '
+                            'stay as they are, the step counter still advances.  Decided on the device from the global norm; '
+                            'events.jsonl then carries grad_norm and skipped_steps.  Not part of the model config.')
+ARGPARSER.add_argument('--max_skipped_steps', type=int, default=None,
+                       help='With --skip_nonfinite: stop training (RuntimeError, nothing saved) once this many consecutive steps were '
+                            'skipped; an integer >= 1.  Default: 100.')
 ARGPARSER.add_argument('--lr_schedule', type=str, default=None, choices=['constant', 'exponential', 'cosine', 'piecewise'],
                        help='Learning-rate schedule, evaluated on the device from its step counter (a resumed run continues it); '
                             'events.jsonl then carries learning_rate.  After --lr_warmup_steps, with u the steps since: exponential = '
@@ -191,6 +199,10 @@ def estimator_params(args, e2evmc_config):
     params['clip_norm'] = args.clip_norm
   if args.lr_schedule:
     params['lr_schedule'] = lr_schedule_of(args)
+  if args.skip_nonfinite:
+    params['skip_nonfinite'] = True if args.max_skipped_steps is None else args.max_skipped_steps
+  elif args.max_skipped_steps is not None:
+    raise ValueError('--max_skipped_steps %d without --skip_nonfinite: no step is ever skipped' % args.max_skipped_steps)
   return params
 
 
