@@ -161,6 +161,7 @@ SIGNATURES = {
     'geeco_adam_tf_segments_clip': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _P, _F, _F, _F, _F, _F, _P]),
     'geeco_guard_decide': (_I, [_P, _L, _F, _P, _P, _P]),
     'geeco_adam_tf_segments_guard': (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, _F, _P, _P, _F, _F, _F, _F, _F, _P]),
+    'geeco_adam_tf_segments_scaled': (_I, [_P, _P, _P, _P, _P, _P, POINTER(c_float), _I, _P, _P, _F, _P, _P, _F, _F, _F, _F, _F, _P]),
     'geeco_adam_prepare_schedule': (_I, [_P, POINTER(LrSchedule), _F, _F, _P, _P]),
     'geeco_slab_reduce_batch_prepare_schedule': (_I, [POINTER(SlabReduce), _I, _P, POINTER(LrSchedule), _F, _F, _P, _P]),
     'geeco_lr_schedule_eval': (_I, [POINTER(LrSchedule), _L, POINTER(ctypes.c_double)]),

@@ -16,6 +16,7 @@ State lives in ``model_dir`` as ``model.ckpt-<step>.pt`` + a TF-style ``checkpoi
 from __future__ import annotations
 
 import collections
+import collections.abc
 import json
 import os
 import re
@@ -29,7 +30,7 @@ from . import graph
 from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
 from .tf_checkpoint import EMA_SUFFIX
-from .variables import check_clip_norm, check_ema_decay, check_lr_schedule, check_skip_nonfinite
+from .variables import check_clip_norm, check_ema_decay, check_lr_multipliers, check_lr_schedule, check_skip_nonfinite, model_variable_shapes
 
 
 class ModeKeys:
@@ -135,6 +136,91 @@ def load_checkpoint(store, prefix):
   else:
     from . import tf_checkpoint
     tf_checkpoint.import_checkpoint(store, prefix, load_optimizer=True)
+
+
+def check_warm_start(value, key='warm_start_from'):
+  """``warm_start_from`` normalised (the counterpart of tf.estimator.WarmStartSettings): None = off; a path (a model_dir or a checkpoint
+  prefix), or a mapping with 'ckpt' (such a path), 'vars' (a regular expression ``re.search``es in the NEW model's variable names:
+  which ones to warm-start; default '.*') and 'name_map' ({prefix of the new name: prefix in the checkpoint}, the first that the
+  name starts with is applied).  Returns dict(ckpt=, vars=, name_map=) or None; anything else raises ValueError naming ``key``."""
+  if value is None or value == '':
+    return None
+  if isinstance(value, (str, os.PathLike)):
+    value = {'ckpt': value}
+  if not isinstance(value, collections.abc.Mapping) or not isinstance(value.get('ckpt'), (str, os.PathLike)) or not value.get('ckpt'):
+    raise ValueError("%s=%r: a path, or a mapping with 'ckpt' (a model_dir or a checkpoint prefix), 'vars' and 'name_map'" % (key, value))
+  for field in value:
+    if field not in ('ckpt', 'vars', 'name_map'):
+      raise ValueError("%s: unknown field %r (known: ckpt, vars, name_map)" % (key, field))
+  pattern = value.get('vars', '.*')
+  pattern = '.*' if pattern is None else pattern
+  try:
+    re.compile(pattern)
+  except (re.error, TypeError) as e:
+    raise ValueError('%s: vars=%r is not a regular expression: %s' % (key, pattern, e))
+  name_map = value.get('name_map') or {}
+  if not isinstance(name_map, collections.abc.Mapping) or not all(isinstance(k, str) and isinstance(v, str) for k, v in name_map.items()):
+    raise ValueError('%s: name_map=%r must map prefixes of the new names to prefixes in the checkpoint' % (key, name_map))
+  return {'ckpt': os.fspath(value['ckpt']), 'vars': pattern, 'name_map': collections.OrderedDict(name_map)}
+
+
+def _checkpoint_prefix(path):
+  """A checkpoint prefix from a prefix or a model_dir (its latest checkpoint)."""
+  if os.path.isdir(path):
+    prefix = latest_checkpoint(path)
+    if prefix is None:
+      raise FileNotFoundError('warm_start_from: no checkpoint in %s' % path)
+    return prefix
+  for suffix in ('.pt', '.index'):
+    if path.endswith(suffix):
+      path = path[:-len(suffix)]
+  if not (os.path.exists(path + '.pt') or os.path.exists(path + '.index')):
+    raise FileNotFoundError('warm_start_from: neither %s.pt nor %s.index exists' % (path, path))
+  return path
+
+
+def warm_start(store, settings):
+  """Starts ``store`` from somebody else's checkpoint (tf.estimator.WarmStartSettings).  ``settings``: what
+  ``check_warm_start`` takes.  Every variable whose name matches 'vars' is read from the checkpoint -- the native .pt file when
+  present, else the TF-1.15 bundle of the prefix -- under its name with the first matching 'name_map' prefix rewritten; everything
+  else keeps the value it has (its fresh initialisation).  Parameters only: the Adam moments are zeroed, the step counter is 0, the
+  averaged weights restart from the parameters.  KeyError naming a selected variable the checkpoint lacks, ValueError naming the
+  variable and both shapes where they differ; the store is not touched then.  Returns the names that were warm-started."""
+  import numpy as np
+  st = check_warm_start(settings)
+  prefix = _checkpoint_prefix(st['ckpt'])
+  rx = re.compile(st['vars'])
+  source = collections.OrderedDict()
+  for name in store.shapes:
+    if rx.search(name):
+      old = name
+      for new_prefix, old_prefix in st['name_map'].items():
+        if name.startswith(new_prefix):
+          old = old_prefix + name[len(new_prefix):]
+          break
+      source[name] = old
+  if os.path.exists(prefix + '.pt'):
+    sd = torch.load(prefix + '.pt', map_location='cpu')
+    have = {}
+    for n, shp, off in zip(sd['names'], sd['shapes'], sd['offsets']):
+      if n in set(source.values()):
+        have[n] = sd['params'][off:off + int(np.prod(shp))].reshape(tuple(shp)).numpy()
+  else:
+    from . import tf_checkpoint
+    have = tf_checkpoint.read_checkpoint(prefix, names=set(source.values()))
+  for name, old in source.items():
+    if old not in have:
+      raise KeyError('%s: warm start selects it, but checkpoint %s holds no variable %s' % (name, prefix, old))
+    if tuple(have[old].shape) != tuple(store.shapes[name]):
+      raise ValueError('%s: checkpoint %s holds %s with shape %s, the model needs %s'
+                       % (name, prefix, old, tuple(have[old].shape), tuple(store.shapes[name])))
+  for name, old in source.items():
+    store.var(name).copy_(torch.from_numpy(np.ascontiguousarray(have[old], dtype=np.float32)))
+  store.adam_m.zero_()
+  store.adam_v.zero_()
+  store.global_step.zero_()
+  store._params_rewritten()
+  return list(source)
 
 
 def restore_for_inference(store, model_dir, checkpoint_name=None, use_ema=False):
@@ -263,6 +349,16 @@ def _model_fn(features, labels, mode, params, goal):
   if training and check_lr_schedule(params.get('lr_schedule'), cfg.lr, "params['lr_schedule']") is not None:
     ema['lr_schedule'] = params['lr_schedule']
   shared = params.get('shared_frames')
+  # params['lr_multipliers']: a learning rate per variable, frozen variables, and a backward that stops above them
+  mults = check_lr_multipliers(params.get('lr_multipliers'), model_variable_shapes(cfg, goal), "params['lr_multipliers']")
+  if training and mults is not None:
+    if gdist.world_size() > 1:
+      raise ValueError("params['lr_multipliers'] is single-GPU: with %d ranks the buckets of the gradient exchange would have to "
+                       "shrink with the backward's cut point, which has not been decided" % gdist.world_size())
+    if shared:
+      raise ValueError("params['lr_multipliers'] with params['shared_frames']: the shared-frame backward has no cut points; drop one "
+                       "of the two options")
+    ema['lr_multipliers'] = params['lr_multipliers']
   tables = {}
   if shared:
     # params['shared_frames'] (True, or a capacity F): encode each distinct frame of the batch once
@@ -364,7 +460,9 @@ def _eval_metric_fn(model):
 class Estimator:
   """tf.estimator.Estimator counterpart (train_e2evmc.py:260-264, 284-291)."""
 
-  def __init__(self, model_fn, model_dir=None, config=None, params=None):
+  def __init__(self, model_fn, model_dir=None, config=None, params=None, warm_start_from=None):
+    """``warm_start_from`` (or params['warm_start_from']): ``check_warm_start``; applies only while ``model_dir`` holds no checkpoint
+    of its own (``warm_start``)."""
     self._model_fn = model_fn
     self.model_dir = model_dir
     self.config = config or RunConfig()
@@ -373,10 +471,16 @@ class Estimator:
     check_clip_norm(self.params.get('clip_norm'), "params['clip_norm']")
     check_skip_nonfinite(self.params.get('skip_nonfinite'), "params['skip_nonfinite']")
     check_lr_schedule(self.params.get('lr_schedule'), getattr(self.params.get('e2evmc_config'), 'lr', 0.0), "params['lr_schedule']")
+    if self.params.get('lr_multipliers') is not None and not isinstance(self.params['lr_multipliers'], collections.abc.Mapping):
+      raise ValueError("params['lr_multipliers']=%r: must be None or a mapping {regular expression: multiplier}" % (self.params['lr_multipliers'],))
+    if warm_start_from is None:
+      warm_start_from = self.params.get('warm_start_from')
+    self.warm_start_from = check_warm_start(warm_start_from, "params['warm_start_from']" if 'warm_start_from' in self.params else 'warm_start_from')
     self._specs = {}          # (mode, N) -> (spec, feature buffers, label buffers)
     self.last_train_stats = None
     self._store = None
     self._restored = False
+    self._finetune_logged = False
     if model_dir and gdist.rank() == 0:
       os.makedirs(model_dir, exist_ok=True)
     frac = getattr(self.config.session_config.gpu_options, 'per_process_gpu_memory_fraction', None)
@@ -472,6 +576,7 @@ class Estimator:
       self._store = spec.model.store.base      # (an eval / predict model of a run with ema_decay sits on the shadow view)
       self._store.initialize(seed=self.config.init_seed)
     self._restore_once()
+    self._log_finetune(mode, spec.model)
     self._specs[key] = (spec,) + feed.adopted_slots(fbuf, lbuf, spec.model.inputs)
     return self._specs[key]
 
@@ -483,7 +588,27 @@ class Estimator:
     if ckpt:
       load_checkpoint(self._store, ckpt)
       print('INFO: restored parameters from %s' % ckpt)
+      if self.warm_start_from is not None:      # TensorFlow's rule: a run that resumes its own checkpoint is not warm-started again
+        print('INFO: warm_start_from=%s is ignored: %s holds a checkpoint of its own' % (self.warm_start_from['ckpt'], self.model_dir))
+    elif self.warm_start_from is not None:
+      names = warm_start(self._store, self.warm_start_from)
+      print('INFO: warm-started %d of %d variables from %s' % (len(names), len(self._store.shapes), self.warm_start_from['ckpt']))
     gdist.broadcast_variables(self._store)
+
+  def _log_finetune(self, mode, model):
+    """params['lr_multipliers']: one line of events.jsonl at the start of training -- trainable and frozen parameters, the cut point."""
+    mults = getattr(model, 'lr_multipliers', None)
+    if mode != ModeKeys.TRAIN or mults is None or self._finetune_logged:
+      return
+    self._finetune_logged = True
+    import numpy as np
+    count = lambda keep: int(sum(int(np.prod(model.store.shapes[n])) for n, mul in mults.items() if keep(mul)))
+    line = {'trainable_parameters': count(lambda mul: mul != 0.0), 'frozen_parameters': count(lambda mul: mul == 0.0),
+            'backward_cut': model.backward_cut, 'global_step': int(self._store.global_step.item()), 'wall_time': time.time()}
+    print('INFO: fine-tuning: %(trainable_parameters)d trainable and %(frozen_parameters)d frozen parameters, backward: %(backward_cut)s' % line)
+    if self.model_dir and gdist.rank() == 0:
+      with open(os.path.join(self.model_dir, 'events.jsonl'), 'a') as f:
+        f.write(json.dumps(line) + '\n')
 
   _feed_step = staticmethod(feed.feed_step)      # (fbuf, lbuf, feats, labels): one step's batch into the slots of _get_spec
 

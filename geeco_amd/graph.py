@@ -27,7 +27,8 @@ from . import ops
 from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
-from .variables import _CELLS, VariableStore, check_clip_norm, check_ema_decay, check_lr_schedule, check_skip_nonfinite, model_variable_shapes
+from .variables import (_CELLS, VariableStore, backward_cut, check_clip_norm, check_ema_decay, check_lr_multipliers, check_lr_schedule,
+                        check_skip_nonfinite, lr_multiplier_runs, model_variable_shapes)
 
 
 def build_store(cfg, goal, device, ema=False):
@@ -81,7 +82,7 @@ class _ModelBase:
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
   def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None, lr_schedule=None,
-               skip_nonfinite=None):
+               skip_nonfinite=None, lr_multipliers=None):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
     self.ema_decay = check_ema_decay(ema_decay)
     self.clip_norm = check_clip_norm(clip_norm)
@@ -135,6 +136,21 @@ class _ModelBase:
       self.inputs['target_rgb'] = torch.zeros(N, H, W, 3, **f32)
       if self.C == 4:
         self.inputs['target_depth'] = torch.zeros(N, H, W, 1, **f32)
+    # lr_multipliers: the optimiser step is made of ``lr_runs``, the arena's maximal contiguous runs (offset, count,
+    # multiplier) of one multiplier each with the frozen ones left out, and the backward stops at ``backward_cut``, the lowest layer
+    # with anything to train.  None / 'full': the model without the option.
+    self.lr_multipliers = check_lr_multipliers(lr_multipliers, self.store.shapes) if training else None
+    self.lr_runs, self.backward_cut = None, 'full'
+    if self.lr_multipliers is not None:
+      if self.shared_frames is not None:
+        raise ValueError('lr_multipliers with shared_frames: the shared-frame backward has no cut points; drop one of the two options')
+      self.lr_runs = lr_multiplier_runs(self.store.offsets, self.store.size, self.lr_multipliers)
+      if not self.lr_runs:
+        raise ValueError('lr_multipliers freezes every variable: there is nothing to train')
+      if len(self.lr_runs) > ops._native.ADAM_SEGMENTS_MAX:
+        raise ValueError('lr_multipliers: the table splits the arena into %d runs of one multiplier each; the optimiser step is one launch '
+                         'over at most %d' % (len(self.lr_runs), ops._native.ADAM_SEGMENTS_MAX))
+      self.backward_cut = backward_cut(self.lr_multipliers)
     self.scal = torch.zeros(4, **f32)          # [0] = Adam lr_t, [1] = sum of squares of the arena, [2] = lr(s) under lr_schedule
     self.world = 1
     self._prepared = False      # this step's backward has done adam_prepare's work (_prepare_args; runtime.py sets it too)
@@ -267,7 +283,10 @@ class _ModelBase:
     separately (runtime.py): everything down to conv3, then the encoder bottom (conv2 / conv1).  ``adam_prepare``: see
     _prepare_args (the optimiser's scalars ride in the slab-sum launch of the part it is passed to -- once per step).
     ``defer_sums`` (a list, part 'upper'): the part's pending slab sums are handed to the caller instead of launched (no
-    ``adam_prepare`` then); ``before_bottom`` (part 'bottom'): ConvEncoderStack.backward_bottom.  Both are BesideBottom's."""
+    ``adam_prepare`` then); ``before_bottom`` (part 'bottom'): ConvEncoderStack.backward_bottom.  Both are BesideBottom's.
+    Under ``lr_multipliers`` the backward stops at ``backward_cut``: 'no_bottom' runs no ``enc.backward_bottom`` (conv3's input
+    gradient has no consumer either), 'decoder_only' no encoder launch at all.  The gradient arena of a variable below the cut is NOT
+    written (it keeps what it held); any other frozen variable has its gradient computed and simply not applied."""
     pending = []      # the slab sums of every layer of this call: ONE launch at the end
     if part != 'bottom':
       if self.shared_frames is not None:
@@ -275,13 +294,14 @@ class _ModelBase:
         self._scatter_shared()
       else:
         self._decoder_backward()      # ... down to the encoders' feature gradients
-      self.enc.backward_upper(pending)
+      if self.backward_cut != 'decoder_only':
+        self.enc.backward_upper(pending)
       if defer_sums is not None:
         if part == 'upper':
           defer_sums.extend(pending)
           return
         adam_prepare = False
-    if part != 'upper':
+    if part != 'upper' and self.backward_cut == 'full':
       self.enc.backward_bottom(pending, before_bottom if part == 'bottom' else None)
     prepare = self._prepare_args(adam_prepare)
     if pending or prepare is not None:
@@ -325,6 +345,8 @@ class _ModelBase:
     """The optimiser step of SOME pieces of the arena (``ops.adam_tf_segments``; data parallel: everything that came with the early
     bucket first, the late bucket's variables when it has arrived).  ``last``: the pieces complete the step (weight copies are
     re-derived behind it)."""
+    if self.lr_runs is not None:
+      return self._apply_scaled(segments, g_out, last)
     if self.clip_ws is not None:
       return self._apply_clipped(segments, g_out, last)
     s, kw = self.store, dict(g_out=g_out, grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
@@ -367,7 +389,57 @@ class _ModelBase:
         ops.adam_tf_segments_clip(s.params, s.adam_m, s.adam_v, segs, self.scal, self.clip_out, g_out=out, **ema, **kw)
     self._refresh_after_update()
 
+  def _apply_scaled(self, segments, g_out, last):
+    """apply_gradients_of under ``lr_multipliers``: the pieces are intersected with ``lr_runs``, so every piece that is
+    launched lies in one run and takes its multiplier, and what is frozen is in no piece: neither read nor written.  One launch of
+    ``ops.adam_tf_segments_scaled`` per call that has anything trainable.  Under ``clip_norm`` / ``skip_nonfinite`` the calls wait for the
+    one that completes the step, as in ``_apply_clipped``, and the sum of squares gets the same pieces: the global norm is that of the
+    trainable variables' gradients (tf.clip_by_global_norm over var_list), and a NaN in a frozen variable's gradient slot cannot
+    cause a skip.  The number of launches depends on the multiplier table alone: the step stays one captured graph."""
+    pieces = []
+    for g, off, n in segments:
+      for lo, cnt, mul in self.lr_runs:
+        a, b = max(off, lo), min(off + n, lo + cnt)
+        if a < b:
+          pieces.append((g[a - off:b - off], a, b - a, mul))
+    if len(pieces) > ops._native.ADAM_SEGMENTS_MAX:
+      raise ValueError('lr_multipliers: one call of the optimiser step came in %d pieces; a launch takes at most %d'
+                       % (len(pieces), ops._native.ADAM_SEGMENTS_MAX))
+    s = self.store
+    kw = dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
+    ema = dict(ema=s.ema, global_step=s.global_step, decay=self.ema_decay) if s.ema is not None else {}
+    if self.clip_ws is None:
+      self._prepare_unless_done(last)
+      if pieces:
+        ops.adam_tf_segments_scaled(s.params, s.adam_m, s.adam_v, [q[:3] for q in pieces], [q[3] for q in pieces], self.scal, g_out=g_out,
+                                    **ema, **kw)
+      if last:
+        self._refresh_after_update()
+      return
+    self._clip_calls.append((pieces, g_out))
+    if not last:
+      return
+    calls, self._clip_calls = self._clip_calls, []
+    every = [q[:3] for ps, _ in calls for q in ps]
+    if len(every) > ops._native.ADAM_SEGMENTS_MAX:
+      raise ValueError('clip_norm / skip_nonfinite with lr_multipliers: the optimiser step came in %d pieces; the norm of the whole '
+                       'gradient is one launch over at most %d' % (len(every), ops._native.ADAM_SEGMENTS_MAX))
+    self._prepare_unless_done()
+    ops.grad_sumsq_segments(self.clip_ws, s.params, every, s.size, **kw)
+    if self.guard is not None:
+      ops.guard_decide(self.clip_out, self.guard, self.clip_ws, self.clip_ws.numel(), self.clip_norm or 0.0)
+    else:
+      ops.clip_scale(self.clip_out, self.clip_ws, self.clip_ws.numel(), self.clip_norm)
+    for ps, out in calls:
+      if ps:
+        ops.adam_tf_segments_scaled(s.params, s.adam_m, s.adam_v, [q[:3] for q in ps], [q[3] for q in ps], self.scal, clip_dev=self.clip_out,
+                                    guard=self.guard, g_out=out, **ema, **kw)
+    self._refresh_after_update()
+
   def apply_gradients(self):
+    if self.lr_runs is not None:      # the whole arena: the runs themselves
+      del self._clip_calls[:]
+      return self._apply_scaled([(self.store.grads, 0, self.store.size)], None, True)
     if self.clip_ws is not None:      # the whole arena is the one-piece call
       del self._clip_calls[:]
       return self._apply_clipped([(self.store.grads, 0, self.store.size)], None, True)
@@ -380,8 +452,9 @@ class _ModelBase:
     self._refresh_after_update()
 
   def can_apply_beside_bottom(self):
-    """backward_and_apply needs a training encoder on a CUDA device."""
-    return bool(self.enc.training and self.store.params.is_cuda)
+    """backward_and_apply needs a training encoder on a CUDA device, and a backward that has a bottom to hide the optimiser beside
+    (``backward_cut`` 'full')."""
+    return bool(self.enc.training and self.store.params.is_cuda and self.backward_cut == 'full')
 
   def optimizer_stream(self):
     """The second stream of backward_and_apply: the first of the training encoder's two streams (a process gets 4 hardware queues
@@ -467,11 +540,11 @@ class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None):
-    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``, ``lr_schedule``, ``skip_nonfinite``: see
-    E2EVMC."""
+               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None):
+    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``, ``lr_schedule``, ``skip_nonfinite``,
+    ``lr_multipliers``: see E2EVMC."""
     super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite)
+                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -602,7 +675,7 @@ class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None):
+               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None):
     """``ema_decay`` (a float in (0, 1); None / 0 = off): the optimiser step also keeps an exponential moving average of the
     parameters in ``store.ema`` (tf.train.ExponentialMovingAverage with num_updates = global_step); a store passed in
     must have been built with the arena (``build_store(..., ema=True)``).
@@ -614,12 +687,16 @@ class E2EVMC(_ModelBase):
     ``skip_nonfinite`` (True, or the tolerated number of consecutive skipped steps, an integer >= 1; None / False = off): an optimiser
     step whose gradient has a non-finite global norm leaves p, m, v and the shadow arena as they are -- the step counter still
     advances; ``guard`` then holds [last verdict, skipped steps in all, in a row] and ``clip_out`` [scale, norm].
+    ``lr_multipliers`` (``variables.check_lr_multipliers``: an ordered mapping {regular expression: multiplier}, first match wins, 0 =
+    frozen; None, empty or all ones = off): every variable is updated with lr * its multiplier inside the one Adam pass, a frozen
+    variable's p, m, v and averaged weight keep every bit, and the backward stops at the lowest layer with anything to train
+    (``backward_cut``).  Single GPU, not with ``shared_frames``.
     ``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
     'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
     super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite)
+                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     self.window_mode, self.feat_ch = 'plain', [256]
     # frames are processed time-major ([K][N]) so that step t's features are one dense block

@@ -830,6 +830,20 @@ def adam_tf_segments_guard(p, m, v, segments, scal, clip_dev, guard, ema=None, g
                                             _p(clip_dev), _p(guard), beta1, beta2, eps, grad_scale, l2, _stream()), 'geeco_adam_tf_segments_guard')
 
 
+def adam_tf_segments_scaled(p, m, v, segments, lr_mul, scal, clip_dev=None, guard=None, ema=None, global_step=None, decay=0.0, g_out=None,
+                            beta1=0.9, beta2=0.999, eps=1e-8, grad_scale=1.0, l2=0.0):
+  """``geeco_adam_tf_segments_scaled``: the update of ``adam_tf_segments_guard`` with piece k at ``scal[0] * lr_mul[k]`` (``lr_mul``: one
+  finite number > 0 per piece; a frozen piece is one that is left out).  ``clip_dev`` None: the gradient is not scaled; ``guard`` None:
+  the step is always applied.  Every multiplier 1.0 gives bitwise the entry point without multipliers."""
+  arr = _adam_segments(segments)
+  if len(lr_mul) != len(segments):
+    raise ValueError('adam_tf_segments_scaled: %d pieces with %d multipliers' % (len(segments), len(lr_mul)))
+  mul = (ctypes.c_float * len(segments))(*[float(x) for x in lr_mul])
+  check(_lib().geeco_adam_tf_segments_scaled(_p(p), _p(g_out), _p(m), _p(v), _p(ema), arr, mul, len(segments), _p(scal), _p(global_step), decay,
+                                             _p(clip_dev), _p(guard), beta1, beta2, eps, grad_scale, l2, _stream()),
+        'geeco_adam_tf_segments_scaled')
+
+
 def sumsq_into(out, p, n):
   check(_lib().geeco_sumsq(_p(p), n, _p(out), _stream()), 'geeco_sumsq')
 

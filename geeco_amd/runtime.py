@@ -107,6 +107,8 @@ class TrainStepRunner:
     model.world = self.world
     self.dp = (self.world > 1) if dp is None else bool(dp)
     self.overlap = bool(overlap)
+    if self.dp and getattr(model, 'lr_runs', None) is not None:
+      raise ValueError('lr_multipliers is single-GPU: the buckets of the gradient exchange would have to shrink with the backward\'s cut point')
     self.use_graph = bool(use_graph) and torch.cuda.is_available()
     self._graphs = None
     self._warm = warmup

@@ -108,8 +108,10 @@ def _parse_entry(value):
   return e
 
 
-def read_checkpoint(prefix, verify=True):
-  """-> {variable name: numpy array} for every tensor of the bundle ``<prefix>.index`` / ``.data-*``."""
+def read_checkpoint(prefix, verify=True, names=None):
+  """-> {variable name: numpy array} for every tensor of the bundle ``<prefix>.index`` / ``.data-*``; ``names``: only the tensors of
+  that collection (the others are neither read nor verified; a name the bundle lacks is simply absent from the result)."""
+  names = None if names is None else set(names)
   entries = _read_table(prefix + '.index', verify)
   num_shards = 1
   tensors = {}
@@ -121,6 +123,8 @@ def read_checkpoint(prefix, verify=True):
           num_shards = val
         elif fnum == 2 and val != 0:
           raise NotImplementedError('big-endian bundles are not supported')
+      continue
+    if names is not None and key.decode() not in names:
       continue
     e = _parse_entry(value)
     if e['dtype'] not in _DTYPES:

@@ -14,6 +14,7 @@ import collections
 import collections.abc
 import math
 import numbers
+import re
 
 import numpy as np
 import torch
@@ -126,8 +127,73 @@ def check_skip_nonfinite(value, key='skip_nonfinite'):
                    '(None or False = off)' % (key, value))
 
 
+def check_lr_multipliers(value, names, key='lr_multipliers'):
+  """Per-variable learning-rate multipliers.  ``value``: None or an empty mapping = off (returns None); else an ordered
+  mapping {regular expression: multiplier}.  A variable of ``names`` takes the multiplier of the FIRST expression that ``re.search``
+  finds in its name, 1 if none does; a multiplier is a finite number >= 0 that float32 holds, 0 = the variable is frozen.  Returns
+  {name: float} in the order of ``names``, or None when every variable ends up at exactly 1 (that model is the model without the
+  option).  An expression that matches no variable, or anything else, raises ValueError naming ``key``."""
+  if value is None or (isinstance(value, collections.abc.Mapping) and not value):
+    return None
+  if not isinstance(value, collections.abc.Mapping):
+    raise ValueError('%s=%r: must be None or a mapping {regular expression: multiplier}' % (key, value))
+  names = list(names)
+  patterns = []
+  for pat, mul in value.items():
+    if not isinstance(pat, str):
+      raise ValueError('%s: the pattern %r is not a string' % (key, pat))
+    try:
+      rx = re.compile(pat)
+    except re.error as e:
+      raise ValueError('%s: the pattern %r is not a regular expression: %s' % (key, pat, e))
+    if isinstance(mul, (bool, np.bool_)) or not isinstance(mul, numbers.Real) or not 0.0 <= float(mul) <= float(np.finfo(np.float32).max):
+      raise ValueError('%s: %r: the multiplier %r must be a finite number >= 0 that float32 holds (0 = frozen)' % (key, pat, mul))
+    if not any(rx.search(n) for n in names):
+      raise ValueError('%s: the pattern %r matches no variable of the model' % (key, pat))
+    patterns.append((rx, float(np.float32(mul))))
+  out = collections.OrderedDict()
+  for n in names:
+    out[n] = next((mul for rx, mul in patterns if rx.search(n)), 1.0)
+  return None if all(mul == 1.0 for mul in out.values()) else out
+
+
+def lr_multiplier_runs(offsets, size, multipliers):
+  """The arena as maximal contiguous runs [(offset, count, multiplier)] of one multiplier each.  ``offsets``: {name: offset} in arena
+  order (``VariableStore.offsets``), ``size``: the arena's length.  A variable's span runs up to the next variable's offset, so the
+  alignment pads and the pads of the uniform stride join the variable in front of them; frozen runs (multiplier 0) are dropped.
+  Offsets and counts are multiples of 4 floats."""
+  names = list(offsets)
+  runs = []
+  for i, n in enumerate(names):
+    lo, hi = offsets[n], offsets[names[i + 1]] if i + 1 < len(names) else size
+    mul = float(multipliers[n])
+    if runs and runs[-1][2] == mul and runs[-1][1] == lo:
+      runs[-1][1] = hi
+    else:
+      runs.append([lo, hi, mul])
+  return [(lo, hi - lo, mul) for lo, hi, mul in runs if mul != 0.0 and hi > lo]
+
+
+BACKWARD_CUTS = ('full', 'no_bottom', 'decoder_only')
+_ENC_BOTTOM = re.compile(r'/conv[12]/(kernel|bias)$')
+_ENC_ANY = re.compile(r'/conv\d+/(kernel|bias)$')
+
+
+def backward_cut(multipliers):
+  """Where the backward of a model with these per-variable multipliers (None: no option) stops: 'full' (anything trainable in conv1 /
+  conv2 of any encoder), 'no_bottom' (conv1 and conv2, kernel and bias, frozen in every encoder), 'decoder_only' (every encoder
+  variable frozen)."""
+  if multipliers is None:
+    return 'full'
+  if all(mul == 0.0 for n, mul in multipliers.items() if _ENC_ANY.search(n)):
+    return 'decoder_only'
+  if all(mul == 0.0 for n, mul in multipliers.items() if _ENC_BOTTOM.search(n)):
+    return 'no_bottom'
+  return 'full'
+
+
 LR_KINDS = ('constant', 'exponential', 'cosine', 'piecewise')
-LR_BOUNDARIES_MAX = 8       # GEECO_LR_BOUNDARIES_MAX of include/geeco_hip.h
+LR_BOUNDARIES_MAX = 8      # GEECO_LR_BOUNDARIES_MAX of include/geeco_hip.h
 _LR_FIELDS = ('kind', 'warmup_steps', 'decay_steps', 'decay_rate', 'alpha', 'staircase', 'boundaries', 'values')
 
 

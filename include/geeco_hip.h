@@ -30,7 +30,7 @@ extern "C" {
  * geeco_gather_windows_augmented, geeco_adam_tf_ema, geeco_adam_tf_segments_ema, geeco_clip_ws_floats,
  * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip, geeco_gather_windows_scene,
  * geeco_adam_prepare_schedule, geeco_slab_reduce_batch_prepare_schedule, geeco_lr_schedule_eval, geeco_guard_decide,
- * geeco_adam_tf_segments_guard */
+ * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -621,6 +621,20 @@ int geeco_adam_tf_segments_guard(float* p, float* g_out, float* m, float* v, flo
                                  int nseg, const float* lr_t_dev, const int64_t* global_step_dev, float decay, const float* clip_dev,
                                  const int64_t* guard_dev, float beta1, float beta2, float eps, float grad_scale, float l2,
                                  void* stream);
+/* Opt-in fine-tuning: the update of geeco_adam_tf_segments_guard with a learning-rate multiplier per piece.  Piece k runs
+ * lr_t_dev[0] * lr_mul[k], one float32 product per piece formed on the device from lr_t_dev[0] as the prepare work left it.
+ * lr_mul: nseg floats on the HOST, each a finite number > 0.  A frozen variable is not a multiplier of 0 but a piece the caller leaves
+ * out: what no piece covers is neither read nor written, its p, m, v and shadow weights keep every bit.
+ * clip_dev_or_null == NULL: the gradient is not scaled (s is exactly 1.0f).  guard_dev_or_null == NULL: the step is always applied; a
+ * verdict of 0 writes only g_out.  ema_or_null, g_out, offsets (multiples of 4 floats) and counts (any number >= 1, a piece ends in a
+ * scalar tail) as geeco_adam_tf_segments_guard.  With every multiplier 1.0f the results are bit for bit those of
+ * geeco_adam_tf_segments_clip (clip given), geeco_adam_tf_segments_guard (guard given), geeco_adam_tf_segments / _ema (neither).
+ * GEECO_EINVAL (nothing launched): what geeco_adam_tf_segments_clip refuses, lr_mul NULL, a multiplier that is 0, negative or not
+ * finite. */
+int geeco_adam_tf_segments_scaled(float* p, float* g_out, float* m, float* v, float* ema_or_null, const geeco_adam_segment* segs,
+                                  const float* lr_mul, int nseg, const float* lr_t_dev, const int64_t* global_step_dev, float decay,
+                                  const float* clip_dev_or_null, const int64_t* guard_dev_or_null, float beta1, float beta2, float eps,
+                                  float grad_scale, float l2, void* stream);
 /* Opt-in learning-rate schedules, evaluated on the device from the step counter by the thread that does the prepare work: no
  * launch, no host synchronisation and no re-capture of a recorded step; a restored counter continues the schedule.
  * With t the counter after the increment (the t of lr_t), s = t - 1 the updates completed (the global_step TF 1.15's

@@ -13,6 +13,7 @@ batch_size / world windows (geeco_amd.input_fn.pickplace_input_fn(shard=...)).
 ``--dataset_dir synthetic:<num_batches>`` trains on seeded synthetic windows (no dataset on disk).
 """
 import argparse
+import collections
 import json
 import os
 import pprint
@@ -141,6 +142,25 @@ ARGPARSER.add_argument('--lr_boundaries', type=str, default='',
                        help='Piecewise schedule: at most 8 strictly increasing step counts (after the warm-up), comma-separated: a,b,..')
 ARGPARSER.add_argument('--lr_values', type=str, default='',
                        help='Piecewise schedule: one rate more than boundaries, comma-separated: x,y,..; value i runs while u <= boundary i.')
+ARGPARSER.add_argument('--warm_start_from', type=str, default=None,
+                       help='Fine-tuning: start from the weights of this checkpoint (a model_dir or a checkpoint prefix; a native .pt '
+                            'file or a TF-1.15 bundle such as the published geeco_models_icra21 weights), as '
+                            'tf.estimator.WarmStartSettings does: parameters only, Adam moments and the step counter start at zero.  '
+                            'Ignored once --model_dir holds a checkpoint of its own.  Not part of the model config.')
+ARGPARSER.add_argument('--warm_start_vars', type=str, default='.*',
+                       help='With --warm_start_from: regular expression (re.search) of the variables to warm-start; the others keep '
+                            'their fresh initialisation.')
+ARGPARSER.add_argument('--warm_start_map', type=str, default='',
+                       help='With --warm_start_from: NEW=OLD[,NEW=OLD...], prefixes of this model\'s variable names and what stands in '
+                            'their place in the checkpoint, e.g. GoalVMC/ConvEncoder=VMC/ConvEncoder.')
+ARGPARSER.add_argument('--lr_multipliers', type=str, default='',
+                       help="Fine-tuning: 'REGEX=MULT[,REGEX=MULT...]', a learning-rate multiplier per variable (re.search on its "
+                            'name, the first match wins, unmatched variables run at 1); 0 freezes a variable, and the backward stops at '
+                            'the lowest layer with anything to train.  One GPU, not with --shared_frames.  Not part of the model config.')
+ARGPARSER.add_argument('--freeze_encoder_bottom', default=False, action='store_true',
+                       help="Shorthand for the --lr_multipliers entry '/conv[12]/=0': conv1 and conv2 of every encoder are frozen.")
+ARGPARSER.add_argument('--freeze_encoders', default=False, action='store_true',
+                       help="Shorthand for the --lr_multipliers entry 'Encoder/=0': only the decoder is trained.")
 
 _OBSERVATION_FORMAT_TO_CHANNELS = {'rgb': 3, 'rgbd': 4}                      # train_e2evmc.py:129-132
 _GOAL_CONDITION_TO_MODEL = {'none': (e2evmc_model_fn, 'VMC'),               # train_e2evmc.py:134-137
@@ -203,7 +223,42 @@ def estimator_params(args, e2evmc_config):
     params['skip_nonfinite'] = True if args.max_skipped_steps is None else args.max_skipped_steps
   elif args.max_skipped_steps is not None:
     raise ValueError('--max_skipped_steps %d without --skip_nonfinite: no step is ever skipped' % args.max_skipped_steps)
+  multipliers = lr_multipliers_of(args)
+  if multipliers:
+    params['lr_multipliers'] = multipliers
+  if args.warm_start_from:
+    params['warm_start_from'] = {'ckpt': args.warm_start_from, 'vars': args.warm_start_vars, 'name_map': _pairs('--warm_start_map', args.warm_start_map)}
+  elif args.warm_start_map or args.warm_start_vars != '.*':
+    raise ValueError('--warm_start_vars / --warm_start_map without --warm_start_from: there is no checkpoint to read')
   return params
+
+
+def _pairs(flag, text):
+  """'A=B,C=D' -> OrderedDict([(A, B), (C, D)]) (split at the LAST '=' of an entry: a regular expression may hold one)."""
+  out = collections.OrderedDict()
+  for entry in (e.strip() for e in text.split(',')):
+    if not entry:
+      continue
+    left, eq, right = entry.rpartition('=')
+    if not eq or not left or not right:
+      raise ValueError('%s: %r is not of the form LEFT=RIGHT' % (flag, entry))
+    out[left] = right
+  return out
+
+
+def lr_multipliers_of(args):
+  """params['lr_multipliers'] from --lr_multipliers and its two shorthands (the shorthands first: the first match wins)."""
+  out = collections.OrderedDict()
+  if args.freeze_encoders:
+    out['Encoder/'] = 0.0
+  if args.freeze_encoder_bottom:
+    out['/conv[12]/'] = 0.0
+  for pattern, mul in _pairs('--lr_multipliers', args.lr_multipliers).items():
+    try:
+      out.setdefault(pattern, float(mul))
+    except ValueError:
+      raise ValueError('--lr_multipliers: %r: the multiplier %r is not a number' % (pattern, mul))
+  return out
 
 
 def lr_schedule_of(args):
