@@ -1,8 +1,9 @@
 // Opt-in global-norm gradient clipping (tf.clip_by_global_norm in front of Adam), kept on the device: the sum of squares
-// of the total gradient in fixed chunks of the arena, the scale from it, and the Adam update that consumes the scaled gradient.
-#include "clip_internal.h"      // the norm from the partials and the Adam pass on the scaled gradient, shared with csrc/guard.hip
+// of the total gradient in fixed chunks of the arena and the scale from it.  The Adam update that consumes the scaled gradient:
+// geeco_adam_tf_segments_clip, csrc/adam.hip.
+#include "clip_internal.h"      // the norm from the partials, shared with csrc/guard.hip
 
-// The total gradient of element i is the one the Adam kernels form: G_i = g_i * grad_scale + l2 * p_i (csrc/misc.hip: adam_element).
+// The total gradient of element i is the one the Adam kernel forms: G_i = g_i * grad_scale + l2 * p_i (csrc/adam.hip: adam_element).
 // Here it is written with explicit operations, so that every path of the kernel below (16-byte or scalar load, any piece) rounds it
 // alike: the product l2 * p rounded, then one FMA.
 __device__ __forceinline__ float clip_total_grad(float g, float p, float gscale, float l2) { return fmaf(g, gscale, l2 * p); }
@@ -129,12 +130,4 @@ extern "C" int geeco_clip_scale(const float* partials, int64_t nchunks, float cl
   hipLaunchKernelGGL(clip_scale_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (long long)nchunks, clip, out2);
   GEECO_LAUNCH_CHECK();
   return 0;
-}
-
-// ---- Adam on the clipped gradient: csrc/clip_internal.h -------------------------------------------------
-extern "C" int geeco_adam_tf_segments_clip(float* p, float* g_out, float* m, float* v, float* ema_or_null, const geeco_adam_segment* segs, int nseg,
-                                           const float* lr_t_dev, const int64_t* global_step_dev, float decay, const float* clip_dev, float beta1,
-                                           float beta2, float eps, float grad_scale, float l2, void* stream) {
-  return adam_segments_clip_launch<false>("adam_tf_segments_clip", p, g_out, m, v, ema_or_null, segs, nseg, lr_t_dev, global_step_dev, decay, clip_dev,
-                                          nullptr, beta1, beta2, eps, grad_scale, l2, stream);
 }

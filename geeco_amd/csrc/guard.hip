@@ -1,5 +1,6 @@
 // Opt-in skipping of optimiser steps whose gradient is not finite, kept on the device: the decision from the partial
-// sums of squares that geeco_grad_sumsq_segments (csrc/clip.hip) leaves, and the Adam update that honours it.
+// sums of squares that geeco_grad_sumsq_segments (csrc/clip.hip) leaves.  The Adam update that honours it: geeco_adam_tf_segments_guard,
+// csrc/adam.hip.
 #include "clip_internal.h"
 
 // ---- the decision -----------------------------------------------------------------------------------
@@ -29,12 +30,4 @@ extern "C" int geeco_guard_decide(const float* partials, int64_t nchunks, float 
   hipLaunchKernelGGL(guard_decide_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, (long long)nchunks, clip, out2, (long long*)guard);
   GEECO_LAUNCH_CHECK();
   return 0;
-}
-
-// ---- Adam behind the decision: csrc/clip_internal.h, GUARD = true ------------------------------------
-extern "C" int geeco_adam_tf_segments_guard(float* p, float* g_out, float* m, float* v, float* ema_or_null, const geeco_adam_segment* segs, int nseg,
-                                            const float* lr_t_dev, const int64_t* global_step_dev, float decay, const float* clip_dev,
-                                            const int64_t* guard_dev, float beta1, float beta2, float eps, float grad_scale, float l2, void* stream) {
-  return adam_segments_clip_launch<true>("adam_tf_segments_guard", p, g_out, m, v, ema_or_null, segs, nseg, lr_t_dev, global_step_dev, decay, clip_dev,
-                                         guard_dev, beta1, beta2, eps, grad_scale, l2, stream);
 }

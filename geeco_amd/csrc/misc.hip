@@ -1,4 +1,4 @@
-// Small HBM-bound helpers: kernel transposes/padding, fused TF-style Adam, reductions.
+// Small HBM-bound helpers: kernel transposes/padding, the Adam step's scalars, reductions.
 #include "geeco_common.h"
 
 // ---- [G][9][A][B] -> [G][9][B][A] ----------------------------------------------------------------
@@ -144,7 +144,7 @@ extern "C" int geeco_derive_conv_weights(int nlayers, const float* const* w, flo
   return 0;
 }
 
-// ---- Adam (tf.train.AdamOptimizer semantics) -------------------------------------------------------
+// ---- Adam's scalars (the update itself: csrc/adam.hip) ---------------------------------------------
 // scal[0] = lr_t for this step; the step counter lives in device memory so that a captured
 // hipGraph replays with the right bias correction.
 __global__ void adam_prepare_kernel(long long* step, float lr, float b1, float b2, float* scal) {
@@ -161,265 +161,6 @@ extern "C" int geeco_adam_prepare(int64_t* global_step_dev, float lr, float beta
   GEECO_CHECK_ARG(global_step_dev && scal_dev, "adam_prepare: null pointer");
   hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (long long*)global_step_dev, lr,
                      beta1, beta2, scal_dev);
-  GEECO_LAUNCH_CHECK();
-  return 0;
-}
-
-// One element of the update: the arithmetic of every Adam kernel below, plain or with the shadow arena.
-__device__ __forceinline__ void adam_element(float& p, float g, float& m, float& v, float lr_t, float b1, float b2, float eps,
-                                             float gscale, float l2) {
-  float gg = g * gscale + l2 * p;
-  m = b1 * m + (1.f - b1) * gg;
-  v = b2 * v + (1.f - b2) * gg * gg;
-  p = p - lr_t * m / (sqrtf(v) + eps);
-}
-
-// Exponential moving average of the parameters (tf.train.ExponentialMovingAverage, zero_debias=False, num_updates=global_step),
-// kept by the same pass: d_t = min(decay, (1 + t) / (10 + t)), t = the step counter the prepare work has already advanced (stream
-// order).  Uniform over the launch and a handful of instructions, so every thread computes it.
-__device__ __forceinline__ float ema_decay_now(const long long* __restrict__ step, float decay) {
-  const float t = (float)*step;
-  return fminf(decay, (1.f + t) / (10.f + t));
-}
-
-// s' = s - (s - p') (1 - d_t), p' = the parameter this step has just computed (still in registers), evaluated as p' + (s - p') d_t
-// in one subtraction and one FMA: the same value with two roundings instead of four (1 - d_t is not formed, so not rounded), at
-// most 0.5 ulp(s - p') d_t + 0.5 ulp(s') < 1.5 ulp of max(|s|, |p'|) from the exact result whatever the signs of s and p'.
-__device__ __forceinline__ float ema_element(float s, float p, float d) { return fmaf(s - p, d, p); }
-
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, long long n,
-                                                   const float* __restrict__ scal, float b1, float b2, float eps,
-                                                   float gscale, float l2) {
-  const float lr_t = scal[0];
-  const long long n4 = n >> 2;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-    f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-    f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
-    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
-    float pe[4] = {pv.x, pv.y, pv.z, pv.w}, ge[4] = {gv.x, gv.y, gv.z, gv.w};
-    float me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) adam_element(pe[k], ge[k], me[k], ve[k], lr_t, b1, b2, eps, gscale, l2);
-    reinterpret_cast<f32x4*>(p)[i] = f32x4{pe[0], pe[1], pe[2], pe[3]};
-    reinterpret_cast<f32x4*>(m)[i] = f32x4{me[0], me[1], me[2], me[3]};
-    reinterpret_cast<f32x4*>(v)[i] = f32x4{ve[0], ve[1], ve[2], ve[3]};
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long long i = (n4 << 2) + threadIdx.x;
-    float gg = g[i] * gscale + l2 * p[i];      // (adam_element's expressions, spelled out: this kernel's code is kept as it was)
-    float mm = b1 * m[i] + (1.f - b1) * gg;
-    float vv = b2 * v[i] + (1.f - b2) * gg * gg;
-    m[i] = mm;
-    v[i] = vv;
-    p[i] = p[i] - lr_t * mm / (sqrtf(vv) + eps);
-  }
-}
-
-// adam_kernel with the shadow arena: the same walk (grid rule, 16-byte accesses, tail), one more arena read and written while the
-// new parameters are in registers.  p, m, v come out bit for bit as adam_kernel leaves them.
-__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                       float* __restrict__ m, float* __restrict__ v, float* __restrict__ ema,
-                                                       long long n, const float* __restrict__ scal,
-                                                       const long long* __restrict__ step, float decay, float b1, float b2, float eps,
-                                                       float gscale, float l2) {
-  const float lr_t = scal[0];
-  const float d = ema_decay_now(step, decay);
-  const long long n4 = n >> 2;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-    f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-    f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
-    f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
-    f32x4 sv = reinterpret_cast<f32x4*>(ema)[i];
-    float pe[4] = {pv.x, pv.y, pv.z, pv.w}, ge[4] = {gv.x, gv.y, gv.z, gv.w};
-    float me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w};
-    float se[4] = {sv.x, sv.y, sv.z, sv.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      adam_element(pe[k], ge[k], me[k], ve[k], lr_t, b1, b2, eps, gscale, l2);
-      se[k] = ema_element(se[k], pe[k], d);
-    }
-    reinterpret_cast<f32x4*>(p)[i] = f32x4{pe[0], pe[1], pe[2], pe[3]};
-    reinterpret_cast<f32x4*>(m)[i] = f32x4{me[0], me[1], me[2], me[3]};
-    reinterpret_cast<f32x4*>(v)[i] = f32x4{ve[0], ve[1], ve[2], ve[3]};
-    reinterpret_cast<f32x4*>(ema)[i] = f32x4{se[0], se[1], se[2], se[3]};
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const long long i = (n4 << 2) + threadIdx.x;
-    float pp = p[i], mm = m[i], vv = v[i];
-    adam_element(pp, g[i], mm, vv, lr_t, b1, b2, eps, gscale, l2);
-    m[i] = mm;
-    v[i] = vv;
-    p[i] = pp;
-    ema[i] = ema_element(ema[i], pp, d);
-  }
-}
-
-static int adam_grid(long long n4) {      // one rule for the four Adam launches
-  long long blocks = cdiv64(n4, 256);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
-extern "C" int geeco_adam_tf(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_t_dev,
-                             float beta1, float beta2, float eps, float grad_scale, float l2, void* stream) {
-  GEECO_CHECK_ARG(p && g && m && v && lr_t_dev && n >= 1, "adam_tf: bad arguments");
-  GEECO_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0,
-                  "adam_tf: arenas must be 16-byte aligned");
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)adam_grid(n >> 2)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, (long long)n,
-                     lr_t_dev, beta1, beta2, eps, grad_scale, l2);
-  GEECO_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int geeco_adam_tf_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* lr_t_dev,
-                                 const int64_t* global_step_dev, float decay, float beta1, float beta2, float eps, float grad_scale,
-                                 float l2, void* stream) {
-  GEECO_CHECK_ARG(p && g && m && v && lr_t_dev && n >= 1, "adam_tf_ema: bad arguments");
-  GEECO_CHECK_ARG(ema && global_step_dev, "adam_tf_ema: null shadow arena or step counter");
-  GEECO_CHECK_ARG(decay > 0.f && decay < 1.f, "adam_tf_ema: decay %g is outside (0, 1)", (double)decay);
-  GEECO_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0,
-                  "adam_tf_ema: arenas must be 16-byte aligned");
-  hipLaunchKernelGGL(adam_ema_kernel, dim3((unsigned)adam_grid(n >> 2)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema,
-                     (long long)n, lr_t_dev, (const long long*)global_step_dev, decay, beta1, beta2, eps, grad_scale, l2);
-  GEECO_LAUNCH_CHECK();
-  return 0;
-}
-
-// The same update over up to GEECO_ADAM_SEGMENTS_MAX pieces of the arena, each with its own gradient source (data parallel: the
-// 99 % of the variables whose gradients arrived with the early bucket are updated while the late bucket is still on the wire;
-// conv1 / conv2 of the encoders follow, their gradients read straight from the late bucket's staging buffer).  Element by element the
-// arithmetic of adam_kernel: any partition of the arena gives bitwise the one-pass result.
-struct AdamSegs {
-  const float* g[GEECO_ADAM_SEGMENTS_MAX];
-  long long p4[GEECO_ADAM_SEGMENTS_MAX];        // first float4 of the piece in the arena
-  long long n4[GEECO_ADAM_SEGMENTS_MAX];        // its float4 count
-  int n;
-};
-
-__global__ __launch_bounds__(256) void adam_segments_kernel(float* __restrict__ p, float* __restrict__ g_out, float* __restrict__ m,
-                                                            float* __restrict__ v, const AdamSegs s, const float* __restrict__ scal,
-                                                            float b1, float b2, float eps, float gscale, float l2) {
-  const float lr_t = scal[0];
-  // Every block walks piece after piece with the whole grid's stride, as adam_kernel walks the arena (pieces dealt to block groups side by
-  // side measured the same: 36.4-36.8 us for the early pieces of the bench model against 33.8 for the undivided pass in the same
-  // place of the step).  The piece loop is unrolled: static indices into the by-value argument (a dynamic index would copy it to scratch).
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < GEECO_ADAM_SEGMENTS_MAX; ++k) {
-    if (k >= s.n) break;
-    const long long e0 = s.p4[k], cnt = s.n4[k];
-    const float* __restrict__ gs = s.g[k];
-    for (long long i = i0; i < cnt; i += stride) {
-      const long long e = e0 + i;
-      f32x4 pv = reinterpret_cast<f32x4*>(p)[e];
-      f32x4 gv = reinterpret_cast<const f32x4*>(gs)[i];
-      f32x4 mv = reinterpret_cast<f32x4*>(m)[e];
-      f32x4 vv = reinterpret_cast<f32x4*>(v)[e];
-      if (g_out) reinterpret_cast<f32x4*>(g_out)[e] = gv;
-      float pe[4] = {pv.x, pv.y, pv.z, pv.w}, ge[4] = {gv.x, gv.y, gv.z, gv.w};
-      float me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) adam_element(pe[c], ge[c], me[c], ve[c], lr_t, b1, b2, eps, gscale, l2);
-      reinterpret_cast<f32x4*>(p)[e] = f32x4{pe[0], pe[1], pe[2], pe[3]};
-      reinterpret_cast<f32x4*>(m)[e] = f32x4{me[0], me[1], me[2], me[3]};
-      reinterpret_cast<f32x4*>(v)[e] = f32x4{ve[0], ve[1], ve[2], ve[3]};
-    }
-  }
-}
-
-// adam_segments_kernel with the shadow arena, indexed like p: element by element adam_ema_kernel's arithmetic, so any partition of
-// the arena gives bitwise the one-pass result for the shadow arena too.
-__global__ __launch_bounds__(256) void adam_segments_ema_kernel(float* __restrict__ p, float* __restrict__ g_out,
-                                                                float* __restrict__ m, float* __restrict__ v,
-                                                                float* __restrict__ ema, const AdamSegs s,
-                                                                const float* __restrict__ scal, const long long* __restrict__ step,
-                                                                float decay, float b1, float b2, float eps, float gscale, float l2) {
-  const float lr_t = scal[0];
-  const float d = ema_decay_now(step, decay);
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < GEECO_ADAM_SEGMENTS_MAX; ++k) {
-    if (k >= s.n) break;
-    const long long e0 = s.p4[k], cnt = s.n4[k];
-    const float* __restrict__ gs = s.g[k];
-    for (long long i = i0; i < cnt; i += stride) {
-      const long long e = e0 + i;
-      f32x4 pv = reinterpret_cast<f32x4*>(p)[e];
-      f32x4 gv = reinterpret_cast<const f32x4*>(gs)[i];
-      f32x4 mv = reinterpret_cast<f32x4*>(m)[e];
-      f32x4 vv = reinterpret_cast<f32x4*>(v)[e];
-      f32x4 sv = reinterpret_cast<f32x4*>(ema)[e];
-      if (g_out) reinterpret_cast<f32x4*>(g_out)[e] = gv;
-      float pe[4] = {pv.x, pv.y, pv.z, pv.w}, ge[4] = {gv.x, gv.y, gv.z, gv.w};
-      float me[4] = {mv.x, mv.y, mv.z, mv.w}, ve[4] = {vv.x, vv.y, vv.z, vv.w};
-      float se[4] = {sv.x, sv.y, sv.z, sv.w};
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        adam_element(pe[c], ge[c], me[c], ve[c], lr_t, b1, b2, eps, gscale, l2);
-        se[c] = ema_element(se[c], pe[c], d);
-      }
-      reinterpret_cast<f32x4*>(p)[e] = f32x4{pe[0], pe[1], pe[2], pe[3]};
-      reinterpret_cast<f32x4*>(m)[e] = f32x4{me[0], me[1], me[2], me[3]};
-      reinterpret_cast<f32x4*>(v)[e] = f32x4{ve[0], ve[1], ve[2], ve[3]};
-      reinterpret_cast<f32x4*>(ema)[e] = f32x4{se[0], se[1], se[2], se[3]};
-    }
-  }
-}
-
-// The pieces as the kernels take them; returns the grid (every block walks every piece), or GEECO_EINVAL with the error set.
-static int adam_segments_table(const char* who, const geeco_adam_segment* segs, int nseg, AdamSegs* s) {
-  *s = {};
-  s->n = nseg;
-  long long longest4 = 1;
-  for (int k = 0; k < nseg; ++k) {
-    GEECO_CHECK_ARG(segs[k].g && ((uintptr_t)segs[k].g & 15) == 0 && segs[k].p_off >= 0 && segs[k].p_off % 4 == 0 && segs[k].count >= 4 &&
-                        segs[k].count % 4 == 0,
-                    "%s: piece %d: offset / count must be multiples of 4 floats, the gradient source 16-byte aligned", who, k);
-    s->g[k] = segs[k].g;
-    s->p4[k] = segs[k].p_off / 4;
-    s->n4[k] = segs[k].count / 4;
-    longest4 = s->n4[k] > longest4 ? s->n4[k] : longest4;
-  }
-  return adam_grid(longest4);      // as geeco_adam_tf
-}
-
-extern "C" int geeco_adam_tf_segments(float* p, float* g_out, float* m, float* v, const geeco_adam_segment* segs, int nseg,
-                                      const float* lr_t_dev, float beta1, float beta2, float eps, float grad_scale, float l2,
-                                      void* stream) {
-  GEECO_CHECK_ARG(p && m && v && lr_t_dev && segs && nseg >= 1 && nseg <= GEECO_ADAM_SEGMENTS_MAX, "adam_tf_segments: bad arguments (1..%d pieces)",
-                  GEECO_ADAM_SEGMENTS_MAX);
-  GEECO_CHECK_ARG((((uintptr_t)p | (uintptr_t)g_out | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adam_tf_segments: arenas must be 16-byte aligned");
-  AdamSegs s;
-  const int b = adam_segments_table("adam_tf_segments", segs, nseg, &s);
-  if (b < 0) return b;
-  hipLaunchKernelGGL(adam_segments_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, p, g_out, m, v, s, lr_t_dev, beta1, beta2,
-                     eps, grad_scale, l2);
-  GEECO_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int geeco_adam_tf_segments_ema(float* p, float* g_out, float* m, float* v, float* ema, const geeco_adam_segment* segs,
-                                          int nseg, const float* lr_t_dev, const int64_t* global_step_dev, float decay, float beta1,
-                                          float beta2, float eps, float grad_scale, float l2, void* stream) {
-  GEECO_CHECK_ARG(p && m && v && lr_t_dev && segs && nseg >= 1 && nseg <= GEECO_ADAM_SEGMENTS_MAX,
-                  "adam_tf_segments_ema: bad arguments (1..%d pieces)", GEECO_ADAM_SEGMENTS_MAX);
-  GEECO_CHECK_ARG(ema && global_step_dev, "adam_tf_segments_ema: null shadow arena or step counter");
-  GEECO_CHECK_ARG(decay > 0.f && decay < 1.f, "adam_tf_segments_ema: decay %g is outside (0, 1)", (double)decay);
-  GEECO_CHECK_ARG((((uintptr_t)p | (uintptr_t)g_out | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0,
-                  "adam_tf_segments_ema: arenas must be 16-byte aligned");
-  AdamSegs s;
-  const int b = adam_segments_table("adam_tf_segments_ema", segs, nseg, &s);
-  if (b < 0) return b;
-  hipLaunchKernelGGL(adam_segments_ema_kernel, dim3((unsigned)b), dim3(256), 0, (hipStream_t)stream, p, g_out, m, v, ema, s, lr_t_dev,
-                     (const long long*)global_step_dev, decay, beta1, beta2, eps, grad_scale, l2);
   GEECO_LAUNCH_CHECK();
   return 0;
 }

@@ -12,10 +12,11 @@ Data layout in HBM: NHWC fp32 activations; the G encoders of a model ("ConvEncod
 "DynBuffEncoder", "DynDiffEncoder") are stacked along a leading group axis and each layer is ONE
 launch over all groups; RGB inputs are channel-padded to 4 so conv1 gathers float4 pixels.
 
-This file holds the two training / evaluation models (``_ModelBase``, ``GoalE2EVMC``, ``E2EVMC``): inputs, the step and the
-optimiser pieces.  Their parts live next door and are re-imported here, so ``graph.X`` names the same object: variable creation
-order in variables.py, ``ConvEncoderStack`` in encoder.py, ``head_table`` / ``LSTMDecoder`` in decoder.py, the one-frame
-predictors' ``E2EVMCStep`` / ``GoalE2EVMCStep`` in step_models.py.
+This file holds the two training / evaluation models (``_ModelBase``, ``GoalE2EVMC``, ``E2EVMC``): inputs, the step and where the
+optimiser runs in it.  Their parts live next door and are re-imported here, so ``graph.X`` names the same object: variable creation
+order in variables.py, ``ConvEncoderStack`` in encoder.py, ``head_table`` / ``LSTMDecoder`` in decoder.py, the optimiser step
+(``OptimizerStep``, which ``_ModelBase`` inherits) in optimizer.py, the one-frame predictors' ``E2EVMCStep`` / ``GoalE2EVMCStep`` in
+step_models.py.
 """
 from __future__ import annotations
 
@@ -26,9 +27,10 @@ import torch
 from . import ops
 from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
+from .optimizer import OptimizerStep
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
-from .variables import (_CELLS, VariableStore, backward_cut, check_clip_norm, check_ema_decay, check_lr_multipliers, check_lr_schedule,
-                        check_skip_nonfinite, lr_multiplier_runs, model_variable_shapes)
+from .variables import (_CELLS, VariableStore, check_clip_norm, check_ema_decay, check_lr_schedule, check_skip_nonfinite,
+                        model_variable_shapes)
 
 
 def build_store(cfg, goal, device, ema=False):
@@ -78,7 +80,7 @@ class BesideBottom:
     self.main.wait_stream(self.side)
 
 
-class _ModelBase:
+class _ModelBase(OptimizerStep):
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
   def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None, lr_schedule=None,
@@ -136,36 +138,8 @@ class _ModelBase:
       self.inputs['target_rgb'] = torch.zeros(N, H, W, 3, **f32)
       if self.C == 4:
         self.inputs['target_depth'] = torch.zeros(N, H, W, 1, **f32)
-    # lr_multipliers: the optimiser step is made of ``lr_runs``, the arena's maximal contiguous runs (offset, count,
-    # multiplier) of one multiplier each with the frozen ones left out, and the backward stops at ``backward_cut``, the lowest layer
-    # with anything to train.  None / 'full': the model without the option.
-    self.lr_multipliers = check_lr_multipliers(lr_multipliers, self.store.shapes) if training else None
-    self.lr_runs, self.backward_cut = None, 'full'
-    if self.lr_multipliers is not None:
-      if self.shared_frames is not None:
-        raise ValueError('lr_multipliers with shared_frames: the shared-frame backward has no cut points; drop one of the two options')
-      self.lr_runs = lr_multiplier_runs(self.store.offsets, self.store.size, self.lr_multipliers)
-      if not self.lr_runs:
-        raise ValueError('lr_multipliers freezes every variable: there is nothing to train')
-      if len(self.lr_runs) > ops._native.ADAM_SEGMENTS_MAX:
-        raise ValueError('lr_multipliers: the table splits the arena into %d runs of one multiplier each; the optimiser step is one launch '
-                         'over at most %d' % (len(self.lr_runs), ops._native.ADAM_SEGMENTS_MAX))
-      self.backward_cut = backward_cut(self.lr_multipliers)
-    self.scal = torch.zeros(4, **f32)          # [0] = Adam lr_t, [1] = sum of squares of the arena, [2] = lr(s) under lr_schedule
-    self.world = 1
-    self._prepared = False      # this step's backward has done adam_prepare's work (_prepare_args; runtime.py sets it too)
+    self._setup_optimizer(training, lr_multipliers)      # scal, lr_runs / backward_cut, the clip and guard buffers (optimizer.py)
     self._opt_stream = None     # optimizer_stream()
-    # clip_norm: the sums of squares of the arena's chunks, [s, norm] of the last optimiser step, and the pieces of
-    # the arena whose update waits for the norm of all of them (apply_gradients_of); a model without the option has none of it
-    # skip_nonfinite shares them -- the norm decides whether the step is applied -- and adds ``guard``: int64 [verdict
-    # of the last step (1 applied, 0 skipped), skipped steps in all, skipped steps in a row]
-    self.clip_ws = self.clip_out = self.guard = None
-    self._clip_calls = []
-    if (self.clip_norm is not None or self.skip_limit is not None) and training:
-      self.clip_ws = torch.zeros(ops.clip_ws_floats(self.store.size), **f32)
-      self.clip_out = torch.zeros(2, **f32)
-      if self.skip_limit is not None:
-        self.guard = torch.zeros(3, dtype=torch.int64, device=self.device)
     # GoalE2EVMC's branch and the control block of its one-pass input stage; the gather mode of a model that takes shared_frames
     self.mode = self.dyn_ws2 = self.window_mode = None
     # RGB-D: rgb || depth (estimator.py:36,169,172).  The dynimg branch of the goal model forms the concat inside its
@@ -322,135 +296,7 @@ class _ModelBase:
   def redirect_late_gradients(self, staging, late_ranges):
     return self.enc.redirect_late_gradients(staging, late_ranges)
 
-  # -- optimiser step (estimator.py:243-244) -------------------------------------------------
-  def _prepare_args(self, adam_prepare):
-    """backward(adam_prepare=True): the step counter / lr_t update rides in the backward's last slab-sum launch (one dependent
-    launch less); apply_gradients() then skips its own adam_prepare.  Only callers that DO apply the gradients next pass it
-    (train_step, runtime.TrainStepRunner): the counter must advance exactly once per optimiser step."""
-    if not adam_prepare:
-      return None
-    self._prepared = True
-    return (self.store.global_step, self._lr_arg, self.scal)
-
-  def _prepare_unless_done(self, last=True):
-    """adam_prepare unless this step's backward carried it; ``last``: the optimiser step is complete behind this piece."""
-    if not self._prepared:
-      if self.lr_schedule is None:
-        ops.adam_prepare(self.store.global_step, self._lr_arg, self.scal)
-      else:
-        ops.adam_prepare_schedule(self.store.global_step, self._lr_arg, self.scal)
-    self._prepared = not last
-
-  def apply_gradients_of(self, segments, g_out=None, last=True):
-    """The optimiser step of SOME pieces of the arena (``ops.adam_tf_segments``; data parallel: everything that came with the early
-    bucket first, the late bucket's variables when it has arrived).  ``last``: the pieces complete the step (weight copies are
-    re-derived behind it)."""
-    if self.lr_runs is not None:
-      return self._apply_scaled(segments, g_out, last)
-    if self.clip_ws is not None:
-      return self._apply_clipped(segments, g_out, last)
-    s, kw = self.store, dict(g_out=g_out, grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
-    self._prepare_unless_done(last)
-    if s.ema is not None:      # the averaged weights follow in the same launch (DESIGN 5.15)
-      ops.adam_tf_segments_ema(s.params, s.adam_m, s.adam_v, s.ema, segments, self.scal, s.global_step, self.ema_decay, **kw)
-    else:
-      ops.adam_tf_segments(s.params, s.adam_m, s.adam_v, segments, self.scal, **kw)
-    if last:
-      self._refresh_after_update()
-
-  def _apply_clipped(self, segments, g_out, last):
-    """apply_gradients_of under ``clip_norm`` and / or ``skip_nonfinite``: no piece may move before the norm of ALL of them is known, so the pieces of a call that
-    does not complete the step are recorded and nothing is launched for them; the call that does runs, in order, the sum of squares
-    over every recorded piece and its own (ONE launch: the partial sums are then bitwise those of the undivided arena, whatever the
-    pieces), the scale, and the clipped Adam update call by call (each with its own ``g_out``).  Three launches for the whole arena,
-    four for the two pieces of the schedules in runtime.py -- constant per schedule, so the step stays one captured graph.
-    Under ``skip_nonfinite`` the scale comes from ``guard_decide`` (clip 0 = no clipping) with the verdict on the step, and the update
-    is the one that honours it: the same launches whether the step is applied or skipped."""
-    self._clip_calls.append((list(segments), g_out))
-    if not last:
-      return
-    s, calls = self.store, self._clip_calls
-    self._clip_calls = []
-    pieces = [seg for segs, _ in calls for seg in segs]
-    if len(pieces) > ops._native.ADAM_SEGMENTS_MAX:
-      raise ValueError('clip_norm / skip_nonfinite: the optimiser step came in %d pieces; the norm of the whole gradient is one launch over at most %d'
-                       % (len(pieces), ops._native.ADAM_SEGMENTS_MAX))
-    kw = dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
-    self._prepare_unless_done()
-    ops.grad_sumsq_segments(self.clip_ws, s.params, pieces, s.size, **kw)
-    ema = dict(ema=s.ema, global_step=s.global_step, decay=self.ema_decay) if s.ema is not None else {}
-    if self.guard is not None:
-      ops.guard_decide(self.clip_out, self.guard, self.clip_ws, self.clip_ws.numel(), self.clip_norm or 0.0)
-      for segs, out in calls:
-        ops.adam_tf_segments_guard(s.params, s.adam_m, s.adam_v, segs, self.scal, self.clip_out, self.guard, g_out=out, **ema, **kw)
-    else:
-      ops.clip_scale(self.clip_out, self.clip_ws, self.clip_ws.numel(), self.clip_norm)
-      for segs, out in calls:
-        ops.adam_tf_segments_clip(s.params, s.adam_m, s.adam_v, segs, self.scal, self.clip_out, g_out=out, **ema, **kw)
-    self._refresh_after_update()
-
-  def _apply_scaled(self, segments, g_out, last):
-    """apply_gradients_of under ``lr_multipliers``: the pieces are intersected with ``lr_runs``, so every piece that is
-    launched lies in one run and takes its multiplier, and what is frozen is in no piece: neither read nor written.  One launch of
-    ``ops.adam_tf_segments_scaled`` per call that has anything trainable.  Under ``clip_norm`` / ``skip_nonfinite`` the calls wait for the
-    one that completes the step, as in ``_apply_clipped``, and the sum of squares gets the same pieces: the global norm is that of the
-    trainable variables' gradients (tf.clip_by_global_norm over var_list), and a NaN in a frozen variable's gradient slot cannot
-    cause a skip.  The number of launches depends on the multiplier table alone: the step stays one captured graph."""
-    pieces = []
-    for g, off, n in segments:
-      for lo, cnt, mul in self.lr_runs:
-        a, b = max(off, lo), min(off + n, lo + cnt)
-        if a < b:
-          pieces.append((g[a - off:b - off], a, b - a, mul))
-    if len(pieces) > ops._native.ADAM_SEGMENTS_MAX:
-      raise ValueError('lr_multipliers: one call of the optimiser step came in %d pieces; a launch takes at most %d'
-                       % (len(pieces), ops._native.ADAM_SEGMENTS_MAX))
-    s = self.store
-    kw = dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
-    ema = dict(ema=s.ema, global_step=s.global_step, decay=self.ema_decay) if s.ema is not None else {}
-    if self.clip_ws is None:
-      self._prepare_unless_done(last)
-      if pieces:
-        ops.adam_tf_segments_scaled(s.params, s.adam_m, s.adam_v, [q[:3] for q in pieces], [q[3] for q in pieces], self.scal, g_out=g_out,
-                                    **ema, **kw)
-      if last:
-        self._refresh_after_update()
-      return
-    self._clip_calls.append((pieces, g_out))
-    if not last:
-      return
-    calls, self._clip_calls = self._clip_calls, []
-    every = [q[:3] for ps, _ in calls for q in ps]
-    if len(every) > ops._native.ADAM_SEGMENTS_MAX:
-      raise ValueError('clip_norm / skip_nonfinite with lr_multipliers: the optimiser step came in %d pieces; the norm of the whole '
-                       'gradient is one launch over at most %d' % (len(every), ops._native.ADAM_SEGMENTS_MAX))
-    self._prepare_unless_done()
-    ops.grad_sumsq_segments(self.clip_ws, s.params, every, s.size, **kw)
-    if self.guard is not None:
-      ops.guard_decide(self.clip_out, self.guard, self.clip_ws, self.clip_ws.numel(), self.clip_norm or 0.0)
-    else:
-      ops.clip_scale(self.clip_out, self.clip_ws, self.clip_ws.numel(), self.clip_norm)
-    for ps, out in calls:
-      if ps:
-        ops.adam_tf_segments_scaled(s.params, s.adam_m, s.adam_v, [q[:3] for q in ps], [q[3] for q in ps], self.scal, clip_dev=self.clip_out,
-                                    guard=self.guard, g_out=out, **ema, **kw)
-    self._refresh_after_update()
-
-  def apply_gradients(self):
-    if self.lr_runs is not None:      # the whole arena: the runs themselves
-      del self._clip_calls[:]
-      return self._apply_scaled([(self.store.grads, 0, self.store.size)], None, True)
-    if self.clip_ws is not None:      # the whole arena is the one-piece call
-      del self._clip_calls[:]
-      return self._apply_clipped([(self.store.grads, 0, self.store.size)], None, True)
-    s, kw = self.store, dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
-    self._prepare_unless_done()
-    if s.ema is not None:
-      ops.adam_tf_ema(s.params, s.grads, s.adam_m, s.adam_v, s.ema, s.size, self.scal, s.global_step, self.ema_decay, **kw)
-    else:
-      ops.adam_tf(s.params, s.grads, s.adam_m, s.adam_v, s.size, self.scal, **kw)
-    self._refresh_after_update()
-
+  # -- optimiser step: optimizer.OptimizerStep; what follows places it in the backward ---------
   def can_apply_beside_bottom(self):
     """backward_and_apply needs a training encoder on a CUDA device, and a backward that has a bottom to hide the optimiser beside
     (``backward_cut`` 'full')."""

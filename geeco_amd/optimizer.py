@@ -1,0 +1,153 @@
+"""The optimiser step of the training models (estimator.py:243-244), ONE path behind every option: ``OptimizerStep`` is the part of
+``graph._ModelBase`` that owns the optimiser's device scalars and runs Adam over the arena or pieces of it -- plain, with averaged weights
+(DESIGN 5.15), behind the global norm of the gradient (5.16, 5.19), under a schedule (5.18), with per-scope multipliers (5.20).  The host
+class provides ``cfg``, ``store``, ``device``, the checked options and ``_refresh_after_update()``."""
+from __future__ import annotations
+
+import torch
+
+from . import ops
+from .variables import backward_cut, check_lr_multipliers, lr_multiplier_runs
+
+
+class OptimizerStep:
+  def _setup_optimizer(self, training, lr_multipliers):
+    """The optimiser's state on the device, once the store exists."""
+    f32 = dict(dtype=torch.float32, device=self.device)
+    # lr_multipliers: the optimiser step is made of ``lr_runs``, the arena's maximal contiguous runs (offset, count,
+    # multiplier) of one multiplier each with the frozen ones left out, and the backward stops at ``backward_cut``, the lowest layer
+    # with anything to train.  None / 'full': the model without the option.
+    self.lr_multipliers = check_lr_multipliers(lr_multipliers, self.store.shapes) if training else None
+    self.lr_runs, self.backward_cut = None, 'full'
+    if self.lr_multipliers is not None:
+      if self.shared_frames is not None:
+        raise ValueError('lr_multipliers with shared_frames: the shared-frame backward has no cut points; drop one of the two options')
+      self.lr_runs = lr_multiplier_runs(self.store.offsets, self.store.size, self.lr_multipliers)
+      if not self.lr_runs:
+        raise ValueError('lr_multipliers freezes every variable: there is nothing to train')
+      if len(self.lr_runs) > ops._native.ADAM_SEGMENTS_MAX:
+        raise ValueError('lr_multipliers: the table splits the arena into %d runs of one multiplier each; the optimiser step is one launch '
+                         'over at most %d' % (len(self.lr_runs), ops._native.ADAM_SEGMENTS_MAX))
+      self.backward_cut = backward_cut(self.lr_multipliers)
+    self.scal = torch.zeros(4, **f32)          # [0] = Adam lr_t, [1] = sum of squares of the arena, [2] = lr(s) under lr_schedule
+    self.world = 1
+    self._prepared = False      # this step's backward has done adam_prepare's work (_prepare_args; runtime.py sets it too)
+    # clip_norm: the sums of squares of the arena's chunks, [s, norm] of the last optimiser step, and the calls of
+    # apply_gradients_of whose update waits for the norm of all of them; a model without the option has none of it.
+    # skip_nonfinite shares them -- the norm decides whether the step is applied -- and adds ``guard``: int64 [verdict
+    # of the last step (1 applied, 0 skipped), skipped steps in all, skipped steps in a row]
+    self.clip_ws = self.clip_out = self.guard = None
+    self._clip_calls = []
+    if (self.clip_norm is not None or self.skip_limit is not None) and training:
+      self.clip_ws = torch.zeros(ops.clip_ws_floats(self.store.size), **f32)
+      self.clip_out = torch.zeros(2, **f32)
+      if self.skip_limit is not None:
+        self.guard = torch.zeros(3, dtype=torch.int64, device=self.device)
+
+  def _prepare_args(self, adam_prepare):
+    """backward(adam_prepare=True): the step counter / lr_t update rides in the backward's last slab-sum launch (one dependent
+    launch less); apply_gradients() then skips its own adam_prepare.  Only callers that DO apply the gradients next pass it
+    (train_step, runtime.TrainStepRunner): the counter must advance exactly once per optimiser step."""
+    if not adam_prepare:
+      return None
+    self._prepared = True
+    return (self.store.global_step, self._lr_arg, self.scal)
+
+  def _prepare_unless_done(self, last=True):
+    """adam_prepare unless this step's backward carried it; ``last``: the optimiser step is complete behind this piece."""
+    if not self._prepared:
+      if self.lr_schedule is None:
+        ops.adam_prepare(self.store.global_step, self._lr_arg, self.scal)
+      else:
+        ops.adam_prepare_schedule(self.store.global_step, self._lr_arg, self.scal)
+    self._prepared = not last
+
+  def _pieces(self, segments):
+    """``segments`` as [(gradients, offset, count, multiplier)].  Under ``lr_multipliers`` they are intersected with ``lr_runs``: every
+    piece then lies in one run and takes its multiplier, and what is frozen is in no piece, neither read nor written."""
+    if self.lr_runs is None:
+      return [(g, off, n, None) for g, off, n in segments]
+    pieces = []
+    for g, off, n in segments:
+      for lo, cnt, mul in self.lr_runs:
+        a, b = max(off, lo), min(off + n, lo + cnt)
+        if a < b:
+          pieces.append((g[a - off:b - off], a, b - a, mul))
+    return pieces
+
+  def _check_piece_count(self, n, what):
+    if n > ops._native.ADAM_SEGMENTS_MAX:
+      option = ' with '.join(o for o, on in (('clip_norm / skip_nonfinite', self.clip_ws is not None), ('lr_multipliers', self.lr_runs is not None)) if on)
+      raise ValueError('%s: %s came in %d pieces; one launch takes at most %d' % (option, what, n, ops._native.ADAM_SEGMENTS_MAX))
+
+  def _total_gradient_kw(self):      # the total gradient the update and the norm are formed of: g / world + l2 * p
+    return dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
+
+  def _launch_update(self, pieces, g_out, whole=False):
+    """One launch of the Adam kernel over ``pieces`` (nothing for a call whose pieces are all frozen), through the entry point the model's
+    options name; ``whole``: the one piece is the arena."""
+    if not pieces:
+      return
+    s, kw = self.store, self._total_gradient_kw()
+    segs = [q[:3] for q in pieces]
+    ema = dict(ema=s.ema, global_step=s.global_step, decay=self.ema_decay) if s.ema is not None else {}      # the averaged weights follow in the same launch
+    if self.lr_runs is not None:
+      ops.adam_tf_segments_scaled(s.params, s.adam_m, s.adam_v, segs, [q[3] for q in pieces], self.scal, clip_dev=self.clip_out, guard=self.guard,
+                                  g_out=g_out, **ema, **kw)
+    elif self.guard is not None:
+      ops.adam_tf_segments_guard(s.params, s.adam_m, s.adam_v, segs, self.scal, self.clip_out, self.guard, g_out=g_out, **ema, **kw)
+    elif self.clip_ws is not None:
+      ops.adam_tf_segments_clip(s.params, s.adam_m, s.adam_v, segs, self.scal, self.clip_out, g_out=g_out, **ema, **kw)
+    elif whole and s.ema is not None:
+      ops.adam_tf_ema(s.params, segs[0][0], s.adam_m, s.adam_v, s.ema, s.size, self.scal, s.global_step, self.ema_decay, **kw)
+    elif whole:
+      ops.adam_tf(s.params, segs[0][0], s.adam_m, s.adam_v, s.size, self.scal, **kw)
+    elif s.ema is not None:
+      ops.adam_tf_segments_ema(s.params, s.adam_m, s.adam_v, s.ema, segs, self.scal, s.global_step, self.ema_decay, g_out=g_out, **kw)
+    else:
+      ops.adam_tf_segments(s.params, s.adam_m, s.adam_v, segs, self.scal, g_out=g_out, **kw)
+
+  def apply_gradients_of(self, segments, g_out=None, last=True):
+    """The optimiser step of SOME pieces of the arena (data parallel: everything that came with the early bucket first, the late
+    bucket's variables when it has arrived).  ``last``: the pieces complete the step (weight copies are re-derived behind it).
+    One launch per call that has anything trainable.
+    Under ``clip_norm`` and / or ``skip_nonfinite`` no piece may move before the norm of ALL of them is known, so the pieces of a call that
+    does not complete the step are recorded and nothing is launched for them; the call that does runs, in order, the sum of squares
+    over every recorded piece and its own (ONE launch: the partial sums are then bitwise those of the undivided arena, whatever the
+    pieces), the scale, and the update call by call (each with its own ``g_out``).  Three launches for the whole arena, four for the
+    two pieces of the schedules in runtime.py -- constant per schedule, so the step stays one captured graph.  Under ``skip_nonfinite``
+    the scale comes from ``guard_decide`` (clip 0 = no clipping) with the verdict on the step, and the update is the one that honours it:
+    the same launches whether the step is applied or skipped.  Under ``lr_multipliers`` the sum of squares gets the trainable pieces: the
+    global norm is that of the trainable variables' gradients (tf.clip_by_global_norm over var_list), and a NaN in a frozen variable's
+    gradient slot cannot cause a skip."""
+    self._optimizer_step(segments, g_out, last)
+
+  def _optimizer_step(self, segments, g_out, last, whole=False):
+    pieces = self._pieces(segments)
+    if self.clip_ws is None:      # nothing to wait for
+      if self.lr_runs is not None:      # (without the option ops.adam_tf_segments refuses the count)
+        self._check_piece_count(len(pieces), 'one call of the optimiser step')
+      self._prepare_unless_done(last)
+      self._launch_update(pieces, g_out, whole)
+    else:
+      self._clip_calls.append((pieces, g_out))
+      if not last:
+        return
+      s, calls, self._clip_calls = self.store, self._clip_calls, []
+      every = [q[:3] for ps, _ in calls for q in ps]
+      self._check_piece_count(len(every), 'the optimiser step')      # the norm of the whole gradient is one launch
+      self._prepare_unless_done()
+      ops.grad_sumsq_segments(self.clip_ws, s.params, every, s.size, **self._total_gradient_kw())
+      if self.guard is not None:
+        ops.guard_decide(self.clip_out, self.guard, self.clip_ws, self.clip_ws.numel(), self.clip_norm or 0.0)
+      else:
+        ops.clip_scale(self.clip_out, self.clip_ws, self.clip_ws.numel(), self.clip_norm)
+      for ps, out in calls:
+        self._launch_update(ps, out)
+    if last:
+      self._refresh_after_update()
+
+  def apply_gradients(self):
+    """The whole arena through the same path: the one-piece call (under ``lr_multipliers``: the runs themselves)."""
+    del self._clip_calls[:]
+    self._optimizer_step([(self.store.grads, 0, self.store.size)], None, True, whole=True)

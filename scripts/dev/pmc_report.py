@@ -16,11 +16,13 @@ P = [load(i) for i in (1, 2, 3, 4)]
 D = durations(1)
 # dispatch ids should align between passes (same program); take last step: after the second-to-last adam
 ids = list(P[0].keys())
-adam = [i for i in ids if P[0][i]['name'].startswith('adam_kernel')]
-if len(adam) >= 2:
+# every optimiser launch is adam_update_kernel<...> ('void ' already stripped), once or twice per step: a step = from one input-stage
+# dispatch to the next; a model without an input-stage kernel: from one Adam dispatch to the next
+starts = [i for i in ids if 'dynimg' in P[0][i]['name'] or 'window' in P[0][i]['name']]
+if not starts:
+  adam = [i for i in ids if P[0][i]['name'].startswith('adam_update_kernel')]
   lo, hi = adam[-2], adam[-1]
-else:      # round 6: the single-GPU step ends with adam_segments_kernel (twice per step): a step = from one input-stage dispatch to the next
-  starts = [i for i in ids if 'dynimg' in P[0][i]['name'] or 'window' in P[0][i]['name']]
+else:
   first = P[0][starts[0]]['name']
   starts = [i for i in starts if P[0][i]['name'] == first]
   lo, hi = starts[-2] - 1, starts[-1] - 1

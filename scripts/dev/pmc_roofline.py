@@ -13,11 +13,13 @@ def load(i):
   return o
 F, W = load(2), load(3)
 ids = list(F.keys())
-adam = [i for i in ids if F[i]['name'].startswith('adam_kernel')]
-if len(adam) >= 2:
+# every optimiser launch is adam_update_kernel<...> ('void ' already stripped), once or twice per step: a step = from one input-stage
+# dispatch to the next; a model without an input-stage kernel: from one Adam dispatch to the next
+starts = [i for i in ids if 'dynimg' in F[i]['name'] or 'window' in F[i]['name']]
+if not starts:
+  adam = [i for i in ids if F[i]['name'].startswith('adam_update_kernel')]
   lo, hi = adam[-2], adam[-1]
-else:      # round 6: the single-GPU step ends with adam_segments_kernel (twice per step): a step = from one input-stage dispatch to the next
-  starts = [i for i in ids if 'dynimg' in F[i]['name'] or 'window' in F[i]['name']]
+else:
   first = F[starts[0]]['name']
   starts = [i for i in starts if F[i]['name'] == first]
   lo, hi = starts[-2] - 1, starts[-1] - 1

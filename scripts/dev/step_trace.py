@@ -1,17 +1,18 @@
-"""Print the kernels of one training step (between two adam_kernel dispatches, or two input-stage dispatches) from a rocprofv3 kernel trace."""
+"""Print the kernels of one training step (between two input-stage dispatches, or two Adam dispatches) from a rocprofv3 kernel trace."""
 import csv, sys, re
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
-idx = [i for i, r in enumerate(rows) if r['Kernel_Name'].startswith('adam_kernel')]
-which = int(sys.argv[2]) if len(sys.argv) > 2 else len(idx) // 2
-if len(idx) >= 2:
-  a, b = idx[which - 1] + 1, idx[which] + 1
-else:
-  # the single-GPU step of round 6 ends with adam_segments_kernel (twice per step): a step = from one input-stage dispatch to the next
-  first = next(r['Kernel_Name'] for r in rows if 'dynimg' in r['Kernel_Name'] or 'window' in r['Kernel_Name'])
+# Every optimiser launch is an instantiation of adam_update_kernel (a demangled template name starts with 'void '), once or twice per
+# step: a step = from one input-stage dispatch to the next; a model without an input-stage kernel: from one Adam dispatch to the next.
+first = next((r['Kernel_Name'] for r in rows if 'dynimg' in r['Kernel_Name'] or 'window' in r['Kernel_Name']), None)
+if first is not None:
   idx = [i for i, r in enumerate(rows) if r['Kernel_Name'] == first]
   which = int(sys.argv[2]) if len(sys.argv) > 2 else len(idx) // 2
   a, b = idx[which - 1], idx[which]
+else:
+  idx = [i for i, r in enumerate(rows) if r['Kernel_Name'].replace('void ', '').startswith('adam_update_kernel')]
+  which = int(sys.argv[2]) if len(sys.argv) > 2 else len(idx) // 2
+  a, b = idx[which - 1] + 1, idx[which] + 1
 tot = 0
 t0 = int(rows[a]['Start_Timestamp'])
 agg = {}
