@@ -56,6 +56,8 @@ class AdamSegment(Structure):
 
 ADAM_SEGMENTS_MAX = 8
 
+VARSTATS_CHUNK, VARSTATS_CLASSES = 4096, 40      # GEECO_VARSTATS_* of include/geeco_hip.h
+
 LR_KINDS = ('constant', 'exponential', 'cosine', 'piecewise')      # GEECO_LR_* of include/geeco_hip.h, in order
 LR_BOUNDARIES_MAX = 8
 
@@ -165,6 +167,8 @@ SIGNATURES = {
     'geeco_adam_prepare_schedule': (_I, [_P, POINTER(LrSchedule), _F, _F, _P, _P]),
     'geeco_slab_reduce_batch_prepare_schedule': (_I, [POINTER(SlabReduce), _I, _P, POINTER(LrSchedule), _F, _F, _P, _P]),
     'geeco_lr_schedule_eval': (_I, [POINTER(LrSchedule), _L, POINTER(ctypes.c_double)]),
+    'geeco_variable_stats_ws_bytes': (_L, [_L]),      # additive within ABI 7
+    'geeco_variable_stats': (_I, [_P, _P, _P, _P, _I, _L, _F, _F, POINTER(c_int64), POINTER(c_int64), _I, _P, _L, _P, _P, _P]),
     'geeco_sumsq': (_I, [_P, _L, _P, _P]),
 }
 

@@ -18,6 +18,7 @@ from __future__ import annotations
 import collections
 import collections.abc
 import json
+import math
 import os
 import re
 import time
@@ -30,7 +31,7 @@ from . import graph
 from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
 from .tf_checkpoint import EMA_SUFFIX
-from .variables import check_clip_norm, check_ema_decay, check_lr_multipliers, check_lr_schedule, check_skip_nonfinite, model_variable_shapes
+from .variables import check_clip_norm, check_ema_decay, check_lr_multipliers, check_lr_schedule, check_skip_nonfinite, check_variable_stats, model_variable_shapes
 
 
 class ModeKeys:
@@ -275,6 +276,7 @@ class _SummarySaverHook:
     if gdist.rank() != 0:
       return
     parts = {k: float(v) for k, v in self.model.loss_parts().items()}
+    stats = self.model.variable_stats() if getattr(self.model, 'stats_plan', None) is not None else None      # params['variable_stats']
     if getattr(self.model, 'clip_out', None) is not None:      # params['clip_norm'] / ['skip_nonfinite']: the norm of this step's gradient before clipping
       parts['grad_norm'] = float(self.model.clip_out[1])
     if getattr(self.model, 'guard', None) is not None:         # params['skip_nonfinite']: steps this model has skipped so far (not checkpointed)
@@ -283,10 +285,27 @@ class _SummarySaverHook:
       parts['learning_rate'] = float(self.model.scal[2])
     parts['global_step'] = step
     parts['wall_time'] = time.time()
+    scalars = {k: v for k, v in parts.items() if k.startswith('loss') or k == 'learning_rate'}
+    histograms = {}
+    if stats is not None:
+      # params['variable_stats']: the scalars per variable, and on a step that was skipped the variables whose gradient was not finite
+      # (a float that is not finite -- a sum of squares beyond float32 -- goes in as the string 'inf' / '-inf' / 'nan': strict JSON)
+      parts['variables'] = {n: {k: (v if not isinstance(v, float) or math.isfinite(v) else str(v)) for k, v in d.items() if k != 'histograms'}
+                            for n, d in stats.items()}
+      if getattr(self.model, 'guard', None) is not None and not int(self.model.guard[0]):
+        parts['nonfinite_variables'] = self.model.nonfinite_gradient_variables(stats)
+      for n, d in stats.items():
+        for key in ('grad_norm', 'weight_norm', 'update_ratio', 'grad_zero_fraction'):
+          if d[key] is not None:
+            scalars['%s/%s' % (key, n)] = d[key]
+        for kind, h in d.get('histograms', {}).items():
+          histograms['%s/%s' % (kind, n)] = h
     if model_dir:
       with open(os.path.join(model_dir, 'events.jsonl'), 'a') as f:
         f.write(json.dumps(parts) + '\n')
-      self._writer(model_dir).add_scalars({k: v for k, v in parts.items() if k.startswith('loss') or k == 'learning_rate'}, step, parts['wall_time'])
+      self._writer(model_dir).add_scalars(scalars, step, parts['wall_time'])
+      if histograms:
+        self._writer(model_dir).add_histograms(histograms, step, parts['wall_time'])
     print('INFO: loss = %.6f, step = %d' % (parts['loss'], step), flush=True)
 
 
@@ -298,9 +317,14 @@ def check_skipped_steps(model):
     return 0
   _, total, row = (int(x) for x in model.guard.tolist())
   if row >= model.skip_limit:
+    where = ''
+    if getattr(model, 'stats_plan', None) is not None:      # params['variable_stats']: which variables held the non-finite elements
+      bad = model.nonfinite_gradient_variables()
+      where = '; non-finite gradient elements of the last skipped step: ' + (', '.join('%s: %d' % kv for kv in bad.items()) or 'none '
+                                                                            '(the squares overflowed float32)')
     raise RuntimeError('geeco_amd: the last %d optimiser steps in a row were skipped for a non-finite gradient (%d skipped in all; norm of the '
-                       "last one: %r; params['skip_nonfinite'] allows fewer than %d in a row); nothing was saved"
-                       % (row, total, float(model.clip_out[1]), model.skip_limit))
+                       "last one: %r; params['skip_nonfinite'] allows fewer than %d in a row); nothing was saved%s"
+                       % (row, total, float(model.clip_out[1]), model.skip_limit, where))
   return total
 
 
@@ -359,6 +383,13 @@ def _model_fn(features, labels, mode, params, goal):
       raise ValueError("params['lr_multipliers'] with params['shared_frames']: the shared-frame backward has no cut points; drop one "
                        "of the two options")
     ema['lr_multipliers'] = params['lr_multipliers']
+  # params['variable_stats']: per-variable gradient, weight and update statistics on logging steps, one pass on the device
+  vstats = check_variable_stats(params.get('variable_stats'), "params['variable_stats']")
+  if training and vstats is not None:
+    if gdist.world_size() > 1:
+      raise ValueError("params['variable_stats'] is single-GPU: with %d ranks where the late bucket's gradient lives after the "
+                       "exchange has not been decided" % gdist.world_size())
+    ema['variable_stats'] = params['variable_stats']
   tables = {}
   if shared:
     # params['shared_frames'] (True, or a capacity F): encode each distinct frame of the batch once
@@ -470,6 +501,7 @@ class Estimator:
     check_ema_decay(self.params.get('ema_decay'), "params['ema_decay']")
     check_clip_norm(self.params.get('clip_norm'), "params['clip_norm']")
     check_skip_nonfinite(self.params.get('skip_nonfinite'), "params['skip_nonfinite']")
+    check_variable_stats(self.params.get('variable_stats'), "params['variable_stats']")
     check_lr_schedule(self.params.get('lr_schedule'), getattr(self.params.get('e2evmc_config'), 'lr', 0.0), "params['lr_schedule']")
     if self.params.get('lr_multipliers') is not None and not isinstance(self.params['lr_multipliers'], collections.abc.Mapping):
       raise ValueError("params['lr_multipliers']=%r: must be None or a mapping {regular expression: multiplier}" % (self.params['lr_multipliers'],))

@@ -29,7 +29,7 @@ from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .optimizer import OptimizerStep
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
-from .variables import (_CELLS, VariableStore, check_clip_norm, check_ema_decay, check_lr_schedule, check_skip_nonfinite,
+from .variables import (_CELLS, VariableStore, check_clip_norm, check_ema_decay, check_lr_schedule, check_skip_nonfinite, check_variable_stats,
                         model_variable_shapes)
 
 
@@ -84,8 +84,9 @@ class _ModelBase(OptimizerStep):
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
   def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None, lr_schedule=None,
-               skip_nonfinite=None, lr_multipliers=None):
+               skip_nonfinite=None, lr_multipliers=None, variable_stats=None):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
+    self.variable_stats_mode = check_variable_stats(variable_stats) if training else None      # None: the option is off (DESIGN 5.21)
     self.ema_decay = check_ema_decay(ema_decay)
     self.clip_norm = check_clip_norm(clip_norm)
     self.skip_limit = check_skip_nonfinite(skip_nonfinite)      # consecutive skipped steps the caller tolerates (None: option off)
@@ -244,6 +245,7 @@ class _ModelBase(OptimizerStep):
       # alone to look at gradients) must not make THIS step's apply_gradients skip its adam_prepare.
       self._prepared = False
       del self._clip_calls[:]      # ... nor may the pieces it had handed to apply_gradients_of(last=False) join this step's
+      del self._open_pieces[:]
     if self.shared_frames is not None:
       self._encode_shared()
     else:
@@ -386,11 +388,12 @@ class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None):
+               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None):
     """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``, ``lr_schedule``, ``skip_nonfinite``,
     ``lr_multipliers``: see E2EVMC."""
     super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers)
+                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers,
+                     variable_stats=variable_stats)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -521,7 +524,7 @@ class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None):
+               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None):
     """``ema_decay`` (a float in (0, 1); None / 0 = off): the optimiser step also keeps an exponential moving average of the
     parameters in ``store.ema`` (tf.train.ExponentialMovingAverage with num_updates = global_step); a store passed in
     must have been built with the arena (``build_store(..., ema=True)``).
@@ -537,12 +540,15 @@ class E2EVMC(_ModelBase):
     frozen; None, empty or all ones = off): every variable is updated with lr * its multiplier inside the one Adam pass, a frozen
     variable's p, m, v and averaged weight keep every bit, and the backward stops at the lowest layer with anything to train
     (``backward_cut``).  Single GPU, not with ``shared_frames``.
+    ``variable_stats`` (True, or 'histograms'; None / False = off): ``variable_stats()`` reports, per variable, the norms and counts of
+    the last step's gradient, weights and update from one statistics pass on the device.  The step itself is unchanged.
     ``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
     'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
     super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers)
+                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers,
+                     variable_stats=variable_stats)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     self.window_mode, self.feat_ch = 'plain', [256]
     # frames are processed time-major ([K][N]) so that step t's features are one dense block

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import math
 
+import numpy as np
 import torch
 
 from . import _native
@@ -846,6 +847,74 @@ def adam_tf_segments_scaled(p, m, v, segments, lr_mul, scal, clip_dev=None, guar
 
 def sumsq_into(out, p, n):
   check(_lib().geeco_sumsq(_p(p), n, _p(out), _stream()), 'geeco_sumsq')
+
+
+# --------------------------------------------------------------------------------------------
+# per-variable statistics
+# --------------------------------------------------------------------------------------------
+_VS_TENSOR = [('nonfinite', '<i8'), ('zeros', '<i8'), ('sum', '<f4'), ('sumsq', '<f4'), ('min', '<f4'), ('max', '<f4'),
+              ('neg', '<i8', (_native.VARSTATS_CLASSES,)), ('pos', '<i8', (_native.VARSTATS_CLASSES,))]
+# geeco_varstats_record of include/geeco_hip.h, field for field
+VARSTATS_DTYPE = np.dtype([('grad_covered', '<i8'), ('grad', _VS_TENSOR), ('param', _VS_TENSOR), ('update_nonfinite', '<i8'),
+                           ('update_sumsq', '<f4'), ('update_max_abs', '<f4')])
+assert VARSTATS_DTYPE.itemsize == 1368
+
+
+def variable_stats_ws_bytes(nchunks):
+  return int(_lib().geeco_variable_stats_ws_bytes(int(nchunks)))
+
+
+def variable_stats_table(variables, chunk=_native.VARSTATS_CHUNK):
+  """The table ``geeco_variable_stats`` reads on the device, on the host (int64, flat): per variable of ``variables`` = [(offset, count)]
+  its first chunk and its number of chunks, then per chunk its arena offset and element count.  A variable is cut from its own first
+  element into chunks of ``chunk`` elements, the last one shorter: no chunk straddles two variables or holds a pad float.  Needs no GPU."""
+  head, chunks = [], []
+  for off, cnt in variables:
+    off, cnt = int(off), int(cnt)
+    if off < 0 or off % 4 or cnt < 1:
+      raise ValueError('variable_stats_table: a variable at offset %d with %d elements (offsets are multiples of 4, counts >= 1)' % (off, cnt))
+    nc = -(-cnt // chunk)
+    head += [len(chunks), nc]
+    chunks += [(off + k * chunk, min(chunk, cnt - k * chunk)) for k in range(nc)]
+  return np.array(head + [x for c in chunks for x in c], dtype=np.int64)
+
+
+def variable_stats(out, ws, table, p, m, v, segments, n, variables, nchunks, grad_scale=1.0, eps=1e-8):
+  """``geeco_variable_stats``: one record per variable of ``variables`` = [(offset, count)] into ``out`` (uint8, VARSTATS_DTYPE.itemsize
+  bytes per variable); ``table``: ``variable_stats_table(variables)`` on the device, ``ws``: ``variable_stats_ws_bytes(nchunks)`` bytes;
+  ``segments``: the gradient's pieces as ``grad_sumsq_segments`` takes them."""
+  nvar = len(variables)
+  if out is not None and out.numel() * out.element_size() < nvar * VARSTATS_DTYPE.itemsize:
+    raise ValueError('variable_stats: %d bytes of records for %d variables' % (out.numel() * out.element_size(), nvar))
+  if ws is not None and ws.numel() * ws.element_size() < variable_stats_ws_bytes(nchunks):
+    raise ValueError('variable_stats: a workspace of %d bytes, %d needed' % (ws.numel() * ws.element_size(), variable_stats_ws_bytes(nchunks)))
+  if table is not None and (table.dtype != torch.int64 or table.numel() < 2 * nvar + 2 * max(int(nchunks), 0)):
+    raise ValueError('variable_stats: the table holds 2 int64 per variable and 2 per chunk')
+  arr = _adam_segments(segments)
+  offs = (ctypes.c_int64 * max(nvar, 1))(*[int(o) for o, _ in variables])
+  cnts = (ctypes.c_int64 * max(nvar, 1))(*[int(c) for _, c in variables])
+  check(_lib().geeco_variable_stats(_p(p), _p(m), _p(v), arr, len(segments), int(n), grad_scale, eps, offs, cnts, nvar, _p(table), int(nchunks),
+                                    _p(ws), _p(out), _stream()), 'geeco_variable_stats')
+
+
+class VariableStatsPlan:
+  """What one model's statistics pass keeps on the device: the table of ``variables`` = [(offset, count)], the workspace and the
+  records.  Allocated once; ``run`` enqueues the two launches and allocates nothing."""
+
+  def __init__(self, variables, device):
+    self.variables = [(int(o), int(c)) for o, c in variables]
+    host = variable_stats_table(self.variables)
+    self.nchunks = (host.size - 2 * len(self.variables)) // 2
+    self.table = torch.from_numpy(host).to(device)
+    self.ws = torch.zeros(variable_stats_ws_bytes(self.nchunks) // 4, dtype=torch.int32, device=device)
+    self.out = torch.zeros(len(self.variables) * VARSTATS_DTYPE.itemsize, dtype=torch.uint8, device=device)
+
+  def run(self, p, m, v, segments, n, grad_scale=1.0, eps=1e-8):
+    variable_stats(self.out, self.ws, self.table, p, m, v, segments, n, self.variables, self.nchunks, grad_scale, eps)
+
+  def records(self):
+    """The records on the host (numpy, VARSTATS_DTYPE).  SYNCHRONISES: the copy waits for the stream."""
+    return self.out.cpu().numpy().view(VARSTATS_DTYPE).copy()
 
 
 # --------------------------------------------------------------------------------------------

@@ -4,10 +4,11 @@
 class provides ``cfg``, ``store``, ``device``, the checked options and ``_refresh_after_update()``."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from . import ops
-from .variables import backward_cut, check_lr_multipliers, lr_multiplier_runs
+from .variables import backward_cut, check_lr_multipliers, lr_multiplier_runs, variable_stats_scalars
 
 
 class OptimizerStep:
@@ -43,6 +44,13 @@ class OptimizerStep:
       self.clip_out = torch.zeros(2, **f32)
       if self.skip_limit is not None:
         self.guard = torch.zeros(3, dtype=torch.int64, device=self.device)
+    # variable_stats: the chunk table, the workspace and the records of the statistics pass, and ``step_pieces``, where
+    # the gradient of the step that ran last lives: the pieces (gradient source, offset, count) its optimiser step was handed.  A
+    # replayed step runs no python, but its pieces are the ones recorded at capture.  A model without the option has none of it.
+    self.stats_plan, self.step_pieces, self._open_pieces = None, None, []
+    if getattr(self, 'variable_stats_mode', None) is not None and training:
+      s = self.store
+      self.stats_plan = ops.VariableStatsPlan([(s.offsets[n], int(np.prod(s.shapes[n]))) for n in s.shapes], self.device)
 
   def _prepare_args(self, adam_prepare):
     """backward(adam_prepare=True): the step counter / lr_t update rides in the backward's last slab-sum launch (one dependent
@@ -124,6 +132,10 @@ class OptimizerStep:
 
   def _optimizer_step(self, segments, g_out, last, whole=False):
     pieces = self._pieces(segments)
+    if self.stats_plan is not None:
+      self._open_pieces += [q[:3] for q in pieces]
+      if last:
+        self.step_pieces, self._open_pieces = self._open_pieces, []
     if self.clip_ws is None:      # nothing to wait for
       if self.lr_runs is not None:      # (without the option ops.adam_tf_segments refuses the count)
         self._check_piece_count(len(pieces), 'one call of the optimiser step')
@@ -150,4 +162,34 @@ class OptimizerStep:
   def apply_gradients(self):
     """The whole arena through the same path: the one-piece call (under ``lr_multipliers``: the runs themselves)."""
     del self._clip_calls[:]
+    del self._open_pieces[:]
     self._optimizer_step([(self.store.grads, 0, self.store.size)], None, True, whole=True)
+
+  # -- per-variable statistics (DESIGN 5.21) ---------------------------------------------------
+  def variable_stats(self):
+    """{variable name: dict} of the step that ran last (``variables.variable_stats_scalars``: grad_norm, grad_max_abs, grad_mean,
+    grad_zero_fraction, grad_nonfinite, weight_norm, weight_max_abs, weight_nonfinite, update_norm, update_ratio, and 'histograms'
+    under ``variable_stats='histograms'``).  Two launches on the current stream, eagerly, then the records, lr_t and the verdict are
+    READ: the call synchronises, so it belongs where the host waits anyway (the logging hook), never inside a captured step."""
+    if self.stats_plan is None:
+      raise RuntimeError("variable_stats(): the model was built without variable_stats (params['variable_stats'])")
+    if not self.step_pieces:
+      raise RuntimeError('variable_stats(): no optimiser step has run yet')
+    s = self.store
+    if len(self.step_pieces) > ops._native.ADAM_SEGMENTS_MAX:
+      raise ValueError('variable_stats: the gradient of the last step came in %d pieces; one launch takes at most %d'
+                       % (len(self.step_pieces), ops._native.ADAM_SEGMENTS_MAX))
+    self.stats_plan.run(s.params, s.adam_m, s.adam_v, self.step_pieces, s.size, grad_scale=self._total_gradient_kw()['grad_scale'])
+    recs = self.stats_plan.records()
+    lr_t = float(self.scal[0])
+    applied = True if self.guard is None else bool(int(self.guard[0]))
+    out = {}
+    for rec, name in zip(recs, s.shapes):
+      mul = 1.0 if self.lr_multipliers is None else self.lr_multipliers[name]
+      out[name] = variable_stats_scalars(rec, int(np.prod(s.shapes[name])), lr_t, mul, applied, self.variable_stats_mode == 'histograms')
+    return out
+
+  def nonfinite_gradient_variables(self, stats=None):
+    """{variable name: number of non-finite gradient elements} of the step that ran last, the variables with none left out."""
+    stats = self.variable_stats() if stats is None else stats
+    return {n: d['grad_nonfinite'] for n, d in stats.items() if d['grad_nonfinite']}

@@ -127,6 +127,55 @@ def check_skip_nonfinite(value, key='skip_nonfinite'):
                    '(None or False = off)' % (key, value))
 
 
+def check_variable_stats(value, key='variable_stats'):
+  """Per-variable statistics on logging steps: None or False = off (returns None); True = the scalars (returns
+  'scalars'); 'histograms' = the scalars and the magnitude histograms (returns 'histograms').  Anything else raises ValueError naming
+  ``key``."""
+  if value is None or value is False:
+    return None
+  if value is True:
+    return 'scalars'
+  if isinstance(value, str) and value == 'histograms':
+    return 'histograms'
+  raise ValueError("%s=%r: True (scalars per variable) or 'histograms' (scalars and histograms); None or False = off" % (key, value))
+
+
+def variable_stats_scalars(rec, count, lr_t, multiplier=1.0, applied=True, histograms=False):
+  """One variable's record of ``geeco_variable_stats`` (a numpy scalar of ``ops.VARSTATS_DTYPE``, or any mapping with its fields) of ``count`` elements as the
+  dictionary ``model.variable_stats()`` reports.  Square roots and ratios are formed here, in float64, from the device's sums.
+  ``update_norm`` = lr_t * multiplier * sqrt(sum of u^2): the length of the step Adam just took in this variable; 0 for a frozen variable
+  (``multiplier`` 0) and for a step that was skipped (``applied`` false).  A frozen variable -- one whose gradient no piece of the
+  step covered -- reports every ``grad_*`` as None.  ``update_ratio`` is None where the weights' norm is 0."""
+  def tensor(t, covered):
+    finite = int(covered) - int(t['nonfinite'])
+    lo, hi = float(t['min']), float(t['max'])
+    return dict(norm=math.sqrt(float(t['sumsq'])), max_abs=max(abs(lo), abs(hi)) if finite > 0 else 0.0,
+                mean=float(t['sum']) / finite if finite > 0 else 0.0, zero_fraction=int(t['zeros']) / float(covered) if covered else 0.0,
+                nonfinite=int(t['nonfinite']), finite=finite)
+  count = int(count)
+  covered = int(rec['grad_covered'])
+  out = {}
+  if covered and float(multiplier) != 0.0:
+    g = tensor(rec['grad'], covered)
+    out.update(grad_norm=g['norm'], grad_max_abs=g['max_abs'], grad_mean=g['mean'], grad_zero_fraction=g['zero_fraction'], grad_nonfinite=g['nonfinite'])
+  else:
+    out.update(grad_norm=None, grad_max_abs=None, grad_mean=None, grad_zero_fraction=None, grad_nonfinite=None)
+  w = tensor(rec['param'], count)
+  out.update(weight_norm=w['norm'], weight_max_abs=w['max_abs'], weight_nonfinite=w['nonfinite'])
+  moved = applied and float(multiplier) != 0.0
+  out['update_norm'] = float(lr_t) * float(multiplier) * math.sqrt(float(rec['update_sumsq'])) if moved else 0.0
+  out['update_ratio'] = out['update_norm'] / out['weight_norm'] if out['weight_norm'] > 0.0 else None
+  if histograms:
+    out['histograms'] = {}
+    for name, key, n in (('gradients', 'grad', covered if out['grad_norm'] is not None else 0), ('weights', 'param', count)):
+      if n:
+        t = rec[key]
+        out['histograms'][name] = dict(neg=[int(x) for x in t['neg']], pos=[int(x) for x in t['pos']], zeros=int(t['zeros']),
+                                       min=float(t['min']), max=float(t['max']), sum=float(t['sum']), sum_squares=float(t['sumsq']),
+                                       num=n - int(t['nonfinite']))
+  return out
+
+
 def check_lr_multipliers(value, names, key='lr_multipliers'):
   """Per-variable learning-rate multipliers.  ``value``: None or an empty mapping = off (returns None); else an ordered
   mapping {regular expression: multiplier}.  A variable of ``names`` takes the multiplier of the FIRST expression that ``re.search``

@@ -30,7 +30,7 @@ extern "C" {
  * geeco_gather_windows_augmented, geeco_adam_tf_ema, geeco_adam_tf_segments_ema, geeco_clip_ws_floats,
  * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip, geeco_gather_windows_scene,
  * geeco_adam_prepare_schedule, geeco_slab_reduce_batch_prepare_schedule, geeco_lr_schedule_eval, geeco_guard_decide,
- * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled */
+ * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled, geeco_variable_stats_ws_bytes, geeco_variable_stats */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -671,6 +671,46 @@ int geeco_slab_reduce_batch_prepare_schedule(const geeco_slab_reduce* items, int
                                              const geeco_lr_schedule* schedule, float beta1, float beta2, float* scal_dev,
                                              void* stream);
 int geeco_lr_schedule_eval(const geeco_lr_schedule* schedule, int64_t step, double* lr_out);
+/* Opt-in per-variable statistics of the gradient, the parameters and the update direction: two launches, read-only on
+ * the four arenas, meant for logging steps and never part of a captured step.
+ * Variables: nvar >= 1 spans [var_off[i], var_off[i] + var_cnt[i]) of the arenas [0, n), offsets multiples of 4 floats, counts any
+ *   number >= 1, disjoint, in any order, pad floats between them allowed.  Only the variables' own elements are read: no pad, no slack.
+ *   var_off / var_cnt are HOST arrays (checked on every call); `table` is the DEVICE table the caller builds from them once, int64:
+ *     table[2 i], table[2 i + 1]                       first chunk of variable i and its number of chunks, ceil(var_cnt[i] / CH)
+ *     table[2 nvar + 2 c], table[2 nvar + 2 c + 1]     arena offset and element count (1..CH) of chunk c
+ *   the chunks of a variable are consecutive, each CH = GEECO_VARSTATS_CHUNK elements but the variable's last, variables in the
+ *   order of var_off, nchunks = the sum of their chunk counts.  The table is the caller's to get right (ops.VariableStatsPlan).
+ * Gradient: G_i = g_i * grad_scale (one float32 product; no l2 term), g_i found through the pieces exactly as
+ *   geeco_grad_sumsq_segments finds it (1..GEECO_ADAM_SEGMENTS_MAX disjoint pieces, any offset and count inside [0, n), sources 4-byte
+ *   aligned).  An element no piece covers has no gradient: it is in none of the gradient's fields.  A variable no piece touches has
+ *   grad_covered == 0 (its gradient is absent); a half-covered variable is NOT refused, its record describes the covered elements.
+ * Update direction: u_i = m_i / (sqrtf(v_i) + eps) from the moments as they stand.
+ * Record (one per variable, out[nvar]): counts are exact integers; sums are float32, over the FINITE elements only -- a NaN or an
+ *   infinity is counted in `nonfinite` and is in no sum, extremum or class; min = +inf and max = -inf where nothing is finite.
+ *   Magnitude classes of a finite non-zero x: e = ((bits >> 23) & 0xff) - 127 clamped to [-32, 7], class e + 32 (denormals: class 0,
+ *   |x| >= 128: class 39), counted in `neg` or `pos` by sign; zeros (+-0) are counted in `zeros` and are in no class.
+ * ws: geeco_variable_stats_ws_bytes(nchunks) bytes, 16-byte aligned (one partial record per chunk).  Reduction order: csrc/varstats.hip;
+ *   the record is bitwise the same for any partition of the gradient into pieces and from call to call.
+ * GEECO_EINVAL (nothing launched): a null pointer, p / m / v / ws / out / table misaligned (16 / 16 / 16 / 16 / 8 / 8 bytes), nvar < 1,
+ *   an offset that is no multiple of 4, a count < 1, a variable outside [0, n), overlapping variables, nchunks other than the table's,
+ *   nseg outside 1..GEECO_ADAM_SEGMENTS_MAX and whatever geeco_grad_sumsq_segments refuses of a piece, eps negative or not finite. */
+#define GEECO_VARSTATS_CHUNK 4096
+#define GEECO_VARSTATS_CLASSES 40
+typedef struct geeco_varstats_tensor {
+  int64_t nonfinite, zeros;
+  float sum, sumsq, min, max;                    /* over the finite elements (zeros included) */
+  int64_t neg[GEECO_VARSTATS_CLASSES], pos[GEECO_VARSTATS_CLASSES];
+} geeco_varstats_tensor;
+typedef struct geeco_varstats_record {
+  int64_t grad_covered;                          /* elements of the variable that a piece covers; 0: the gradient is absent */
+  geeco_varstats_tensor grad, param;
+  int64_t update_nonfinite;
+  float update_sumsq, update_max_abs;            /* over the finite u_i */
+} geeco_varstats_record;
+int64_t geeco_variable_stats_ws_bytes(int64_t nchunks);
+int geeco_variable_stats(const float* p, const float* m, const float* v, const geeco_adam_segment* segs, int nseg, int64_t n,
+                         float grad_scale, float eps, const int64_t* var_off, const int64_t* var_cnt, int nvar,
+                         const int64_t* table, int64_t nchunks, void* ws, geeco_varstats_record* out, void* stream);
 /* sum of squares of an arena (for the L2 regularisation loss term); out[0] overwritten. */
 int geeco_sumsq(const float* p, int64_t n, float* out, void* stream);
 

@@ -125,6 +125,15 @@ ARGPARSER.add_argument('--skip_nonfinite', default=False, action='store_true',
 ARGPARSER.add_argument('--max_skipped_steps', type=int, default=None,
                        help='With --skip_nonfinite: stop training (RuntimeError, nothing saved) once this many consecutive steps were '
                             'skipped; an integer >= 1.  Default: 100.')
+ARGPARSER.add_argument('--variable_stats', default=False, action='store_true',
+                       help='On every logging step (--log_steps) report, per variable, the norm / largest magnitude / mean / share of exact '
+                            'zeros / non-finite count of the gradient, the norm of the weights and the update-to-weight ratio: one '
+                            'statistics pass on the device outside the captured step; events.jsonl carries them under "variables", the '
+                            'event file as grad_norm/<var>, weight_norm/<var>, update_ratio/<var>, grad_zero_fraction/<var>.  With '
+                            '--skip_nonfinite the variables that held the NaN are named.  One GPU.  Not part of the model config.')
+ARGPARSER.add_argument('--variable_stats_histograms', default=False, action='store_true',
+                       help='--variable_stats, and the event file also gets a magnitude histogram (by binary exponent, per sign) of every '
+                            "variable's gradient and weights: gradients/<var>, weights/<var>.")
 ARGPARSER.add_argument('--lr_schedule', type=str, default=None, choices=['constant', 'exponential', 'cosine', 'piecewise'],
                        help='Learning-rate schedule, evaluated on the device from its step counter (a resumed run continues it); '
                             'events.jsonl then carries learning_rate.  After --lr_warmup_steps, with u the steps since: exponential = '
@@ -223,6 +232,10 @@ def estimator_params(args, e2evmc_config):
     params['skip_nonfinite'] = True if args.max_skipped_steps is None else args.max_skipped_steps
   elif args.max_skipped_steps is not None:
     raise ValueError('--max_skipped_steps %d without --skip_nonfinite: no step is ever skipped' % args.max_skipped_steps)
+  if args.variable_stats_histograms:
+    params['variable_stats'] = 'histograms'
+  elif args.variable_stats:
+    params['variable_stats'] = True
   multipliers = lr_multipliers_of(args)
   if multipliers:
     params['lr_multipliers'] = multipliers
