@@ -43,6 +43,12 @@ class HeadsFinish(Structure):
   _fields_ = [('opaque', ctypes.c_ubyte * 1024)]
 
 
+class LossShaping(Structure):
+  """geeco_loss_shaping (include/geeco_hip.h): tf.losses' optional arguments for the shaped heads entry points."""
+  _fields_ = [('sample_weight', c_void_p), ('sample_weight_stride', c_int64), ('class_weight', c_void_p),
+              ('label_smoothing', c_float), ('huber_delta', c_float * 5)]
+
+
 class SlabReduce(Structure):
   """geeco_slab_reduce (include/geeco_hip.h): one pending slab sum of a filter-gradient kernel."""
   _fields_ = [('part', c_void_p), ('dw', c_void_p), ('db', c_void_p), ('gs_dw', c_int64), ('gs_db', c_int64),
@@ -151,6 +157,14 @@ SIGNATURES = {
     'geeco_lstm_step_heads_fwd_bwd': (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _PP, _PP, POINTER(_I),
                                            POINTER(_I), POINTER(_F), _PP, POINTER(_L), _F, _I, _P, _P, _I, _P, _P, _P, _PP, _PP,
                                            _P, _P, _P]),
+    # additive within ABI 7: the two entry points above with a geeco_loss_shaping* behind Hfc
+    'geeco_loss_shaping_sizeof': (_L, []),
+    'geeco_heads_loss_shaped_fwd_bwd': (_I, [_P, _P, _P, _I, _PP, _PP, POINTER(_I), POINTER(_I), POINTER(_F), _PP,
+                                             POINTER(_L), _F, _I, _I, _I, POINTER(LossShaping), _P, _P, _I, _P, _P, _P, _PP, _PP,
+                                             _P, _P]),
+    'geeco_lstm_step_heads_shaped_fwd_bwd': (_I, [_P, _L, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _PP, _PP,
+                                                  POINTER(_I), POINTER(_I), POINTER(_F), _PP, POINTER(_L), _F, _I,
+                                                  POINTER(LossShaping), _P, _P, _I, _P, _P, _P, _PP, _PP, _P, _P, _P]),
     'geeco_lstm_seq_heads_fwd': (_I, [_P, _L, _P, _L, _P, _P, _P, _I, _PP, _PP, POINTER(_I), _I, _I, _I, _I, _P, _P, _P, _P]),
     'geeco_adam_prepare': (_I, [_P, _F, _F, _F, _P, _P]),
     'geeco_adam_tf': (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _P]),

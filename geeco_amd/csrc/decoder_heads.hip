@@ -36,10 +36,17 @@ __device__ __forceinline__ void block_mfma_gemm(int M, int N, int K, const float
   }
 }
 
+// SHAPED: P3 and the loss means follow tf.losses' weights= / label_smoothing= / huber_loss (decoder_internal.h); the unshaped
+// instantiation keeps the arithmetic it always had
+template <bool SHAPED>
 __global__ __launch_bounds__(1024) void heads_loss_kernel(const HeadsParams p) {
-  const int tid = threadIdx.x, NT = 1024;
+  constexpr int NT = 1024;
+  const int tid = threadIdx.x;
   const int N = p.N, H = p.H, F = p.Hfc, OT = p.OT;
   __shared__ float s_red[16][GEECO_MAX_HEADS];
+  __shared__ int s_cnt[SHAPED ? NT / 64 : 1][2];
+  [[maybe_unused]] int cnt_reg = N, cnt_cls = N;
+  if constexpr (SHAPED) shaped_counts<NT>(p, s_cnt, &cnt_reg, &cnt_cls);
   __shared__ float s_hb[32];
   __shared__ int s_hd[32], s_hc[32];
   float* whm = p.dpred + (long long)N * OT;     // ws: [OT][F] = the head kernels side by side, transposed
@@ -82,7 +89,12 @@ __global__ __launch_bounds__(1024) void heads_loss_kernel(const HeadsParams p) {
       const int sz = p.size[hd], of = p.off[hd];
       const float* tg = p.tgt[hd] + (long long)n * p.tstride[hd];
       const float wsc = p.weight[hd] * p.loss_scale;
-      if (p.kind[hd] == 0) {
+      if constexpr (SHAPED) {
+        const bool cls = p.class_w && hd == p.cls_head;
+        const float sw = shaped_sample_w(p, n);
+        lsum[hd] += shaped_head_terms(p, hd, pr + of, tg, dp + of, cls ? shaped_class_w(p, sw, tg[0]) : sw,
+                                      cls ? cnt_cls : cnt_reg);
+      } else if (p.kind[hd] == 0) {
         const float c2 = 2.f / (float)(N * sz) * wsc;
         for (int c = 0; c < sz; ++c) {
           const float d = pr[of + c] - tg[c];
@@ -113,7 +125,12 @@ __global__ __launch_bounds__(1024) void heads_loss_kernel(const HeadsParams p) {
     for (int hd = 0; hd < p.nheads; ++hd) {
       float a = 0.f;
       for (int w = 0; w < 16; ++w) a += s_red[w][hd];
-      a *= p.kind[hd] == 0 ? 1.f / (float)(N * p.size[hd]) : invn;
+      if constexpr (SHAPED) {
+        const int cnt = (p.class_w && hd == p.cls_head) ? cnt_cls : cnt_reg;
+        a *= cnt == 0 ? 0.f : (p.kind[hd] == 1 ? 1.f / cnt : 1.f / (float)(cnt * p.size[hd]));
+      } else {
+        a *= p.kind[hd] == 0 ? 1.f / (float)(N * p.size[hd]) : invn;
+      }
       p.losses[1 + hd] = a;
       total += p.weight[hd] * a;
     }
@@ -176,7 +193,10 @@ struct StepFuse {
   float* dz;                // backward: gate gradients [N][4H]
 };
 
-template <bool FUSE, int G>              // G = Hfc / 4: float4 column groups of fc1/kernel, 16 or 32
+// SHAPED: P3 follows tf.losses' weights= / label_smoothing= / huber_loss (decoder_internal.h).  Every workgroup forms the batch's
+// two counts of non-zero effective weights itself, from the N <= 4096 weights and gripper labels (four loads per thread, issued
+// with the rest of P0): no atomics, no extra launch, no dependency on another block.
+template <bool FUSE, int G, bool SHAPED>   // G = Hfc / 4: float4 column groups of fc1/kernel, 16 or 32
 __global__ __launch_bounds__(HS_THREADS) void heads_sample_kernel(const HeadsParams p, const StepFuse sf) {
   const int tid = threadIdx.x, n = blockIdx.x;
   const int H = p.H, OT = p.OT, N = p.N;
@@ -190,6 +210,7 @@ __global__ __launch_bounds__(HS_THREADS) void heads_sample_kernel(const HeadsPar
   __shared__ float sPr[32], sDp[32], sHb[32], sTg[32];
   __shared__ int sHd[32], sHc[32];
   __shared__ float sWh[32 * HS_FMAX];     // the head kernels side by side, transposed: [o][f] (both uses walk f across lanes)
+  __shared__ int sCnt[SHAPED ? HS_THREADS / 64 : 1][2];
   // ---- P0: fc1/kernel -> LDS (issued first: independent of everything), small tables, the sample's LSTM output -----------
   f32x4 wv[4];
   const int W4 = H * G;                  // float4 of fc1/kernel (<= 4096 = 4 per thread)
@@ -204,9 +225,15 @@ __global__ __launch_bounds__(HS_THREADS) void heads_sample_kernel(const HeadsPar
     sHd[tid] = hd;
     sHc[tid] = cc;
     sHb[tid] = sel5(p.hb, hd)[cc];
-    if (sel5(p.kind, hd) == 0 || cc == 0) sTg[tid] = sel5(p.tgt, hd)[(long long)n * sel5(p.tstride, hd) + cc];
+    if (sel5(p.kind, hd) != 1 || cc == 0) sTg[tid] = sel5(p.tgt, hd)[(long long)n * sel5(p.tstride, hd) + cc];
   }
   if (tid < F) sB1[tid] = p.fc1_b[tid];
+  [[maybe_unused]] float s_w = 1.f;
+  [[maybe_unused]] int cnt_reg = N, cnt_cls = N;
+  if constexpr (SHAPED) {
+    s_w = shaped_sample_w(p, n);
+    shaped_counts<HS_THREADS>(p, sCnt, &cnt_reg, &cnt_cls);
+  }
   for (int e = tid; e < OT * F; e += HS_THREADS) {      // consecutive threads: consecutive o of one f (the variables are [f][size])
     const int f = e / OT, o = e - f * OT;
     const int hd = heads_head_of(p, o);
@@ -303,7 +330,10 @@ __global__ __launch_bounds__(HS_THREADS) void heads_sample_kernel(const HeadsPar
     const float wsc = sel5(p.weight, hd) * p.loss_scale;
     const float invn = 1.f / N;
     float l = 0.f;
-    if (sel5(p.kind, hd) == 0) {
+    if constexpr (SHAPED) {
+      const bool cls = p.class_w && hd == p.cls_head;
+      l = shaped_head_terms(p, hd, sPr + of, tg, sDp + of, cls ? shaped_class_w(p, s_w, tg[0]) : s_w, cls ? cnt_cls : cnt_reg);
+    } else if (sel5(p.kind, hd) == 0) {
       const float c2 = 2.f / (float)(N * sz) * wsc;
       for (int cc = 0; cc < sz; ++cc) {
         const float d = sPr[of + cc] - tg[cc];
@@ -322,6 +352,10 @@ __global__ __launch_bounds__(HS_THREADS) void heads_sample_kernel(const HeadsPar
         sDp[of + cc] = lv ? (expf(sPr[of + cc] - mx) / se - (cc == label ? 1.f : 0.f)) * invn * wsc : 0.f;
     }
     p.lterm[(long long)n * 8 + hd] = l;
+  }
+  if constexpr (SHAPED) {      // the counts travel to the finish role in the free slots of the lterm row (every block: the same values)
+    if (tid == HS_CNT_REG) p.lterm[(long long)n * 8 + HS_CNT_REG] = (float)cnt_reg;
+    if (tid == HS_CNT_CLS) p.lterm[(long long)n * 8 + HS_CNT_CLS] = (float)cnt_cls;
   }
   if (!p.backward) return;
   __syncthreads();
@@ -378,7 +412,9 @@ static int heads_fill(HeadsParams* pp, const float* h, const float* fc1_w, const
                       const float* const* heads_w, const float* const* heads_b, const int* head_size, const int* head_kind,
                       const float* head_weight, const float* const* targets, const int64_t* target_stride, float loss_scale,
                       int N, int H, int Hfc, float* preds, float* losses, int backward, float* dh, float* d_fc1_w,
-                      float* d_fc1_b, float* const* d_heads_w, float* const* d_heads_b, float* ws) {
+                      float* d_fc1_b, float* const* d_heads_w, float* const* d_heads_b, float* ws,
+                      const geeco_loss_shaping* shaping = nullptr, int shaped = 0) {
+  GEECO_CHECK_ARG(!shaped || shaping, "heads_loss: shaping is null");
   GEECO_CHECK_ARG(fc1_w && fc1_b && heads_w && heads_b && head_size && head_kind && head_weight && targets &&
                       target_stride && preds && losses && ws, "heads_loss: null pointer");
   GEECO_CHECK_ARG(nheads >= 1 && nheads <= GEECO_MAX_HEADS, "heads_loss: nheads=%d outside 1..%d", nheads, GEECO_MAX_HEADS);
@@ -392,7 +428,8 @@ static int heads_fill(HeadsParams* pp, const float* h, const float* fc1_w, const
   int off = 0;
   for (int i = 0; i < nheads; ++i) {
     GEECO_CHECK_ARG(head_size[i] >= 1 && head_size[i] <= 16, "heads_loss: head %d size %d", i, head_size[i]);
-    GEECO_CHECK_ARG(head_kind[i] == 0 || head_kind[i] == 1, "heads_loss: head %d kind %d", i, head_kind[i]);
+    GEECO_CHECK_ARG(head_kind[i] == 0 || head_kind[i] == 1 || (shaped && head_kind[i] == 2), "heads_loss: head %d kind %d", i,
+                    head_kind[i]);
     GEECO_CHECK_ARG(heads_w[i] && heads_b[i] && targets[i], "heads_loss: head %d null pointer", i);
     p.hw[i] = heads_w[i]; p.hb[i] = heads_b[i]; p.tgt[i] = targets[i]; p.tstride[i] = target_stride[i];
     p.size[i] = head_size[i]; p.off[i] = off; p.kind[i] = head_kind[i]; p.weight[i] = head_weight[i];
@@ -406,21 +443,71 @@ static int heads_fill(HeadsParams* pp, const float* h, const float* fc1_w, const
   p.OT = off;
   p.a1 = ws; p.da1 = ws + (long long)N * Hfc; p.dpred = ws + 2ll * N * Hfc;
   p.lterm = ws + 2ll * N * Hfc + (long long)N * 32 + 32ll * Hfc;
+  p.cls_head = -1;
+  if (!shaped) return 0;
+  p.shaped = 1;
+  GEECO_CHECK_ARG(shaping->label_smoothing >= 0.f && shaping->label_smoothing < 1.f,
+                  "heads_loss: shaping->label_smoothing=%g outside [0, 1)", (double)shaping->label_smoothing);
+  GEECO_CHECK_ARG(!shaping->sample_weight || shaping->sample_weight_stride >= 1 || N == 1,
+                  "heads_loss: shaping->sample_weight_stride=%lld", (long long)shaping->sample_weight_stride);
+  int ncls = 0;
+  for (int i = 0; i < nheads; ++i) {
+    if (head_kind[i] == 1) {
+      if (ncls++ == 0) p.cls_head = i;
+    } else if (head_kind[i] == 2) {
+      const float d = shaping->huber_delta[i];
+      GEECO_CHECK_ARG(d > 0.f && d <= 3.402823466e38f, "heads_loss: shaping->huber_delta[%d]=%g must be finite and > 0", i, (double)d);
+      p.huber[i] = d;
+    }
+  }
+  GEECO_CHECK_ARG(!shaping->class_weight || ncls == 1, "heads_loss: shaping->class_weight needs exactly one kind-1 head (%d given)",
+                  ncls);
+  p.sample_w = shaping->sample_weight; p.sample_w_stride = shaping->sample_weight_stride;
+  p.class_w = shaping->class_weight; p.smooth = shaping->label_smoothing;
+  if (!p.class_w) p.cls_head = -1;
   return 0;
 }
 
-template <bool FUSE, int G>
+template <bool FUSE, int G, bool SHAPED>
 static int launch_heads_sample_g(const HeadsParams& p, const StepFuse& sf, hipStream_t stream) {
-  if (int rc = geeco_lds_opt_in<&heads_sample_kernel<FUSE, G>>(HS_LDS_BYTES)) return rc;
-  geeco_note_kernel("heads_sample_kernel<%s>", FUSE ? "true" : "false");
-  hipLaunchKernelGGL((heads_sample_kernel<FUSE, G>), dim3((unsigned)p.N), dim3(HS_THREADS), HS_LDS_BYTES, stream, p, sf);
+  if (int rc = geeco_lds_opt_in<&heads_sample_kernel<FUSE, G, SHAPED>>(HS_LDS_BYTES)) return rc;
+  geeco_note_kernel(SHAPED ? "heads_sample_kernel<%s, shaped>" : "heads_sample_kernel<%s>", FUSE ? "true" : "false");
+  hipLaunchKernelGGL((heads_sample_kernel<FUSE, G, SHAPED>), dim3((unsigned)p.N), dim3(HS_THREADS), HS_LDS_BYTES, stream, p, sf);
   GEECO_LAUNCH_CHECK();
   return 0;
 }
 
 template <bool FUSE>
 static int launch_heads_sample(const HeadsParams& p, const StepFuse& sf, hipStream_t stream) {
-  return p.Hfc == 128 ? launch_heads_sample_g<FUSE, 32>(p, sf, stream) : launch_heads_sample_g<FUSE, 16>(p, sf, stream);
+  if (p.shaped)
+    return p.Hfc == 128 ? launch_heads_sample_g<FUSE, 32, true>(p, sf, stream) : launch_heads_sample_g<FUSE, 16, true>(p, sf, stream);
+  return p.Hfc == 128 ? launch_heads_sample_g<FUSE, 32, false>(p, sf, stream) : launch_heads_sample_g<FUSE, 16, false>(p, sf, stream);
+}
+
+static int heads_loss_impl(const float* h, const float* fc1_w, const float* fc1_b, int nheads, const float* const* heads_w,
+                           const float* const* heads_b, const int* head_size, const int* head_kind, const float* head_weight,
+                           const float* const* targets, const int64_t* target_stride, float loss_scale, int N, int H, int Hfc,
+                           float* preds, float* losses, int backward, float* dh, float* d_fc1_w, float* d_fc1_b,
+                           float* const* d_heads_w, float* const* d_heads_b, float* ws, const geeco_loss_shaping* shaping,
+                           int shaped, void* stream) {
+  GEECO_CHECK_ARG(h && (!backward || dh), "heads_loss: null pointer");
+  HeadsParams p;
+  if (int rc = heads_fill(&p, h, fc1_w, fc1_b, nheads, heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride,
+                          loss_scale, N, H, Hfc, preds, losses, backward, dh, d_fc1_w, d_fc1_b, d_heads_w, d_heads_b, ws, shaping,
+                          shaped))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (heads_sample_shapes(H, Hfc, p.OT)) {
+    if (int rc = launch_heads_sample<false>(p, StepFuse{}, s)) return rc;
+    return launch_heads_finish(p, h, s);
+  }
+  geeco_note_kernel(shaped ? "heads_loss_kernel<shaped>" : "heads_loss_kernel");
+  if (shaped)
+    hipLaunchKernelGGL(heads_loss_kernel<true>, dim3(1), dim3(1024), 0, s, p);
+  else
+    hipLaunchKernelGGL(heads_loss_kernel<false>, dim3(1), dim3(1024), 0, s, p);
+  GEECO_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int geeco_heads_loss_fwd_bwd(const float* h, const float* fc1_w, const float* fc1_b, int nheads,
@@ -430,41 +517,44 @@ extern "C" int geeco_heads_loss_fwd_bwd(const float* h, const float* fc1_w, cons
                                         int N, int H, int Hfc, float* preds, float* losses, int backward, float* dh,
                                         float* d_fc1_w, float* d_fc1_b, float* const* d_heads_w,
                                         float* const* d_heads_b, float* ws, void* stream) {
-  GEECO_CHECK_ARG(h && (!backward || dh), "heads_loss: null pointer");
-  HeadsParams p;
-  if (int rc = heads_fill(&p, h, fc1_w, fc1_b, nheads, heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride,
-                          loss_scale, N, H, Hfc, preds, losses, backward, dh, d_fc1_w, d_fc1_b, d_heads_w, d_heads_b, ws))
-    return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (heads_sample_shapes(H, Hfc, p.OT)) {
-    if (int rc = launch_heads_sample<false>(p, StepFuse{}, s)) return rc;
-    return launch_heads_finish(p, h, s);
-  }
-  geeco_note_kernel("heads_loss_kernel");
-  hipLaunchKernelGGL(heads_loss_kernel, dim3(1), dim3(1024), 0, s, p);
-  GEECO_LAUNCH_CHECK();
-  return 0;
+  return heads_loss_impl(h, fc1_w, fc1_b, nheads, heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride,
+                         loss_scale, N, H, Hfc, preds, losses, backward, dh, d_fc1_w, d_fc1_b, d_heads_w, d_heads_b, ws, nullptr, 0,
+                         stream);
 }
+
+// geeco_heads_loss_fwd_bwd with tf.losses' optional arguments (head_kind 2 = tf.losses.huber_loss): the same launches, shaped kernels
+extern "C" int geeco_heads_loss_shaped_fwd_bwd(const float* h, const float* fc1_w, const float* fc1_b, int nheads,
+                                               const float* const* heads_w, const float* const* heads_b,
+                                               const int* head_size, const int* head_kind, const float* head_weight,
+                                               const float* const* targets, const int64_t* target_stride, float loss_scale,
+                                               int N, int H, int Hfc, const geeco_loss_shaping* shaping, float* preds,
+                                               float* losses, int backward, float* dh, float* d_fc1_w, float* d_fc1_b,
+                                               float* const* d_heads_w, float* const* d_heads_b, float* ws, void* stream) {
+  return heads_loss_impl(h, fc1_w, fc1_b, nheads, heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride,
+                         loss_scale, N, H, Hfc, preds, losses, backward, dh, d_fc1_w, d_fc1_b, d_heads_w, d_heads_b, ws, shaping, 1,
+                         stream);
+}
+
+extern "C" int64_t geeco_loss_shaping_sizeof(void) { return (int64_t)sizeof(geeco_loss_shaping); }
 
 // One-step decoder (zero initial state): gate GEMM, then ONE per-sample launch for the gate math, fc1, the heads, the losses and --
 // with `backward` -- everything back to the gate gradients dz.  `pending` non-null: the batch sums of the heads' backward (and
 // the loss means) are left for geeco_lstm_step_bwd to run at the end of its second grid; null: heads_finish_kernel runs here.
-extern "C" int geeco_lstm_step_heads_fwd_bwd(const float* x, int64_t ldx, const float* wx, int64_t ldw, const float* bias,
-                                             float* z, float* c, float* h, float* gates, int N, int H, int D, void* gemm_ws,
-                                             const float* fc1_w, const float* fc1_b, int nheads, const float* const* heads_w,
-                                             const float* const* heads_b, const int* head_size, const int* head_kind,
-                                             const float* head_weight, const float* const* targets,
-                                             const int64_t* target_stride, float loss_scale, int Hfc, float* preds,
-                                             float* losses, int backward, float* dz, float* d_fc1_w, float* d_fc1_b,
-                                             float* const* d_heads_w, float* const* d_heads_b, float* heads_ws,
-                                             geeco_heads_finish* pending, void* stream) {
+static int lstm_step_heads_impl(const float* x, int64_t ldx, const float* wx, int64_t ldw, const float* bias, float* z, float* c,
+                                float* h, float* gates, int N, int H, int D, void* gemm_ws, const float* fc1_w,
+                                const float* fc1_b, int nheads, const float* const* heads_w, const float* const* heads_b,
+                                const int* head_size, const int* head_kind, const float* head_weight,
+                                const float* const* targets, const int64_t* target_stride, float loss_scale, int Hfc,
+                                float* preds, float* losses, int backward, float* dz, float* d_fc1_w, float* d_fc1_b,
+                                float* const* d_heads_w, float* const* d_heads_b, float* heads_ws, geeco_heads_finish* pending,
+                                const geeco_loss_shaping* shaping, int shaped, void* stream) {
   GEECO_CHECK_ARG(x && wx && bias && z && c && h && gates && (!backward || dz), "lstm_step_heads: null pointer");
   GEECO_CHECK_ARG(N >= 1 && H >= 1 && D >= 1 && ldx >= D && ldw >= 4 * (int64_t)H, "lstm_step_heads: bad dims");
   if (pending) reinterpret_cast<HeadsPending*>(pending)->valid = 0;
   HeadsPending hp;
   if (int rc = heads_fill(&hp.p, h, fc1_w, fc1_b, nheads, heads_w, heads_b, head_size, head_kind, head_weight, targets,
                           target_stride, loss_scale, N, H, Hfc, preds, losses, backward, nullptr, d_fc1_w, d_fc1_b, d_heads_w,
-                          d_heads_b, heads_ws))
+                          d_heads_b, heads_ws, shaping, shaped))
     return rc;
   if (!heads_sample_shapes(H, Hfc, hp.p.OT)) return GEECO_ENOSUP;      // nothing launched: the caller runs the separate entry points
   GemmParams g = {};
@@ -487,4 +577,34 @@ extern "C" int geeco_lstm_step_heads_fwd_bwd(const float* x, int64_t ldx, const 
     return launch_heads_finish(hp.p, h, s);
   }
   return 0;
+}
+
+extern "C" int geeco_lstm_step_heads_fwd_bwd(const float* x, int64_t ldx, const float* wx, int64_t ldw, const float* bias,
+                                             float* z, float* c, float* h, float* gates, int N, int H, int D, void* gemm_ws,
+                                             const float* fc1_w, const float* fc1_b, int nheads, const float* const* heads_w,
+                                             const float* const* heads_b, const int* head_size, const int* head_kind,
+                                             const float* head_weight, const float* const* targets,
+                                             const int64_t* target_stride, float loss_scale, int Hfc, float* preds,
+                                             float* losses, int backward, float* dz, float* d_fc1_w, float* d_fc1_b,
+                                             float* const* d_heads_w, float* const* d_heads_b, float* heads_ws,
+                                             geeco_heads_finish* pending, void* stream) {
+  return lstm_step_heads_impl(x, ldx, wx, ldw, bias, z, c, h, gates, N, H, D, gemm_ws, fc1_w, fc1_b, nheads, heads_w, heads_b,
+                              head_size, head_kind, head_weight, targets, target_stride, loss_scale, Hfc, preds, losses, backward,
+                              dz, d_fc1_w, d_fc1_b, d_heads_w, d_heads_b, heads_ws, pending, nullptr, 0, stream);
+}
+
+// geeco_lstm_step_heads_fwd_bwd with tf.losses' optional arguments: the same launches, the shaped per-sample kernel
+extern "C" int geeco_lstm_step_heads_shaped_fwd_bwd(const float* x, int64_t ldx, const float* wx, int64_t ldw, const float* bias,
+                                                    float* z, float* c, float* h, float* gates, int N, int H, int D,
+                                                    void* gemm_ws, const float* fc1_w, const float* fc1_b, int nheads,
+                                                    const float* const* heads_w, const float* const* heads_b,
+                                                    const int* head_size, const int* head_kind, const float* head_weight,
+                                                    const float* const* targets, const int64_t* target_stride,
+                                                    float loss_scale, int Hfc, const geeco_loss_shaping* shaping, float* preds,
+                                                    float* losses, int backward, float* dz, float* d_fc1_w, float* d_fc1_b,
+                                                    float* const* d_heads_w, float* const* d_heads_b, float* heads_ws,
+                                                    geeco_heads_finish* pending, void* stream) {
+  return lstm_step_heads_impl(x, ldx, wx, ldw, bias, z, c, h, gates, N, H, D, gemm_ws, fc1_w, fc1_b, nheads, heads_w, heads_b,
+                              head_size, head_kind, head_weight, targets, target_stride, loss_scale, Hfc, preds, losses, backward,
+                              dz, d_fc1_w, d_fc1_b, d_heads_w, d_heads_b, heads_ws, pending, shaping, 1, stream);
 }

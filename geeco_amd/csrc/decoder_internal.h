@@ -197,7 +197,19 @@ struct HeadsParams {
   float* da1;   // ws: [N][Hfc]
   float* dpred; // ws: [N][OT]  (the single-workgroup kernel keeps its packed head matrix behind it: [N * OT ...)
   float* lterm; // ws: [N][8] per-sample loss terms of every head (per-sample kernel -> finish role)
+  // ---- loss shaping (tf.losses' weights= / label_smoothing= / huber_loss(delta=)); all optional, read only where shaped != 0 ----
+  int shaped;              // the shaped entry points: kind 2 heads allowed, means over the non-zero weights
+  int cls_head;            // the kind-1 head class_w belongs to (-1: none)
+  const float* sample_w;   // [N] at sample_w[n * sample_w_stride], or null (every weight 1)
+  long long sample_w_stride;
+  const float* class_w;    // device table [size of head cls_head], or null
+  float smooth;            // label_smoothing of the kind-1 heads
+  float huber[GEECO_MAX_HEADS];      // delta of the kind-2 heads
 };
+
+// slots of a sample's lterm row behind the (<= 5) loss terms: the batch's counts of non-zero effective weights, as every
+// workgroup of the shaped per-sample kernel forms them (identical in every row; the finish role reads row 0)
+constexpr int HS_CNT_REG = 5, HS_CNT_CLS = 6;
 
 template <class T>
 __device__ __forceinline__ T sel5(T const (&a)[GEECO_MAX_HEADS], int i) {
@@ -205,6 +217,105 @@ __device__ __forceinline__ T sel5(T const (&a)[GEECO_MAX_HEADS], int i) {
 }
 
 constexpr int HS_THREADS = 1024, HS_HMAX = 128, HS_FMAX = 128;
+
+// ---- loss shaping: what the shaped P3 of both heads kernels shares ----------------------------------------------------------
+// effective weight of sample n for the regression heads
+__device__ __forceinline__ float shaped_sample_w(const HeadsParams& p, int n) {
+  return p.sample_w ? p.sample_w[(long long)n * p.sample_w_stride] : 1.f;
+}
+// ... and for the kind-1 head that carries the class table: sample weight x class_weight[label] (an out-of-range label: 0)
+__device__ __forceinline__ float shaped_class_w(const HeadsParams& p, float sw, float target) {
+  const int label = (int)rintf(target) + 1;
+  return sw * ((label >= 0 && label < sel5(p.size, p.cls_head)) ? p.class_w[label] : 0.f);
+}
+
+// The two integer counts of non-zero effective weights over the whole batch (x: regression heads and kind-1 heads without the
+// class table, y: the head with the class table), formed by ONE workgroup of NT threads from the N <= 4096 weights and labels
+// (L2-resident): integer adds through a wave reduction and `s_cnt` ([NT / 64][2] ints of LDS).  Every thread must call this; the
+// result is valid in every thread.  Contains two barriers.
+template <int NT>
+__device__ __forceinline__ void shaped_counts(const HeadsParams& p, int (*s_cnt)[2], int* cnt_reg, int* cnt_cls) {
+  if (!p.sample_w && !p.class_w) {      // uniform
+    *cnt_reg = p.N;
+    *cnt_cls = p.N;
+    return;
+  }
+  const int tid = threadIdx.x;
+  int c0 = 0, c1 = 0;
+  for (int m = tid; m < p.N; m += NT) {
+    const float sw = shaped_sample_w(p, m);
+    c0 += sw != 0.f;
+    if (p.class_w) c1 += shaped_class_w(p, sw, sel5(p.tgt, p.cls_head)[(long long)m * sel5(p.tstride, p.cls_head)]) != 0.f;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    c0 += __shfl_xor(c0, o, 64);
+    c1 += __shfl_xor(c1, o, 64);
+  }
+  if ((tid & 63) == 0) {
+    s_cnt[tid >> 6][0] = c0;
+    s_cnt[tid >> 6][1] = c1;
+  }
+  __syncthreads();
+  c0 = 0;
+  c1 = 0;
+#pragma unroll
+  for (int w = 0; w < NT / 64; ++w) {
+    c0 += s_cnt[w][0];
+    c1 += s_cnt[w][1];
+  }
+  __syncthreads();
+  *cnt_reg = c0;
+  *cnt_cls = p.class_w ? c1 : c0;
+}
+
+// One head of one sample, shaped (TF 1.15 tf.losses with reduction SUM_BY_NONZERO_WEIGHTS): returns w * sum_c l_c and writes
+// d(loss)/d(pred) of the head's `sz` outputs to dp.  pr / tg / dp: the head's predictions, targets and gradient slots; w: the
+// sample's effective weight for this head; cnt: the batch's count of non-zero effective weights for this head.  With w == 1,
+// cnt == N, smooth == 0 and kind != 2 every product below is by 1.0f or a sum with 0.0f: bitwise the unshaped arithmetic.
+__device__ __forceinline__ float shaped_head_terms(const HeadsParams& p, int hd, const float* pr, const float* tg, float* dp,
+                                                   float w, int cnt) {
+  const int sz = sel5(p.size, hd), kind = sel5(p.kind, hd);
+  const float wsc = sel5(p.weight, hd) * p.loss_scale;
+  float l = 0.f;
+  if (cnt == 0 || w == 0.f) {      // a zero weight contributes exact zeros (and no non-zero weight at all: tf.div_no_nan gives 0)
+    for (int c = 0; c < sz; ++c) dp[c] = 0.f;
+    return 0.f;
+  }
+  if (kind == 0) {
+    const float c2 = 2.f / (float)(cnt * sz) * wsc;
+    for (int c = 0; c < sz; ++c) {
+      const float d = pr[c] - tg[c];
+      l += d * d;
+      dp[c] = d * c2 * w;
+    }
+  } else if (kind == 2) {          // tf.losses.huber_loss: 0.5 q^2 + delta (a - q), q = min(a, delta)
+    const float dl = sel5(p.huber, hd);
+    const float c1 = 1.f / (float)(cnt * sz) * wsc;
+    for (int c = 0; c < sz; ++c) {
+      const float d = pr[c] - tg[c];
+      const float a = fabsf(d), q = fminf(a, dl);
+      l += 0.5f * q * q + dl * (a - q);
+      dp[c] = (a <= dl ? d : copysignf(dl, d)) * c1 * w;
+    }
+  } else {                         // softmax cross-entropy against one_hot * (1 - smooth) + smooth / C
+    const int label = (int)rintf(tg[0]) + 1;             // estimator.py:213-215
+    float mx = pr[0];
+    for (int c = 1; c < sz; ++c) mx = fmaxf(mx, pr[c]);
+    float se = 0.f;
+    for (int c = 0; c < sz; ++c) se += expf(pr[c] - mx);
+    const float lo = p.smooth / (float)sz, hi = 1.f * (1.f - p.smooth) + lo;      // one_hot of an out-of-range label is all-zero
+    float ysum = 0.f;
+    for (int c = 0; c < sz; ++c) {
+      const float y = c == label ? hi : lo;
+      ysum += y;
+      if (y != 0.f) l += y * (mx + logf(se) - pr[c]);
+    }
+    const float invc = 1.f / cnt;
+    for (int c = 0; c < sz; ++c) dp[c] = (expf(pr[c] - mx) / se * ysum - (c == label ? hi : lo)) * invc * wsc * w;
+  }
+  return l * w;
+}
 
 __device__ __forceinline__ int heads_head_of(const HeadsParams& p, int o) {
   int hd = 0;

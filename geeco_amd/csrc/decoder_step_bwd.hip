@@ -106,7 +106,12 @@ __device__ __forceinline__ void heads_finish_role(const HeadsParams& p, const fl
   }
   __shared__ float s_l[GEECO_MAX_HEADS];
   if (tid < p.nheads) {
-    const float sum = accl * (sel5(p.kind, tid) == 0 ? 1.f / (float)(N * sel5(p.size, tid)) : 1.f / N);
+    float mean = sel5(p.kind, tid) == 0 ? 1.f / (float)(N * sel5(p.size, tid)) : 1.f / N;
+    if (p.shaped) {      // means over the non-zero effective weights: the counts heads_sample_kernel<.., SHAPED> left in row 0 of lterm
+      const int cnt = (int)p.lterm[(p.class_w && tid == p.cls_head) ? HS_CNT_CLS : HS_CNT_REG];
+      mean = cnt == 0 ? 0.f : (sel5(p.kind, tid) == 1 ? 1.f / cnt : 1.f / (float)(cnt * sel5(p.size, tid)));
+    }
+    const float sum = accl * mean;
     p.losses[1 + tid] = sum;
     s_l[tid] = sum;
   }

@@ -8,31 +8,38 @@ from . import _native, ops
 from .variables import VariableStore
 
 
-def head_table(cfg):
+def head_table(cfg, loss_shaping=None):
   """(variable name, prediction key, size, kind, loss weight) per head, in variable creation order.
-  kind 0 = mean_squared_error, 1 = softmax cross-entropy (graph.py:233-259, 430-500; estimator.py:224-237)."""
+  kind 0 = mean_squared_error, 1 = softmax cross-entropy (graph.py:233-259, 430-500; estimator.py:224-237); 2 = huber_loss for the
+  regression heads ``loss_shaping['huber_delta']`` (``variables.check_loss_shaping``'s result) names."""
   if cfg.control_mode == 'cartesian':
     lam = float(cfg.lambda_aux)
-    return [('pred_cmd_ee', 'cmd_ee', 3, 0, 1.0), ('logits_cmd_grp', 'logits_cmd_grp', cfg.num_grp_states, 1, 1.0),
-            ('pred_aux_ee', 'pos_ee', 3, 0, lam), ('pred_aux_obj', 'pos_obj', 3, 0, lam)]
-  if cfg.control_mode == 'velocity':   # mse_loss sums all five terms unweighted (graph.py:446-449)
-    return [('pred_cmd_vel', 'cmd_vel', cfg.dim_jnt_state, 0, 1.0), ('pred_cmd_ee', 'cmd_ee', 3, 0, 1.0),
-            ('pred_cmd_grp', 'cmd_grp', cfg.dim_grp_command, 0, 1.0), ('pred_aux_ee', 'pos_ee', 3, 0, 1.0),
-            ('pred_aux_obj', 'pos_obj', 3, 0, 1.0)]
-  raise ValueError("Unknown control mode '%s'" % (cfg.control_mode,))
+    heads = [('pred_cmd_ee', 'cmd_ee', 3, 0, 1.0), ('logits_cmd_grp', 'logits_cmd_grp', cfg.num_grp_states, 1, 1.0),
+             ('pred_aux_ee', 'pos_ee', 3, 0, lam), ('pred_aux_obj', 'pos_obj', 3, 0, lam)]
+  elif cfg.control_mode == 'velocity':   # mse_loss sums all five terms unweighted (graph.py:446-449)
+    heads = [('pred_cmd_vel', 'cmd_vel', cfg.dim_jnt_state, 0, 1.0), ('pred_cmd_ee', 'cmd_ee', 3, 0, 1.0),
+             ('pred_cmd_grp', 'cmd_grp', cfg.dim_grp_command, 0, 1.0), ('pred_aux_ee', 'pos_ee', 3, 0, 1.0),
+             ('pred_aux_obj', 'pos_obj', 3, 0, 1.0)]
+  else:
+    raise ValueError("Unknown control mode '%s'" % (cfg.control_mode,))
+  huber = (loss_shaping or {}).get('huber_delta') or {}
+  return [(name, key, size, 2 if kind == 0 and key in huber else kind, w) for name, key, size, kind, w in heads]
 
 
 class LSTMDecoder:
   """T LSTM steps over states [T][N][D] from a zero state, fc1 + heads on the last output."""
 
-  def __init__(self, store: VariableStore, scope, cfg, N, T, D, training, one_launch=False):
-    """``one_launch`` (inference decoders with T > 1 only; the batched predictor engine sets it): forward(False) is the hoisted
+  def __init__(self, store: VariableStore, scope, cfg, N, T, D, training, one_launch=False, loss_shaping=None):
+    """``loss_shaping`` (``variables.check_loss_shaping``'s result, None = off): the losses and their gradients come from the shaped
+    entry points; with ``sample_weights`` the model binds ``sample_weight`` [N] beside the targets.
+    ``one_launch`` (inference decoders with T > 1 only; the batched predictor engine sets it): forward(False) is the hoisted
     input projection + ONE launch for the T steps, fc1 and the heads (ops.lstm_seq_heads_into).  No per-step gates / c / h history
     is kept, no loss terms are computed and ``targets`` are not read; ``losses`` stays zero."""
     self.store, self.scope, self.cfg, self.N, self.T, self.D = store, scope, cfg, N, T, D
     self.H, self.F, self.training = cfg.dim_h_lstm, cfg.dim_h_fc, training
     self.one_launch = bool(one_launch) and not training and T > 1
-    self.heads = head_table(cfg)
+    self.loss_shaping = loss_shaping
+    self.heads = head_table(cfg, loss_shaping)
     self.OT = sum(h[2] for h in self.heads)
     f32 = dict(dtype=torch.float32, device=store.device)
     H = self.H
@@ -52,6 +59,9 @@ class LSTMDecoder:
       gemm_shapes += [(D, 4 * H, T * N), (H, 4 * H, max((T - 1) * N, 1)), (T * N, D, 4 * H), (N, H, 4 * H)]
     self.gemm_ws = torch.empty(max(ops.gemm_ws_bytes(*s) for s in gemm_shapes) // 4 + 4, **f32)
     self.targets, self.target_strides, self.loss_scale = None, None, 1.0     # bound by the model
+    self.sample_weight, self.class_weight = None, None                      # loss_shaping: bound by the model; the table, made once
+    if loss_shaping is not None and loss_shaping['grp_class_weights'] is not None:
+      self.class_weight = torch.tensor(loss_shaping['grp_class_weights'], **f32)
     self.heads_pending, self.dz_from_heads = None, False
 
   def _alloc_chain(self):
@@ -81,6 +91,12 @@ class LSTMDecoder:
             *([h[i] for h in self.heads] for i in (2, 3, 4)), self.targets, self.target_strides, float(self.loss_scale))
     grads = dict(d_fc1_w=self._g('fc1/kernel'), d_fc1_b=self._g('fc1/bias'), d_heads_w=[self._g(n + '/kernel') for n in names],
                  d_heads_b=[self._g(n + '/bias') for n in names]) if backward_too else {}
+    if self.loss_shaping is not None:
+      ls = self.loss_shaping
+      if ls['sample_weights'] and self.sample_weight is None:
+        raise RuntimeError("LSTMDecoder: loss_shaping['sample_weights'] is on but no sample_weight buffer is bound")
+      grads['shaping'] = ops.loss_shaping(self.sample_weight if ls['sample_weights'] else None, self.class_weight, ls['label_smoothing'],
+                                          [ls['huber_delta'].get(h[1], 0.0) for h in self.heads])
     return args, grads
 
   def forward(self, backward_too):
@@ -102,7 +118,7 @@ class LSTMDecoder:
     N, T, D, H = self.N, self.T, self.D, self.H
     Wx, Wh, bias = self._weights()
     ops.gemm_into(self.zx, self.states, Wx, T * N, 4 * H, D, D, 4 * H, 4 * H, ws=self.gemm_ws)
-    return ops.lstm_seq_heads_into(self.preds, self.zx, Wh, bias, *args[:5], N, T, H, self.F, 4 * H, 4 * H)
+    return ops.lstm_seq_heads_into(self.preds, self.zx, Wh, bias, *args[:5], N, T, H, self.F, 4 * H, 4 * H)      # (no losses: nothing to shape)
 
   def _forward_one_step(self, backward_too, args, grads):
     """One step from a zero state (round 5): gate GEMM + ONE per-sample launch for the slab sum, the gate math, fc1, the heads, the
@@ -132,7 +148,7 @@ class LSTMDecoder:
     self._heads_loss(backward_too, args, grads)
 
   def _heads_loss(self, backward_too, args, grads):
-    kw = dict(dh=self.dh, **grads) if backward_too else {}
+    kw = dict(dh=self.dh, **grads) if backward_too else dict(grads)      # (forward only: grads holds at most the shaping)
     ops.heads_loss_into(self.preds, self.losses, self.h[self.T - 1], *args, self.N, self.H, self.F, self.heads_ws, **kw)
 
   def backward(self, concat=None):

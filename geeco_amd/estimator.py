@@ -31,7 +31,7 @@ from . import graph
 from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
 from .tf_checkpoint import EMA_SUFFIX
-from .variables import check_clip_norm, check_ema_decay, check_lr_multipliers, check_lr_schedule, check_skip_nonfinite, check_variable_stats, model_variable_shapes
+from .variables import check_clip_norm, check_ema_decay, check_loss_shaping, check_lr_multipliers, check_lr_schedule, check_skip_nonfinite, check_variable_stats, model_variable_shapes
 
 
 class ModeKeys:
@@ -390,6 +390,16 @@ def _model_fn(features, labels, mode, params, goal):
       raise ValueError("params['variable_stats'] is single-GPU: with %d ranks where the late bucket's gradient lives after the "
                        "exchange has not been decided" % gdist.world_size())
     ema['variable_stats'] = params['variable_stats']
+  # params['loss_shaping']: tf.losses' weights= / label_smoothing= / huber_loss; the reference builds the same loss in
+  # TRAIN and EVAL, so both modes' models take it (PREDICT forms no loss)
+  shaping = check_loss_shaping(params.get('loss_shaping'), cfg, "params['loss_shaping']")
+  if mode != ModeKeys.PREDICT and shaping is not None:
+    weighted = [k for k in ('sample_weights', 'grp_class_weights') if shaping[k]]
+    if weighted and gdist.world_size() > 1:
+      raise ValueError("params['loss_shaping'][%s] is single-GPU: with %d ranks the global count of non-zero weights is not the sum the "
+                       "loss_scale arithmetic assumes, and the exchange has not been decided"
+                       % ('], ['.join(repr(k) for k in weighted), gdist.world_size()))
+    ema['loss_shaping'] = params['loss_shaping']
   tables = {}
   if shared:
     # params['shared_frames'] (True, or a capacity F): encode each distinct frame of the batch once
@@ -502,6 +512,8 @@ class Estimator:
     check_clip_norm(self.params.get('clip_norm'), "params['clip_norm']")
     check_skip_nonfinite(self.params.get('skip_nonfinite'), "params['skip_nonfinite']")
     check_variable_stats(self.params.get('variable_stats'), "params['variable_stats']")
+    if self.params.get('loss_shaping') is not None and self.params.get('e2evmc_config') is not None:
+      check_loss_shaping(self.params['loss_shaping'], self.params['e2evmc_config'], "params['loss_shaping']")
     check_lr_schedule(self.params.get('lr_schedule'), getattr(self.params.get('e2evmc_config'), 'lr', 0.0), "params['lr_schedule']")
     if self.params.get('lr_multipliers') is not None and not isinstance(self.params['lr_multipliers'], collections.abc.Mapping):
       raise ValueError("params['lr_multipliers']=%r: must be None or a mapping {regular expression: multiplier}" % (self.params['lr_multipliers'],))
@@ -513,6 +525,7 @@ class Estimator:
     self._store = None
     self._restored = False
     self._finetune_logged = False
+    self._loss_shaping_logged = False
     if model_dir and gdist.rank() == 0:
       os.makedirs(model_dir, exist_ok=True)
     frac = getattr(self.config.session_config.gpu_options, 'per_process_gpu_memory_fraction', None)
@@ -609,6 +622,7 @@ class Estimator:
       self._store.initialize(seed=self.config.init_seed)
     self._restore_once()
     self._log_finetune(mode, spec.model)
+    self._log_loss_shaping(spec.model)
     self._specs[key] = (spec,) + feed.adopted_slots(fbuf, lbuf, spec.model.inputs)
     return self._specs[key]
 
@@ -638,6 +652,19 @@ class Estimator:
     line = {'trainable_parameters': count(lambda mul: mul != 0.0), 'frozen_parameters': count(lambda mul: mul == 0.0),
             'backward_cut': model.backward_cut, 'global_step': int(self._store.global_step.item()), 'wall_time': time.time()}
     print('INFO: fine-tuning: %(trainable_parameters)d trainable and %(frozen_parameters)d frozen parameters, backward: %(backward_cut)s' % line)
+    if self.model_dir and gdist.rank() == 0:
+      with open(os.path.join(self.model_dir, 'events.jsonl'), 'a') as f:
+        f.write(json.dumps(line) + '\n')
+
+  def _log_loss_shaping(self, model):
+    """params['loss_shaping']: one line of events.jsonl, the option as the model took it, the first time a model with a loss is built."""
+    shaping = getattr(model, 'loss_shaping', None)
+    if shaping is None or self._loss_shaping_logged:
+      return
+    self._loss_shaping_logged = True
+    line = {'loss_shaping': dict(shaping, grp_class_weights=list(shaping['grp_class_weights']) if shaping['grp_class_weights'] else None),
+            'global_step': int(self._store.global_step.item()), 'wall_time': time.time()}
+    print('INFO: loss shaping: %s' % json.dumps(line['loss_shaping'], sort_keys=True))
     if self.model_dir and gdist.rank() == 0:
       with open(os.path.join(self.model_dir, 'events.jsonl'), 'a') as f:
         f.write(json.dumps(line) + '\n')

@@ -29,7 +29,7 @@ from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .optimizer import OptimizerStep
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
-from .variables import (_CELLS, VariableStore, check_clip_norm, check_ema_decay, check_lr_schedule, check_skip_nonfinite, check_variable_stats,
+from .variables import (_CELLS, VariableStore, check_clip_norm, check_ema_decay, check_loss_shaping, check_lr_schedule, check_skip_nonfinite, check_variable_stats,
                         model_variable_shapes)
 
 
@@ -84,8 +84,9 @@ class _ModelBase(OptimizerStep):
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
   def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None, lr_schedule=None,
-               skip_nonfinite=None, lr_multipliers=None, variable_stats=None):
+               skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
+    self.loss_shaping = check_loss_shaping(loss_shaping, cfg)      # None: the option is off (DESIGN 5.22)
     self.variable_stats_mode = check_variable_stats(variable_stats) if training else None      # None: the option is off (DESIGN 5.21)
     self.ema_decay = check_ema_decay(ema_decay)
     self.clip_norm = check_clip_norm(clip_norm)
@@ -133,6 +134,9 @@ class _ModelBase(OptimizerStep):
       self.inputs['grp_target'] = torch.zeros(N, cfg.dim_grp_command, **f32)
     else:
       raise ValueError("Unknown control mode '%s'" % (cfg.control_mode,))
+    if self.loss_shaping is not None and self.loss_shaping['sample_weights']:      # tf.losses' weights=, one per sample
+      self.label_keys.append('sample_weight')
+      self.inputs['sample_weight'] = torch.ones(N, **f32)
     if self.C == 4:
       self.inputs['depth'] = torch.zeros(N, K, H, W, 1, **f32)
     if goal and F is None:
@@ -294,6 +298,7 @@ class _ModelBase(OptimizerStep):
             (inp['grp_target'], inp['grp_target'].shape[1]), (ee_last, K * 7), (obj_last, K * 7)]
     self.decoder.targets = [t for t, _ in tg]
     self.decoder.target_strides = [s for _, s in tg]
+    self.decoder.sample_weight = inp.get('sample_weight')
 
   def redirect_late_gradients(self, staging, late_ranges):
     return self.enc.redirect_late_gradients(staging, late_ranges)
@@ -388,12 +393,12 @@ class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None):
+               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None):
     """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``, ``lr_schedule``, ``skip_nonfinite``,
-    ``lr_multipliers``: see E2EVMC."""
+    ``lr_multipliers``, ``variable_stats``, ``loss_shaping``: see E2EVMC."""
     super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
                      clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers,
-                     variable_stats=variable_stats)
+                     variable_stats=variable_stats, loss_shaping=loss_shaping)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -417,7 +422,7 @@ class GoalE2EVMC(_ModelBase):
       dims = self.feat_ch
     self.enc = ConvEncoderStack(self.store, scopes, Nf, H, W, C, dims, training)
     D = _CELLS * (sum(self.feat_ch) + jn)
-    self.decoder = LSTMDecoder(self.store, root + '/LSTMDecoder', cfg, N, T, D, training, one_launch=one_launch_decoder)
+    self.decoder = LSTMDecoder(self.store, root + '/LSTMDecoder', cfg, N, T, D, training, one_launch=one_launch_decoder, loss_shaping=self.loss_shaping)
     self._bind_labels()
     if self.shared_frames is None:      # (the shared-frame step forms no dynamic image)
       self.dyn_ws = ops.dynimg_ws(N, H * W * 4, self.device)
@@ -524,7 +529,7 @@ class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None):
+               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None):
     """``ema_decay`` (a float in (0, 1); None / 0 = off): the optimiser step also keeps an exponential moving average of the
     parameters in ``store.ema`` (tf.train.ExponentialMovingAverage with num_updates = global_step); a store passed in
     must have been built with the arena (``build_store(..., ema=True)``).
@@ -542,19 +547,23 @@ class E2EVMC(_ModelBase):
     (``backward_cut``).  Single GPU, not with ``shared_frames``.
     ``variable_stats`` (True, or 'histograms'; None / False = off): ``variable_stats()`` reports, per variable, the norms and counts of
     the last step's gradient, weights and update from one statistics pass on the device.  The step itself is unchanged.
+    ``loss_shaping`` (``variables.check_loss_shaping``; None or all-neutral = off): the losses take tf.losses' optional arguments (DESIGN
+    5.22) -- ``sample_weights``: a weight per sample, the input 'sample_weight' [N] (a label; ones until fed); ``grp_class_weights``: a weight
+    per gripper class; ``label_smoothing``; ``huber_delta``: Huber in place of MSE on the named regression heads.  Means run over the samples
+    whose weight is not zero; ``loss_parts()`` reports the shaped terms.  Same launches as without it.
     ``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
     'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
     super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
                      clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers,
-                     variable_stats=variable_stats)
+                     variable_stats=variable_stats, loss_shaping=loss_shaping)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     self.window_mode, self.feat_ch = 'plain', [256]
     # frames are processed time-major ([K][N]) so that step t's features are one dense block
     self.enc = ConvEncoderStack(self.store, ['VMC/ConvEncoder'], self.shared_frames or K * N, H, W, C, 256, training)
     D = _CELLS * (256 + cfg.dim_jnt_state)
-    self.decoder = LSTMDecoder(self.store, 'VMC/LSTMDecoder', cfg, N, K, D, training, one_launch=one_launch_decoder)
+    self.decoder = LSTMDecoder(self.store, 'VMC/LSTMDecoder', cfg, N, K, D, training, one_launch=one_launch_decoder, loss_shaping=self.loss_shaping)
     self._bind_labels()
 
   def _encode(self):

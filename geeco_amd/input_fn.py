@@ -399,6 +399,20 @@ def _augment_batch(feats, rng, aug, scene_rng=None, scene=None, hw=None):
   return feats
 
 
+def weigh_batch(fn, features, labels):
+  """``pickplace_input_fn(sample_weight=fn)``: ``fn(features, labels)`` -> one weight per sample of the batch, checked ([n], finite,
+  >= 0) and stored as labels['sample_weight'] (float32) of a NEW label dict; nothing else of the batch is touched."""
+  n = len(features['step'])
+  w = np.asarray(fn(features, labels))
+  if w.shape != (n,) or w.dtype == np.bool_ or not (np.issubdtype(w.dtype, np.floating) or np.issubdtype(w.dtype, np.integer)):
+    raise ValueError('sample_weight: the function must return one number per sample, shape (%d,); got shape %s, dtype %s'
+                     % (n, w.shape, w.dtype))
+  w = w.astype(np.float32)
+  if not np.isfinite(w).all() or (w < 0).any():
+    raise ValueError('sample_weight: weights must be finite and >= 0, got %r' % (w,))
+  return features, dict(labels, sample_weight=w)
+
+
 class _Prefetcher:
   """Runs an iterator factory in a background thread (tf.data's prefetch); the episode readers it draws from are a
   thread pool of their own (``_EpisodeSource``)."""
@@ -582,7 +596,7 @@ def default_reader_threads(world=1):
 
 def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size=4, fetch_target=False,
                        shuffle_buffer=128, batch_size=1, num_epochs=1, num_threads=4, prefetch_size=4, seed=None,
-                       shard=None, device=None, device_keys=None, cache=True, shuffle_windows=False, augment=None):
+                       shard=None, device=None, device_keys=None, cache=True, shuffle_windows=False, augment=None, sample_weight=None):
   """Same signature as the reference's pickplace_input_fn (geeco_gym.py:234-279).  Returns an iterable of
   (features, labels) numpy batches.  ``num_threads`` episodes are read in parallel, in order (num_parallel_reads /
   num_parallel_calls of :442-473; None = ``default_reader_threads``: this rank's share of the host cores); ``prefetch_size`` batches are prepared ahead of the consumer (:473).
@@ -614,7 +628,11 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
   each, the same in its K frames and its 'target_rgb' (a static distractor), with sides up to ``occlude_size`` (default 0.25) of
   the frame's.  Order per element: shift / tint, rectangles, noise.  Their draws (``draw_augment_scene``) come from
   ``default_rng([seed, rank, AUGMENT_SCENE_STREAM])``, so file order, shuffle picks and the shift / colour draws are those without
-  them."""
+  them.
+  ``sample_weight`` = None | fn(features, labels) -> [n] array (every mode, host and ``device`` path, ``synthetic:`` inputs too): the
+  weight per sample that params['loss_shaping']['sample_weights'] reads.  Called on every emitted batch, the ragged
+  last one included, behind the augmentation draws; its result is checked (shape, finite, >= 0: ``weigh_batch``) and stored as
+  labels['sample_weight'].  Every other feature and label is what it is without the option."""
   if shuffle_windows and int(shuffle_buffer) < 1:
     raise ValueError('shuffle_windows needs shuffle_buffer >= 1, got %r' % (shuffle_buffer,))
   check_augment(augment)
@@ -624,8 +642,11 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
     raise KeyError(encoding)
   if num_threads is None:
     num_threads = default_reader_threads(shard[1] if shard is not None else 1)
+  if sample_weight is not None and not callable(sample_weight):
+    raise ValueError('sample_weight=%r: None or a function (features, labels) -> one weight per sample' % (sample_weight,))
   if dataset_dir.startswith('synthetic:'):
-    return synthetic_from_spec(dataset_dir, mode, window_size, fetch_target, batch_size, seed)
+    it = synthetic_from_spec(dataset_dir, mode, window_size, fetch_target, batch_size, seed)
+    return it if sample_weight is None else (weigh_batch(sample_weight, f, l) for f, l in it)
   meta = get_meta_v4(dataset_dir)
   paths = collect_tfrecords(dataset_dir, split_name, mode)
   if mode == 'train':   # record-level shuffle only (:436-437)
@@ -661,12 +682,13 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
   print('[pickplace_input_fn_v4] #tfrecords: %d' % len(paths))
 
   def emitter():
-    """What a finished batch passes through on its way out: the augmentation draws, in emission order."""
+    """What a finished batch passes through on its way out: the augmentation draws, in emission order, then the sample weights."""
+    weigh = (lambda f, l: (f, l)) if sample_weight is None else (lambda f, l: weigh_batch(sample_weight, f, l))
     if aug is None and scene is None:
-      return lambda f, l: (f, l)
+      return weigh
     stream = lambda word: np.random.default_rng(None if seed is None else [seed, shard[0] if shard is not None else 0, word])
     rng, scene_rng = stream(AUGMENT_STREAM), stream(AUGMENT_SCENE_STREAM)
-    return lambda f, l: (_augment_batch(f, rng, aug, scene_rng, scene, (meta.img_height, meta.img_width)), l)
+    return lambda f, l: weigh(_augment_batch(f, rng, aug, scene_rng, scene, (meta.img_height, meta.img_width)), l)
 
   def shuffled_batches():
     import itertools

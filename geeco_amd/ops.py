@@ -649,34 +649,64 @@ def _head_arrays(heads_w, heads_b, head_size, head_kind, head_weight, targets, t
           _parr(targets), (ctypes.c_int64 * nh)(*[int(v) for v in target_stride]))
 
 
+def loss_shaping(sample_weight=None, class_weight=None, label_smoothing=0.0, huber_delta=None):
+  """A geeco_loss_shaping for ``heads_loss_into`` / ``lstm_step_heads_into`` (``shaping=``): tf.losses' ``weights=`` as a device
+  vector ``sample_weight`` [N] (a strided view is fine) and / or a device table ``class_weight`` [size of the cross-entropy head],
+  ``label_smoothing``, and ``huber_delta`` = one delta per head (read for the heads of kind 2).  The tensors are read by the
+  kernels when they run: the struct holds a reference to each, and whoever replays a captured call keeps them alive beyond it."""
+  s = _native.LossShaping()
+  s.tensors = (sample_weight, class_weight)
+  for t in (sample_weight, class_weight):
+    assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.dim() == 1), (t.device, t.dtype, t.shape)
+  if sample_weight is not None:
+    s.sample_weight, s.sample_weight_stride = sample_weight.data_ptr(), int(sample_weight.stride(0))
+  if class_weight is not None:
+    assert class_weight.is_contiguous()
+    s.class_weight = class_weight.data_ptr()
+  s.label_smoothing = float(label_smoothing)
+  for i, d in enumerate(huber_delta or ()):
+    s.huber_delta[i] = float(d)
+  return s
+
+
 def heads_loss_into(preds, losses, h, fc1_w, fc1_b, heads_w, heads_b, head_size, head_kind, head_weight, targets,
                     target_stride, loss_scale, N, H, Hfc, ws, dh=None, d_fc1_w=None, d_fc1_b=None, d_heads_w=None,
-                    d_heads_b=None):
-  """fc1 + heads + losses (+ their gradients when ``dh`` is given); see include/geeco_hip.h."""
+                    d_heads_b=None, shaping=None):
+  """fc1 + heads + losses (+ their gradients when ``dh`` is given); see include/geeco_hip.h.  ``shaping`` (a ``loss_shaping``):
+  the shaped entry point, which also takes heads of kind 2 (Huber)."""
   backward = dh is not None
-  check(_lib().geeco_heads_loss_fwd_bwd(
-      _p(h), _p(fc1_w), _p(fc1_b), *_head_arrays(heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride),
-      loss_scale, N, H, Hfc, _p(preds), _p(losses), 1 if backward else 0, _p(dh),
-      _p(d_fc1_w), _p(d_fc1_b), _parr(d_heads_w) if backward else None, _parr(d_heads_b) if backward else None,
-      _p(ws), _stream()), 'geeco_heads_loss_fwd_bwd')
+  heads = _head_arrays(heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride)
+  tail = (_p(preds), _p(losses), 1 if backward else 0, _p(dh), _p(d_fc1_w), _p(d_fc1_b), _parr(d_heads_w) if backward else None,
+          _parr(d_heads_b) if backward else None, _p(ws), _stream())
+  if shaping is None:
+    check(_lib().geeco_heads_loss_fwd_bwd(_p(h), _p(fc1_w), _p(fc1_b), *heads, loss_scale, N, H, Hfc, *tail),
+          'geeco_heads_loss_fwd_bwd')
+  else:
+    check(_lib().geeco_heads_loss_shaped_fwd_bwd(_p(h), _p(fc1_w), _p(fc1_b), *heads, loss_scale, N, H, Hfc,
+                                                 ctypes.byref(shaping), *tail), 'geeco_heads_loss_shaped_fwd_bwd')
 
 
 def lstm_step_heads_into(z, c, h, gates, x, wx, bias, N, H, D, ldx, ldw, gemm_ws, preds, losses, fc1_w, fc1_b, heads_w, heads_b,
                          head_size, head_kind, head_weight, targets, target_stride, loss_scale, Hfc, heads_ws, dz=None,
-                         d_fc1_w=None, d_fc1_b=None, d_heads_w=None, d_heads_b=None, pending=None):
+                         d_fc1_w=None, d_fc1_b=None, d_heads_w=None, d_heads_b=None, pending=None, shaping=None):
   """One-step decoder from a zero state: the gate GEMM + ONE per-sample launch (slab sum, gate math, fc1, heads, loss terms and,
   when ``dz`` is given, everything back to the gate gradients).  ``pending`` (an _native.HeadsFinish): the batch sums are left for
-  lstm_step_bwd_into(pending=...); None: they run here.  Returns False (nothing launched) for shapes the per-sample kernel does
-  not serve: the caller then runs lstm_input_step_fwd_into + heads_loss_into (+ lstm_gates_bwd_into)."""
+  lstm_step_bwd_into(pending=...); None: they run here.  ``shaping`` (a ``loss_shaping``): the shaped entry point.  Returns False
+  (nothing launched) for shapes the per-sample kernel does not serve: the caller then runs lstm_input_step_fwd_into +
+  heads_loss_into (+ lstm_gates_bwd_into)."""
   backward = dz is not None
-  rc = _lib().geeco_lstm_step_heads_fwd_bwd(
-      _p(x), ldx, _p(wx), ldw, _p(bias), _p(z), _p(c), _p(h), _p(gates), N, H, D, _p(gemm_ws), _p(fc1_w), _p(fc1_b),
-      *_head_arrays(heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride), loss_scale, Hfc, _p(preds),
-      _p(losses), 1 if backward else 0, _p(dz), _p(d_fc1_w), _p(d_fc1_b), _parr(d_heads_w) if backward else None,
-      _parr(d_heads_b) if backward else None, _p(heads_ws), ctypes.byref(pending) if pending is not None else None, _stream())
+  head = (_p(x), ldx, _p(wx), ldw, _p(bias), _p(z), _p(c), _p(h), _p(gates), N, H, D, _p(gemm_ws), _p(fc1_w), _p(fc1_b),
+          *_head_arrays(heads_w, heads_b, head_size, head_kind, head_weight, targets, target_stride), loss_scale, Hfc)
+  tail = (_p(preds), _p(losses), 1 if backward else 0, _p(dz), _p(d_fc1_w), _p(d_fc1_b), _parr(d_heads_w) if backward else None,
+          _parr(d_heads_b) if backward else None, _p(heads_ws), ctypes.byref(pending) if pending is not None else None, _stream())
+  if shaping is None:
+    rc, what = _lib().geeco_lstm_step_heads_fwd_bwd(*head, *tail), 'geeco_lstm_step_heads_fwd_bwd'
+  else:
+    rc, what = (_lib().geeco_lstm_step_heads_shaped_fwd_bwd(*head, ctypes.byref(shaping), *tail),
+                'geeco_lstm_step_heads_shaped_fwd_bwd')
   if rc == _native.GEECO_ENOSUP:
     return False
-  check(rc, 'geeco_lstm_step_heads_fwd_bwd')
+  check(rc, what)
   return True
 
 

@@ -140,6 +140,78 @@ def check_variable_stats(value, key='variable_stats'):
   raise ValueError("%s=%r: True (scalars per variable) or 'histograms' (scalars and histograms); None or False = off" % (key, value))
 
 
+LOSS_SHAPING_KEYS = ('sample_weights', 'grp_class_weights', 'label_smoothing', 'huber_delta')
+
+
+def regression_prediction_keys(cfg):
+  """Prediction keys of the regression heads (decoder.head_table's, in its order): the heads ``huber_delta`` may name."""
+  if cfg.control_mode == 'cartesian':
+    return ('cmd_ee', 'pos_ee', 'pos_obj')
+  if cfg.control_mode == 'velocity':
+    return ('cmd_vel', 'cmd_ee', 'cmd_grp', 'pos_ee', 'pos_obj')
+  raise ValueError("Unknown control mode '%s'" % (cfg.control_mode,))
+
+
+def check_loss_shaping(value, cfg, key='loss_shaping'):
+  """Loss shaping (tf.losses' ``weights=``, ``label_smoothing=`` and ``tf.losses.huber_loss(delta=)``): None = off, or a dict
+  with any of ``sample_weights`` (bool: the loss reads a weight per sample, labels['sample_weight']), ``grp_class_weights`` (one finite
+  weight >= 0 per gripper class, ``cfg.num_grp_states`` of them; cartesian mode only), ``label_smoothing`` (a float in [0, 1); cartesian
+  mode only) and ``huber_delta`` (a finite float > 0 for every regression head, or {prediction key: delta}).  Returns None when every entry
+  is neutral, else dict(sample_weights=bool, grp_class_weights=tuple or None, label_smoothing=float, huber_delta={prediction key: delta});
+  anything else raises ValueError naming ``key``."""
+  if value is None:
+    return None
+  if not isinstance(value, collections.abc.Mapping):
+    raise ValueError('%s=%r: None or a dict with the keys %s' % (key, value, ', '.join(LOSS_SHAPING_KEYS)))
+  unknown = sorted(set(value) - set(LOSS_SHAPING_KEYS), key=str)
+  if unknown:
+    raise ValueError('%s: unknown key(s) %s (known: %s)' % (key, ', '.join(repr(k) for k in unknown), ', '.join(LOSS_SHAPING_KEYS)))
+  real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(float(v))
+  f32max = float(np.finfo(np.float32).max)
+  cartesian = cfg.control_mode == 'cartesian'
+  sw = value.get('sample_weights')
+  if sw is not None and not isinstance(sw, bool):
+    raise ValueError("%s['sample_weights']=%r: True or False" % (key, sw))
+  cw = value.get('grp_class_weights')
+  if cw is not None:
+    if not cartesian:
+      raise ValueError("%s['grp_class_weights']: control_mode=%r has no gripper classes (cartesian mode only)" % (key, cfg.control_mode))
+    if isinstance(cw, (str, bytes)) or not isinstance(cw, (collections.abc.Sequence, np.ndarray)) or len(cw) != cfg.num_grp_states or \
+        not all(real(v) and 0.0 <= float(v) <= f32max for v in cw):
+      raise ValueError("%s['grp_class_weights']=%r: %d finite weights >= 0, one per gripper class" % (key, cw, cfg.num_grp_states))
+    cw = tuple(float(v) for v in cw)
+    if all(v == 1.0 for v in cw):
+      cw = None
+  eps = value.get('label_smoothing')
+  if eps is None:
+    eps = 0.0
+  if not real(eps) or not 0.0 <= float(eps) < 1.0:
+    raise ValueError("%s['label_smoothing']=%r: a float in [0, 1)" % (key, eps))
+  if float(eps) != 0.0 and not cartesian:
+    raise ValueError("%s['label_smoothing']: control_mode=%r has no cross-entropy head (cartesian mode only)" % (key, cfg.control_mode))
+  heads = regression_prediction_keys(cfg)
+  hd = value.get('huber_delta')
+  ok = lambda v: real(v) and 0.0 < float(v) <= f32max
+  if hd is None:
+    hd = {}
+  elif isinstance(hd, collections.abc.Mapping):
+    bad = sorted(set(hd) - set(heads), key=str)
+    if bad:
+      raise ValueError("%s['huber_delta']: %s is no regression head of control_mode=%r (heads: %s)"
+                       % (key, ', '.join(repr(k) for k in bad), cfg.control_mode, ', '.join(heads)))
+    for k, v in hd.items():
+      if not ok(v):
+        raise ValueError("%s['huber_delta'][%r]=%r: a finite float > 0" % (key, k, v))
+    hd = {k: float(hd[k]) for k in heads if k in hd}
+  elif ok(hd):
+    hd = {k: float(hd) for k in heads}
+  else:
+    raise ValueError("%s['huber_delta']=%r: a finite float > 0, or {prediction key: delta}" % (key, hd))
+  if not sw and cw is None and float(eps) == 0.0 and not hd:
+    return None
+  return dict(sample_weights=bool(sw), grp_class_weights=cw, label_smoothing=float(eps), huber_delta=hd)
+
+
 def variable_stats_scalars(rec, count, lr_t, multiplier=1.0, applied=True, histograms=False):
   """One variable's record of ``geeco_variable_stats`` (a numpy scalar of ``ops.VARSTATS_DTYPE``, or any mapping with its fields) of ``count`` elements as the
   dictionary ``model.variable_stats()`` reports.  Square roots and ratios are formed here, in float64, from the device's sums.

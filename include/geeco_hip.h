@@ -30,7 +30,8 @@ extern "C" {
  * geeco_gather_windows_augmented, geeco_adam_tf_ema, geeco_adam_tf_segments_ema, geeco_clip_ws_floats,
  * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip, geeco_gather_windows_scene,
  * geeco_adam_prepare_schedule, geeco_slab_reduce_batch_prepare_schedule, geeco_lr_schedule_eval, geeco_guard_decide,
- * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled, geeco_variable_stats_ws_bytes, geeco_variable_stats */
+ * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled, geeco_variable_stats_ws_bytes, geeco_variable_stats,
+ * geeco_heads_loss_shaped_fwd_bwd, geeco_lstm_step_heads_shaped_fwd_bwd, geeco_loss_shaping_sizeof */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -520,6 +521,48 @@ int geeco_lstm_step_heads_fwd_bwd(const float* x, int64_t ldx, const float* wx, 
                                   float* preds, float* losses, int backward, float* dz, float* d_fc1_w, float* d_fc1_b,
                                   float* const* d_heads_w, float* const* d_heads_b, float* heads_ws,
                                   geeco_heads_finish* pending, void* stream);
+
+/* ---- loss shaping: the optional arguments of the tf.losses calls above (TF 1.15: weights=, label_smoothing=,
+ * tf.losses.huber_loss(delta=)), reduction SUM_BY_NONZERO_WEIGHTS.  The shaped entry points take the arguments of the entry
+ * points they extend plus a geeco_loss_shaping (host struct, read during the call; its pointers are DEVICE pointers that the
+ * kernels read when they RUN, so a captured graph follows new weights in the same buffers), and allow
+ *   head_kind 2: tf.losses.huber_loss against target rows, delta = huber_delta[i] (finite, > 0):
+ *                l = 0.5 q^2 + delta (|e| - q), q = min(|e|, delta), e = pred - target.
+ * Effective weight of sample n: sample_weight[n * sample_weight_stride] (NULL: 1) for every head, times
+ * class_weight[label_n] for the single kind-1 head when class_weight (device table [size of that head], NULL: none) is given;
+ * an out-of-range label then weighs 0.  Weights are finite and >= 0.  Kind-1 targets are
+ * one_hot * (1 - label_smoothing) + label_smoothing / size, label_smoothing in [0, 1).
+ *   L_i = sum_n w_n sum_c l_{n,c} / (size_i * #{n : w_n != 0})   (kind 1: size_i = 1;  0, with zero gradients, when no w_n != 0)
+ * and d(loss)/d(pred) carries w_n / (size_i * count_i) in place of 1 / (size_i * N).  The counts are integer counts formed inside
+ * the same launches (every workgroup of the per-sample kernel reads the N weights and labels): the launches are those of the
+ * unshaped entry points, with shaped kernels.  With every weight 1 (or NULL), label_smoothing 0 and no kind-2 head all outputs
+ * are bitwise those of the unshaped entry points (single-workgroup kernel: for N <= 1024, where a thread sums one sample).
+ * GEECO_EINVAL: shaping NULL, label_smoothing outside [0, 1), huber_delta[i] <= 0 or not finite on a kind-2 head, class_weight
+ * without exactly one kind-1 head.  The unshaped entry points refuse head_kind 2. */
+typedef struct geeco_loss_shaping {
+  const float* sample_weight;
+  int64_t sample_weight_stride;
+  const float* class_weight;
+  float label_smoothing;
+  float huber_delta[5];
+} geeco_loss_shaping;
+int64_t geeco_loss_shaping_sizeof(void);
+int geeco_heads_loss_shaped_fwd_bwd(const float* h, const float* fc1_w, const float* fc1_b, int nheads,
+                                    const float* const* heads_w, const float* const* heads_b, const int* head_size,
+                                    const int* head_kind, const float* head_weight, const float* const* targets,
+                                    const int64_t* target_stride, float loss_scale, int N, int H, int Hfc,
+                                    const geeco_loss_shaping* shaping, float* preds, float* losses, int backward, float* dh,
+                                    float* d_fc1_w, float* d_fc1_b, float* const* d_heads_w, float* const* d_heads_b, float* ws,
+                                    void* stream);
+int geeco_lstm_step_heads_shaped_fwd_bwd(const float* x, int64_t ldx, const float* wx, int64_t ldw, const float* bias, float* z,
+                                         float* c, float* h, float* gates, int N, int H, int D, void* gemm_ws,
+                                         const float* fc1_w, const float* fc1_b, int nheads, const float* const* heads_w,
+                                         const float* const* heads_b, const int* head_size, const int* head_kind,
+                                         const float* head_weight, const float* const* targets, const int64_t* target_stride,
+                                         float loss_scale, int Hfc, const geeco_loss_shaping* shaping, float* preds,
+                                         float* losses, int backward, float* dz, float* d_fc1_w, float* d_fc1_b,
+                                         float* const* d_heads_w, float* const* d_heads_b, float* heads_ws,
+                                         geeco_heads_finish* pending, void* stream);
 
 /* The INFERENCE decoder of the per-frame controllers (e2e_vmc, goal_e2evmc 'sequence': T = window_size steps from the zero state,
  * graph.py:217-260) after the hoisted input projection, as ONE launch: the T - 1 recurrent h wh products, the gate math of all T

@@ -170,6 +170,15 @@ ARGPARSER.add_argument('--freeze_encoder_bottom', default=False, action='store_t
                        help="Shorthand for the --lr_multipliers entry '/conv[12]/=0': conv1 and conv2 of every encoder are frozen.")
 ARGPARSER.add_argument('--freeze_encoders', default=False, action='store_true',
                        help="Shorthand for the --lr_multipliers entry 'Encoder/=0': only the decoder is trained.")
+ARGPARSER.add_argument('--loss_grp_class_weights', type=str, default='',
+                       help='Cartesian mode: a weight per gripper class for the cross-entropy of the gripper command, comma-separated in '
+                            "label order (close, hold, open), e.g. 1,0.2,1 (tf.losses' weights=tf.gather(w, labels)); the mean runs over "
+                            'the samples whose weight is not zero.  One GPU.  Not part of the model config.')
+ARGPARSER.add_argument('--loss_label_smoothing', type=float, default=0.0,
+                       help='Cartesian mode: label_smoothing of the gripper cross-entropy (tf.losses.softmax_cross_entropy), in [0, 1); '
+                            '0 = off.')
+ARGPARSER.add_argument('--loss_huber_delta', type=float, default=0.0,
+                       help='tf.losses.huber_loss with this delta (> 0) in place of mean_squared_error on every regression head; 0 = off.')
 
 _OBSERVATION_FORMAT_TO_CHANNELS = {'rgb': 3, 'rgbd': 4}                      # train_e2evmc.py:129-132
 _GOAL_CONDITION_TO_MODEL = {'none': (e2evmc_model_fn, 'VMC'),               # train_e2evmc.py:134-137
@@ -236,6 +245,18 @@ def estimator_params(args, e2evmc_config):
     params['variable_stats'] = 'histograms'
   elif args.variable_stats:
     params['variable_stats'] = True
+  shaping = {}
+  if args.loss_grp_class_weights:
+    try:
+      shaping['grp_class_weights'] = [float(v) for v in args.loss_grp_class_weights.split(',')]
+    except ValueError:
+      raise ValueError('--loss_grp_class_weights %r: comma-separated numbers, e.g. 1,0.2,1' % args.loss_grp_class_weights)
+  if args.loss_label_smoothing:
+    shaping['label_smoothing'] = args.loss_label_smoothing
+  if args.loss_huber_delta:
+    shaping['huber_delta'] = args.loss_huber_delta
+  if shaping:
+    params['loss_shaping'] = shaping
   multipliers = lr_multipliers_of(args)
   if multipliers:
     params['lr_multipliers'] = multipliers
