@@ -183,6 +183,7 @@ SIGNATURES = {
     'geeco_lr_schedule_eval': (_I, [POINTER(LrSchedule), _L, POINTER(ctypes.c_double)]),
     'geeco_variable_stats_ws_bytes': (_L, [_L]),      # additive within ABI 7
     'geeco_variable_stats': (_I, [_P, _P, _P, _P, _I, _L, _F, _F, POINTER(c_int64), POINTER(c_int64), _I, _P, _L, _P, _P, _P]),
+    'geeco_grad_accumulate_segments': (_I, [_P, _P, _I, _L, _I, _P]),      # additive within ABI 7
     'geeco_sumsq': (_I, [_P, _L, _P, _P]),
 }
 

@@ -2,6 +2,7 @@
 // five entry points that take pieces of the arena, and the two whole-arena kernels.  The step counter and lr_t = scal[0] are the prepare work's (csrc/misc.hip: geeco_adam_prepare, or the last
 // slab-sum launch of the backward).
 #include "geeco_common.h"
+#include "adam_grid.h"
 
 // ---- one element -----------------------------------------------------------------------------------
 // The total gradient G = g * gscale + l2 * p, under CLIP times s = clip_dev[0] once it has been formed.  The multiplication feeds only
@@ -147,13 +148,7 @@ __global__ __launch_bounds__(256) void adam_update_kernel(float* __restrict__ p,
 }
 
 // ---- the launcher ----------------------------------------------------------------------------------
-static int adam_grid(long long n4) {      // the one grid rule: every block walks every piece, n4 = the longest piece's float4s
-  long long blocks = cdiv64(n4, 256);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  return (int)blocks;
-}
-
+// (the grid: adam_grid of csrc/adam_grid.h, shared with the accumulate launch of csrc/grad_accum.hip)
 // What every entry point checks (``who`` names it in messages), the table of pieces, the grid and the launch.  ``count_multiple``: 4 for
 // the entry points that take whole float4s alone, 1 for those whose pieces may end in a tail.  ``lr_mul``: one multiplier per piece
 // under MUL, else null.  The template arguments are the entry point's; EMA follows from ``ema_or_null``.

@@ -31,7 +31,7 @@ from . import graph
 from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
 from .tf_checkpoint import EMA_SUFFIX
-from .variables import check_clip_norm, check_ema_decay, check_loss_shaping, check_lr_multipliers, check_lr_schedule, check_skip_nonfinite, check_variable_stats, model_variable_shapes
+from .variables import check_clip_norm, check_ema_decay, check_grad_accum_steps, check_loss_shaping, check_lr_multipliers, check_lr_schedule, check_skip_nonfinite, check_variable_stats, model_variable_shapes
 
 
 class ModeKeys:
@@ -400,6 +400,13 @@ def _model_fn(features, labels, mode, params, goal):
                        "loss_scale arithmetic assumes, and the exchange has not been decided"
                        % ('], ['.join(repr(k) for k in weighted), gdist.world_size()))
     ema['loss_shaping'] = params['loss_shaping']
+  # params['grad_accum_steps']: one optimiser step per A batches, their gradients summed on the device
+  accum = check_grad_accum_steps(params.get('grad_accum_steps'), "params['grad_accum_steps']")
+  if training and accum is not None:
+    if gdist.world_size() > 1:
+      raise ValueError("params['grad_accum_steps'] is single-GPU: with %d ranks the micro-steps that apply nothing should skip the "
+                       "gradient exchange altogether, which has not been built" % gdist.world_size())
+    ema['grad_accum_steps'] = accum
   tables = {}
   if shared:
     # params['shared_frames'] (True, or a capacity F): encode each distinct frame of the batch once
@@ -512,6 +519,7 @@ class Estimator:
     check_clip_norm(self.params.get('clip_norm'), "params['clip_norm']")
     check_skip_nonfinite(self.params.get('skip_nonfinite'), "params['skip_nonfinite']")
     check_variable_stats(self.params.get('variable_stats'), "params['variable_stats']")
+    check_grad_accum_steps(self.params.get('grad_accum_steps'), "params['grad_accum_steps']")
     if self.params.get('loss_shaping') is not None and self.params.get('e2evmc_config') is not None:
       check_loss_shaping(self.params['loss_shaping'], self.params['e2evmc_config'], "params['loss_shaping']")
     check_lr_schedule(self.params.get('lr_schedule'), getattr(self.params.get('e2evmc_config'), 'lr', 0.0), "params['lr_schedule']")
@@ -682,8 +690,12 @@ class Estimator:
     return list(self._store.shapes.keys())
 
   def train(self, input_fn, steps=None, max_steps=None):
+    """``steps`` / ``max_steps`` count optimiser steps, as TensorFlow's count ``global_step``.  Under params['grad_accum_steps'] a batch is a
+    micro-step and every A-th applies an optimiser step: hooks, checkpoints by step and the step count advance on those alone, and
+    ``last_train_stats['micro_steps']`` counts the batches.  A group the input leaves incomplete stays in the accumulator (on the
+    device, not in the checkpoint) and the next ``train()`` of this Estimator completes it."""
     world, rank = gdist.world_size(), gdist.rank()
-    t0, nsteps, step = time.time(), 0, None
+    t0, nsteps, step, micro = time.time(), 0, None, 0
     last_runner = None
     source = input_fn()
     for feats, labels, n, n_global in self._local_batches(source, world, rank):
@@ -699,6 +711,9 @@ class Estimator:
         self._feed_step(fbuf, lbuf, feats, labels)
         spec.train_op()
         last_runner = spec.train_op.__self__
+      micro += 1
+      if last_runner is not None and not last_runner.applied:      # params['grad_accum_steps']: a micro-step that applied no optimiser step
+        continue
       nsteps += 1
       if (spec is not None and spec.training_hooks) or self.config.save_checkpoints_steps:
         step = int(self._store.global_step.item()) if (nsteps == 1 or step is None) else step + 1
@@ -715,7 +730,7 @@ class Estimator:
     if hasattr(source, 'close'):
       source.close()      # an epoch left early must not leave reader threads filling a queue nobody drains
     skipped = 0
-    if nsteps and torch.cuda.is_available():
+    if micro and torch.cuda.is_available():
       torch.cuda.synchronize()
       for sp, _, _ in self._specs.values():      # a device-side error of any model that ran this epoch (input-stage timeout)
         sp.model.check_device_errors()
@@ -727,6 +742,8 @@ class Estimator:
                          '(dp_form=%s); nothing was saved' % (nsteps, rank, getattr(self.config, 'dp_form', None) or 'three_graphs_reserve16'))
     # wall time of the input + step loop alone (the checkpoint written below is not part of the data path)
     self.last_train_stats = {'steps': nsteps, 'loop_seconds': time.time() - t0}
+    if check_grad_accum_steps(self.params.get('grad_accum_steps')) is not None:
+      self.last_train_stats['micro_steps'] = micro
     if check_skip_nonfinite(self.params.get('skip_nonfinite')) is not None:
       self.last_train_stats['skipped_steps'] = skipped
     if nsteps and rank == 0 and self.model_dir:

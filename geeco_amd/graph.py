@@ -84,7 +84,7 @@ class _ModelBase(OptimizerStep):
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
   def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None, lr_schedule=None,
-               skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None):
+               skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None, grad_accum_steps=None):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
     self.loss_shaping = check_loss_shaping(loss_shaping, cfg)      # None: the option is off (DESIGN 5.22)
     self.variable_stats_mode = check_variable_stats(variable_stats) if training else None      # None: the option is off (DESIGN 5.21)
@@ -143,7 +143,7 @@ class _ModelBase(OptimizerStep):
       self.inputs['target_rgb'] = torch.zeros(N, H, W, 3, **f32)
       if self.C == 4:
         self.inputs['target_depth'] = torch.zeros(N, H, W, 1, **f32)
-    self._setup_optimizer(training, lr_multipliers)      # scal, lr_runs / backward_cut, the clip and guard buffers (optimizer.py)
+    self._setup_optimizer(training, lr_multipliers, grad_accum_steps)      # scal, lr_runs / backward_cut, the clip and guard buffers (optimizer.py)
     self._opt_stream = None     # optimizer_stream()
     # GoalE2EVMC's branch and the control block of its one-pass input stage; the gather mode of a model that takes shared_frames
     self.mode = self.dyn_ws2 = self.window_mode = None
@@ -319,7 +319,7 @@ class _ModelBase(OptimizerStep):
   def bottom_handoff(self, sums=None):
     return BesideBottom(self, sums)
 
-  def backward_and_apply(self, early, late):
+  def backward_and_apply(self, early, late, form=None):
     """Backward + optimiser step of a single-GPU training step with the optimiser's HBM-streaming work hidden beside the fused
     encoder-bottom backward (round 6, profiles/HARDWARE_FINDINGS.md 38).  ``early`` / ``late`` = runtime.gradient_buckets(store):
     late = conv1 / conv2 of the encoders, whose gradients the last launch of the backward produces; early = everything else
@@ -333,17 +333,50 @@ class _ModelBase(OptimizerStep):
     8 the HBM has.  Beside it the 35 + 33 us of streaming work take 190 + 155 us and end long before its 455 us are over, which
     stay 455.  Where `*` sits and that the side launches are issued behind the bottom's: BesideBottom.  Element by element the
     arithmetic of backward(adam_prepare=True) + apply_gradients(): bitwise the same parameters, slots and gradients
-    (tests/test_model_gpu.py)."""
+    (tests/test_model_gpu.py).
+    ``form`` (``grad_accum_steps``, DESIGN 5.23: 'first' / 'middle' / 'last'; None = the model without the option): the accumulate launch
+    over each half takes Adam's place, and in the last form Adam follows it there, reading the accumulator; the step counter and lr_t
+    are prepared in the last form alone."""
     g, sums = self.store.grads, []
+    apply = form in (None, 'last')
+    src = g if form is None else self.store.accum      # what the optimiser step reads
+
+    def half(ranges, last):
+      if form is not None:
+        self.accumulate_gradients_of([(g[off:off + n], off, n) for off, n in ranges], overwrite=form == 'first')
+      if apply:
+        self.apply_gradients_of([(src[off:off + n], off, n) for off, n in ranges], last=last)
+
     h = self.bottom_handoff(sums)
     self.backward(part='upper', defer_sums=sums)
-    prepare = self._prepare_args(True)
+    prepare = self._prepare_args(apply)
     h.run_bottom(lambda mark: self.backward(part='bottom', before_bottom=mark))
     with h.side_work():
       ops.slab_reduce_batch(sums, prepare)
-      self.apply_gradients_of([(g[off:off + n], off, n) for off, n in early], last=False)
+      half(early, False)
     h.join()
-    self.apply_gradients_of([(g[off:off + n], off, n) for off, n in late], last=True)
+    half(late, True)
+
+  def backward_accumulate_apply(self, form):
+    """The plain order of a micro-step (``grad_accum_steps``), where there is no bottom to hide streaming work beside (shared frames, a
+    cut backward): the backward, ONE accumulate launch, and in the last form the optimiser step on the accumulator."""
+    self.backward(adam_prepare=form == 'last')
+    self.accumulate_gradients_of([(self.store.grads, 0, self.store.size)], overwrite=form == 'first')
+    if form == 'last':
+      self.apply_gradients()
+
+  def micro_step(self, buckets=None):
+    """One eager micro-step of a model with ``grad_accum_steps`` on the batch in ``inputs``, in the form the store's count asks for;
+    ``buckets`` = (early, late) of runtime.gradient_buckets: the beside-bottom layout, None: the plain one.  Returns True when it
+    applied the optimiser step."""
+    form = self.micro_step_form()
+    self.forward(backward_too=True)
+    if buckets is not None:
+      self.backward_and_apply(buckets[0], buckets[1], form=form)
+    else:
+      self.backward_accumulate_apply(form)
+    self._accumulate_losses(form)
+    return self.micro_step_done(form)
 
   def _refresh_after_update(self):
     s = self.store
@@ -375,8 +408,13 @@ class _ModelBase(OptimizerStep):
     return l
 
   def loss_parts(self):
+    """The loss terms of the last forward; under ``grad_accum_steps`` their mean over the micro-batches of the last optimiser step
+    (zeros before the first one; the regulariser is that of the weights the last micro-batch ran on, the group's)."""
     l = self.decoder.losses
     out = {'loss': self.loss}
+    if self.grad_accum is not None:
+      l = self.store.accum_loss_mean
+      out['loss'] = l[0] + (0.5 * float(self.cfg.l2_regularizer)) * self.scal[1] if self.cfg.l2_regularizer > 0.0 else l[0]
     for i, (_, key, _, _, _) in enumerate(self.decoder.heads):
       out['loss_' + key.replace('logits_', '')] = l[1 + i]
     if self.cfg.l2_regularizer > 0.0:
@@ -384,6 +422,8 @@ class _ModelBase(OptimizerStep):
     return out
 
   def train_step(self):
+    if self.grad_accum is not None:
+      return self.micro_step()
     self.forward(backward_too=True)
     self.backward(adam_prepare=True)
     self.apply_gradients()
@@ -393,12 +433,12 @@ class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None):
+               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None, grad_accum_steps=None):
     """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``, ``lr_schedule``, ``skip_nonfinite``,
-    ``lr_multipliers``, ``variable_stats``, ``loss_shaping``: see E2EVMC."""
+    ``lr_multipliers``, ``variable_stats``, ``loss_shaping``, ``grad_accum_steps``: see E2EVMC."""
     super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
                      clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers,
-                     variable_stats=variable_stats, loss_shaping=loss_shaping)
+                     variable_stats=variable_stats, loss_shaping=loss_shaping, grad_accum_steps=grad_accum_steps)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -424,6 +464,7 @@ class GoalE2EVMC(_ModelBase):
     D = _CELLS * (sum(self.feat_ch) + jn)
     self.decoder = LSTMDecoder(self.store, root + '/LSTMDecoder', cfg, N, T, D, training, one_launch=one_launch_decoder, loss_shaping=self.loss_shaping)
     self._bind_labels()
+    self._keep_accumulator()
     if self.shared_frames is None:      # (the shared-frame step forms no dynamic image)
       self.dyn_ws = ops.dynimg_ws(N, H * W * 4, self.device)
       self.dyn_ws2 = ops.goal_dynimgs_ws(N, H * W, self.device)      # control block of the one-pass input stage (zero-filled once)
@@ -529,7 +570,7 @@ class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
   def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None):
+               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None, grad_accum_steps=None):
     """``ema_decay`` (a float in (0, 1); None / 0 = off): the optimiser step also keeps an exponential moving average of the
     parameters in ``store.ema`` (tf.train.ExponentialMovingAverage with num_updates = global_step); a store passed in
     must have been built with the arena (``build_store(..., ema=True)``).
@@ -551,13 +592,18 @@ class E2EVMC(_ModelBase):
     5.22) -- ``sample_weights``: a weight per sample, the input 'sample_weight' [N] (a label; ones until fed); ``grp_class_weights``: a weight
     per gripper class; ``label_smoothing``; ``huber_delta``: Huber in place of MSE on the named regression heads.  Means run over the samples
     whose weight is not zero; ``loss_parts()`` reports the shaped terms.  Same launches as without it.
+    ``grad_accum_steps`` (an integer A >= 2; None / 1 = off): one optimiser step per A micro-batches -- each micro-step's
+    gradient is stored into / added to ``store.accum`` by one launch, and the A-th runs the optimiser step, every option with it, on the
+    accumulator with grad_scale 1 / A: the mean of the micro-batch gradients.  ``micro_step()`` / ``runtime.TrainStepRunner`` choose the
+    form from ``store.accum_count``; ``loss_parts()`` reports the mean over the micro-batches of the last optimiser step.  Single GPU;
+    the accumulator is not checkpointed.
     ``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
     'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
     super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
                      clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers,
-                     variable_stats=variable_stats, loss_shaping=loss_shaping)
+                     variable_stats=variable_stats, loss_shaping=loss_shaping, grad_accum_steps=grad_accum_steps)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     self.window_mode, self.feat_ch = 'plain', [256]
     # frames are processed time-major ([K][N]) so that step t's features are one dense block
@@ -565,6 +611,7 @@ class E2EVMC(_ModelBase):
     D = _CELLS * (256 + cfg.dim_jnt_state)
     self.decoder = LSTMDecoder(self.store, 'VMC/LSTMDecoder', cfg, N, K, D, training, one_launch=one_launch_decoder, loss_shaping=self.loss_shaping)
     self._bind_labels()
+    self._keep_accumulator()
 
   def _encode(self):
     N, K, H, W = self.N, self.K, self.H, self.W

@@ -875,6 +875,17 @@ def adam_tf_segments_scaled(p, m, v, segments, lr_mul, scal, clip_dev=None, guar
         'geeco_adam_tf_segments_scaled')
 
 
+def grad_accumulate_segments(acc, segments, n, overwrite):
+  """``geeco_grad_accumulate_segments``: the pieces of ``segments`` (as ``adam_tf_segments_clip`` takes them) stored into
+  (``overwrite``: the accumulator is not read) or added to the accumulator arena ``acc`` of ``n`` floats; what no piece covers keeps
+  every bit."""
+  if acc.numel() < n:
+    raise ValueError('grad_accumulate_segments: an accumulator of %d floats for an arena of %d' % (acc.numel(), n))
+  arr = _adam_segments(segments)
+  check(_lib().geeco_grad_accumulate_segments(_p(acc), arr, len(segments), int(n), int(bool(overwrite)), _stream()),
+        'geeco_grad_accumulate_segments')
+
+
 def sumsq_into(out, p, n):
   check(_lib().geeco_sumsq(_p(p), n, _p(out), _stream()), 'geeco_sumsq')
 

@@ -8,13 +8,16 @@ import numpy as np
 import torch
 
 from . import ops
-from .variables import backward_cut, check_lr_multipliers, lr_multiplier_runs, variable_stats_scalars
+from .variables import backward_cut, check_grad_accum_steps, check_lr_multipliers, lr_multiplier_runs, variable_stats_scalars
 
 
 class OptimizerStep:
-  def _setup_optimizer(self, training, lr_multipliers):
+  def _setup_optimizer(self, training, lr_multipliers, grad_accum_steps=None):
     """The optimiser's state on the device, once the store exists."""
     f32 = dict(dtype=torch.float32, device=self.device)
+    # grad_accum_steps (DESIGN 5.23): A micro-batches per optimiser step; the store then carries the accumulator (``_keep_accumulator``,
+    # once the decoder exists).  None: the model without the option.
+    self.grad_accum = check_grad_accum_steps(grad_accum_steps) if training else None
     # lr_multipliers (DESIGN 5.20): the optimiser step is made of ``lr_runs``, the arena's maximal contiguous runs (offset, count,
     # multiplier) of one multiplier each with the frozen ones left out, and the backward stops at ``backward_cut``, the lowest layer
     # with anything to train.  None / 'full': the model without the option.
@@ -89,7 +92,8 @@ class OptimizerStep:
       raise ValueError('%s: %s came in %d pieces; one launch takes at most %d' % (option, what, n, ops._native.ADAM_SEGMENTS_MAX))
 
   def _total_gradient_kw(self):      # the total gradient the update and the norm are formed of: g / world + l2 * p
-    return dict(grad_scale=1.0 / self.world, l2=float(self.cfg.l2_regularizer))
+    # (grad_accum_steps: g is the sum over the A micro-batches, so g / (world A) is the mean of their gradients and l2 * p is added once)
+    return dict(grad_scale=1.0 / (self.world * (self.grad_accum or 1)), l2=float(self.cfg.l2_regularizer))
 
   def _launch_update(self, pieces, g_out, whole=False):
     """One launch of the Adam kernel over ``pieces`` (nothing for a call whose pieces are all frozen), through the entry point the model's
@@ -163,7 +167,52 @@ class OptimizerStep:
     """The whole arena through the same path: the one-piece call (under ``lr_multipliers``: the runs themselves)."""
     del self._clip_calls[:]
     del self._open_pieces[:]
-    self._optimizer_step([(self.store.grads, 0, self.store.size)], None, True, whole=True)
+    self._optimizer_step([(self.gradient_source(), 0, self.store.size)], None, True, whole=True)
+
+  # -- gradient accumulation over micro-batches (DESIGN 5.23) -----------------------------------
+  def _keep_accumulator(self):
+    """Once the decoder exists: the store's accumulator and loss buffers (shared with every model built on the store)."""
+    if self.grad_accum is not None:
+      self.store.keep_accumulator(self.decoder.losses.numel())
+
+  def gradient_source(self):
+    """The arena the optimiser step reads: the gradients of this batch, or under ``grad_accum_steps`` their sum over the group."""
+    return self.store.grads if self.grad_accum is None else self.store.accum
+
+  def micro_step_form(self):
+    """The form of the next micro-step, from the store's count of accumulated micro-batches: 'first' (the accumulator is overwritten),
+    'middle' (added to), 'last' (added to, then the optimiser step on the accumulator); None for a model without the option."""
+    if self.grad_accum is None:
+      return None
+    c = self.store.accum_count
+    return 'first' if c == 0 else 'last' if c == self.grad_accum - 1 else 'middle'
+
+  def micro_step_done(self, form):
+    """Advances the store's count behind a micro-step of ``form``; True when that micro-step applied the optimiser step."""
+    self.store.accum_count = 0 if form == 'last' else self.store.accum_count + 1
+    return form == 'last'
+
+  def accumulate_gradients_of(self, segments, overwrite):
+    """One launch: the pieces of ``segments`` (as apply_gradients_of takes them, under ``lr_multipliers`` cut down to what is trained:
+    a frozen variable is neither read nor accumulated) stored into (``overwrite``) or added to ``store.accum``."""
+    pieces = [q[:3] for q in self._pieces(segments)]
+    if not pieces:
+      return
+    if len(pieces) > ops._native.ADAM_SEGMENTS_MAX:
+      raise ValueError('grad_accum_steps: one call of the accumulate launch came in %d pieces; one launch takes at most %d'
+                       % (len(pieces), ops._native.ADAM_SEGMENTS_MAX))
+    ops.grad_accumulate_segments(self.store.accum, pieces, self.store.size, overwrite)
+
+  def _accumulate_losses(self, form):
+    """The loss terms of this micro-batch into the store's sum, and behind the group's last one their mean: tensor work on the
+    stream (captured with the micro-step), no host read."""
+    s, l = self.store, self.decoder.losses
+    if form == 'first':
+      s.accum_loss_sum.copy_(l)
+    else:
+      s.accum_loss_sum.add_(l)
+    if form == 'last':
+      torch.mul(s.accum_loss_sum, 1.0 / self.grad_accum, out=s.accum_loss_mean)
 
   # -- per-variable statistics (DESIGN 5.21) ---------------------------------------------------
   def variable_stats(self):

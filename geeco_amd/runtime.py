@@ -107,6 +107,12 @@ class TrainStepRunner:
     model.world = self.world
     self.dp = (self.world > 1) if dp is None else bool(dp)
     self.overlap = bool(overlap)
+    # grad_accum_steps: the micro-step has three forms (model.micro_step_form), one captured graph each
+    self.accum = getattr(model, 'grad_accum', None)
+    self.applied = True                  # whether the last call of step() applied an optimiser step (always, without the option)
+    if self.accum is not None and (self.dp or self.world > 1):
+      raise ValueError('grad_accum_steps is single-GPU: under data parallelism the micro-steps that apply nothing should skip the gradient '
+                       'exchange altogether, which reshapes the three-part step')
     if self.dp and getattr(model, 'lr_runs', None) is not None:
       raise ValueError('lr_multipliers is single-GPU: the buckets of the gradient exchange would have to shrink with the backward\'s cut point')
     self.use_graph = bool(use_graph) and torch.cuda.is_available()
@@ -211,7 +217,15 @@ class TrainStepRunner:
         g[off:off + n].copy_(packed)
     self.model.apply_gradients()
 
-  def _whole_step(self):
+  def _whole_step(self, form=None):
+    if form is not None:      # grad_accum_steps: the same step with the accumulate launch where Adam's pieces go (and Adam behind it in the last form)
+      self.model.forward(backward_too=True)
+      if self.beside_bottom:
+        self.model.backward_and_apply(self.early, self.late, form=form)
+      else:
+        self.model.backward_accumulate_apply(form)
+      self.model._accumulate_losses(form)
+      return
     if self.beside_bottom:
       self.model.forward(backward_too=True)
       self.model.backward_and_apply(self.early, self.late)
@@ -332,8 +346,27 @@ class TrainStepRunner:
     while self.use_graph and self._graphs is None:
       self.step()
 
+  def _micro_step(self):
+    """grad_accum_steps: the micro-step in the form the store's count asks for, eagerly until every form has run once and a group
+    begins, then as one captured graph per form -- the forms differ in one kernel argument and in the tail, so they are three captures
+    over the same buffers.  Returns whether the optimiser step was applied."""
+    form = self.model.micro_step_form()
+    if self.use_graph and self._graphs is None and form == 'first' and self._calls >= max(self._warm, self.accum):
+      forms = ('first', 'middle', 'last') if self.accum > 2 else ('first', 'last')
+      self._graphs = dict(zip(forms, capture_graphs([(lambda f=f: self._whole_step(f)) for f in forms])))
+    self._calls += 1
+    if self._graphs is None:
+      self._whole_step(form)
+    else:
+      self._graphs[form]()
+    self.applied = self.model.micro_step_done(form)
+    return self.applied
+
   def step(self):
-    """One optimiser step on the batch currently in ``model.inputs``."""
+    """One optimiser step on the batch currently in ``model.inputs`` (``grad_accum_steps``: one micro-step; ``applied`` and the value
+    returned tell whether it applied the optimiser step)."""
+    if self.accum is not None:
+      return self._micro_step()
     if self.use_graph and self._graphs is None and self._calls >= self._warm:
       # NB capture itself does not execute the step; fall through to replay
       self._capture()

@@ -140,6 +140,16 @@ def check_variable_stats(value, key='variable_stats'):
   raise ValueError("%s=%r: True (scalars per variable) or 'histograms' (scalars and histograms); None or False = off" % (key, value))
 
 
+def check_grad_accum_steps(value, key='grad_accum_steps'):
+  """Gradient accumulation over micro-batches: None or 1 = off (returns None); an integer A >= 2 = one optimiser step
+  per A micro-batches (returns A).  Anything else raises ValueError naming ``key``."""
+  if value is None:
+    return None
+  if isinstance(value, (bool, np.bool_)) or not isinstance(value, numbers.Integral) or value < 1:
+    raise ValueError('%s=%r: the number of micro-batches per optimiser step must be an integer >= 1 (None or 1 = off)' % (key, value))
+  return None if int(value) == 1 else int(value)
+
+
 LOSS_SHAPING_KEYS = ('sample_weights', 'grp_class_weights', 'label_smoothing', 'huber_delta')
 
 
@@ -429,6 +439,20 @@ class VariableStore:
     self.version = 0      # bumped whenever the parameters are (re)written from the host side
     self.primary_stack = None     # the first training ConvEncoderStack built on this store (encoder.py: lazy_refresh)
     self.late_staging = None      # data parallel: the conv1 / conv2 gradients on their way to the exchange (runtime.TrainStepRunner)
+    # grad_accum_steps (keep_accumulator()): the accumulator arena, the micro-batches it holds so far (a HOST count) and
+    # the losses' sum over them / mean over the last complete group.  None / 0 for a store without the option.  On the store because
+    # the model built for a ragged final batch shares them; NOT checkpointed: a restart drops a partly filled group.
+    self.accum = self.accum_loss_sum = self.accum_loss_mean = None
+    self.accum_count = 0
+
+  def keep_accumulator(self, losses):
+    """The option's state, created once by the first training model with ``grad_accum_steps``: ``accum`` (float32, the arena's size
+    and alignment, zeros) and the two loss buffers of ``losses`` floats."""
+    if self.accum is None:
+      f32 = dict(dtype=torch.float32, device=self.device)
+      self.accum = torch.zeros(self.size, **f32)
+      self.accum_loss_sum, self.accum_loss_mean = torch.zeros(losses, **f32), torch.zeros(losses, **f32)
+      self.accum_count = 0
 
   # -- views ------------------------------------------------------------------------------
   def _view(self, arena, name):

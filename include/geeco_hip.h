@@ -31,7 +31,8 @@ extern "C" {
  * geeco_grad_sumsq_segments, geeco_clip_scale, geeco_adam_tf_segments_clip, geeco_gather_windows_scene,
  * geeco_adam_prepare_schedule, geeco_slab_reduce_batch_prepare_schedule, geeco_lr_schedule_eval, geeco_guard_decide,
  * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled, geeco_variable_stats_ws_bytes, geeco_variable_stats,
- * geeco_heads_loss_shaped_fwd_bwd, geeco_lstm_step_heads_shaped_fwd_bwd, geeco_loss_shaping_sizeof */
+ * geeco_heads_loss_shaped_fwd_bwd, geeco_lstm_step_heads_shaped_fwd_bwd, geeco_loss_shaping_sizeof,
+ * geeco_grad_accumulate_segments */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -754,6 +755,16 @@ int64_t geeco_variable_stats_ws_bytes(int64_t nchunks);
 int geeco_variable_stats(const float* p, const float* m, const float* v, const geeco_adam_segment* segs, int nseg, int64_t n,
                          float grad_scale, float eps, const int64_t* var_off, const int64_t* var_cnt, int nvar,
                          const int64_t* table, int64_t nchunks, void* ws, geeco_varstats_record* out, void* stream);
+/* Opt-in gradient accumulation over micro-batches (additive within ABI 7): one streaming launch that stores or adds the
+ * pieces of a micro-batch's gradient into the accumulator arena acc[0, n).  For every piece k and every i < count_k:
+ *   overwrite != 0:  acc[p_off_k + i] = g_k[i]                      (acc is NOT read: an accumulator full of NaN comes out finite)
+ *   overwrite == 0:  acc[p_off_k + i] = acc[p_off_k + i] + g_k[i]   (one float32 addition)
+ * Pieces as geeco_adam_tf_segments_clip takes them: 1..GEECO_ADAM_SEGMENTS_MAX of them, offsets multiples of 4 floats, counts any
+ * number >= 1 (a piece ends in a scalar tail), sources and acc 16-byte aligned.  Floats no piece covers, and those past n, keep every
+ * bit.  The addition has nothing to contract with, so any partition of a range gives bitwise the one-piece result.
+ * GEECO_EINVAL (nothing launched): a null pointer, nseg outside 1..GEECO_ADAM_SEGMENTS_MAX, n < 1, a misaligned offset, source or
+ * accumulator, a count < 1, a piece not inside [0, n), a source that overlaps a range of acc the launch writes. */
+int geeco_grad_accumulate_segments(float* acc, const geeco_adam_segment* segs, int nseg, int64_t n, int overwrite, void* stream);
 /* sum of squares of an arena (for the L2 regularisation loss term); out[0] overwritten. */
 int geeco_sumsq(const float* p, int64_t n, float* out, void* stream);
 

@@ -117,6 +117,12 @@ ARGPARSER.add_argument('--clip_norm', type=float, default=0.0,
                        help='Clip the gradient (L2 term included, as TF clips the gradient of the total loss) by its global norm before '
                             'the optimiser step (tf.clip_by_global_norm), on the device; events.jsonl then carries grad_norm, the norm '
                             'before clipping.  A finite number > 0, e.g. 5.0; 0 = off.  Not part of the model config.')
+ARGPARSER.add_argument('--grad_accum_steps', type=int, default=1,
+                       help='Apply one optimiser step per this many batches: their gradients are summed on the device and the step uses '
+                            'their mean (an effective batch of A x batch_size at the memory of one batch).  Steps, --log_steps and '
+                            'checkpoints count optimiser steps; a group the input leaves incomplete is completed by the next epoch, '
+                            'and dropped by a restart (the accumulator is not checkpointed).  An integer >= 2; 1 = off.  One GPU.  Not '
+                            'part of the model config.')
 ARGPARSER.add_argument('--skip_nonfinite', default=False, action='store_true',
                        help='Skip an optimiser step whose gradient is not finite (a NaN or an infinity anywhere in it, or a norm that '
                             'overflows float32) instead of writing NaN into every weight: weights, Adam moments and averaged weights '
@@ -235,6 +241,8 @@ def estimator_params(args, e2evmc_config):
     params['ema_decay'] = args.ema_decay
   if args.clip_norm:
     params['clip_norm'] = args.clip_norm
+  if args.grad_accum_steps != 1:
+    params['grad_accum_steps'] = args.grad_accum_steps
   if args.lr_schedule:
     params['lr_schedule'] = lr_schedule_of(args)
   if args.skip_nonfinite:
