@@ -11,7 +11,7 @@ from .variables import VariableStore
 def head_table(cfg, loss_shaping=None):
   """(variable name, prediction key, size, kind, loss weight) per head, in variable creation order.
   kind 0 = mean_squared_error, 1 = softmax cross-entropy (graph.py:233-259, 430-500; estimator.py:224-237); 2 = huber_loss for the
-  regression heads ``loss_shaping['huber_delta']`` (``variables.check_loss_shaping``'s result) names."""
+  regression heads ``loss_shaping['huber_delta']`` (``train_options.check_loss_shaping``'s result) names."""
   if cfg.control_mode == 'cartesian':
     lam = float(cfg.lambda_aux)
     heads = [('pred_cmd_ee', 'cmd_ee', 3, 0, 1.0), ('logits_cmd_grp', 'logits_cmd_grp', cfg.num_grp_states, 1, 1.0),
@@ -30,7 +30,7 @@ class LSTMDecoder:
   """T LSTM steps over states [T][N][D] from a zero state, fc1 + heads on the last output."""
 
   def __init__(self, store: VariableStore, scope, cfg, N, T, D, training, one_launch=False, loss_shaping=None):
-    """``loss_shaping`` (``variables.check_loss_shaping``'s result, None = off): the losses and their gradients come from the shaped
+    """``loss_shaping`` (``train_options.check_loss_shaping``'s result, None = off): the losses and their gradients come from the shaped
     entry points; with ``sample_weights`` the model binds ``sample_weight`` [N] beside the targets.
     ``one_launch`` (inference decoders with T > 1 only; the batched predictor engine sets it): forward(False) is the hoisted
     input projection + ONE launch for the T steps, fc1 and the heads (ops.lstm_seq_heads_into).  No per-step gates / c / h history

@@ -31,7 +31,8 @@ from . import graph
 from .device_windows import DeviceWindows
 from .runtime import EvalStepRunner, TrainStepRunner, dp_form_kwargs
 from .tf_checkpoint import EMA_SUFFIX
-from .variables import check_clip_norm, check_ema_decay, check_grad_accum_steps, check_loss_shaping, check_lr_multipliers, check_lr_schedule, check_skip_nonfinite, check_variable_stats, model_variable_shapes
+from .train_options import PARAMS, TrainOptions, check_exclusions
+from .variables import model_variable_shapes
 
 
 class ModeKeys:
@@ -351,79 +352,33 @@ def _model_fn(features, labels, mode, params, goal):
   N = int(rgb.shape[0])
   training = mode == ModeKeys.TRAIN
   ctor = graph.GoalE2EVMC if goal else graph.E2EVMC
+  # the options of params, checked once; what the model of this mode takes of them; what they do not go with (train_options.py)
+  checked = TrainOptions.from_params(params, cfg, model_variable_shapes(cfg, goal))
+  opts = checked.for_mode(mode)
+  shared = params.get('shared_frames')
+  check_exclusions(opts, gdist.world_size(), shared_frames=shared, key=PARAMS)
   # params['ema_decay']: the store carries the shadow arena, the training step keeps it, and every other mode's model
   # is built on the store's shadow view -- its parameters ARE the averaged weights (an inference stack re-derives its weight
   # copies from them on every forward)
-  decay = check_ema_decay(params.get('ema_decay'), "params['ema_decay']")
   store = params.get('_variable_store')
-  if decay is not None:
+  if checked.ema_decay is not None:
     store = store or graph.build_store(cfg, goal, rgb.device, ema=True)
     if not training:
       store = store.shadow_view()
-  ema = dict(ema_decay=decay) if training else {}
-  # params['clip_norm']: the training step clips the gradient by its global norm, on the device
-  clip = check_clip_norm(params.get('clip_norm'), "params['clip_norm']")
-  if training and clip is not None:
-    ema['clip_norm'] = clip
-  # params['skip_nonfinite']: a step whose gradient is not finite updates nothing, decided on the device
-  skip = check_skip_nonfinite(params.get('skip_nonfinite'), "params['skip_nonfinite']")
-  if training and skip is not None:
-    ema['skip_nonfinite'] = skip
-  # params['lr_schedule']: the learning rate follows the device's step counter, from cfg.lr as the base rate
-  if training and check_lr_schedule(params.get('lr_schedule'), cfg.lr, "params['lr_schedule']") is not None:
-    ema['lr_schedule'] = params['lr_schedule']
-  shared = params.get('shared_frames')
-  # params['lr_multipliers']: a learning rate per variable, frozen variables, and a backward that stops above them
-  mults = check_lr_multipliers(params.get('lr_multipliers'), model_variable_shapes(cfg, goal), "params['lr_multipliers']")
-  if training and mults is not None:
-    if gdist.world_size() > 1:
-      raise ValueError("params['lr_multipliers'] is single-GPU: with %d ranks the buckets of the gradient exchange would have to "
-                       "shrink with the backward's cut point, which has not been decided" % gdist.world_size())
-    if shared:
-      raise ValueError("params['lr_multipliers'] with params['shared_frames']: the shared-frame backward has no cut points; drop one "
-                       "of the two options")
-    ema['lr_multipliers'] = params['lr_multipliers']
-  # params['variable_stats']: per-variable gradient, weight and update statistics on logging steps, one pass on the device
-  vstats = check_variable_stats(params.get('variable_stats'), "params['variable_stats']")
-  if training and vstats is not None:
-    if gdist.world_size() > 1:
-      raise ValueError("params['variable_stats'] is single-GPU: with %d ranks where the late bucket's gradient lives after the "
-                       "exchange has not been decided" % gdist.world_size())
-    ema['variable_stats'] = params['variable_stats']
-  # params['loss_shaping']: tf.losses' weights= / label_smoothing= / huber_loss; the reference builds the same loss in
-  # TRAIN and EVAL, so both modes' models take it (PREDICT forms no loss)
-  shaping = check_loss_shaping(params.get('loss_shaping'), cfg, "params['loss_shaping']")
-  if mode != ModeKeys.PREDICT and shaping is not None:
-    weighted = [k for k in ('sample_weights', 'grp_class_weights') if shaping[k]]
-    if weighted and gdist.world_size() > 1:
-      raise ValueError("params['loss_shaping'][%s] is single-GPU: with %d ranks the global count of non-zero weights is not the sum the "
-                       "loss_scale arithmetic assumes, and the exchange has not been decided"
-                       % ('], ['.join(repr(k) for k in weighted), gdist.world_size()))
-    ema['loss_shaping'] = params['loss_shaping']
-  # params['grad_accum_steps']: one optimiser step per A batches, their gradients summed on the device
-  accum = check_grad_accum_steps(params.get('grad_accum_steps'), "params['grad_accum_steps']")
-  if training and accum is not None:
-    if gdist.world_size() > 1:
-      raise ValueError("params['grad_accum_steps'] is single-GPU: with %d ranks the micro-steps that apply nothing should skip the "
-                       "gradient exchange altogether, which has not been built" % gdist.world_size())
-    ema['grad_accum_steps'] = accum
   tables = {}
   if shared:
     # params['shared_frames'] (True, or a capacity F): encode each distinct frame of the batch once
-    if gdist.world_size() > 1:
-      raise ValueError("params['shared_frames'] is single-GPU: with %d ranks the gradient exchange of the shared-frame step "
-                       "has not been decided" % gdist.world_size())
     if getattr(rgb, 'shared', None) is None:
       raise ValueError("params['shared_frames'] needs the windows as DeviceWindows (pickplace_input_fn(device='cuda')): "
                        "dense 'rgb' tensors hold every frame K times and no frame addresses")
     F = shared_frames_capacity(shared, N, cfg.window_size, goal)
-    model = ctor(cfg, N, rgb.device, training=training, store=store, shared_frames=F, **ema)
+    model = ctor(cfg, N, rgb.device, training=training, store=store, shared_frames=F, options=opts)
     tables = rgb.frame_table(F, with_targets=goal)
     model.frames_u8 = rgb.u8
     for k, v in tables.items():
       model.inputs[k] = v
   else:
-    model = ctor(cfg, N, rgb.device, training=training, store=store, **ema)
+    model = ctor(cfg, N, rgb.device, training=training, store=store, options=opts)
   # adopt the caller's static buffers as the model inputs (placeholders)
   source = lambda k: labels.get(k) if (labels is not None and k in model.label_keys) else features.get(k)
   # all of the model's image inputs that CAN come as window addresses must, or none does
@@ -515,16 +470,9 @@ class Estimator:
     self.model_dir = model_dir
     self.config = config or RunConfig()
     self.params = dict(params or {})
-    check_ema_decay(self.params.get('ema_decay'), "params['ema_decay']")
-    check_clip_norm(self.params.get('clip_norm'), "params['clip_norm']")
-    check_skip_nonfinite(self.params.get('skip_nonfinite'), "params['skip_nonfinite']")
-    check_variable_stats(self.params.get('variable_stats'), "params['variable_stats']")
-    check_grad_accum_steps(self.params.get('grad_accum_steps'), "params['grad_accum_steps']")
-    if self.params.get('loss_shaping') is not None and self.params.get('e2evmc_config') is not None:
-      check_loss_shaping(self.params['loss_shaping'], self.params['e2evmc_config'], "params['loss_shaping']")
-    check_lr_schedule(self.params.get('lr_schedule'), getattr(self.params.get('e2evmc_config'), 'lr', 0.0), "params['lr_schedule']")
-    if self.params.get('lr_multipliers') is not None and not isinstance(self.params['lr_multipliers'], collections.abc.Mapping):
-      raise ValueError("params['lr_multipliers']=%r: must be None or a mapping {regular expression: multiplier}" % (self.params['lr_multipliers'],))
+    # the options are checked here, as far as they can be before the model is known, so that a bad value raises at construction;
+    # train() reads this record: ``params`` is final once the Estimator is built
+    self.options = TrainOptions.from_params(self.params, self.params.get('e2evmc_config'), None)
     if warm_start_from is None:
       warm_start_from = self.params.get('warm_start_from')
     self.warm_start_from = check_warm_start(warm_start_from, "params['warm_start_from']" if 'warm_start_from' in self.params else 'warm_start_from')
@@ -742,9 +690,9 @@ class Estimator:
                          '(dp_form=%s); nothing was saved' % (nsteps, rank, getattr(self.config, 'dp_form', None) or 'three_graphs_reserve16'))
     # wall time of the input + step loop alone (the checkpoint written below is not part of the data path)
     self.last_train_stats = {'steps': nsteps, 'loop_seconds': time.time() - t0}
-    if check_grad_accum_steps(self.params.get('grad_accum_steps')) is not None:
+    if self.options.grad_accum is not None:
       self.last_train_stats['micro_steps'] = micro
-    if check_skip_nonfinite(self.params.get('skip_nonfinite')) is not None:
+    if self.options.skip_limit is not None:
       self.last_train_stats['skipped_steps'] = skipped
     if nsteps and rank == 0 and self.model_dir:
       path = save_checkpoint(self._store, self.model_dir, self.config.keep_checkpoint_max, self.config.save_tf_bundle,

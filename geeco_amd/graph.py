@@ -29,8 +29,8 @@ from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .optimizer import OptimizerStep
 from .step_models import E2EVMCStep, GoalE2EVMCStep  # noqa: F401
-from .variables import (_CELLS, VariableStore, check_clip_norm, check_ema_decay, check_loss_shaping, check_lr_schedule, check_skip_nonfinite, check_variable_stats,
-                        model_variable_shapes)
+from .train_options import TrainOptions
+from .variables import _CELLS, VariableStore, model_variable_shapes
 
 
 def build_store(cfg, goal, device, ema=False):
@@ -83,29 +83,27 @@ class BesideBottom:
 class _ModelBase(OptimizerStep):
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
 
-  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, ema_decay=None, clip_norm=None, lr_schedule=None,
-               skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None, grad_accum_steps=None):
+  def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, options=None, **raw):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
-    self.loss_shaping = check_loss_shaping(loss_shaping, cfg)      # None: the option is off (DESIGN 5.22)
-    self.variable_stats_mode = check_variable_stats(variable_stats) if training else None      # None: the option is off (DESIGN 5.21)
-    self.ema_decay = check_ema_decay(ema_decay)
-    self.clip_norm = check_clip_norm(clip_norm)
-    self.skip_limit = check_skip_nonfinite(skip_nonfinite)      # consecutive skipped steps the caller tolerates (None: option off)
-    # lr_schedule (DESIGN 5.18): the normalised schedule, and the struct the prepare work is handed in place of cfg.lr
-    # (_prepare_args, _prepare_unless_done); the device then leaves lr(s) of the step in scal[2].  None: cfg.lr, as ever.
-    self.lr_schedule = check_lr_schedule(lr_schedule, cfg.lr)
-    self._lr_arg = float(cfg.lr) if self.lr_schedule is None else ops.lr_schedule_struct(self.lr_schedule)
+    # the options: ``raw``, checked here once (train_options.py), or ``options``, a record checked already (for THIS config and these
+    # variables: it is taken as it is).  The attributes the step reads are set from the record in _setup_optimizer
+    if options is not None and raw:
+      raise TypeError('options= is a checked record; it does not go with %s' % ', '.join(sorted(raw)))
+    if options is None:
+      names = store.shapes if store is not None else model_variable_shapes(cfg, goal)
+      options = TrainOptions.from_raw(raw, cfg, names, training=training)
+    self.options = options if training else options._replace(lr_multipliers=None, variable_stats_mode=None, grad_accum=None)
     self.shared_frames = self._check_shared_frames(cfg, goal, shared_frames)
     self.device = torch.device(device)
     self.K = cfg.window_size
     self.H, self.W, self.C = cfg.img_height, cfg.img_width, cfg.img_channels
     check_image_size(self.H, self.W)
-    self.store = store or build_store(cfg, goal, self.device, ema=self.ema_decay is not None)
-    if training and (self.ema_decay is None) != (self.store.ema is None):
+    self.store = store or build_store(cfg, goal, self.device, ema=self.options.ema_decay is not None)
+    if training and (self.options.ema_decay is None) != (self.store.ema is None):
       # the store decides which optimiser entry point runs (apply_gradients / apply_gradients_of): one that keeps averaged weights needs the
       # decay, and a decay without the arena would silently average nothing
       raise ValueError('ema_decay=%r, but the VariableStore %s (VariableStore(ema=True) goes with a decay in (0, 1))'
-                       % (ema_decay, 'keeps no averaged weights' if self.store.ema is None else 'keeps averaged weights'))
+                       % (raw.get('ema_decay', self.options.ema_decay), 'keeps no averaged weights' if self.store.ema is None else 'keeps averaged weights'))
     f32 = dict(dtype=torch.float32, device=self.device)
     N, K, H, W = self.N, self.K, self.H, self.W
     F = self.shared_frames
@@ -134,7 +132,7 @@ class _ModelBase(OptimizerStep):
       self.inputs['grp_target'] = torch.zeros(N, cfg.dim_grp_command, **f32)
     else:
       raise ValueError("Unknown control mode '%s'" % (cfg.control_mode,))
-    if self.loss_shaping is not None and self.loss_shaping['sample_weights']:      # tf.losses' weights=, one per sample
+    if self.options.loss_shaping is not None and self.options.loss_shaping['sample_weights']:      # tf.losses' weights=, one per sample
       self.label_keys.append('sample_weight')
       self.inputs['sample_weight'] = torch.ones(N, **f32)
     if self.C == 4:
@@ -143,7 +141,7 @@ class _ModelBase(OptimizerStep):
       self.inputs['target_rgb'] = torch.zeros(N, H, W, 3, **f32)
       if self.C == 4:
         self.inputs['target_depth'] = torch.zeros(N, H, W, 1, **f32)
-    self._setup_optimizer(training, lr_multipliers, grad_accum_steps)      # scal, lr_runs / backward_cut, the clip and guard buffers (optimizer.py)
+    self._setup_optimizer(training)      # the options' attributes, scal, lr_runs / backward_cut, the clip and guard buffers (optimizer.py)
     self._opt_stream = None     # optimizer_stream()
     # GoalE2EVMC's branch and the control block of its one-pass input stage; the gather mode of a model that takes shared_frames
     self.mode = self.dyn_ws2 = self.window_mode = None
@@ -432,13 +430,9 @@ class _ModelBase(OptimizerStep):
 class GoalE2EVMC(_ModelBase):
   """``goal_e2evmc`` (graph.py:321-416), every proc_obs x proc_tgt branch (scope 'GoalVMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None, grad_accum_steps=None):
-    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only), ``ema_decay``, ``clip_norm``, ``lr_schedule``, ``skip_nonfinite``,
-    ``lr_multipliers``, ``variable_stats``, ``loss_shaping``, ``grad_accum_steps``: see E2EVMC."""
-    super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers,
-                     variable_stats=variable_stats, loss_shaping=loss_shaping, grad_accum_steps=grad_accum_steps)
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, **options):
+    """``shared_frames=F`` ('sequence' x 'constant' / 'residual' only) and ``**options``: see E2EVMC."""
+    super().__init__(cfg, N, device, goal=True, training=training, store=store, shared_frames=shared_frames, **options)
     if cfg.proc_tgt not in ('constant', 'residual', 'dyndiff'):
       raise ValueError("Unknown processing mode for target image: %s!" % (cfg.proc_tgt,))
     if cfg.proc_obs not in ('sequence', 'dynimg'):
@@ -569,41 +563,14 @@ class GoalE2EVMC(_ModelBase):
 class E2EVMC(_ModelBase):
   """``e2e_vmc`` (graph.py:268-319): per-frame encoder, K LSTM steps (scope 'VMC')."""
 
-  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, ema_decay=None, clip_norm=None,
-               lr_schedule=None, skip_nonfinite=None, lr_multipliers=None, variable_stats=None, loss_shaping=None, grad_accum_steps=None):
-    """``ema_decay`` (a float in (0, 1); None / 0 = off): the optimiser step also keeps an exponential moving average of the
-    parameters in ``store.ema`` (tf.train.ExponentialMovingAverage with num_updates = global_step); a store passed in
-    must have been built with the arena (``build_store(..., ema=True)``).
-    ``clip_norm`` (a finite number > 0; None / 0 = off): the optimiser step clips the total gradient g / world + l2 * p by its global norm
-    first (tf.clip_by_global_norm), on the device; ``clip_out`` then holds [scale, norm before clipping] of the last step.
-    ``lr_schedule`` (``variables.check_lr_schedule``; None, or 'constant' without warm-up = off): the learning rate of every step is the
-    schedule's value at the device's step counter, with ``cfg.lr`` as its base rate, evaluated by the thread that forms Adam's lr_t
-    (DESIGN 5.18): a captured step follows it and a restored counter continues it; ``scal[2]`` then holds the rate of the last step.
-    ``skip_nonfinite`` (True, or the tolerated number of consecutive skipped steps, an integer >= 1; None / False = off): an optimiser
-    step whose gradient has a non-finite global norm leaves p, m, v and the shadow arena as they are -- the step counter still
-    advances; ``guard`` then holds [last verdict, skipped steps in all, in a row] and ``clip_out`` [scale, norm].
-    ``lr_multipliers`` (``variables.check_lr_multipliers``: an ordered mapping {regular expression: multiplier}, first match wins, 0 =
-    frozen; None, empty or all ones = off): every variable is updated with lr * its multiplier inside the one Adam pass, a frozen
-    variable's p, m, v and averaged weight keep every bit, and the backward stops at the lowest layer with anything to train
-    (``backward_cut``).  Single GPU, not with ``shared_frames``.
-    ``variable_stats`` (True, or 'histograms'; None / False = off): ``variable_stats()`` reports, per variable, the norms and counts of
-    the last step's gradient, weights and update from one statistics pass on the device.  The step itself is unchanged.
-    ``loss_shaping`` (``variables.check_loss_shaping``; None or all-neutral = off): the losses take tf.losses' optional arguments (DESIGN
-    5.22) -- ``sample_weights``: a weight per sample, the input 'sample_weight' [N] (a label; ones until fed); ``grp_class_weights``: a weight
-    per gripper class; ``label_smoothing``; ``huber_delta``: Huber in place of MSE on the named regression heads.  Means run over the samples
-    whose weight is not zero; ``loss_parts()`` reports the shaped terms.  Same launches as without it.
-    ``grad_accum_steps`` (an integer A >= 2; None / 1 = off): one optimiser step per A micro-batches -- each micro-step's
-    gradient is stored into / added to ``store.accum`` by one launch, and the A-th runs the optimiser step, every option with it, on the
-    accumulator with grad_scale 1 / A: the mean of the micro-batch gradients.  ``micro_step()`` / ``runtime.TrainStepRunner`` choose the
-    form from ``store.accum_count``; ``loss_parts()`` reports the mean over the micro-batches of the last optimiser step.  Single GPU;
-    the accumulator is not checkpointed.
+  def __init__(self, cfg, N, device, training=True, store=None, one_launch_decoder=False, shared_frames=None, **options):
+    """``**options``: the training options by their public names (``train_options.TrainOptions`` documents them and
+    ``train_options.EXCLUSIONS`` what they do not go with), or ``options=`` a record checked already.
     ``shared_frames=F``: the inputs are 'frame_table' [F] (int64 addresses of resident RGB frames, 0 = unused slot) and
     'frame_index' [N][K] (int32, window position -> slot) in place of 'rgb' (device_windows.DeviceWindows.frame_table); the encoder
     runs on the F slots once, forward and backward, instead of on all K * N window positions.  Same variables, same loss and
     gradients up to summation order."""
-    super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, ema_decay=ema_decay,
-                     clip_norm=clip_norm, lr_schedule=lr_schedule, skip_nonfinite=skip_nonfinite, lr_multipliers=lr_multipliers,
-                     variable_stats=variable_stats, loss_shaping=loss_shaping, grad_accum_steps=grad_accum_steps)
+    super().__init__(cfg, N, device, goal=False, training=training, store=store, shared_frames=shared_frames, **options)
     N, K, H, W, C = self.N, self.K, self.H, self.W, self.C
     self.window_mode, self.feat_ch = 'plain', [256]
     # frames are processed time-major ([K][N]) so that step t's features are one dense block

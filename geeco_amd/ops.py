@@ -733,7 +733,7 @@ def adam_prepare(global_step, lr, scal, beta1=0.9, beta2=0.999):
 
 
 def lr_schedule_struct(schedule):
-  """``geeco_lr_schedule`` of a normalised schedule (the dictionary ``variables.check_lr_schedule`` returns); a struct is passed
+  """``geeco_lr_schedule`` of a normalised schedule (the dictionary ``train_options.check_lr_schedule`` returns); a struct is passed
   through.  Rates and values are rounded to float32 here: the struct is what the device evaluates."""
   if isinstance(schedule, _native.LrSchedule):
     return schedule

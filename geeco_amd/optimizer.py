@@ -1,31 +1,36 @@
 """The optimiser step of the training models (estimator.py:243-244), ONE path behind every option: ``OptimizerStep`` is the part of
 ``graph._ModelBase`` that owns the optimiser's device scalars and runs Adam over the arena or pieces of it -- plain, with averaged weights
 (DESIGN 5.15), behind the global norm of the gradient (5.16, 5.19), under a schedule (5.18), with per-scope multipliers (5.20).  The host
-class provides ``cfg``, ``store``, ``device``, the checked options and ``_refresh_after_update()``."""
+class provides ``cfg``, ``store``, ``device``, ``shared_frames``, the checked options (``options``) and ``_refresh_after_update()``."""
 from __future__ import annotations
 
 import numpy as np
 import torch
 
 from . import ops
-from .variables import backward_cut, check_grad_accum_steps, check_lr_multipliers, lr_multiplier_runs, variable_stats_scalars
+from .train_options import check_exclusions
+from .variables import backward_cut, lr_multiplier_runs, variable_stats_scalars
 
 
 class OptimizerStep:
-  def _setup_optimizer(self, training, lr_multipliers, grad_accum_steps=None):
-    """The optimiser's state on the device, once the store exists."""
+  def _setup_optimizer(self, training):
+    """The options' attributes, from the record ``self.options`` (train_options.TrainOptions; None = the option is off), and the
+    optimiser's state on the device, once the store exists."""
     f32 = dict(dtype=torch.float32, device=self.device)
-    # grad_accum_steps: A micro-batches per optimiser step; the store then carries the accumulator (``_keep_accumulator``,
-    # once the decoder exists).  None: the model without the option.
-    self.grad_accum = check_grad_accum_steps(grad_accum_steps) if training else None
+    o = self.options
+    check_exclusions(o, shared_frames=self.shared_frames is not None)
+    # skip_limit: the consecutive skipped steps the caller tolerates.  grad_accum (5.23): A micro-batches per optimiser
+    # step; the store then carries the accumulator (``_keep_accumulator``, once the decoder exists)
+    self.ema_decay, self.clip_norm, self.skip_limit, self.lr_schedule = o.ema_decay, o.clip_norm, o.skip_limit, o.lr_schedule
+    self.lr_multipliers, self.variable_stats_mode, self.loss_shaping, self.grad_accum = o.lr_multipliers, o.variable_stats_mode, o.loss_shaping, o.grad_accum
+    # lr_schedule: the normalised schedule, and the struct the prepare work is handed in place of cfg.lr
+    # (_prepare_args, _prepare_unless_done); the device then leaves lr(s) of the step in scal[2].  None: cfg.lr, as ever.
+    self._lr_arg = float(self.cfg.lr) if self.lr_schedule is None else ops.lr_schedule_struct(self.lr_schedule)
     # lr_multipliers: the optimiser step is made of ``lr_runs``, the arena's maximal contiguous runs (offset, count,
     # multiplier) of one multiplier each with the frozen ones left out, and the backward stops at ``backward_cut``, the lowest layer
     # with anything to train.  None / 'full': the model without the option.
-    self.lr_multipliers = check_lr_multipliers(lr_multipliers, self.store.shapes) if training else None
     self.lr_runs, self.backward_cut = None, 'full'
     if self.lr_multipliers is not None:
-      if self.shared_frames is not None:
-        raise ValueError('lr_multipliers with shared_frames: the shared-frame backward has no cut points; drop one of the two options')
       self.lr_runs = lr_multiplier_runs(self.store.offsets, self.store.size, self.lr_multipliers)
       if not self.lr_runs:
         raise ValueError('lr_multipliers freezes every variable: there is nothing to train')
@@ -51,7 +56,7 @@ class OptimizerStep:
     # the gradient of the step that ran last lives: the pieces (gradient source, offset, count) its optimiser step was handed.  A
     # replayed step runs no python, but its pieces are the ones recorded at capture.  A model without the option has none of it.
     self.stats_plan, self.step_pieces, self._open_pieces = None, None, []
-    if getattr(self, 'variable_stats_mode', None) is not None and training:
+    if self.variable_stats_mode is not None:
       s = self.store
       self.stats_plan = ops.VariableStatsPlan([(s.offsets[n], int(np.prod(s.shapes[n]))) for n in s.shapes], self.device)
 

@@ -25,6 +25,7 @@ import threading
 import torch
 
 from . import dist as gdist
+from .train_options import check_exclusions
 
 # hipGraph capture in the default ("global") mode is invalidated by a hipMalloc / synchronous copy issued by ANOTHER
 # thread during the capture window (the input prefetcher uploads episodes in a background thread): both sides take
@@ -110,11 +111,8 @@ class TrainStepRunner:
     # grad_accum_steps: the micro-step has three forms (model.micro_step_form), one captured graph each
     self.accum = getattr(model, 'grad_accum', None)
     self.applied = True                  # whether the last call of step() applied an optimiser step (always, without the option)
-    if self.accum is not None and (self.dp or self.world > 1):
-      raise ValueError('grad_accum_steps is single-GPU: under data parallelism the micro-steps that apply nothing should skip the gradient '
-                       'exchange altogether, which reshapes the three-part step')
-    if self.dp and getattr(model, 'lr_runs', None) is not None:
-      raise ValueError('lr_multipliers is single-GPU: the buckets of the gradient exchange would have to shrink with the backward\'s cut point')
+    if getattr(model, 'options', None) is not None:      # what the data-parallel step does not run (train_options.EXCLUSIONS)
+      check_exclusions(model.options, self.world, self.dp, getattr(model, 'shared_frames', None) is not None)
     self.use_graph = bool(use_graph) and torch.cuda.is_available()
     self._graphs = None
     self._warm = warmup

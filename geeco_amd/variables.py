@@ -7,17 +7,22 @@ optimiser is a single fused pass and data-parallel training all-reduces a single
 sibling is opt-in: ``ema``, the exponential moving average of the parameters the same pass keeps.
 Each variable starts on a 16-byte boundary (float4 loads in the conv kernels); the few pad floats
 are zero and stay zero under Adam (g = 0).
+
+The training options are checked in train_options.py; its names are re-imported here, where they used to live.  What an option needs
+of the arena stays here: ``lr_multiplier_runs``, ``backward_cut``, ``variable_stats_scalars``, ``ema_decay_at``.
 """
 from __future__ import annotations
 
 import collections
-import collections.abc
 import math
-import numbers
 import re
 
 import numpy as np
 import torch
+
+from .train_options import (LOSS_SHAPING_KEYS, LR_BOUNDARIES_MAX, LR_KINDS, SKIP_NONFINITE_DEFAULT_LIMIT, _LR_FIELDS,  # noqa: F401
+                            check_clip_norm, check_ema_decay, check_grad_accum_steps, check_loss_shaping, check_lr_multipliers,
+                            check_lr_schedule, check_skip_nonfinite, check_variable_stats, regression_prediction_keys)
 
 ENC_FILTERS = (32, 48, 64, 128, 192, 256, 256)      # conv1..conv7 (graph.py:76-110); conv8 = dim_out
 ENC_STRIDES = (1, 2, 2, 2, 2, 2, 2, 2)
@@ -89,139 +94,6 @@ def model_variable_shapes(cfg, goal: bool):
   return s
 
 
-def check_ema_decay(value, key='ema_decay'):
-  """The decay of the shadow weights: None or 0 = off (returns None), else a float in (0, 1); anything else raises ValueError
-  naming ``key``."""
-  if value is None or (isinstance(value, numbers.Real) and value == 0):
-    return None
-  if isinstance(value, bool) or not isinstance(value, numbers.Real) or not 0.0 < float(value) < 1.0:
-    raise ValueError('%s=%r: the decay of the averaged weights must lie in (0, 1) (None or 0 = off)' % (key, value))
-  return float(value)
-
-
-def check_clip_norm(value, key='clip_norm'):
-  """The global norm the gradient is clipped to: None or 0 = off (returns None), else a finite number > 0 that float32 holds;
-  anything else raises ValueError naming ``key``."""
-  if value is None or (isinstance(value, numbers.Real) and not isinstance(value, bool) and value == 0):
-    return None
-  f32 = np.finfo(np.float32)
-  if isinstance(value, bool) or not isinstance(value, numbers.Real) or not float(f32.tiny) <= float(value) <= float(f32.max):
-    raise ValueError('%s=%r: the norm to clip the gradient to must be a finite number > 0, a normal float32 (None or 0 = off)' % (key, value))
-  return float(value)
-
-
-SKIP_NONFINITE_DEFAULT_LIMIT = 100
-
-
-def check_skip_nonfinite(value, key='skip_nonfinite'):
-  """Skipping of optimiser steps whose gradient is not finite: None or False = off (returns None); True = on with the
-  default limit of 100 consecutive skipped steps; an integer L >= 1 = on with limit L.  Returns the limit; anything else raises
-  ValueError naming ``key``."""
-  if value is None or value is False:
-    return None
-  if value is True:
-    return SKIP_NONFINITE_DEFAULT_LIMIT
-  if isinstance(value, numbers.Integral) and value >= 1:
-    return int(value)
-  raise ValueError('%s=%r: True, or the number of consecutive skipped steps after which training stops, an integer >= 1 '
-                   '(None or False = off)' % (key, value))
-
-
-def check_variable_stats(value, key='variable_stats'):
-  """Per-variable statistics on logging steps: None or False = off (returns None); True = the scalars (returns
-  'scalars'); 'histograms' = the scalars and the magnitude histograms (returns 'histograms').  Anything else raises ValueError naming
-  ``key``."""
-  if value is None or value is False:
-    return None
-  if value is True:
-    return 'scalars'
-  if isinstance(value, str) and value == 'histograms':
-    return 'histograms'
-  raise ValueError("%s=%r: True (scalars per variable) or 'histograms' (scalars and histograms); None or False = off" % (key, value))
-
-
-def check_grad_accum_steps(value, key='grad_accum_steps'):
-  """Gradient accumulation over micro-batches: None or 1 = off (returns None); an integer A >= 2 = one optimiser step
-  per A micro-batches (returns A).  Anything else raises ValueError naming ``key``."""
-  if value is None:
-    return None
-  if isinstance(value, (bool, np.bool_)) or not isinstance(value, numbers.Integral) or value < 1:
-    raise ValueError('%s=%r: the number of micro-batches per optimiser step must be an integer >= 1 (None or 1 = off)' % (key, value))
-  return None if int(value) == 1 else int(value)
-
-
-LOSS_SHAPING_KEYS = ('sample_weights', 'grp_class_weights', 'label_smoothing', 'huber_delta')
-
-
-def regression_prediction_keys(cfg):
-  """Prediction keys of the regression heads (decoder.head_table's, in its order): the heads ``huber_delta`` may name."""
-  if cfg.control_mode == 'cartesian':
-    return ('cmd_ee', 'pos_ee', 'pos_obj')
-  if cfg.control_mode == 'velocity':
-    return ('cmd_vel', 'cmd_ee', 'cmd_grp', 'pos_ee', 'pos_obj')
-  raise ValueError("Unknown control mode '%s'" % (cfg.control_mode,))
-
-
-def check_loss_shaping(value, cfg, key='loss_shaping'):
-  """Loss shaping (tf.losses' ``weights=``, ``label_smoothing=`` and ``tf.losses.huber_loss(delta=)``): None = off, or a dict
-  with any of ``sample_weights`` (bool: the loss reads a weight per sample, labels['sample_weight']), ``grp_class_weights`` (one finite
-  weight >= 0 per gripper class, ``cfg.num_grp_states`` of them; cartesian mode only), ``label_smoothing`` (a float in [0, 1); cartesian
-  mode only) and ``huber_delta`` (a finite float > 0 for every regression head, or {prediction key: delta}).  Returns None when every entry
-  is neutral, else dict(sample_weights=bool, grp_class_weights=tuple or None, label_smoothing=float, huber_delta={prediction key: delta});
-  anything else raises ValueError naming ``key``."""
-  if value is None:
-    return None
-  if not isinstance(value, collections.abc.Mapping):
-    raise ValueError('%s=%r: None or a dict with the keys %s' % (key, value, ', '.join(LOSS_SHAPING_KEYS)))
-  unknown = sorted(set(value) - set(LOSS_SHAPING_KEYS), key=str)
-  if unknown:
-    raise ValueError('%s: unknown key(s) %s (known: %s)' % (key, ', '.join(repr(k) for k in unknown), ', '.join(LOSS_SHAPING_KEYS)))
-  real = lambda v: isinstance(v, numbers.Real) and not isinstance(v, bool) and math.isfinite(float(v))
-  f32max = float(np.finfo(np.float32).max)
-  cartesian = cfg.control_mode == 'cartesian'
-  sw = value.get('sample_weights')
-  if sw is not None and not isinstance(sw, bool):
-    raise ValueError("%s['sample_weights']=%r: True or False" % (key, sw))
-  cw = value.get('grp_class_weights')
-  if cw is not None:
-    if not cartesian:
-      raise ValueError("%s['grp_class_weights']: control_mode=%r has no gripper classes (cartesian mode only)" % (key, cfg.control_mode))
-    if isinstance(cw, (str, bytes)) or not isinstance(cw, (collections.abc.Sequence, np.ndarray)) or len(cw) != cfg.num_grp_states or \
-        not all(real(v) and 0.0 <= float(v) <= f32max for v in cw):
-      raise ValueError("%s['grp_class_weights']=%r: %d finite weights >= 0, one per gripper class" % (key, cw, cfg.num_grp_states))
-    cw = tuple(float(v) for v in cw)
-    if all(v == 1.0 for v in cw):
-      cw = None
-  eps = value.get('label_smoothing')
-  if eps is None:
-    eps = 0.0
-  if not real(eps) or not 0.0 <= float(eps) < 1.0:
-    raise ValueError("%s['label_smoothing']=%r: a float in [0, 1)" % (key, eps))
-  if float(eps) != 0.0 and not cartesian:
-    raise ValueError("%s['label_smoothing']: control_mode=%r has no cross-entropy head (cartesian mode only)" % (key, cfg.control_mode))
-  heads = regression_prediction_keys(cfg)
-  hd = value.get('huber_delta')
-  ok = lambda v: real(v) and 0.0 < float(v) <= f32max
-  if hd is None:
-    hd = {}
-  elif isinstance(hd, collections.abc.Mapping):
-    bad = sorted(set(hd) - set(heads), key=str)
-    if bad:
-      raise ValueError("%s['huber_delta']: %s is no regression head of control_mode=%r (heads: %s)"
-                       % (key, ', '.join(repr(k) for k in bad), cfg.control_mode, ', '.join(heads)))
-    for k, v in hd.items():
-      if not ok(v):
-        raise ValueError("%s['huber_delta'][%r]=%r: a finite float > 0" % (key, k, v))
-    hd = {k: float(hd[k]) for k in heads if k in hd}
-  elif ok(hd):
-    hd = {k: float(hd) for k in heads}
-  else:
-    raise ValueError("%s['huber_delta']=%r: a finite float > 0, or {prediction key: delta}" % (key, hd))
-  if not sw and cw is None and float(eps) == 0.0 and not hd:
-    return None
-  return dict(sample_weights=bool(sw), grp_class_weights=cw, label_smoothing=float(eps), huber_delta=hd)
-
-
 def variable_stats_scalars(rec, count, lr_t, multiplier=1.0, applied=True, histograms=False):
   """One variable's record of ``geeco_variable_stats`` (a numpy scalar of ``ops.VARSTATS_DTYPE``, or any mapping with its fields) of ``count`` elements as the
   dictionary ``model.variable_stats()`` reports.  Square roots and ratios are formed here, in float64, from the device's sums.
@@ -258,36 +130,6 @@ def variable_stats_scalars(rec, count, lr_t, multiplier=1.0, applied=True, histo
   return out
 
 
-def check_lr_multipliers(value, names, key='lr_multipliers'):
-  """Per-variable learning-rate multipliers.  ``value``: None or an empty mapping = off (returns None); else an ordered
-  mapping {regular expression: multiplier}.  A variable of ``names`` takes the multiplier of the FIRST expression that ``re.search``
-  finds in its name, 1 if none does; a multiplier is a finite number >= 0 that float32 holds, 0 = the variable is frozen.  Returns
-  {name: float} in the order of ``names``, or None when every variable ends up at exactly 1 (that model is the model without the
-  option).  An expression that matches no variable, or anything else, raises ValueError naming ``key``."""
-  if value is None or (isinstance(value, collections.abc.Mapping) and not value):
-    return None
-  if not isinstance(value, collections.abc.Mapping):
-    raise ValueError('%s=%r: must be None or a mapping {regular expression: multiplier}' % (key, value))
-  names = list(names)
-  patterns = []
-  for pat, mul in value.items():
-    if not isinstance(pat, str):
-      raise ValueError('%s: the pattern %r is not a string' % (key, pat))
-    try:
-      rx = re.compile(pat)
-    except re.error as e:
-      raise ValueError('%s: the pattern %r is not a regular expression: %s' % (key, pat, e))
-    if isinstance(mul, (bool, np.bool_)) or not isinstance(mul, numbers.Real) or not 0.0 <= float(mul) <= float(np.finfo(np.float32).max):
-      raise ValueError('%s: %r: the multiplier %r must be a finite number >= 0 that float32 holds (0 = frozen)' % (key, pat, mul))
-    if not any(rx.search(n) for n in names):
-      raise ValueError('%s: the pattern %r matches no variable of the model' % (key, pat))
-    patterns.append((rx, float(np.float32(mul))))
-  out = collections.OrderedDict()
-  for n in names:
-    out[n] = next((mul for rx, mul in patterns if rx.search(n)), 1.0)
-  return None if all(mul == 1.0 for mul in out.values()) else out
-
-
 def lr_multiplier_runs(offsets, size, multipliers):
   """The arena as maximal contiguous runs [(offset, count, multiplier)] of one multiplier each.  ``offsets``: {name: offset} in arena
   order (``VariableStore.offsets``), ``size``: the arena's length.  A variable's span runs up to the next variable's offset, so the
@@ -321,74 +163,6 @@ def backward_cut(multipliers):
   if all(mul == 0.0 for n, mul in multipliers.items() if _ENC_BOTTOM.search(n)):
     return 'no_bottom'
   return 'full'
-
-
-LR_KINDS = ('constant', 'exponential', 'cosine', 'piecewise')
-LR_BOUNDARIES_MAX = 8      # GEECO_LR_BOUNDARIES_MAX of include/geeco_hip.h
-_LR_FIELDS = ('kind', 'warmup_steps', 'decay_steps', 'decay_rate', 'alpha', 'staircase', 'boundaries', 'values')
-
-
-def check_lr_schedule(value, base_lr, key='lr_schedule'):
-  """The learning-rate schedule the device evaluates from its step counter.  ``value``: None, or a mapping with 'kind'
-  ('constant', 'exponential', 'cosine', 'piecewise') and of 'warmup_steps', 'decay_steps', 'decay_rate', 'staircase', 'alpha',
-  'boundaries', 'values' those the kind uses; ``base_lr``: the constant rate it starts from (cfg.lr).  None, or 'constant' without
-  warm-up, is off and returns None; else the normalised schedule, a dictionary with every field (``ops.lr_schedule_struct`` takes
-  it).  Anything else raises ValueError naming ``key`` and the offending field."""
-  if value is None:
-    return None
-
-  def bad(field, why):
-    return ValueError('%s: %s=%r: %s' % (key, field, value.get(field) if isinstance(value, collections.abc.Mapping) else value, why))
-
-  def whole(field, least, default=None):
-    x = value.get(field, default)
-    if isinstance(x, bool) or not isinstance(x, numbers.Integral) or not least <= int(x) < 2 ** 62:
-      raise bad(field, 'must be a whole number >= %d' % least)
-    return int(x)
-
-  def rate(field, x, above_zero=False, most=float(np.finfo(np.float32).max)):
-    ok = not isinstance(x, bool) and isinstance(x, numbers.Real) and 0.0 <= float(x) <= most and not (above_zero and float(np.float32(x)) <= 0.0)
-    if not ok:
-      raise bad(field, 'must be a finite number %s that float32 holds' % ('> 0' if above_zero else ('in [0, 1]' if most == 1.0 else '>= 0')))
-    return float(x)
-
-  if not isinstance(value, collections.abc.Mapping):
-    raise bad('value', "must be None or a mapping with 'kind' and the fields the kind uses")
-  for field in value:
-    if field not in _LR_FIELDS:
-      raise ValueError('%s: unknown field %r (known: %s)' % (key, field, ', '.join(_LR_FIELDS)))
-  kind = value.get('kind')
-  if not isinstance(kind, str) or kind not in LR_KINDS:
-    raise bad('kind', 'must be one of %s' % ', '.join(LR_KINDS))
-  out = dict(kind=kind, base_lr=0.0, warmup_steps=whole('warmup_steps', 0, 0), decay_steps=1, decay_rate=1.0, alpha=0.0, staircase=False,
-             boundaries=(), values=())
-  if kind == 'piecewise':      # base_lr is ignored
-    boundaries, values = value.get('boundaries', ()), value.get('values')
-    if isinstance(boundaries, (str, bytes)) or not isinstance(boundaries, collections.abc.Sequence) or len(boundaries) > LR_BOUNDARIES_MAX:
-      raise bad('boundaries', 'must be a sequence of at most %d step counts' % LR_BOUNDARIES_MAX)
-    for i, b in enumerate(boundaries):
-      if isinstance(b, bool) or not isinstance(b, numbers.Integral) or abs(int(b)) >= 2 ** 62 or (i and int(b) <= int(boundaries[i - 1])):
-        raise bad('boundaries', 'must be whole numbers, strictly increasing (entry %d)' % i)
-    if isinstance(values, (str, bytes)) or not isinstance(values, collections.abc.Sequence) or len(values) != len(boundaries) + 1:
-      raise bad('values', 'must be a sequence of %d rates, one more than boundaries' % (len(boundaries) + 1))
-    out['boundaries'] = tuple(int(b) for b in boundaries)
-    out['values'] = tuple(rate('values', v) for v in values)
-    return out
-  if isinstance(base_lr, bool) or not isinstance(base_lr, numbers.Real) or not 0.0 <= float(base_lr) <= float(np.finfo(np.float32).max):
-    raise ValueError('%s: base_lr=%r (the configured lr) must be a finite number >= 0 that float32 holds' % (key, base_lr))
-  out['base_lr'] = float(base_lr)
-  if kind == 'constant':
-    return out if out['warmup_steps'] else None
-  out['decay_steps'] = whole('decay_steps', 1)
-  if kind == 'exponential':
-    out['decay_rate'] = rate('decay_rate', value.get('decay_rate'), above_zero=True)
-    staircase = value.get('staircase', False)
-    if not isinstance(staircase, (bool, np.bool_)):
-      raise bad('staircase', 'must be True or False')
-    out['staircase'] = bool(staircase)
-  else:
-    out['alpha'] = rate('alpha', value.get('alpha', 0.0), most=1.0)
-  return out
 
 
 def ema_decay_at(decay, t):

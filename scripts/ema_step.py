@@ -10,72 +10,27 @@ The optimiser pass alone is timed the same way on the model's own arenas (geeco_
 launches with nothing beside them), since inside the step most of it hides beside the fused bottom.
 Writes one JSON file (default profiles/ema/step.json).  Needs the GPU: there is no fallback.
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _step_ab as ab
 
 
 def main():
-  ap = argparse.ArgumentParser()
-  ap.add_argument('--size', type=int, default=256)
-  ap.add_argument('--window_size', type=int, default=16)
-  ap.add_argument('--batch_size', type=int, default=32)
+  ap = ab.arguments('ema')
   ap.add_argument('--decay', type=float, default=0.999)
-  ap.add_argument('--steps', type=int, default=40, help='steps per timed block')
-  ap.add_argument('--rounds', type=int, default=7)
-  ap.add_argument('--warmup', type=int, default=6)
-  ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'ema', 'step.json'))
   args = ap.parse_args()
+  w = ab.workload(args, 'ema_step.py')
 
   import torch
-  from geeco_amd import graph, ops
-  from geeco_amd.params import create_e2evmc_config
-  from geeco_amd.runtime import TrainStepRunner
-  from oracle import geeco_oracle as O
-
-  if not torch.cuda.is_available():
-    raise SystemExit('ema_step.py measures on the GPU; none is visible')
-  dev = torch.device('cuda', torch.cuda.current_device())
-  H, K, N = args.size, args.window_size, args.batch_size
-  kw = dict(proc_obs='dynimg', proc_tgt='dyndiff', window_size=K, img_height=H, img_width=H, batch_size=N)
-  ocfg = O.make_config(**kw)
-  cfg = create_e2evmc_config(kw)
-  P = O.init_params(O.model_param_shapes(ocfg, True), seed=0)
-  feats, labels = O.synthetic_batch(ocfg, True, N, seed=3, H=H, W=H)
-  feats = {k: torch.from_numpy(v) for k, v in feats.items()}
-  labels = {k: torch.from_numpy(v) for k, v in labels.items()}
-
-  def timed_block(step, n):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n):
-      step()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / n
+  from geeco_amd import ops
 
   models, forms = {}, {}
   for name, decay in (('off', None), ('on', args.decay)):
-    m = graph.GoalE2EVMC(cfg, N, dev, training=True, ema_decay=decay)
-    m.store.load_numpy(P)
-    m.load_batch(feats, labels)
-    r = TrainStepRunner(m, use_graph=True)
-    for _ in range(args.warmup):
-      r.step()
-    models[name], forms[name] = m, r.step
+    models[name], r = ab.build(w, args.warmup, ema_decay=decay)
+    forms[name] = r.step
   torch.cuda.synchronize()
   assert models['on'].store.ema is not None and models['off'].store.ema is None
   same = all(torch.equal(getattr(models['on'].store, a), getattr(models['off'].store, a)) for a in ('params', 'adam_m', 'adam_v'))
-  blocks = {'off': [], 'on': []}
-  for _ in range(args.rounds):
-    for k in ('off', 'on'):
-      blocks[k].append(timed_block(forms[k], args.steps))
-  med = {k: statistics.median(v) for k, v in blocks.items()}
+  blocks = ab.alternate(forms, args.rounds, args.steps)
+  med = ab.medians(blocks)
 
   # the optimiser pass alone, on the 'on' model's arenas (lr_t and the step counter as the last step left them)
   m = models['on']
@@ -84,36 +39,24 @@ def main():
       'adam_tf': lambda: ops.adam_tf(s.params, s.grads, s.adam_m, s.adam_v, s.size, m.scal),
       'adam_tf_ema': lambda: ops.adam_tf_ema(s.params, s.grads, s.adam_m, s.adam_v, s.ema, s.size, m.scal, s.global_step, args.decay),
   }
-  pass_blocks = {k: [] for k in passes}
-  for k, fn in passes.items():
-    timed_block(fn, 20)
-  for _ in range(args.rounds):
-    for k, fn in passes.items():
-      pass_blocks[k].append(timed_block(fn, 200) * 1e3)
-  pass_med = {k: statistics.median(v) for k, v in pass_blocks.items()}
+  pass_blocks = ab.alternate(passes, args.rounds, 200, warm=20, scale=1e3)
+  pass_med = ab.medians(pass_blocks)
   arena_mb = 4 * s.size / 1e6
-  results = {
-      'shape': dict(size=H, window_size=K, batch_size=N, model='geeco-f', arena_floats=int(s.size), decay=args.decay),
-      'timing': dict(steps_per_block=args.steps, rounds=args.rounds, warmup=args.warmup,
-                     method='device events around blocks of steps (and of 200 back-to-back optimiser launches), option off and '
-                            'on alternating in one process; medians of the blocks'),
-      'device': torch.cuda.get_device_name(dev),
+  ab.write({
+      'shape': dict(size=w.H, window_size=w.K, batch_size=w.N, model='geeco-f', arena_floats=int(s.size), decay=args.decay),
+      'timing': ab.timing(args, 'device events around blocks of steps (and of 200 back-to-back optimiser launches), option off and '
+                                'on alternating in one process; medians of the blocks'),
+      'device': torch.cuda.get_device_name(w.dev),
       'bitwise_same_params_and_slots_after_warmup': bool(same),
       'step_ms': {k: round(v, 4) for k, v in med.items()},
-      'step_ms_blocks': {k: [round(x, 4) for x in v] for k, v in blocks.items()},
+      'step_ms_blocks': ab.rounded(blocks, 4),
       'step_added_us': round((med['on'] - med['off']) * 1e3, 2),
       'optimiser_pass_us': {k: round(v, 2) for k, v in pass_med.items()},
-      'optimiser_pass_us_blocks': {k: [round(x, 2) for x in v] for k, v in pass_blocks.items()},
+      'optimiser_pass_us_blocks': ab.rounded(pass_blocks, 2),
       'optimiser_pass_added_us': round(pass_med['adam_tf_ema'] - pass_med['adam_tf'], 2),
       'optimiser_pass_tb_per_s': {'adam_tf': round(7 * arena_mb / pass_med['adam_tf'], 3),            # p g m v read, p m v written
                                   'adam_tf_ema': round(9 * arena_mb / pass_med['adam_tf_ema'], 3)},   # + the shadow arena read and written
-  }
-  print(json.dumps(results), flush=True)
-  os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-  with open(args.out, 'w') as fp:
-    json.dump(results, fp, indent=1, sort_keys=True)
-    fp.write('\n')
-  print('wrote', args.out)
+  }, args.out)
 
 
 if __name__ == '__main__':

@@ -15,14 +15,7 @@ The optimiser pass alone (the whole arena as one piece through geeco_adam_tf aga
 geeco_adam_tf_segments_scaled) is timed the same way.
 Writes one JSON file (default profiles/finetune/step.json).  Needs the GPU: there is no fallback.
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _step_ab as ab
 
 VARIANTS = [('off', None, None), ('enc_x0.1', {'Encoder/': 0.1}, None), ('enc_x0.1_plain', {'Encoder/': 0.1}, False),
             ('bottom_frozen', {'/conv[12]/': 0}, None), ('enc_frozen', {'Encoder/': 0}, None)]
@@ -44,50 +37,16 @@ class _Counting:
 
 
 def main():
-  ap = argparse.ArgumentParser()
-  ap.add_argument('--size', type=int, default=256)
-  ap.add_argument('--window_size', type=int, default=16)
-  ap.add_argument('--batch_size', type=int, default=32)
-  ap.add_argument('--steps', type=int, default=40, help='steps per timed block')
-  ap.add_argument('--rounds', type=int, default=7)
-  ap.add_argument('--warmup', type=int, default=6)
-  ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'finetune', 'step.json'))
-  args = ap.parse_args()
+  args = ab.arguments('finetune').parse_args()
+  w = ab.workload(args, 'finetune_step.py')
 
   import torch
-  from geeco_amd import _native, graph, ops
-  from geeco_amd.params import create_e2evmc_config
-  from geeco_amd.runtime import TrainStepRunner
-  from oracle import geeco_oracle as O
+  from geeco_amd import _native, ops
 
-  if not torch.cuda.is_available():
-    raise SystemExit('finetune_step.py measures on the GPU; none is visible')
-  dev = torch.device('cuda', torch.cuda.current_device())
-  H, K, N = args.size, args.window_size, args.batch_size
-  kw = dict(proc_obs='dynimg', proc_tgt='dyndiff', window_size=K, img_height=H, img_width=H, batch_size=N)
-  ocfg = O.make_config(**kw)
-  cfg = create_e2evmc_config(kw)
-  P = O.init_params(O.model_param_shapes(ocfg, True), seed=0)
-  feats, labels = O.synthetic_batch(ocfg, True, N, seed=3, H=H, W=H)
-  feats = {k: torch.from_numpy(v) for k, v in feats.items()}
-  labels = {k: torch.from_numpy(v) for k, v in labels.items()}
-
-  def timed_block(step, n):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n):
-      step()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / n
-
-  models, forms, launches, info = {}, {}, {}, {}
+  models, forms, info = {}, {}, {}
   lib = _native.load()
   for name, table, beside in VARIANTS:
-    m = graph.GoalE2EVMC(cfg, N, dev, training=True, lr_multipliers=table)
-    m.store.load_numpy(P)
-    m.load_batch(feats, labels)
-    r = TrainStepRunner(m, use_graph=True)
+    m, r = ab.build(w, lr_multipliers=table)
     if beside is not None:
       r.beside_bottom = beside
     counter = _Counting(lib)
@@ -97,18 +56,14 @@ def main():
       torch.cuda.synchronize()
     finally:
       _native._lib = lib
-    launches[name] = len(counter.calls)
     info[name] = dict(backward_cut=m.backward_cut, runs=len(m.lr_runs or []), beside_bottom=bool(r.beside_bottom), library_calls=len(counter.calls),
                       optimiser_calls=[c for c in counter.calls if 'adam_tf' in c])
     for _ in range(args.warmup):
       r.step()
     models[name], forms[name] = m, r.step
   torch.cuda.synchronize()
-  blocks = {name: [] for name, _, _ in VARIANTS}
-  for _ in range(args.rounds):
-    for name, _, _ in VARIANTS:
-      blocks[name].append(timed_block(forms[name], args.steps))
-  med = {k: statistics.median(v) for k, v in blocks.items()}
+  blocks = ab.alternate(forms, args.rounds, args.steps)
+  med = ab.medians(blocks)
 
   # the optimiser pass alone, on the models' own arenas (the gradients are what the last step left)
   off, on = models['off'], models['enc_x0.1']
@@ -119,34 +74,20 @@ def main():
       'adam_tf_whole_arena': lambda: ops.adam_tf(off.store.params, off.store.grads, off.store.adam_m, off.store.adam_v, off.store.size, off.scal),
       'adam_tf_segments_scaled_runs': lambda: ops.adam_tf_segments_scaled(s.params, s.adam_m, s.adam_v, pieces, muls, on.scal),
   }
-  pass_blocks = {k: [] for k in passes}
-  for fn in passes.values():
-    for _ in range(args.warmup):
-      fn()
-  for _ in range(args.rounds):
-    for k, fn in passes.items():
-      pass_blocks[k].append(timed_block(fn, args.steps))
-  pass_med = {k: statistics.median(v) for k, v in pass_blocks.items()}
-
-  results = {
-      'shape': dict(size=H, window_size=K, batch_size=N, model='geeco-f', arena_floats=int(s.size)),
-      'timing': dict(steps_per_block=args.steps, rounds=args.rounds, warmup=args.warmup,
-                     method='device events around blocks of steps, the variants alternating in one process; medians of the blocks'),
-      'device': torch.cuda.get_device_name(dev),
+  pass_blocks = ab.alternate(passes, args.rounds, args.steps, warm=args.warmup, scale=1e3)
+  pass_med = ab.medians(pass_blocks)
+  ab.write({
+      'shape': dict(size=w.H, window_size=w.K, batch_size=w.N, model='geeco-f', arena_floats=int(s.size)),
+      'timing': ab.timing(args, 'device events around blocks of steps, the variants alternating in one process; medians of the blocks'),
+      'device': torch.cuda.get_device_name(w.dev),
       'variants': info,
       'step_ms': {k: round(v, 4) for k, v in med.items()},
-      'step_ms_blocks': {k: [round(x, 4) for x in v] for k, v in blocks.items()},
+      'step_ms_blocks': ab.rounded(blocks, 4),
       'step_minus_off_us': {k: round((v - med['off']) * 1e3, 2) for k, v in med.items()},
       'off_spread_us': round((max(blocks['off']) - min(blocks['off'])) * 1e3, 2),
-      'optimiser_pass_us': {k: round(v * 1e3, 2) for k, v in pass_med.items()},
-      'optimiser_pass_us_blocks': {k: [round(x * 1e3, 2) for x in v] for k, v in pass_blocks.items()},
-  }
-  print(json.dumps(results), flush=True)
-  os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-  with open(args.out, 'w') as fp:
-    json.dump(results, fp, indent=1, sort_keys=True)
-    fp.write('\n')
-  print('wrote', args.out)
+      'optimiser_pass_us': {k: round(v, 2) for k, v in pass_med.items()},
+      'optimiser_pass_us_blocks': ab.rounded(pass_blocks, 2),
+  }, args.out)
 
 
 if __name__ == '__main__':

@@ -18,14 +18,9 @@ Writes one JSON file (default profiles/skip_nonfinite/step.json).  Needs the GPU
 parent commit -- FILE holds one line {"tree": "parent" | "new", "run": i, "result": <bench.py's JSON line>} per run of
 ``bench.py --gpus 1 --steps 200`` in the two trees, alternating, in one session on one machine.
 """
-import argparse
 import json
-import os
-import statistics
-import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _step_ab as ab
 
 
 def merge_bench_ab(out, path):
@@ -48,70 +43,32 @@ def merge_bench_ab(out, path):
 
 
 def main():
-  ap = argparse.ArgumentParser()
-  ap.add_argument('--size', type=int, default=256)
-  ap.add_argument('--window_size', type=int, default=16)
-  ap.add_argument('--batch_size', type=int, default=32)
+  ap = ab.arguments('skip_nonfinite')
   ap.add_argument('--clip_norm', type=float, default=1.0)
-  ap.add_argument('--steps', type=int, default=40, help='steps per timed block')
-  ap.add_argument('--rounds', type=int, default=7)
-  ap.add_argument('--warmup', type=int, default=6)
-  ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'skip_nonfinite', 'step.json'))
   ap.add_argument('--merge_bench_ab', default=None, help='measure nothing: add the bench.py runs of this file to --out (module docstring)')
   args = ap.parse_args()
   if args.merge_bench_ab:
     return merge_bench_ab(args.out, args.merge_bench_ab)
+  w = ab.workload(args, 'skip_nonfinite_step.py')
 
   import torch
-  from geeco_amd import graph, ops
-  from geeco_amd.params import create_e2evmc_config
-  from geeco_amd.runtime import TrainStepRunner
-  from oracle import geeco_oracle as O
+  from geeco_amd import ops
 
-  if not torch.cuda.is_available():
-    raise SystemExit('skip_nonfinite_step.py measures on the GPU; none is visible')
-  dev = torch.device('cuda', torch.cuda.current_device())
-  H, K, N = args.size, args.window_size, args.batch_size
-  kw = dict(proc_obs='dynimg', proc_tgt='dyndiff', window_size=K, img_height=H, img_width=H, batch_size=N)
-  ocfg = O.make_config(**kw)
-  cfg = create_e2evmc_config(kw)
-  P = O.init_params(O.model_param_shapes(ocfg, True), seed=0)
-  feats, labels = O.synthetic_batch(ocfg, True, N, seed=3, H=H, W=H)
-  bad = {k: v.copy() for k, v in labels.items()}
+  feats, labels = w.feats, w.labels
+  bad = {k: v.clone() for k, v in labels.items()}
   bad['cmd'][0, 0] = float('nan')
-  feats = {k: torch.from_numpy(v) for k, v in feats.items()}
-  labels = {k: torch.from_numpy(v) for k, v in labels.items()}
-  bad = {k: torch.from_numpy(v) for k, v in bad.items()}
-
-  def timed_block(step, n):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n):
-      step()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / n
-
   options = {'off': {}, 'clip': dict(clip_norm=args.clip_norm), 'skip': dict(skip_nonfinite=True),
              'skip_clip': dict(skip_nonfinite=True, clip_norm=args.clip_norm)}
   models, forms = {}, {}
   for name, opt in options.items():
-    m = graph.GoalE2EVMC(cfg, N, dev, training=True, **opt)
-    m.store.load_numpy(P)
-    m.load_batch(feats, labels)
-    r = TrainStepRunner(m, use_graph=True)
-    for _ in range(args.warmup):
-      r.step()
-    models[name], forms[name] = m, r.step
+    models[name], r = ab.build(w, args.warmup, **opt)
+    forms[name] = r.step
   torch.cuda.synchronize()
   assert models['off'].clip_ws is None and models['clip'].guard is None and models['skip'].guard is not None
   assert models['skip'].guard.tolist() == [1, 0, 0] and models['skip_clip'].guard.tolist() == [1, 0, 0]
   scale, norm = (float(x) for x in models['skip'].clip_out.cpu())
-  blocks = {k: [] for k in options}
-  for _ in range(args.rounds):
-    for k in options:
-      blocks[k].append(timed_block(forms[k], args.steps))
-  med = {k: statistics.median(v) for k, v in blocks.items()}
+  blocks = ab.alternate(forms, args.rounds, args.steps)
+  med = ab.medians(blocks)
 
   # applied against skipped steps: the ``skip`` model alone, the batch alternating
   m = models['skip']
@@ -120,10 +77,10 @@ def main():
     for k, lab in (('applied', labels), ('skipped', bad)):
       m.load_batch(feats, lab)
       forms['skip']()      # (the first step on the new labels is outside the block)
-      verdict_blocks[k].append(timed_block(forms['skip'], args.steps))
+      verdict_blocks[k].append(ab.timed_block(forms['skip'], args.steps))
       torch.cuda.synchronize()
       assert int(m.guard[0]) == (1 if k == 'applied' else 0), (k, m.guard.tolist())
-  verdict_med = {k: statistics.median(v) for k, v in verdict_blocks.items()}
+  verdict_med = ab.medians(verdict_blocks)
   skipped_total = int(m.guard[1])
   assert bool(torch.isfinite(m.store.params).all())
   m.load_batch(feats, labels)
@@ -154,43 +111,31 @@ def main():
       'guard_decide': lambda: ops.guard_decide(m.clip_out, m.guard, m.clip_ws, nch, 0.0),
       'clip_scale': lambda: ops.clip_scale(m.clip_out, m.clip_ws, nch, args.clip_norm),
   }
-  pass_blocks = {k: [] for k in passes}
-  for k, fn in passes.items():
-    timed_block(fn, 20)
-  for _ in range(args.rounds):
-    for k, fn in passes.items():
-      pass_blocks[k].append(timed_block(fn, 200) * 1e3)
-  pass_med = {k: statistics.median(v) for k, v in pass_blocks.items()}
+  pass_blocks = ab.alternate(passes, args.rounds, 200, warm=20, scale=1e3)
+  pass_med = ab.medians(pass_blocks)
   us = lambda a, b: round((med[a] - med[b]) * 1e3, 2)
-  results = {
-      'shape': dict(size=H, window_size=K, batch_size=N, model='geeco-f', arena_floats=int(s.size), clip_norm=args.clip_norm, chunks=int(nch)),
-      'timing': dict(steps_per_block=args.steps, rounds=args.rounds, warmup=args.warmup,
-                     method='device events around blocks of steps (and of 200 back-to-back optimiser passes), the forms alternating in '
-                            'one process; medians of the blocks'),
-      'device': torch.cuda.get_device_name(dev),
+  ab.write({
+      'shape': dict(size=w.H, window_size=w.K, batch_size=w.N, model='geeco-f', arena_floats=int(s.size), clip_norm=args.clip_norm, chunks=int(nch)),
+      'timing': ab.timing(args, 'device events around blocks of steps (and of 200 back-to-back optimiser passes), the forms alternating in '
+                                'one process; medians of the blocks'),
+      'device': torch.cuda.get_device_name(w.dev),
       'scale_and_norm_after_warmup': [scale, norm],
       'step_ms': {k: round(v, 4) for k, v in med.items()},
-      'step_ms_blocks': {k: [round(x, 4) for x in v] for k, v in blocks.items()},
+      'step_ms_blocks': ab.rounded(blocks, 4),
       'step_added_us': {'clip_over_off': us('clip', 'off'), 'skip_over_off': us('skip', 'off'), 'skip_clip_over_off': us('skip_clip', 'off'),
                         'skip_over_clip': us('skip', 'clip'), 'skip_clip_over_clip': us('skip_clip', 'clip')},
       'step_added_percent': {k: round(100.0 * (med[k] - med['off']) / med['off'], 3) for k in ('clip', 'skip', 'skip_clip')},
       'skip_model_step_ms': {k: round(v, 4) for k, v in verdict_med.items()},
-      'skip_model_step_ms_blocks': {k: [round(x, 4) for x in v] for k, v in verdict_blocks.items()},
+      'skip_model_step_ms_blocks': ab.rounded(verdict_blocks, 4),
       'skip_model_steps_skipped': skipped_total,
       'optimiser_pass_us': {k: round(v, 2) for k, v in pass_med.items()},
-      'optimiser_pass_us_blocks': {k: [round(x, 2) for x in v] for k, v in pass_blocks.items()},
+      'optimiser_pass_us_blocks': ab.rounded(pass_blocks, 2),
       'optimiser_pass_added_us': {'clipped_over_adam_tf': round(pass_med['clipped_three_launches'] - pass_med['adam_tf'], 2),
                                   'guarded_over_adam_tf': round(pass_med['guarded_three_launches'] - pass_med['adam_tf'], 2),
                                   'guarded_over_clipped': round(pass_med['guarded_three_launches'] - pass_med['clipped_three_launches'], 2)},
       'not_measured': ['the data-parallel forms', 'l2 != 0 (the sum of squares then reads the parameter arena too)', 'ema_decay together with the option',
                        'any model but geeco-f, any shape but this one'],
-  }
-  print(json.dumps(results), flush=True)
-  os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-  with open(args.out, 'w') as fp:
-    json.dump(results, fp, indent=1, sort_keys=True)
-    fp.write('\n')
-  print('wrote', args.out)
+  }, args.out)
 
 
 if __name__ == '__main__':

@@ -14,76 +14,26 @@ Timing: device events around blocks of ``--steps`` calls, the forms alternating 
 the median block and every block are reported.  Writes one JSON file (default profiles/variable_stats/step.json).  Needs the GPU:
 there is no fallback.
 """
-import argparse
-import json
-import os
-import statistics
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import _step_ab as ab
 
 
 def main():
-  ap = argparse.ArgumentParser()
-  ap.add_argument('--size', type=int, default=256)
-  ap.add_argument('--window_size', type=int, default=16)
-  ap.add_argument('--batch_size', type=int, default=32)
-  ap.add_argument('--steps', type=int, default=40, help='calls per timed block')
-  ap.add_argument('--rounds', type=int, default=7)
-  ap.add_argument('--warmup', type=int, default=6)
-  ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'variable_stats', 'step.json'))
-  args = ap.parse_args()
+  args = ab.arguments('variable_stats', steps_help='calls per timed block').parse_args()
+  w = ab.workload(args, 'variable_stats_step.py')
 
   import numpy as np
   import torch
-  from geeco_amd import graph, ops
-  from geeco_amd.params import create_e2evmc_config
-  from geeco_amd.runtime import TrainStepRunner
-  from oracle import geeco_oracle as O
-
-  if not torch.cuda.is_available():
-    raise SystemExit('variable_stats_step.py measures on the GPU; none is visible')
-  dev = torch.device('cuda', torch.cuda.current_device())
-  H, K, N = args.size, args.window_size, args.batch_size
-  kw = dict(proc_obs='dynimg', proc_tgt='dyndiff', window_size=K, img_height=H, img_width=H, batch_size=N)
-  ocfg = O.make_config(**kw)
-  cfg = create_e2evmc_config(kw)
-  P = O.init_params(O.model_param_shapes(ocfg, True), seed=0)
-  feats, labels = O.synthetic_batch(ocfg, True, N, seed=3, H=H, W=H)
-  feats = {k: torch.from_numpy(v) for k, v in feats.items()}
-  labels = {k: torch.from_numpy(v) for k, v in labels.items()}
-
-  def timed_block(step, n):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(n):
-      step()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / n
-
-  def alternate(forms):
-    blocks = {k: [] for k in forms}
-    for _ in range(args.rounds):
-      for name, step in forms.items():
-        blocks[name].append(timed_block(step, args.steps))
-    return blocks
+  from geeco_amd import ops
 
   # ---- (a) the step ------------------------------------------------------------------------------
   models, forms = {}, {}
   for name, opt in (('off', {}), ('on', dict(variable_stats='histograms'))):
-    m = graph.GoalE2EVMC(cfg, N, dev, training=True, **opt)
-    m.store.load_numpy(P)
-    m.load_batch(feats, labels)
-    r = TrainStepRunner(m, use_graph=True)
-    for _ in range(args.warmup):
-      r.step()
-    models[name], forms[name] = m, r.step
+    models[name], r = ab.build(w, args.warmup, **opt)
+    forms[name] = r.step
   torch.cuda.synchronize()
   assert models['off'].stats_plan is None and models['on'].stats_plan is not None
-  blocks = alternate(forms)
-  med = {k: statistics.median(v) for k, v in blocks.items()}
+  blocks = ab.alternate(forms, args.rounds, args.steps)
+  med = ab.medians(blocks)
   spread = [min(blocks['off']), max(blocks['off'])]
   step = {'ms_per_step_median': med, 'ms_per_step_blocks': blocks, 'off_spread_ms': spread,
           'on_minus_off_us': 1e3 * (med['on'] - med['off']),
@@ -95,18 +45,14 @@ def main():
   stats = m.variable_stats()      # (the records of the last replayed step: the call works behind a captured step)
   assert len(stats) == len(s.shapes) and all(np.isfinite(d['grad_norm']) for d in stats.values())
   elements = int(sum(int(np.prod(shp)) for shp in s.shapes.values()))
-  partials = torch.zeros(ops.clip_ws_floats(s.size), dtype=torch.float32, device=dev)
+  partials = torch.zeros(ops.clip_ws_floats(s.size), dtype=torch.float32, device=w.dev)
   pieces = m.step_pieces
   alone = {
       'variable_stats': lambda: m.stats_plan.run(s.params, s.adam_m, s.adam_v, pieces, s.size),
       'grad_sumsq': lambda: ops.grad_sumsq_segments(partials, None, pieces, s.size),
   }
-  for f in alone.values():
-    for _ in range(args.warmup):
-      f()
-  torch.cuda.synchronize()
-  ablocks = alternate(alone)
-  amed = {k: statistics.median(v) for k, v in ablocks.items()}
+  ablocks = ab.alternate(alone, args.rounds, args.steps, warm=args.warmup)
+  amed = ab.medians(ablocks)
   nbytes = {'variable_stats': 16 * elements, 'grad_sumsq': 4 * s.size}
   rate = {k: nbytes[k] / (amed[k] * 1e-3) for k in alone}
   call = {'us_per_call_median': {k: 1e3 * v for k, v in amed.items()}, 'us_per_call_blocks': {k: [1e3 * x for x in v] for k, v in ablocks.items()},
@@ -114,14 +60,11 @@ def main():
           'time_ratio_stats_over_sumsq': amed['variable_stats'] / amed['grad_sumsq'], 'pieces': len(pieces),
           'chunks': m.stats_plan.nchunks, 'variables': len(s.shapes), 'arena_floats': s.size, 'variable_floats': elements}
 
-  results = {'workload': dict(kw, model='geeco-f'), 'steps_per_block': args.steps, 'rounds': args.rounds, 'warmup': args.warmup,
-             'device': torch.cuda.get_device_name(dev), 'step': step, 'statistics_call': call}
-  os.makedirs(os.path.dirname(args.out), exist_ok=True)
-  with open(args.out, 'w') as fp:
-    json.dump(results, fp, indent=1, sort_keys=True)
-    fp.write('\n')
-  print(json.dumps({'step': {k: step[k] for k in ('ms_per_step_median', 'off_spread_ms', 'on_minus_off_us', 'on_within_the_spread_of_off')},
-                    'statistics_call': {k: call[k] for k in ('us_per_call_median', 'bytes_per_second', 'bandwidth_ratio_stats_over_sumsq')}}))
+  results = {'workload': dict(w.kw, model='geeco-f'), 'steps_per_block': args.steps, 'rounds': args.rounds, 'warmup': args.warmup,
+             'device': torch.cuda.get_device_name(w.dev), 'step': step, 'statistics_call': call}
+  ab.write(results, args.out, show={
+      'step': {k: step[k] for k in ('ms_per_step_median', 'off_spread_ms', 'on_minus_off_us', 'on_within_the_spread_of_off')},
+      'statistics_call': {k: call[k] for k in ('us_per_call_median', 'bytes_per_second', 'bandwidth_ratio_stats_over_sumsq')}})
 
 
 if __name__ == '__main__':
