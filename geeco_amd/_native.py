@@ -185,6 +185,11 @@ SIGNATURES = {
     'geeco_variable_stats': (_I, [_P, _P, _P, _P, _I, _L, _F, _F, POINTER(c_int64), POINTER(c_int64), _I, _P, _L, _P, _P, _P]),
     'geeco_grad_accumulate_segments': (_I, [_P, _P, _I, _L, _I, _P]),      # additive within ABI 7
     'geeco_sumsq': (_I, [_P, _L, _P, _P]),
+    # additive within ABI 7: input gradients
+    'geeco_conv1_dgrad': (_I, [_P, _P, _P, _I, _L, _L, _L, _I, _I, _I, _I, _I, _P]),
+    'geeco_pack_pixels_bwd': (_I, [_P, _P, _L, _I, _P, _L, _I, _I, _L, _I, _I, _I, _P]),
+    'geeco_dynimg_bwd_ws_bytes': (_L, [_I, _L, _I]),
+    'geeco_dynimg_bwd': (_I, [_P, _P, _P, _L, _L, _P, _I, _I, _L, _I, _I, _P, _L, _L, _I, _P, _I, _P, _P]),
 }
 
 _lib = None

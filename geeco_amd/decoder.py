@@ -63,6 +63,23 @@ class LSTMDecoder:
     if loss_shaping is not None and loss_shaping['grp_class_weights'] is not None:
       self.class_weight = torch.tensor(loss_shaping['grp_class_weights'], **f32)
     self.heads_pending, self.dz_from_heads = None, False
+    self.head_weights = None      # select_loss_heads: the loss weights of an eager pass of its own; None = the table's (training)
+
+  def select_loss_heads(self, heads=None):
+    """The loss this decoder differentiates from now on: the sum of the named heads' losses with weight 1, every other head 0
+    (``heads``: head names of ``predictions()``, 'logits_cmd_grp' also as 'cmd_grp'); None = the training loss again.  The weights are
+    the host ``head_weight`` array of every heads call, so a step captured into a graph keeps the ones it was captured with: this is
+    for models that run eagerly and never train (``Estimator.input_gradients``)."""
+    if heads is None:
+      self.head_weights = None
+      return
+    keys = [h[1] for h in self.heads]
+    short = {k.replace('logits_', ''): k for k in keys}
+    picked = {short.get(h, h) for h in ([heads] if isinstance(heads, str) else heads)}
+    unknown = sorted(picked - set(keys))
+    if unknown or not picked:
+      raise ValueError('heads=%r: this model has the heads %s' % (heads, ', '.join(sorted(short))))
+    self.head_weights = [1.0 if k in picked else 0.0 for k in keys]
 
   def _alloc_chain(self):
     """The per-step buffers of the launch-per-step chain."""
@@ -88,7 +105,8 @@ class LSTMDecoder:
     """The head arguments of the ops (variables, sizes, kinds, loss weights, targets) and the gradient views, from the store as it is now."""
     names = [h[0] for h in self.heads]
     args = (self._v('fc1/kernel'), self._v('fc1/bias'), [self._v(n + '/kernel') for n in names], [self._v(n + '/bias') for n in names],
-            *([h[i] for h in self.heads] for i in (2, 3, 4)), self.targets, self.target_strides, float(self.loss_scale))
+            [h[2] for h in self.heads], [h[3] for h in self.heads], self.head_weights or [h[4] for h in self.heads], self.targets,
+            self.target_strides, float(self.loss_scale))
     grads = dict(d_fc1_w=self._g('fc1/kernel'), d_fc1_b=self._g('fc1/bias'), d_heads_w=[self._g(n + '/kernel') for n in names],
                  d_heads_b=[self._g(n + '/bias') for n in names]) if backward_too else {}
     if self.loss_shaping is not None:

@@ -387,3 +387,38 @@ class ConvEncoderStack:
         before_bottom(pending)
       self.launch_dgrad(l, pending)
     self.launch_wgrad(0, pending)
+
+  # -- beyond the training backward: the gradient of conv1's INPUT, for saliency maps ----------------------
+
+  def check_input_gradient(self):
+    """ValueError unless ``input_gradient`` can run on this stack."""
+    if not self.training:
+      raise ValueError('input gradients need a training stack (an inference stack keeps no gradient buffers)')
+    L0 = self.layers[0]
+    if self.Cpad != 4 or self.Cin not in (3, 4) or L0['Cout'] != 32 or L0['stride'] != 1:
+      raise ValueError('input gradients: geeco_conv1_dgrad serves conv1 of the reference encoder (3 or 4 -> 32 channels, stride 1), '
+                       'not %d -> %d stride %d' % (self.Cin, L0['Cout'], L0['stride']))
+
+  def input_gradient(self, chunk_frames=96):
+    """d(loss)/d(``x_in``) into ``dx_in`` (shaped like ``x_in``; channel 3 of an RGB stack is 0), which it returns.  Valid after
+    ``backward_upper`` has left ``dz[1]``; the training backward, its launches and its buffers stay as they are.  Per encoder and per
+    chunk of at most ``chunk_frames`` frames: conv2's input gradient under conv1's ReLU decisions (``geeco_conv3x3_dgrad``, the generic
+    entry: every shape) into a chunk buffer, then ``geeco_conv1_dgrad``.  The chunk bounds the workspace: conv1's pre-activation
+    gradient is 8.4 MB per 256 x 256 frame (805 MB at 96 frames, 8.6 GB for the 1024 frames of a K = 32 batch of 32)."""
+    self.check_input_gradient()
+    chunk = max(1, min(int(chunk_frames), self.Nf))
+    L0, L1 = self.layers[0], self.layers[1]
+    H, W = L0['H'], L0['W']
+    if getattr(self, 'dx_in', None) is None:
+      self.dx_in = torch.zeros_like(self.x_in)
+    if getattr(self, 'dz1_chunk', None) is None or self.dz1_chunk.shape[0] < chunk:
+      self.dz1_chunk = torch.empty(chunk, H, W, L0['Cout'], dtype=torch.float32, device=self.x_in.device)
+    for g in range(self.G):
+      wt = self.wt[1][g] if self.wt[1] is not None else None
+      for f0 in range(0, self.Nf, chunk):
+        n = min(chunk, self.Nf - f0)
+        ops.conv3x3_dgrad_into(self.dz1_chunk, self.dz[1][g][f0:f0 + n], wt, self.acts[0][g][f0:f0 + n], 1, 0, 0, 0, n, L1['H'], L1['W'],
+                               L1['Cin'], L1['Cout'], L1['stride'], ws=self.dws, w=self._w(1, g), gs_w=0)
+        if not ops.conv1_dgrad_into(self.dx_in[g][f0:f0 + n], self.dz1_chunk, self._w(0, g), 1, 0, 0, 0, n, H, W, self.Cin, L0['Cout']):
+          raise RuntimeError('geeco_conv1_dgrad does not serve this conv1')      # (check_input_gradient said it would)
+    return self.dx_in

@@ -757,3 +757,61 @@ class Estimator:
       spec.train_op()
       torch.cuda.synchronize()
       yield {k: v.detach().cpu().numpy().copy() for k, v in spec.predictions.items()}
+
+  def input_gradients(self, input_fn, heads=None, checkpoint_path=None):
+    """d(loss)/d(frames) per batch of ``input_fn``, a generator beside ``predict()`` (saliency maps).  Every batch is
+    (features, labels) of dense float arrays or tensors.  Yields numpy arrays: the gradients of ``_ModelBase.input_gradients`` ('rgb',
+    'target_rgb', 'depth', 'target_depth' as the model has them), 'loss', and the predictions ``predict()`` yields.
+    ``heads``: a subset of the model's head names, e.g. ('cmd_ee',) or ('cmd_grp',): the loss differentiated is the sum of those
+    heads' losses with weight 1 (``LSTMDecoder.select_loss_heads``); None = the training loss.  ``checkpoint_path`` (a checkpoint
+    prefix or a model_dir): parameters from there, in a store of their own, instead of the estimator's.
+    The model of this pass is training-capable but takes no training option, runs eagerly and never calls the optimiser: parameters,
+    optimiser state and the step counter are only read."""
+    cfg = self.params['e2evmc_config']
+    goal = self._model_fn is goal_e2evmc_model_fn
+    if not goal and self._model_fn is not e2evmc_model_fn:
+      raise ValueError('input_gradients: needs an Estimator built on e2evmc_model_fn or goal_e2evmc_model_fn')
+    if self.params.get('shared_frames'):
+      raise ValueError("input_gradients: params['shared_frames'] encodes frame slots, not windows; use dense windows for this pass")
+    dev = self._device()
+    if checkpoint_path is not None:
+      store = graph.build_store(cfg, goal, dev)
+      prefix = _checkpoint_prefix(os.fspath(checkpoint_path))
+      restore_for_inference(store, os.path.dirname(prefix), os.path.basename(prefix))
+    else:
+      if self._store is None:
+        self._store = graph.build_store(cfg, goal, dev, ema=self.options.ema_decay is not None)
+        self._store.initialize(seed=self.config.init_seed)
+      self._restore_once()
+      store = self._store
+    if store.ema is not None:
+      raise ValueError("input_gradients: the estimator's store keeps averaged weights (params['ema_decay']); pass checkpoint_path= to "
+                       "differentiate a checkpoint's parameters")
+    models = {}
+    for batch in input_fn():
+      feats, labels = batch if isinstance(batch, tuple) else (batch, None)
+      for k, v in feats.items():
+        if hasattr(v, 'pointers'):
+          raise ValueError("input_gradients: feature '%s' comes as device windows; this pass takes dense float32 batches" % k)
+      n = int(feats['rgb'].shape[0])
+      if n not in models:
+        ctor = graph.GoalE2EVMC if goal else graph.E2EVMC
+        # built beside the training stack: it re-derives its weight copies on every forward and never becomes the store's primary
+        primary = store.primary_stack
+        models[n] = ctor(cfg, n, dev, training=True, store=store)
+        if primary is None:
+          store.primary_stack = None
+          models[n].enc.lazy_refresh = False
+        models[n].decoder.select_loss_heads(heads)
+      model = models[n]
+      as_t = lambda d: {k: torch.as_tensor(v) for k, v in (d or {}).items()}
+      model.load_batch(as_t(feats), as_t(labels))
+      model.forward(backward_too=True)
+      model.backward()
+      grads = model.input_gradients()
+      torch.cuda.synchronize()
+      model.check_device_errors()
+      out = {k: v.detach().cpu().numpy().copy() for k, v in grads.items()}
+      out['loss'] = float(model.loss)
+      out.update({k: v.detach().cpu().numpy().copy() for k, v in model.predictions().items()})
+      yield out

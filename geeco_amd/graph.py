@@ -285,6 +285,74 @@ class _ModelBase(OptimizerStep):
     if pending or prepare is not None:
       ops.slab_reduce_batch(pending, prepare)
 
+  # -- input gradients: d(loss)/d(frames), for saliency maps ---------------------------------------------
+
+  def check_input_gradients(self):
+    """ValueError, with the reason, unless ``input_gradients`` serves this model."""
+    if not self.training:
+      raise ValueError('input_gradients: the model was built with training=False and has no backward; build it with training=True')
+    if self.shared_frames is not None:
+      raise ValueError('input_gradients: shared_frames encodes frame slots, not windows: a slot\'s gradient is the sum over every window '
+                       'that holds the frame; use a model with dense windows')
+    bound = [k for k, buf in self.inputs.items() if hasattr(buf, 'pointers')]
+    if bound:
+      raise ValueError("input_gradients: input%s %s bound as uint8 window addresses: the gradient is taken with respect to float32 "
+                       "frames; feed dense float32 windows" % ('s' if len(bound) > 1 else '', ', '.join("'%s'" % k for k in bound)))
+    if self.backward_cut != 'full':
+      raise ValueError("input_gradients: backward_cut=%r (lr_multipliers froze the encoder bottom) stops the backward above conv2; "
+                       "the pass needs the full backward" % (self.backward_cut,))
+    self.enc.check_input_gradient()
+
+  def input_gradients(self, chunk_frames=96):
+    """d(loss)/d(image inputs) after ``forward(backward_too=True)`` and ``backward()``: a dict of device tensors shaped like the
+    inputs -- 'rgb' [N][K][H][W][3], 'target_rgb' (goal models), 'depth' / 'target_depth' (RGB-D; views, with the rgb ones, of one
+    4-channel buffer).  Every contribution of a frame is summed: its encoder pass, and each dynamic image it is part of.  Eager
+    launches only; the optimiser is never called and no training buffer is written."""
+    self.check_input_gradients()
+    N, K, H, W, C, HW = self.N, self.K, self.H, self.W, self.C, self.H * self.W
+    dev, f32 = self.device, dict(dtype=torch.float32, device=self.device)
+    dx = self.enc.input_gradient(chunk_frames)
+    # the frames as the forward read them ([N][K][HW][C]); the one-pass RGB-D stage kept no packed copy: pack one now
+    if C == 4 and self.split_rgbd and getattr(self, 'obs4', None) is None:
+      self.obs4, self.tgt4 = torch.empty(N, K, H, W, 4, **f32), torch.empty(N, H, W, 4, **f32)
+    if C == 4 and self.split_rgbd:
+      ops.pack_pixels_into(self.obs4, self.inputs['rgb'], HW * 3, N * K, HW, 3, 4, self.inputs['depth'], HW, 1)
+      ops.pack_pixels_into(self.tgt4, self.inputs['target_rgb'], HW * 3, N, HW, 3, 4, self.inputs['target_depth'], HW, 1)
+      frames, tgt = self.obs4, self.tgt4
+    else:
+      frames, tgt = (self.inputs['rgb'], self.inputs.get('target_rgb')) if C == 3 else (self.obs4, getattr(self, 'tgt4', None))
+    if getattr(self, 'd_frames', None) is None:
+      self.d_frames = torch.zeros(N, K, H, W, C, **f32)
+      self.d_tgt = torch.zeros(N, H, W, C, **f32) if self.goal else None
+      self.dyn_bwd_ws = ops.dynimg_bwd_ws(N, HW, C, dev)
+    df, dt, sK = self.d_frames, self.d_tgt, K * HW * C
+    pack_bwd = lambda dst, g, stride, acc=False: ops.pack_pixels_bwd_into(dst, g, stride, N, HW, C, 4, accumulate=acc)
+    pair_bwd = lambda g, t, acc_tgt: ops.dynimg_bwd_into(df[:, t], g, frames[:, t], 2, N, HW, C, 4, self.dyn_bwd_ws, sK, 0, sK, 0,
+                                                         accumulate=True, frames2=tgt, d_frames2=dt, accumulate2=acc_tgt)
+    if self.mode == 'dynimg':             # geeco-f: x_in = [current frame | buffer image | pair image]
+      ops.dynimg_bwd_into(df, dx[1], frames, K, N, HW, C, 4, self.dyn_bwd_ws, sK, HW * C, sK, HW * C)      # overwrites all K frames
+      pair_bwd(dx[2], K - 1, False)
+      pack_bwd(df[:, K - 1], dx[0], sK, True)
+    elif self.mode == 'seq_dyndiff':      # encoder 0: the frames; encoder 1: the (frame t, target) pair images
+      dxs = dx.view(2, K, N, H, W, 4)
+      for t in range(K):
+        pack_bwd(df[:, t], dxs[0][t], sK)
+        pair_bwd(dxs[1][t], t, t > 0)
+    else:                                 # per-frame controllers, time-major slots; the goal models' slot K = the target
+      dxs = dx[0].view(-1, N, H, W, 4)
+      for t in range(K):
+        pack_bwd(df[:, t], dxs[t], sK)
+      if self.goal:
+        pack_bwd(dt, dxs[K], HW * C)
+    out = {'rgb': df[..., :3]}
+    if self.goal:
+      out['target_rgb'] = dt[..., :3]
+    if C == 4:
+      out['depth'] = df[..., 3:]
+      if self.goal:
+        out['target_depth'] = dt[..., 3:]
+    return out
+
   def _bind_labels(self):
     K, inp = self.K, self.inputs
     ee_last, obj_last = inp['ee_state'][:, K - 1], inp['obj_state'][:, K - 1]   # features[...][:, -1, :3]

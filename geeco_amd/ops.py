@@ -156,6 +156,26 @@ def pack_pixels_into(dst, src, src_sample_stride, N, HW, C1, Cpad, src2=None, sr
                                  _p(dst), _stream()), 'geeco_pack_pixels')
 
 
+def pack_pixels_bwd_into(d_src, d_dst, src_sample_stride, N, HW, C1, Cpad, accumulate=False, d_src2=None, src2_sample_stride=0, C2=0,
+                         accumulate2=False):
+  """The adjoint of pack_pixels_into: d_src[n][p][:C1] (+)= d_dst[n][p][:C1]; d_src2 takes the next C2 channels."""
+  check(_lib().geeco_pack_pixels_bwd(_p(d_dst), _p(d_src), src_sample_stride, 1 if accumulate else 0, _p(d_src2), src2_sample_stride,
+                                     1 if accumulate2 else 0, N, HW, C1, C2, Cpad, _stream()), 'geeco_pack_pixels_bwd')
+
+
+def dynimg_bwd_ws(N, HW, C, device):
+  return torch.empty((int(_lib().geeco_dynimg_bwd_ws_bytes(N, HW, C)) + 3) // 4, dtype=torch.float32, device=device)
+
+
+def dynimg_bwd_into(d_frames, g, frames, K, N, HW, C, Cpad, ws, sample_stride, frame_stride, d_sample_stride, d_frame_stride,
+                    accumulate=False, frames2=None, d_frames2=None, accumulate2=False):
+  """The adjoint of dynimg_into: g [N][HW][Cpad] (gradient of the normalised image) -> d_frames[n][t] (+)= alpha_t dD[n], and in the
+  two-frame form d_frames2[n] (+)= alpha_1 dD[n] (include/geeco_hip.h: the tie rule, the summation order)."""
+  check(_lib().geeco_dynimg_bwd(_p(g), _p(frames), _p(frames2), sample_stride, frame_stride, ctypes.cast(_alpha_buf(K), ctypes.c_void_p),
+                                N, K, HW, C, Cpad, _p(d_frames), d_sample_stride, d_frame_stride, 1 if accumulate else 0, _p(d_frames2),
+                                1 if accumulate2 else 0, _p(ws), _stream()), 'geeco_dynimg_bwd')
+
+
 def gather_windows_into(out, src, starts_dev, N, K, frame_elems, divisor=1.0):
   """out[n][k] <- src[starts[n] + k] / divisor for an episode resident in HBM (uint8 or float32 frames)."""
   assert src.is_cuda and src.dtype in (torch.uint8, torch.float32) and starts_dev.dtype == torch.int32
@@ -316,6 +336,16 @@ def conv3x3_fwd_ws_bytes(G, N, H, W, Cin, Cout, stride):
 def conv3x3_dgrad_into(dx, dz, wt, ymask, G, gs_dz, gs_wt, gs_dx, N, H, W, Cin, Cout, stride, ws=None, w=None, gs_w=0):
   check(_lib().geeco_conv3x3_dgrad(_p(dz), _p(w), _p(wt), _p(ymask), _p(dx), G, gs_dz, gs_w, gs_wt, gs_dx, N, H, W,
                                    Cin, Cout, stride, _p(ws), _stream()), 'geeco_conv3x3_dgrad')
+
+
+def conv1_dgrad_into(dx, dz1, w1, G, gs_dz, gs_w, gs_dx, F, H, W, Cin, Cout=32):
+  """conv1's input gradient: dx [G][F][H][W][4] <- dz1 [G][F][H][W][32], w1 the [3][3][Cin][32] variable (geeco_conv1_dgrad).  Returns
+  False, nothing launched, for a layer the kernel was not built for."""
+  rc = _lib().geeco_conv1_dgrad(_p(dz1), _p(w1), _p(dx), G, gs_dz, gs_w, gs_dx, F, H, W, Cin, Cout, _stream())
+  if rc == _native.GEECO_ENOSUP:
+    return False
+  check(rc, 'geeco_conv1_dgrad')
+  return True
 
 
 def conv3x3_dgrad_ws_bytes(G, N, H, W, Cin, Cout, stride):

@@ -32,7 +32,7 @@ extern "C" {
  * geeco_adam_prepare_schedule, geeco_slab_reduce_batch_prepare_schedule, geeco_lr_schedule_eval, geeco_guard_decide,
  * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled, geeco_variable_stats_ws_bytes, geeco_variable_stats,
  * geeco_heads_loss_shaped_fwd_bwd, geeco_lstm_step_heads_shaped_fwd_bwd, geeco_loss_shaping_sizeof,
- * geeco_grad_accumulate_segments */
+ * geeco_grad_accumulate_segments, geeco_conv1_dgrad, geeco_pack_pixels_bwd, geeco_dynimg_bwd_ws_bytes, geeco_dynimg_bwd */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -767,6 +767,40 @@ int geeco_variable_stats(const float* p, const float* m, const float* v, const g
 int geeco_grad_accumulate_segments(float* acc, const geeco_adam_segment* segs, int nseg, int64_t n, int overwrite, void* stream);
 /* sum of squares of an arena (for the L2 regularisation loss term); out[0] overwritten. */
 int geeco_sumsq(const float* p, int64_t n, float* out, void* stream);
+
+/* ---- input gradients: d(loss)/d(frames), for saliency maps (additive within ABI 7) ----------------------------
+ * The training backward stops at conv1, whose input is data.  These entry points carry it on to the frames; no training step
+ * launches them.  The reference has no counterpart: they are what tf.gradients(loss, features['rgb']) would compute. */
+/* conv1's input gradient, Conv2DBackpropInput of the 3 x 3, stride-1, SAME layer with 32 output channels:
+ *   dx[f][y][x][ci] = sum_{ky,kx,co} dz1[f][y+1-ky][x+1-kx][co] * w1[ky][kx][ci][co]
+ * dz1 [G][F][H][W][32] (conv1's ReLU gradient already applied), w1 [G][3][3][Cin][32] = the variable itself (HWIO, Cin 3 or 4,
+ * no padded copy), dx [G][F][H][W][4]; channel 3 is written as 0 when Cin == 3.  No ReLU mask (the input is data).  Any
+ * H, W >= 1; F and G <= 65535; dz1 / dx 16-byte aligned.  VALU FMAs, dz1 staged through LDS once per 8 x 32 tile, one fmaf chain
+ * per output (ky, kx, co ascending).  GEECO_ENOSUP, having launched nothing, for any other Cin or Cout. */
+int geeco_conv1_dgrad(const float* dz1, const float* w1, float* dx, int groups, int64_t gs_dz, int64_t gs_w, int64_t gs_dx,
+                      int F, int H, int W, int Cin, int Cout, void* stream);
+/* The adjoint of geeco_pack_pixels: d_src[n][p][0..C1) takes d_dst[n][p][0..C1) (d_dst [N][HW][Cpad]; accumulate != 0: is added
+ * to, one float32 addition), at its own sample stride; d_src2 (RGB-D's second tensor; may be NULL, as may d_src) takes the
+ * channels C1..C1+C2 the same way under accumulate2.  The padding channels have no adjoint. */
+int geeco_pack_pixels_bwd(const float* d_dst, float* d_src, int64_t src_sample_stride, int accumulate, float* d_src2,
+                          int64_t src2_sample_stride, int accumulate2, int N, int64_t HW, int C1, int C2, int Cpad,
+                          void* stream);
+/* The adjoint of geeco_dynimg_fwd, both forms (K frames with sample / frame strides; K = 2 with frames2).  g [N][HW][Cpad] = the
+ * gradient with respect to the normalised image (channels >= C are ignored); frames / frames2 / strides / alpha_host as the
+ * forward took them: D = sum_t alpha_t X_t is recomputed in the forward's summation order, so min / max sit where the forward
+ * found them.  Per sample, r = max - min + 1e-6, out = (D - min) / r:
+ *   dD_i = g_i / r + [D_i == min] (sum_j g_j (out_j - 1) / r) / n_min - [D_i == max] (sum_j g_j out_j / r) / n_max
+ * n_min / n_max = the number of elements equal to the extremum: TF 1.15's reduce_min / reduce_max gradient, which shares evenly
+ * among ties.  d_frames[n][t] (+)= alpha_t dD[n] at d_sample_stride / d_frame_stride (accumulate), and in the two-frame form
+ * d_frames[n] (+)= alpha_0 dD[n], d_frames2[n] (+)= alpha_1 dD[n] (dense [N][HW * C]; accumulate2); either destination may be
+ * NULL.  Two launches (reduce, apply); ws: geeco_dynimg_bwd_ws_bytes(N, HW, C) bytes of per-block records.  No atomics; the sums
+ * run in one fixed order (a thread over its elements ascending, the lanes of a wave in a fixed butterfly, the four waves
+ * ascending, the blocks ascending), so two runs are bitwise equal. */
+int64_t geeco_dynimg_bwd_ws_bytes(int N, int64_t HW, int C);
+int geeco_dynimg_bwd(const float* g, const float* frames, const float* frames2, int64_t sample_stride, int64_t frame_stride,
+                     const float* alpha_host, int N, int K, int64_t HW, int C, int Cpad, float* d_frames,
+                     int64_t d_sample_stride, int64_t d_frame_stride, int accumulate, float* d_frames2, int accumulate2,
+                     void* ws, void* stream);
 
 #ifdef __cplusplus
 }
