@@ -95,6 +95,7 @@ SIGNATURES = {
     'geeco_gather_windows_by_address': (_I, [_P, _P, _I, _I, _L, _P, _P]),
     'geeco_gather_windows_augmented': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     'geeco_gather_windows_scene': (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P]),      # additive within ABI 7
+    'geeco_gather_windows_frames': (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P]),     # additive within ABI 7
     'geeco_predict_range_check': (_I, [_P, _I, _L, _I, _F, _F, _P, _P]),
     'geeco_predict_push_dense': (_I, [_P, _I, _P, _P, _P, _I, _I, _L, _I, _I, _P, _P, _P, _P]),
     'geeco_predict_push_ring': (_I, [_P, _P, _P, _P, _I, _I, _L, _I, _P, _P, _P, _P, _P]),

@@ -254,7 +254,8 @@ extern "C" int geeco_gather_windows_augmented(const int64_t* addr, const int32_t
 // (e / 4, k, n, tag) for element offset e of the frame: z depends on (key, tag, n, k, e) alone, whatever path or thread made it.
 // sigma == 0 skips the noise step (no clamp: the output is v2 itself).  The gather is the one above, duplicated: moved into a
 // function shared by both kernels it changed the merged kernel's gfx950 code, so that kernel's source stays as it
-// is.  The rectangles and the key are uniform per block (scalar loads); no address is formed from a rectangle.  Grid, thread
+// is.  This copy is a template over the source of a block's frame address, shared with the frame-table builder at the end of the
+// file; its <3, WindowFrames> instance is, instruction for instruction, the kernel it was before.  The rectangles and the key are uniform per block (scalar loads); no address is formed from a rectangle.  Grid, thread
 // ownership and stores as above; a thread's four elements are e = i4 .. i4 + 3 on either path, so ONE Philox call serves them.
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
                                               unsigned x[4]) {
@@ -304,33 +305,56 @@ __device__ __forceinline__ float scene_occlude(float v, const SceneRect q, unsig
   return in ? (c == 0 ? q.r : (c == 1 ? q.g : q.b)) : v;
 }
 
+// Two sources of a block's frame address: WindowFrames, the K consecutive frames at addr[n] (the scene builder), and TableFrames,
+// the frame at addr[n][k] (the frame-table builder below).  Everything behind the address is ONE body: conversion, shift test,
+// tint, rectangles, Philox / Box-Muller.  Every load-width decision of that body is taken on the element's own address (or on
+// RW % 4, a launch constant), never on the window's first frame, so frames of one window may lie at any alignment of their kind.
+struct WindowFrames {
+  static constexpr bool kTable = false;
+  __device__ static unsigned long long frame(const long long* addr, int n, int k, int K, unsigned fe, bool f32) {
+    return (unsigned long long)addr[n] + (unsigned long long)k * fe * (f32 ? 4u : 1u);
+  }
+};
+struct TableFrames {
+  static constexpr bool kTable = true;
+  __device__ static unsigned long long frame(const long long* addr, int n, int k, int K, unsigned fe, bool f32) {
+    return (unsigned long long)addr[(long long)n * K + k];
+  }
+};
+
+// C = 3: the whole scene chain.  C = 1 (TableFrames only): shift and tint of channel 0; no rectangles, no noise (the entry point
+// refuses them).  ``shift`` may be null under TableFrames alone (no shift).  Extras = false: an instance without the rectangle and
+// noise steps, for launches that carry neither -- the tests for them and the registers they hold cost the bare gather a fifth of
+// its time.
+template <int C, typename Frames, bool Extras>
 __global__ __launch_bounds__(256) void gather_windows_scene_kernel(const long long* __restrict__ addr, const int* __restrict__ kind,
                                                                    const int* __restrict__ shift, const float* __restrict__ colour,
                                                                    const int* __restrict__ occ_rect,
                                                                    const float* __restrict__ occ_colour,
                                                                    const unsigned* __restrict__ noise_key, float sigma,
                                                                    unsigned tag, int K, int H, int W, float* __restrict__ out) {
-  constexpr int C = 3;
   const int n = blockIdx.z, k = blockIdx.y;
   const unsigned RW = (unsigned)W * (unsigned)C, fe = RW * (unsigned)H;      // (the entry point checked H * W * C < 2^31)
   const unsigned i4 = (blockIdx.x * 256u + threadIdx.x) * 4u;
   if (i4 >= fe) return;
   const bool f32 = kind[n] == 1;
-  const long long dy = shift[2 * n], dxe = (long long)shift[2 * n + 1] * C;   // the column shift in ELEMENTS of a row
-  const unsigned long long frame = (unsigned long long)addr[n] + (unsigned long long)k * fe * (f32 ? 4u : 1u);
+  const bool shifted = !Frames::kTable || shift != nullptr;
+  const long long dy = shifted ? shift[2 * n] : 0, dxe = shifted ? (long long)shift[2 * n + 1] * C : 0;   // the column shift in ELEMENTS of a row
+  const unsigned long long frame = Frames::frame(addr, n, k, K, fe, f32);
   float* o = out + ((long long)n * K + k) * fe + i4;
   const bool on = colour != nullptr;
   float g0 = 1.f, g1 = 1.f, g2 = 1.f, b0 = 0.f, b1 = 0.f, b2 = 0.f;
   if (on) {
     const float* col = colour + (long long)n * 2 * C;       // gain[C], bias[C]
-    g0 = col[0], g1 = col[1], g2 = col[2], b0 = col[3], b1 = col[4], b2 = col[5];
+    g0 = col[0], b0 = col[C];
+    if (C == 3) g1 = col[1], g2 = col[2], b1 = col[4], b2 = col[5];
   }
   auto tint = [=](float v, unsigned c) { return aug_tint(v, c, on, g0, g1, g2, b0, b1, b2); };
-  const bool occluded = occ_rect != nullptr;
+  const bool occluded = Extras && C == 3 && occ_rect != nullptr;
   const SceneRect q0 = scene_rect(occ_rect, occ_colour, n, 0), q1 = scene_rect(occ_rect, occ_colour, n, 1),
                   q2 = scene_rect(occ_rect, occ_colour, n, 2), q3 = scene_rect(occ_rect, occ_colour, n, 3);
   float z[4] = {0.f, 0.f, 0.f, 0.f};
-  const bool noisy = sigma != 0.f;
+  const bool noisy = Extras && C == 3 && sigma != 0.f;
   if (noisy) {
     unsigned x[4];
     philox4x32_10(i4 >> 2, (unsigned)k, (unsigned)n, tag, noise_key[0], noise_key[1], x);
@@ -352,13 +376,13 @@ __global__ __launch_bounds__(256) void gather_windows_scene_kernel(const long lo
       const unsigned y = (i4 + j) / RW, r = (i4 + j) - y * RW;
       const long long sy = (long long)y - dy, sr = (long long)r - dxe;
       const bool inside = sy >= 0 && sy < H && sr >= 0 && sr < (long long)RW;
-      o[j] = finish(inside ? tint(aug_load(frame, f32, sy * RW + sr), r % 3u) : 0.f, y, r, j);
+      o[j] = finish(inside ? tint(aug_load(frame, f32, sy * RW + sr), C == 3 ? r % 3u : 0u) : 0.f, y, r, j);
     }
     return;
   }
   const unsigned y = i4 / RW, r = i4 - y * RW;      // r % 4 == 0 and r + 3 < RW: the group lies in row y
   const long long sy = (long long)y - dy, sr = (long long)r - dxe;
-  const unsigned c0 = r % 3u;
+  const unsigned c0 = C == 3 ? r % 3u : 0u;
   float e[4] = {0.f, 0.f, 0.f, 0.f};
   if (sy >= 0 && sy < H && sr + 3 >= 0 && sr < (long long)RW) {      // at least one source inside the frame
     const long long s0 = sy * RW + sr;
@@ -386,11 +410,11 @@ __global__ __launch_bounds__(256) void gather_windows_scene_kernel(const long lo
         }
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) e[j] = tint(e[j], (c0 + j) % 3u);
+      for (int j = 0; j < 4; ++j) e[j] = tint(e[j], C == 3 ? (c0 + j) % 3u : 0u);
     } else {                                                         // the group crosses the left or right edge of the image
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (sr + j >= 0 && sr + j < (long long)RW) e[j] = tint(aug_load(frame, f32, s0 + j), (c0 + j) % 3u);
+        if (sr + j >= 0 && sr + j < (long long)RW) e[j] = tint(aug_load(frame, f32, s0 + j), C == 3 ? (c0 + j) % 3u : 0u);
     }
   }
 #pragma unroll
@@ -418,8 +442,50 @@ extern "C" int geeco_gather_windows_scene(const int64_t* addr, const int32_t* ki
                       (reinterpret_cast<uintptr_t>(noise_key) & 3) == 0,
                   "gather_windows_scene: the tables must be aligned for their element types");
   dim3 grid((unsigned)cdiv64(frame_elems, 1024), (unsigned)K, (unsigned)N);
-  hipLaunchKernelGGL(gather_windows_scene_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const long long*)addr, kind, shift,
+  hipLaunchKernelGGL((gather_windows_scene_kernel<3, WindowFrames, true>), grid, dim3(256), 0, (hipStream_t)stream, (const long long*)addr, kind, shift,
                      colour, occ_rect, occ_colour, noise_key, sigma, (unsigned)tag, K, H, W, out);
+  GEECO_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- frame-table builder: the scene builder following ONE ADDRESS PER FRAME (camera frame drops and latency) ------
+// out[n][k] is built from the frame at frame_addr[n][k]: a window whose slot k shows an earlier frame (a dropped frame delivered
+// again, a camera that lags the encoders) is the same gather with another address source (TableFrames above); the body, and with
+// it every value, is the scene builder's.  The table is read when the kernel runs.  Alignment is a property of the FRAME here: a
+// uint8 frame of H * W * 3 bytes that is no multiple of 4 puts consecutive frames at different residues, and a lagged or dropped
+// slot points where its neighbours do not, so nothing about slot 0 may decide for slot k -- the body takes each load width from
+// the element's own address and blockIdx = (unit, k, n) keeps that choice uniform per block wherever the frame base alone decides
+// it.  The noise counter is (e / 4, k, n, tag) with k the OUTPUT slot: a frame shown twice gets fresh sensor noise each time.
+extern "C" int geeco_gather_windows_frames(const int64_t* frame_addr, const int32_t* kind, const int32_t* shift, const float* colour,
+                                           const int32_t* occ_rect, const float* occ_colour, const uint32_t* noise_key, float sigma,
+                                           int tag, int N, int K, int H, int W, int C, float* out, void* stream) {
+  GEECO_CHECK_ARG(frame_addr && kind && out, "gather_windows_frames: null pointer");
+  GEECO_CHECK_ARG(N >= 1 && N <= 65535 && K >= 1 && K <= 65535, "gather_windows_frames: N=%d, K=%d outside 1..65535", N, K);
+  GEECO_CHECK_ARG(H >= 1 && W >= 1, "gather_windows_frames: H=%d, W=%d must be >= 1", H, W);
+  GEECO_CHECK_ARG(C == 1 || C == 3, "gather_windows_frames: C=%d must be 1 or 3", C);
+  const int64_t frame_elems = (int64_t)H * W * C;
+  GEECO_CHECK_ARG(frame_elems <= 0x7fffffffLL, "gather_windows_frames: a frame of %lld elements is too large", (long long)frame_elems);
+  GEECO_CHECK_ARG(sigma >= 0.f && sigma < 1.f, "gather_windows_frames: sigma=%g outside [0, 1)", (double)sigma);
+  GEECO_CHECK_ARG(tag == 0 || tag == 1, "gather_windows_frames: tag=%d must be 0 (rgb) or 1 (target_rgb)", tag);
+  GEECO_CHECK_ARG((occ_rect == nullptr) == (occ_colour == nullptr), "gather_windows_frames: occ_rect and occ_colour must be null together");
+  GEECO_CHECK_ARG(noise_key || sigma == 0.f, "gather_windows_frames: sigma=%g needs a noise key", (double)sigma);
+  GEECO_CHECK_ARG(C == 3 || (!occ_rect && sigma == 0.f), "gather_windows_frames: C=%d takes the shift only (occluders and noise are built for RGB streams)", C);
+  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "gather_windows_frames: out must be 16-byte aligned");
+  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(frame_addr) & 7) == 0 && (reinterpret_cast<uintptr_t>(kind) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(shift) & 3) == 0 && (reinterpret_cast<uintptr_t>(colour) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(occ_rect) & 3) == 0 && (reinterpret_cast<uintptr_t>(occ_colour) & 3) == 0 &&
+                      (reinterpret_cast<uintptr_t>(noise_key) & 3) == 0,
+                  "gather_windows_frames: the tables must be aligned for their element types");
+  dim3 grid((unsigned)cdiv64(frame_elems, 1024), (unsigned)K, (unsigned)N);
+  if (C == 3 && (occ_rect || sigma != 0.f))
+    hipLaunchKernelGGL((gather_windows_scene_kernel<3, TableFrames, true>), grid, dim3(256), 0, (hipStream_t)stream, (const long long*)frame_addr,
+                       kind, shift, colour, occ_rect, occ_colour, noise_key, sigma, (unsigned)tag, K, H, W, out);
+  else if (C == 3)
+    hipLaunchKernelGGL((gather_windows_scene_kernel<3, TableFrames, false>), grid, dim3(256), 0, (hipStream_t)stream, (const long long*)frame_addr,
+                       kind, shift, colour, nullptr, nullptr, nullptr, 0.f, (unsigned)tag, K, H, W, out);
+  else
+    hipLaunchKernelGGL((gather_windows_scene_kernel<1, TableFrames, false>), grid, dim3(256), 0, (hipStream_t)stream, (const long long*)frame_addr,
+                       kind, shift, colour, nullptr, nullptr, nullptr, 0.f, (unsigned)tag, K, H, W, out);
   GEECO_LAUNCH_CHECK();
   return 0;
 }

@@ -25,9 +25,13 @@ class WindowAugment:
   moves by the same shift[i], the RGB streams are tinted by the same colour[i], depth streams are only moved.
   The scene extras (RGB streams only, each optional): ``occ_rect`` int32 [n][4][4] = (y0, x0, h, w) of up to four
   rectangles per window in output coordinates with ``occ_colour`` float32 [n][4][3] (an all-zero slot is empty), and the sensor
-  noise ``sigma`` in (0, 1) with ``noise_key``, the two uint32 words of the batch's Philox key."""
+  noise ``sigma`` in (0, 1) with ``noise_key``, the two uint32 words of the batch's Philox key.
+  The time extra (optional): ``frame_src`` int32 [n][K], the recorded frame each slot of window i shows as an offset
+  from the window's start (None or arange(K): K consecutive frames).  Only the camera streams of the observation follow it
+  (``DeviceWindows.timed``: 'rgb' and 'depth'); with zero shifts and the neutral colour row (gain 1, bias 0) it is all the object
+  carries."""
 
-  def __init__(self, shift, colour, occ_rect=None, occ_colour=None, noise_key=None, sigma=0.0):
+  def __init__(self, shift, colour, occ_rect=None, occ_colour=None, noise_key=None, sigma=0.0, frame_src=None):
     self.shift = np.ascontiguousarray(shift, np.int32).reshape(-1, 2)
     self.colour = np.ascontiguousarray(colour, np.float32).reshape(-1, 6)
     if len(self.shift) != len(self.colour):
@@ -47,6 +51,11 @@ class WindowAugment:
       if noise_key is None:
         raise ValueError('WindowAugment: sigma > 0 needs a noise key')
       self.noise_key = np.ascontiguousarray(noise_key, np.uint32).reshape(2)
+    self.frame_src = None
+    if frame_src is not None:
+      self.frame_src = np.ascontiguousarray(frame_src, np.int32)
+      if self.frame_src.ndim != 2 or len(self.frame_src) != len(self.shift):
+        raise ValueError('WindowAugment: frame_src of shape %s for %d windows' % (self.frame_src.shape, len(self.shift)))
 
   def __len__(self):
     return len(self.shift)
@@ -58,6 +67,7 @@ class WindowAugment:
 
 
 SCENE_TAGS = {'rgb': 0, 'target_rgb': 1}      # the noise generator's stream number of an RGB feature (counter word 3)
+TIMED_KEYS = ('rgb', 'depth')      # the features whose slots follow WindowAugment.frame_src: the camera delivers both together
 
 
 class DeviceWindows:
@@ -74,6 +84,7 @@ class DeviceWindows:
     self.scattered = False  # built by the shuffling assembler (shuffle_windows): about one episode per window, see window_table
     self.augment = None     # a WindowAugment shared with the other streams of the batch: the windows are these, transformed
     self.scene_tag = 0      # SCENE_TAGS of the feature this stream is (the sensor noise of 'rgb' and 'target_rgb' differs)
+    self.timed = False      # a camera stream of the observation (TIMED_KEYS): its slots follow ``augment.frame_src``
 
   def add(self, frames_dev, starts, divisor=None):
     """``divisor``: what the gather divides this segment's frames by (default: the constructor's).  One batch can hold
@@ -108,6 +119,11 @@ class DeviceWindows:
       return None
     key = None if aug.noise_key is None else aug.noise_key.view(np.int32)
     return aug.occ_rect, aug.occ_colour, key, aug.sigma, self.scene_tag
+
+  @property
+  def frame_src(self):
+    """int32 [n][K] frame offsets of this stream's slots, or None: the windows are K consecutive frames."""
+    return self.augment.frame_src if self.augment is not None and self.timed else None
 
   def __len__(self):
     return self.n
@@ -185,6 +201,33 @@ class DeviceWindows:
     bounds and device checks as ``addresses``."""
     return self._window_addresses(resolve_device(device), 'window_table')[:2]
 
+  def frame_addresses(self, device):
+    """(addresses int64 [n][K], kinds int32 [n]) for ops.gather_windows_frames_into: slot k of window i shows the frame
+    ``max(start_i + frame_src[i][k], 0)`` of its episode (clamped at the episode's first frame, where the scene is at rest);
+    without ``frame_src`` the consecutive table, ``window_table`` spread over K.  EVERY resulting frame index is checked against
+    the segment's resident frames here, on the host, before anything is queued (IndexError): an out-of-range gather is a GPU
+    fault.  uint8 frames may lie at any address, float32 frames must be 4-byte aligned.  Residency, kind and device checks as
+    ``window_table``."""
+    src = self.frame_src
+    if src is None:
+      src = np.broadcast_to(np.arange(self.K, dtype=np.int32), (self.n, self.K))
+    if src.shape != (self.n, self.K):
+      raise ValueError('DeviceWindows.frame_addresses: frame_src of shape %s on %d windows of %d frames' % (src.shape, self.n, self.K))
+    addr, kinds = np.empty((self.n, self.K), np.int64), np.empty(self.n, np.int32)
+    off = 0
+    for frames_dev, starts, _, kind, frame_bytes in self._checked_segments(resolve_device(device), 'frame_addresses'):
+      sl = slice(off, off + len(starts))
+      idx = np.maximum(starts.astype(np.int64)[:, None] + src[sl].astype(np.int64), 0)
+      T = frames_dev.shape[0]
+      if idx.size and int(idx.max()) >= T:
+        raise IndexError('DeviceWindows.frame_addresses: frame %d outside the %d resident frames' % (int(idx.max()), T))
+      if kind == 'f32' and frames_dev.data_ptr() % 4:
+        raise ValueError('DeviceWindows.frame_addresses: float32 frames at an address that is no multiple of 4')
+      addr[sl] = frames_dev.data_ptr() + idx * frame_bytes
+      kinds[sl] = kind == 'f32'
+      off += len(starts)
+    return addr, kinds
+
   def frame_table(self, capacity, targets=None, device=None):
     """The batch's DISTINCT frames, each once (shared-frame training, graph.py ``shared_frames``): returns
     (addresses int64 [capacity], index int32 [n][K], target_index int32 [n] or None, used).  ``addresses[index[n][t]]`` is the
@@ -229,7 +272,8 @@ class DeviceWindows:
     """out [n][K][*frame_shape] <- the windows, one geeco_gather_windows launch per segment.  Every segment is checked on the
     host (residency, device, bounds) before the first launch is queued: an out-of-range gather is a GPU fault.  Augmented
     windows: ONE geeco_gather_windows_augmented launch behind four small copies of its tables (the feed's 'dense_augmented'
-    form sends them in the step's one block instead); geeco_gather_windows_scene when ``scene_tables()`` has extras."""
+    form sends them in the step's one block instead); geeco_gather_windows_scene when ``scene_tables()`` has extras;
+    geeco_gather_windows_frames, with whatever of those tables the draws carry, when ``frame_src`` is set."""
     import torch
     from . import ops
     fe = int(np.prod(self.frame_shape))
@@ -238,7 +282,12 @@ class DeviceWindows:
       addr, kinds = self.window_table(out.device)
       up = lambda a: None if a is None else torch.from_numpy(a).to(out.device, non_blocking=True)
       scene = self.scene_tables()
-      if scene is None:
+      if self.frame_src is not None:
+        addr, kinds = self.frame_addresses(out.device)
+        occ_rect, occ_colour, key, sigma, tag = scene if scene is not None else (None, None, None, 0.0, self.scene_tag)
+        ops.gather_windows_frames_into(out, up(addr), up(kinds), up(shift), up(colour), up(occ_rect), up(occ_colour), up(key), sigma,
+                                       tag, self.n, self.K, *self.frame_shape)
+      elif scene is None:
         ops.gather_windows_augmented_into(out, up(addr), up(kinds), up(shift), up(colour), self.n, self.K, *self.frame_shape)
       else:
         occ_rect, occ_colour, key, sigma, tag = scene

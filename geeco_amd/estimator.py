@@ -556,6 +556,9 @@ class Estimator:
       scene = next((v.augment.scene for v in feats.values() if isinstance(v, DeviceWindows) and v.augmented), None)
       if scene is not None:
         key += ('scene:' + scene,)
+      # ... and per-frame address tables when the draws carry frame sources (frame drops, camera lag: DESIGN 5.26)
+      if any(isinstance(v, DeviceWindows) and v.frame_src is not None for v in feats.values()):
+        key += ('frames',)
     if key in self._specs:
       return self._specs[key]
     shared = self.params.get('shared_frames')

@@ -110,6 +110,10 @@ class WindowFeed:
       Such a slot is never ``u8``: augmented windows exist only as dense windows.  An RGB stream whose draws carry scene extras
       (``DeviceWindows.scene_tables()``: occluders, sensor noise) is filled by ONE geeco_gather_windows_scene launch
       instead; the rectangles, their colours and the noise key ride in the arena too, sigma and the tag are launch arguments.
+    * 'dense_frames' (``dense()`` of an augmented slot whose first batch carries frame sources, ``DeviceWindows.frame_src``: frame
+      drops and camera lag): that buffer filled by ONE geeco_gather_windows_frames launch.  Its [n][K] table of
+      frame addresses rides in the arena in place of the [n] window table, next to whichever of the tables above the draws
+      carry: no copy and no launch more than 'dense_augmented'.  A batch without ``frame_src`` sends the consecutive table.
     * 'frame_table' (``frame_table()``, models built with shared_frames=F): the batch's distinct frames, see there."""
 
   def __init__(self, windows, arena, key, shared_frames=None, shared_targets=None):
@@ -121,7 +125,8 @@ class WindowFeed:
     self.scattered, self.augmented = bool(getattr(windows, 'scattered', False)), getattr(windows, 'augment', None) is not None
     self.u8 = windows.is_u8() and not self.augmented       # the slot can offer ``pointers()``
     self.shape = tuple(windows.shape)
-    # 'pointers', 'dense', 'dense_by_address', 'dense_augmented' or 'frame_table' once the model chose
+    self.frames = getattr(windows, 'frame_src', None) is not None      # the slot follows one address per FRAME
+    # 'pointers', 'dense', 'dense_by_address', 'dense_augmented', 'dense_frames' or 'frame_table' once the model chose
     self.form = None
     self.table = self.buffer = None
     # frame-table slots reserved in the arena (None: built without shared_frames) / in use (``frame_table()`` may take fewer)
@@ -144,7 +149,7 @@ class WindowFeed:
     if self.u8:
       arena.reserve(key, (self.n,), np.int64)
     if self.scattered or self.augmented:
-      arena.reserve(key + ('window_addr',), (self.n,), np.int64)
+      arena.reserve(key + ('window_addr',), (self.n, self.K) if self.frames else (self.n,), np.int64)
       arena.reserve(key + ('window_kind',), (self.n,), np.int32)
     if self.augmented:
       windows.augment_tables()                      # (raises on frames that are not [H, W, 3] / [H, W, 1])
@@ -194,7 +199,7 @@ class WindowFeed:
 
   def dense(self):
     import torch
-    self._choose('dense_augmented' if self.augmented else 'dense_by_address' if self.scattered else 'dense')
+    self._choose('dense_frames' if self.frames else 'dense_augmented' if self.augmented else 'dense_by_address' if self.scattered else 'dense')
     if self.buffer is None:
       self.buffer = torch.empty(self.shape, dtype=torch.float32, device=self.device)
     return self.buffer
@@ -222,7 +227,10 @@ class WindowFeed:
     windows.materialize_into(self.buffer.view((self.n, self.K) + self.frame_shape))
 
   def _feed_dense_by_address(self, windows, batch):
-    addr, kinds = windows.window_table(self.device)
+    if getattr(windows, 'frame_src', None) is not None and not self.frames:
+      raise RuntimeError('WindowFeed: a batch with frame sources in a slot built for consecutive windows (the Estimator keys its '
+                         'models by them)')
+    addr, kinds = windows.frame_addresses(self.device) if self.frames else windows.window_table(self.device)
     self.arena.write(self.key + ('window_addr',), addr)
     self.arena.write(self.key + ('window_kind',), kinds)
     self._live.append(windows)
@@ -246,6 +254,8 @@ class WindowFeed:
       if noise_key is not None:
         self.arena.write(self.key + ('aug_noise_key',), noise_key)
       self._scene_args = (sigma, tag)
+
+  _feed_dense_frames = _feed_dense_augmented      # the same tables; _feed_dense_by_address writes the [n][K] one
 
   def _feed_frame_table(self, windows, batch):
     targets = None
@@ -275,7 +285,11 @@ class WindowFeed:
       self._window_tables = tuple(view(name) for name in ('window_addr', 'window_kind', 'aug_shift', 'aug_colour', 'aug_occ_rect',
                                                           'aug_occ_colour', 'aug_noise_key'))
     addr, kind, shift, colour, occ_rect, occ_colour, noise_key = self._window_tables
-    if self.form == 'dense_augmented' and self.scene is not None:
+    if self.form == 'dense_frames':
+      sigma, tag = self._scene_args if self.scene is not None else (0.0, 0)
+      ops.gather_windows_frames_into(self.buffer, addr, kind, shift, colour, occ_rect, occ_colour, noise_key, sigma, tag, self.n, self.K,
+                                     *self.frame_shape)
+    elif self.form == 'dense_augmented' and self.scene is not None:
       ops.gather_windows_scene_into(self.buffer, addr, kind, shift, colour, occ_rect, occ_colour, noise_key, *self._scene_args,
                                     self.n, self.K, *self.frame_shape)
     elif self.form == 'dense_augmented':

@@ -25,7 +25,7 @@ import numpy as np
 
 from . import tfrecord
 # what is not the reader keeps resolving from here (none of these modules imports this one when it loads)
-from .device_windows import DeviceWindows, EPISODE_CACHE, EpisodeCache, SCENE_TAGS, WindowAugment, _PINNED, _PinnedPool, episode_to_device, resolve_device  # noqa: F401
+from .device_windows import DeviceWindows, EPISODE_CACHE, EpisodeCache, SCENE_TAGS, TIMED_KEYS, WindowAugment, _PINNED, _PinnedPool, episode_to_device, resolve_device  # noqa: F401
 from .feed import FeedArena, WindowFeed  # noqa: F401
 from .synthetic import synthetic_batches, synthetic_from_spec, synthetic_scene_frames, write_episode, write_synthetic_dataset  # noqa: F401
 
@@ -314,6 +314,8 @@ def _assemble_picks(picks, K):
 AUGMENT_STREAM = 0x617567      # third word of the augmentation generator's seed: a stream apart from the file order's and the shuffle's
 AUGMENT_SCENE_STREAM = 0x7363656e      # ... and of the scene draws' generator (occluders, noise key): the shift / colour draws stay put
 AUGMENT_SCENE_KEYS = ('noise', 'occlude', 'occlude_size')      # validated by check_augment_scene
+AUGMENT_TIME_STREAM = 0x74696d65      # ... and of the time draws' generator (frame lag, frame drops): every other draw stays put
+AUGMENT_TIME_KEYS = ('frame_drop', 'frame_lag')      # validated by check_augment_time
 OCCLUDE_MAX = 4      # rectangle slots per window (include/geeco_hip.h: geeco_gather_windows_scene)
 
 
@@ -325,8 +327,9 @@ def check_augment(augment, hw=None):
   if not isinstance(augment, dict):
     raise ValueError('augment must be None or dict(shift=S, gain=g, bias=b), got %r' % (augment,))
   for k in augment:
-    if k not in ('shift', 'gain', 'bias') + AUGMENT_SCENE_KEYS:
-      raise ValueError("augment: unknown key %r (the keys are 'shift', 'gain', 'bias', 'noise', 'occlude' and 'occlude_size')" % (k,))
+    if k not in ('shift', 'gain', 'bias') + AUGMENT_SCENE_KEYS + AUGMENT_TIME_KEYS:
+      raise ValueError("augment: unknown key %r (the keys are 'shift', 'gain', 'bias', 'noise', 'occlude', 'occlude_size', "
+                       "'frame_drop' and 'frame_lag')" % (k,))
   S, g, b = augment.get('shift', 0), augment.get('gain', 0.0), augment.get('bias', 0.0)
   if isinstance(S, (bool, np.bool_)) or not isinstance(S, (int, np.integer)) or S < 0:
     raise ValueError("augment['shift'] must be an integer >= 0 (whole pixels), got %r" % (S,))
@@ -355,6 +358,41 @@ def check_augment_scene(augment, hw=None):
   if not number(f) or not 0 < f <= 1:
     raise ValueError("augment['occlude_size'] must be a number in (0, 1], got %r" % (f,))
   return None if (sigma == 0 and R == 0) else (float(sigma), int(R), float(f))
+
+
+def check_augment_time(augment, K=None):
+  """The time keys of ``pickplace_input_fn(augment=...)`` validated: None (off: no dict, or ``frame_lag`` and
+  ``frame_drop`` both 0) or (L, p) -- ``frame_lag`` = L, an integer >= 0: the camera lags the encoders by d ~ U{0..L} frames per
+  window; ``frame_drop`` = p, a number in [0, 1): the chance that a slot k >= 1 shows what slot k - 1 shows.  ``K`` = the window
+  size, when known: with K == 1 there is no slot to drop, ``frame_drop`` is accepted and does nothing; ``frame_lag`` still
+  applies.  The other keys are ``check_augment``'s and ``check_augment_scene``'s; unknown ones are refused there."""
+  if augment is None:
+    return None
+  if not isinstance(augment, dict):
+    raise ValueError('augment must be None or a dict, got %r' % (augment,))
+  L, p = augment.get('frame_lag', 0), augment.get('frame_drop', 0.0)
+  if isinstance(L, (bool, np.bool_)) or not isinstance(L, (int, np.integer)) or L < 0:
+    raise ValueError("augment['frame_lag'] must be an integer >= 0 (frames), got %r" % (L,))
+  if isinstance(p, (bool, np.bool_)) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0 <= p < 1:      # (NaN fails both)
+    raise ValueError("augment['frame_drop'] must be a number in [0, 1), got %r" % (p,))
+  if K is not None and K == 1:
+    p = 0.0
+  return None if (L == 0 and p == 0) else (int(L), float(p))
+
+
+def draw_augment_time(rng, n, K, L, p):
+  """The time draws of one emitted batch of ``n`` windows of ``K`` slots, in this order: the n lags d ~ integers U{0..L}, then an
+  [n][K - 1] block of uniforms u in [0, 1): slot k >= 1 is dropped when u[i][k - 1] < p (both blocks are drawn whatever L and p
+  are).  Returns ``src`` int32 [n][K], the recorded frame each slot shows as an offset from the window's start: the lag first,
+  src[i][k] = k - d[i], then the drops on the lagged sequence, a dropped slot showing what slot k - 1 shows (drops chain; slot 0 is
+  never dropped).  So src[i][0] = -d[i], rows do not decrease, and src[i][k] <= k.  The clamp at the episode's first frame is
+  ``DeviceWindows.frame_addresses``'s."""
+  d = rng.integers(0, L + 1, size=n)
+  drop = rng.random((n, K - 1)) < p
+  src = np.arange(K, dtype=np.int64)[None, :] - d[:, None]
+  for k in range(1, K):
+    src[:, k] = np.where(drop[:, k - 1], src[:, k - 1], src[:, k])
+  return src.astype(np.int32)
 
 
 def draw_augment(rng, n, S, g, b):
@@ -386,16 +424,19 @@ def draw_augment_scene(rng, n, H, W, sigma, R, f):
   return out
 
 
-def _augment_batch(feats, rng, aug, scene_rng=None, scene=None, hw=None):
+def _augment_batch(feats, rng, aug, scene_rng=None, scene=None, hw=None, time_rng=None, time=None):
   """Marks every DeviceWindows stream of an emitted batch with ONE WindowAugment drawn for it (``scene``: with the scene extras,
-  from their own generator)."""
+  ``time``: with the frame sources, each from their own generator; the frame sources are followed by the TIMED_KEYS streams)."""
   n = len(feats['step'])
   extras = draw_augment_scene(scene_rng, n, hw[0], hw[1], *scene) if scene is not None else {}
+  if time is not None:
+    K = next(v.K for k, v in feats.items() if k in TIMED_KEYS and isinstance(v, DeviceWindows))
+    extras['frame_src'] = draw_augment_time(time_rng, n, K, *time)
   draws = draw_augment(rng, n, *(aug or (0, 0.0, 0.0)))
   draws = WindowAugment(draws.shift, draws.colour, **extras)
   for k, v in feats.items():
     if isinstance(v, DeviceWindows):
-      v.augment, v.scene_tag = draws, SCENE_TAGS.get(k, 0)
+      v.augment, v.scene_tag, v.timed = draws, SCENE_TAGS.get(k, 0), k in TIMED_KEYS
   return feats
 
 
@@ -629,6 +670,15 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
   the frame's.  Order per element: shift / tint, rectangles, noise.  Their draws (``draw_augment_scene``) come from
   ``default_rng([seed, rank, AUGMENT_SCENE_STREAM])``, so file order, shuffle picks and the shift / colour draws are those without
   them.
+  Time keys of the same dict (off by default, independent of the keys above): the deployed camera drops frames and
+  lags the joint encoders, the recorded windows do neither.  ``frame_lag=L`` (integer >= 0): per window one lag d ~ U{0..L}, slot k
+  of its 'rgb' and 'depth' shows recorded frame start + k - d, clamped at the episode's first frame (the scene is at rest there).
+  ``frame_drop=p`` in [0, 1): per window and slot k >= 1 an independent chance p that the slot shows what slot k - 1 shows (drops
+  chain; slot 0 is never dropped).  The lag is applied first, then the drops on the lagged sequence.  'rgb' and 'depth' take the
+  same frame sources (the camera delivers both together).  'target_rgb', 'target_depth', every per-frame state feature and every
+  label are NOT touched: proprioception and labels stay fresh, which is the point -- the images go stale against them.  Their
+  draws (``draw_augment_time``) come from ``default_rng([seed, rank, AUGMENT_TIME_STREAM])``, so file order, shuffle picks, shift /
+  colour draws and scene draws are those without them.
   ``sample_weight`` = None | fn(features, labels) -> [n] array (every mode, host and ``device`` path, ``synthetic:`` inputs too): the
   weight per sample that params['loss_shaping']['sample_weights'] reads.  Called on every emitted batch, the ragged
   last one included, behind the augmentation draws; its result is checked (shape, finite, >= 0: ``weigh_batch``) and stored as
@@ -637,6 +687,7 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
     raise ValueError('shuffle_windows needs shuffle_buffer >= 1, got %r' % (shuffle_buffer,))
   check_augment(augment)
   check_augment_scene(augment)
+  check_augment_time(augment)
   if encoding != 'v4':
     # v1-v3 are dead code in the reference (undefined PickAndPlaceEncodingV1/2/3 -> NameError)
     raise KeyError(encoding)
@@ -668,7 +719,8 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
     paths = paths[rank::world]
   aug = check_augment(augment, (meta.img_height, meta.img_width)) if mode == 'train' else None      # train-only, as the shuffles
   scene = check_augment_scene(augment, (meta.img_height, meta.img_width)) if mode == 'train' else None
-  if (aug is not None or scene is not None) and device is None:
+  time = check_augment_time(augment, K) if mode == 'train' else None
+  if (aug is not None or scene is not None or time is not None) and device is None:
     raise ValueError("augment needs device= (e.g. 'cuda'): the windows are transformed on the device, where the resident frames "
                      "are; the host path has no augmentation")
   if device is not None:
@@ -684,11 +736,11 @@ def pickplace_input_fn(dataset_dir, split_name, mode, encoding='v4', window_size
   def emitter():
     """What a finished batch passes through on its way out: the augmentation draws, in emission order, then the sample weights."""
     weigh = (lambda f, l: (f, l)) if sample_weight is None else (lambda f, l: weigh_batch(sample_weight, f, l))
-    if aug is None and scene is None:
+    if aug is None and scene is None and time is None:
       return weigh
     stream = lambda word: np.random.default_rng(None if seed is None else [seed, shard[0] if shard is not None else 0, word])
-    rng, scene_rng = stream(AUGMENT_STREAM), stream(AUGMENT_SCENE_STREAM)
-    return lambda f, l: weigh(_augment_batch(f, rng, aug, scene_rng, scene, (meta.img_height, meta.img_width)), l)
+    rng, scene_rng, time_rng = stream(AUGMENT_STREAM), stream(AUGMENT_SCENE_STREAM), stream(AUGMENT_TIME_STREAM)
+    return lambda f, l: weigh(_augment_batch(f, rng, aug, scene_rng, scene, (meta.img_height, meta.img_width), time_rng, time), l)
 
   def shuffled_batches():
     import itertools

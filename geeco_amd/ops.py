@@ -233,6 +233,31 @@ def gather_windows_scene_into(out, addr, kind, shift, colour, occ_rect, occ_colo
                                           float(sigma), int(tag), N, K, H, W, C, _p(out), _stream()), 'geeco_gather_windows_scene')
 
 
+def gather_windows_frames_into(out, frame_addr, kind, shift, colour, occ_rect, occ_colour, noise_key, sigma, tag, N, K, H, W, C):
+  """gather_windows_scene_into following ONE ADDRESS PER FRAME: out[n][k] is built from the frame at
+  ``frame_addr[n][k]`` (int64 [N][K] device table, read when the kernel runs), so a slot may show any resident frame of its
+  window's kind -- a dropped frame delivered again, a camera that lags.  ``shift`` may be None (no shift); C == 1 (depth) takes
+  ``shift`` and ``colour`` only.  Everything else, and every value, as gather_windows_scene_into / _augmented_into /
+  _by_address_into for the arguments that are set; the noise counter's k is the OUTPUT slot.  The caller has checked that every
+  address holds a whole frame (DeviceWindows.frame_addresses).  ONE launch (include/geeco_hip.h: geeco_gather_windows_frames)."""
+  if (occ_rect is None) != (occ_colour is None):
+    raise ValueError('gather_windows_frames: occ_rect and occ_colour come together')
+  if C != 3 and (occ_rect is not None or float(sigma) != 0.0):
+    raise ValueError('gather_windows_frames: C=%d takes the shift only (occluders and noise are built for RGB streams)' % C)
+  tables = ((frame_addr, torch.int64, N * K), (kind, torch.int32, N)) + (
+      () if shift is None else ((shift, torch.int32, 2 * N),)) + (
+      () if colour is None else ((colour, torch.float32, 2 * C * N),)) + (
+      () if occ_rect is None else ((occ_rect, torch.int32, 16 * N), (occ_colour, torch.float32, 12 * N))) + (
+      () if noise_key is None else ((noise_key, torch.int32, 2),))
+  _check_tables(tables, out.device, 'gather_windows_frames: the tables must be contiguous int64 frame addresses [N][K], int32 kinds '
+                '[N], int32 shifts [N][2], float32 colour [N][%d], int32 rectangles [N][4][4], float32 rectangle colours [N][4][3] '
+                'and an int32 key [2] for N=%d, K=%d on %s' % (2 * C, N, K, out.device))
+  if out.numel() < N * K * H * W * C:
+    raise ValueError('gather_windows_frames: output of %d floats for %d x %d frames of %d x %d x %d' % (out.numel(), N, K, H, W, C))
+  check(_lib().geeco_gather_windows_frames(_p(frame_addr), _p(kind), _p(shift), _p(colour), _p(occ_rect), _p(occ_colour), _p(noise_key),
+                                           float(sigma), int(tag), N, K, H, W, C, _p(out), _stream()), 'geeco_gather_windows_frames')
+
+
 # -- batched predictor I/O (csrc/predict_io.hip; geeco_amd/batched_predictor.py) --------------------------------------------
 def predict_range_check_into(ctl, frames, B, HW, C, lo, hi):
   """ctl[b] = ctl[B] = 1 when channels 0..2 of env b's float32 frame leave [lo, hi] (or hold a NaN); never clears them."""

@@ -32,7 +32,8 @@ extern "C" {
  * geeco_adam_prepare_schedule, geeco_slab_reduce_batch_prepare_schedule, geeco_lr_schedule_eval, geeco_guard_decide,
  * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled, geeco_variable_stats_ws_bytes, geeco_variable_stats,
  * geeco_heads_loss_shaped_fwd_bwd, geeco_lstm_step_heads_shaped_fwd_bwd, geeco_loss_shaping_sizeof,
- * geeco_grad_accumulate_segments, geeco_conv1_dgrad, geeco_pack_pixels_bwd, geeco_dynimg_bwd_ws_bytes, geeco_dynimg_bwd */
+ * geeco_grad_accumulate_segments, geeco_conv1_dgrad, geeco_pack_pixels_bwd, geeco_dynimg_bwd_ws_bytes, geeco_dynimg_bwd,
+ * geeco_gather_windows_frames */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -158,6 +159,22 @@ int geeco_gather_windows_augmented(const int64_t* addr, const int32_t* kind, con
 int geeco_gather_windows_scene(const int64_t* addr, const int32_t* kind, const int32_t* shift, const float* colour,
                                const int32_t* occ_rect, const float* occ_colour, const uint32_t* noise_key, float sigma, int tag,
                                int N, int K, int H, int W, int C, float* out, void* stream);
+/* The scene builder following one address PER FRAME (camera frame drops and latency: input_fn.pickplace_input_fn(augment=dict(
+ * frame_drop=, frame_lag=)); the reference has none).  frame_addr [N][K] int64 on the device, read when the kernel
+ * RUNS (a captured step follows a re-pointed table): out[n][k] is built from the frame of kind[n] at frame_addr[n][k]; frames may
+ * repeat within and between windows.  Every other argument, the argument checks and the launch shape as above, except: shift may
+ * be NULL (no shift), and C = 1 (depth) is taken with shift and colour only (occ_rect, occ_colour NULL and sigma == 0), as
+ * geeco_gather_windows_augmented takes it.  Per element the output is bitwise what geeco_gather_windows_scene writes for a window
+ * whose k-th frame is that frame; with the scene arguments NULL / sigma == 0 bitwise geeco_gather_windows_augmented; with shift and
+ * colour NULL too bitwise geeco_gather_windows_by_address.  The noise counter stays (e / 4, k, n, tag) with k the OUTPUT slot: a
+ * frame shown in two slots gets independent sensor noise in each.  Alignment is decided per frame, never per window: uint8 frames
+ * may lie at any byte address (frames of H * W * C % 4 != 0 bytes put neighbours at different residues), float32 frames at any
+ * 4-byte aligned one; loads are as wide as each element's own source address allows.  The caller guarantees that every table
+ * entry addresses H * W * C readable elements of kind[n]. */
+int geeco_gather_windows_frames(const int64_t* frame_addr, const int32_t* kind, const int32_t* shift_or_null,
+                                const float* colour_or_null, const int32_t* occ_rect_or_null, const float* occ_colour_or_null,
+                                const uint32_t* noise_key_or_null, float sigma, int tag, int N, int K, int H, int W, int C,
+                                float* out, void* stream);
 
 /* ---- batched predictor I/O: B control loops per call (reference predictor.py:127-209 per env) ----------------------
  * The ingest and output stages of one replayed graph (geeco_amd/batched_predictor.py): range check -> window push ->

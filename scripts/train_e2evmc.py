@@ -104,6 +104,12 @@ ARGPARSER.add_argument('--augment_occlude', type=int, default=0,
 ARGPARSER.add_argument('--augment_occlude_size', type=float, default=0.25,
                        help="The largest side of such a rectangle as a fraction of the frame's, in (0, 1].  Not with --shared_frames "
                             'either.')
+ARGPARSER.add_argument('--augment_frame_drop', type=float, default=0.0,
+                       help='... and let the camera drop frames: each slot k >= 1 of a window shows, with this probability (0 <= p < 1), '
+                            'the image of slot k - 1 again (drops chain).  RGB and depth alike; states and labels stay fresh.  0 = off.')
+ARGPARSER.add_argument('--augment_frame_lag', type=int, default=0,
+                       help='... and let the camera lag the joint encoders: per window a lag of 0..L frames, drawn uniformly, delays its '
+                            "images (clamped at the episode's first frame).  0 = off.  Neither with --shared_frames.")
 ARGPARSER.add_argument('--shared_frames', default=False, action='store_true',
                        help="Per-frame controllers (e2e_vmc; goal 'sequence' x 'constant' / 'residual'), one GPU, RGB: encode every "
                             'distinct frame of a batch once instead of once per window that holds it (same loss and gradients).  Needs '
@@ -323,9 +329,10 @@ def main(args):
     # (before anything is written or initialised)
     raise SystemExit('--shuffle_windows and --shared_frames exclude each other: a shuffled batch of N windows holds about N x K '
                      'distinct frames, so there is nothing for --shared_frames to share')
-  if (args.augment_shift or args.augment_gain or args.augment_bias or args.augment_noise or args.augment_occlude) and args.shared_frames:
-    raise SystemExit('--augment_shift / _gain / _bias / _noise / _occlude and --shared_frames exclude each other: every augmented '
-                     'window is transformed by its own draw, so no two windows share a frame')
+  if (args.augment_shift or args.augment_gain or args.augment_bias or args.augment_noise or args.augment_occlude or
+      args.augment_frame_drop or args.augment_frame_lag) and args.shared_frames:
+    raise SystemExit('--augment_shift / _gain / _bias / _noise / _occlude / _frame_drop / _frame_lag and --shared_frames exclude each '
+                     'other: every augmented window is transformed by its own draw, so no two windows share a frame')
   gdist.init_from_env()
   rank, world = gdist.rank(), gdist.world_size()
   os.makedirs(name=args.model_dir, exist_ok=True)
@@ -386,7 +393,8 @@ def main(args):
         shuffle_buffer=args.shuffle_buffer, num_epochs=1, num_threads=reader_threads,
         prefetch_size=args.prefetch_size, shuffle_windows=args.shuffle_windows,
         augment=dict(shift=args.augment_shift, gain=args.augment_gain, bias=args.augment_bias, noise=args.augment_noise,
-                     occlude=args.augment_occlude, occlude_size=args.augment_occlude_size),
+                     occlude=args.augment_occlude, occlude_size=args.augment_occlude_size, frame_drop=args.augment_frame_drop,
+                     frame_lag=args.augment_frame_lag),
         # episodes are uploaded once (to THIS rank's GPU), stay there across epochs (input_fn.EPISODE_CACHE) and windows are
         # gathered in HBM; an RGB model never reads the depth stream
         device=dev,
