@@ -1,6 +1,6 @@
 // The device code every frame-ingest kernel shares: the uint8 -> unit-float conversion (both forms), the dword unpack, the
 // 4-pixel RGB load and the V-float vector load.  Device-only inline helpers; not a translation unit of its own.  Users:
-// frame_pack.hip, predict_io.hip, shared_frames.hip (the division form) and dynimg_goal.hip (the Newton form).
+// frame_pack.hip, window_gather.hip, predict_io.hip, shared_frames.hip (the division form) and dynimg_goal.hip (the Newton form).
 #pragma once
 #include "geeco_common.h"
 

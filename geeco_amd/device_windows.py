@@ -271,28 +271,19 @@ class DeviceWindows:
   def materialize_into(self, out):
     """out [n][K][*frame_shape] <- the windows, one geeco_gather_windows launch per segment.  Every segment is checked on the
     host (residency, device, bounds) before the first launch is queued: an out-of-range gather is a GPU fault.  Augmented
-    windows: ONE geeco_gather_windows_augmented launch behind four small copies of its tables (the feed's 'dense_augmented'
-    form sends them in the step's one block instead); geeco_gather_windows_scene when ``scene_tables()`` has extras;
-    geeco_gather_windows_frames, with whatever of those tables the draws carry, when ``frame_src`` is set."""
+    windows: ONE launch (``_gather_by_tables``) behind small copies of the tables the draws carry (the feed's 'dense_augmented'
+    and 'dense_frames' forms send them in the step's one block instead)."""
     import torch
     from . import ops
     fe = int(np.prod(self.frame_shape))
     if self.augment is not None:
       shift, colour = self.augment_tables()
-      addr, kinds = self.window_table(out.device)
+      per_frame = self.frame_src is not None
+      addr, kinds = self.frame_addresses(out.device) if per_frame else self.window_table(out.device)
+      occ_rect, occ_colour, key, sigma, tag = self.scene_tables() or (None, None, None, 0.0, self.scene_tag)
       up = lambda a: None if a is None else torch.from_numpy(a).to(out.device, non_blocking=True)
-      scene = self.scene_tables()
-      if self.frame_src is not None:
-        addr, kinds = self.frame_addresses(out.device)
-        occ_rect, occ_colour, key, sigma, tag = scene if scene is not None else (None, None, None, 0.0, self.scene_tag)
-        ops.gather_windows_frames_into(out, up(addr), up(kinds), up(shift), up(colour), up(occ_rect), up(occ_colour), up(key), sigma,
-                                       tag, self.n, self.K, *self.frame_shape)
-      elif scene is None:
-        ops.gather_windows_augmented_into(out, up(addr), up(kinds), up(shift), up(colour), self.n, self.K, *self.frame_shape)
-      else:
-        occ_rect, occ_colour, key, sigma, tag = scene
-        ops.gather_windows_scene_into(out, up(addr), up(kinds), up(shift), up(colour), up(occ_rect), up(occ_colour), up(key), sigma,
-                                      tag, self.n, self.K, *self.frame_shape)
+      _gather_by_tables(out, [up(a) for a in (addr, kinds, shift, colour, occ_rect, occ_colour, key)], sigma, tag, per_frame,
+                        self.n, self.K, self.frame_shape)
       return
     off = 0
     for frames_dev, starts, divisor, _, _ in list(self._checked_segments(out.device)):
@@ -310,6 +301,24 @@ class DeviceWindows:
     torch.cuda.synchronize()
     arr = out.cpu().numpy()
     return arr[:, 0] if self.squeeze_k else arr
+
+
+def _gather_by_tables(out, tables, sigma, tag, per_frame, n, K, frame_shape):
+  """out [n][K][*frame_shape] <- ONE launch of the gather that serves ``tables`` = (addr, kind, shift, colour, occ_rect, occ_colour,
+  noise_key) on ``out``'s device, the last five None where the batch carries none: ops.gather_windows_frames_into when ``addr``
+  holds one address per frame (``per_frame``), else _scene_into with extras, _augmented_into with a shift, _by_address_into
+  without.  ``sigma`` and ``tag`` go to the first two.  The ONE place that answers this, for ``DeviceWindows.materialize_into``
+  (tables uploaded) and ``WindowFeed.after_flush`` (views of the arena); the wrapper is looked up on ``ops`` when called."""
+  from . import ops
+  addr, kind, shift, colour, occ_rect, occ_colour, noise_key = tables
+  if per_frame:
+    ops.gather_windows_frames_into(out, *tables, sigma, tag, n, K, *frame_shape)
+  elif occ_rect is not None or noise_key is not None:
+    ops.gather_windows_scene_into(out, *tables, sigma, tag, n, K, *frame_shape)
+  elif shift is not None:
+    ops.gather_windows_augmented_into(out, addr, kind, shift, colour, n, K, *frame_shape)
+  else:
+    ops.gather_windows_by_address_into(out, addr, kind, n, K, int(np.prod(frame_shape)))
 
 
 # ---- staging memory and the HBM-resident episode cache of the device path ----------------------------------------------

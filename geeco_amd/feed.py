@@ -7,7 +7,7 @@ import collections
 
 import numpy as np
 
-from .device_windows import DeviceWindows, resolve_device
+from .device_windows import DeviceWindows, _gather_by_tables, resolve_device
 
 ARENA_MAX_BYTES = 1 << 20      # host arrays up to this size share the arena's one copy; larger ones (dense windows) go alone
 
@@ -114,7 +114,9 @@ class WindowFeed:
       drops and camera lag): that buffer filled by ONE geeco_gather_windows_frames launch.  Its [n][K] table of
       frame addresses rides in the arena in place of the [n] window table, next to whichever of the tables above the draws
       carry: no copy and no launch more than 'dense_augmented'.  A batch without ``frame_src`` sends the consecutive table.
-    * 'frame_table' (``frame_table()``, models built with shared_frames=F): the batch's distinct frames, see there."""
+    * 'frame_table' (``frame_table()``, models built with shared_frames=F): the batch's distinct frames, see there.
+  The three by-address forms queue their launch through ``device_windows._gather_by_tables``, which picks the entry point from
+  the tables the slot reserved."""
 
   def __init__(self, windows, arena, key, shared_frames=None, shared_targets=None):
     """``shared_frames`` (a capacity F; the 'rgb' slot of a model built with shared_frames=F): the arena also carries the
@@ -278,24 +280,13 @@ class WindowFeed:
     table and augmentation draws) and in front of the replay.  Does nothing for the other forms."""
     if not self._gather_pending:
       return
-    from . import ops
     self._gather_pending = False
     if self._window_tables is None:       # static views of the sealed arena
       view = lambda name: self.arena.view(self.key + (name,)) if self.arena.has(self.key + (name,)) else None
       self._window_tables = tuple(view(name) for name in ('window_addr', 'window_kind', 'aug_shift', 'aug_colour', 'aug_occ_rect',
                                                           'aug_occ_colour', 'aug_noise_key'))
-    addr, kind, shift, colour, occ_rect, occ_colour, noise_key = self._window_tables
-    if self.form == 'dense_frames':
-      sigma, tag = self._scene_args if self.scene is not None else (0.0, 0)
-      ops.gather_windows_frames_into(self.buffer, addr, kind, shift, colour, occ_rect, occ_colour, noise_key, sigma, tag, self.n, self.K,
-                                     *self.frame_shape)
-    elif self.form == 'dense_augmented' and self.scene is not None:
-      ops.gather_windows_scene_into(self.buffer, addr, kind, shift, colour, occ_rect, occ_colour, noise_key, *self._scene_args,
-                                    self.n, self.K, *self.frame_shape)
-    elif self.form == 'dense_augmented':
-      ops.gather_windows_augmented_into(self.buffer, addr, kind, shift, colour, self.n, self.K, *self.frame_shape)
-    else:
-      ops.gather_windows_by_address_into(self.buffer, addr, kind, self.n, self.K, int(np.prod(self.frame_shape)))
+    sigma, tag = self._scene_args if self.scene is not None else (0.0, 0)
+    _gather_by_tables(self.buffer, self._window_tables, sigma, tag, self.form == 'dense_frames', self.n, self.K, self.frame_shape)
 
 
 # ---- the slots of one model (Estimator._get_spec) and the feed of one step ------------------------------------------------

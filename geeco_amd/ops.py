@@ -198,17 +198,34 @@ def gather_windows_by_address_into(out, addr, kind, N, K, frame_elems):
         'geeco_gather_windows_by_address')
 
 
+def _check_window_gather(who, out, tables, sigma, N, K, H, W, C, extras=True, per_frame=False):
+  """The host-side checks of the three transforming gathers (csrc/window_gather.hip) under the entry's name ``who``: ``tables`` =
+  (addr, kind, shift, colour, occ_rect, occ_colour, noise_key), the optional ones None; ``extras``: the entry takes the last
+  three; ``per_frame``: addr is [N][K], shift is optional and C == 1 takes no extras."""
+  addr, kind, shift, colour, occ_rect, occ_colour, noise_key = tables
+  if (occ_rect is None) != (occ_colour is None):
+    raise ValueError('%s: occ_rect and occ_colour come together' % who)
+  if per_frame and C != 3 and (occ_rect is not None or float(sigma) != 0.0):
+    raise ValueError('%s: C=%d takes the shift only (occluders and noise are built for RGB streams)' % (who, C))
+  sized = ((addr, torch.int64, N * K if per_frame else N), (kind, torch.int32, N), (shift, torch.int32, 2 * N),
+           (colour, torch.float32, 2 * C * N), (occ_rect, torch.int32, 16 * N), (occ_colour, torch.float32, 12 * N),
+           (noise_key, torch.int32, 2))
+  required = 2 if per_frame else 3
+  _check_tables([t for i, t in enumerate(sized) if i < required or t[0] is not None], out.device,
+                '%s: the tables must be contiguous int64 %s, int32 kinds [N], int32 shifts [N][2]%s float32 colour [N][%d]%s for N=%d%s on %s' % (
+                    who, 'frame addresses [N][K]' if per_frame else 'addresses [N]', ',' if extras else ' and', 2 * C,
+                    ', int32 rectangles [N][4][4], float32 rectangle colours [N][4][3] and an int32 key [2]' if extras else '', N,
+                    ', K=%d' % K if per_frame else '', out.device))
+  if out.numel() < N * K * H * W * C:
+    raise ValueError('%s: output of %d floats for %d x %d frames of %d x %d x %d' % (who, out.numel(), N, K, H, W, C))
+
+
 def gather_windows_augmented_into(out, addr, kind, shift, colour, N, K, H, W, C):
   """gather_windows_by_address_into with a per-window augmentation: out[n][k][y][x][c] <- pixel (y - dy, x - dx) of frame k of
   the window at addr[n], (dy, dx) = shift[n] (int32 [N][2] device table), times gain[c] plus bias[c] clamped to [0, 1] when
   ``colour`` (float32 [N][2 * C] = gain[C], bias[C]; None: values unchanged); exactly 0 where the source pixel is outside the
   frame.  ONE launch; any shift is safe (include/geeco_hip.h: geeco_gather_windows_augmented)."""
-  tables = ((addr, torch.int64, N), (kind, torch.int32, N), (shift, torch.int32, 2 * N)) + (
-      () if colour is None else ((colour, torch.float32, 2 * C * N),))
-  _check_tables(tables, out.device, 'gather_windows_augmented: the tables must be contiguous int64 addresses [N], int32 kinds [N], '
-                'int32 shifts [N][2] and float32 colour [N][%d] for N=%d on %s' % (2 * C, N, out.device))
-  if out.numel() < N * K * H * W * C:
-    raise ValueError('gather_windows_augmented: output of %d floats for %d x %d frames of %d x %d x %d' % (out.numel(), N, K, H, W, C))
+  _check_window_gather('gather_windows_augmented', out, (addr, kind, shift, colour, None, None, None), 0.0, N, K, H, W, C, extras=False)
   check(_lib().geeco_gather_windows_augmented(_p(addr), _p(kind), _p(shift), _p(colour), N, K, H, W, C, _p(out), _stream()),
         'geeco_gather_windows_augmented')
 
@@ -218,17 +235,7 @@ def gather_windows_scene_into(out, addr, kind, shift, colour, occ_rect, occ_colo
   ``occ_rect`` int32 [N][4][4] = (y0, x0, h, w) per slot and ``occ_colour`` float32 [N][4][3], both None for no occluders;
   ``noise_key`` int32 [2] (the two uint32 words of the Philox key, on the device; None only when ``sigma`` == 0); ``tag`` 0 for
   'rgb', 1 for 'target_rgb'.  ONE launch (include/geeco_hip.h: geeco_gather_windows_scene)."""
-  if (occ_rect is None) != (occ_colour is None):
-    raise ValueError('gather_windows_scene: occ_rect and occ_colour come together')
-  tables = ((addr, torch.int64, N), (kind, torch.int32, N), (shift, torch.int32, 2 * N)) + (
-      () if colour is None else ((colour, torch.float32, 2 * C * N),)) + (
-      () if occ_rect is None else ((occ_rect, torch.int32, 16 * N), (occ_colour, torch.float32, 12 * N))) + (
-      () if noise_key is None else ((noise_key, torch.int32, 2),))
-  _check_tables(tables, out.device, 'gather_windows_scene: the tables must be contiguous int64 addresses [N], int32 kinds [N], '
-                'int32 shifts [N][2], float32 colour [N][%d], int32 rectangles [N][4][4], float32 rectangle colours [N][4][3] and '
-                'an int32 key [2] for N=%d on %s' % (2 * C, N, out.device))
-  if out.numel() < N * K * H * W * C:
-    raise ValueError('gather_windows_scene: output of %d floats for %d x %d frames of %d x %d x %d' % (out.numel(), N, K, H, W, C))
+  _check_window_gather('gather_windows_scene', out, (addr, kind, shift, colour, occ_rect, occ_colour, noise_key), sigma, N, K, H, W, C)
   check(_lib().geeco_gather_windows_scene(_p(addr), _p(kind), _p(shift), _p(colour), _p(occ_rect), _p(occ_colour), _p(noise_key),
                                           float(sigma), int(tag), N, K, H, W, C, _p(out), _stream()), 'geeco_gather_windows_scene')
 
@@ -240,20 +247,8 @@ def gather_windows_frames_into(out, frame_addr, kind, shift, colour, occ_rect, o
   ``shift`` and ``colour`` only.  Everything else, and every value, as gather_windows_scene_into / _augmented_into /
   _by_address_into for the arguments that are set; the noise counter's k is the OUTPUT slot.  The caller has checked that every
   address holds a whole frame (DeviceWindows.frame_addresses).  ONE launch (include/geeco_hip.h: geeco_gather_windows_frames)."""
-  if (occ_rect is None) != (occ_colour is None):
-    raise ValueError('gather_windows_frames: occ_rect and occ_colour come together')
-  if C != 3 and (occ_rect is not None or float(sigma) != 0.0):
-    raise ValueError('gather_windows_frames: C=%d takes the shift only (occluders and noise are built for RGB streams)' % C)
-  tables = ((frame_addr, torch.int64, N * K), (kind, torch.int32, N)) + (
-      () if shift is None else ((shift, torch.int32, 2 * N),)) + (
-      () if colour is None else ((colour, torch.float32, 2 * C * N),)) + (
-      () if occ_rect is None else ((occ_rect, torch.int32, 16 * N), (occ_colour, torch.float32, 12 * N))) + (
-      () if noise_key is None else ((noise_key, torch.int32, 2),))
-  _check_tables(tables, out.device, 'gather_windows_frames: the tables must be contiguous int64 frame addresses [N][K], int32 kinds '
-                '[N], int32 shifts [N][2], float32 colour [N][%d], int32 rectangles [N][4][4], float32 rectangle colours [N][4][3] '
-                'and an int32 key [2] for N=%d, K=%d on %s' % (2 * C, N, K, out.device))
-  if out.numel() < N * K * H * W * C:
-    raise ValueError('gather_windows_frames: output of %d floats for %d x %d frames of %d x %d x %d' % (out.numel(), N, K, H, W, C))
+  _check_window_gather('gather_windows_frames', out, (frame_addr, kind, shift, colour, occ_rect, occ_colour, noise_key), sigma,
+                       N, K, H, W, C, per_frame=True)
   check(_lib().geeco_gather_windows_frames(_p(frame_addr), _p(kind), _p(shift), _p(colour), _p(occ_rect), _p(occ_colour), _p(noise_key),
                                            float(sigma), int(tag), N, K, H, W, C, _p(out), _stream()), 'geeco_gather_windows_frames')
 

@@ -7,6 +7,8 @@ the add; a fused multiply-add has one fewer) of values below 2 in magnitude, eac
 Zero fill: exactly 0.0.  Identity parameters and pure shifts: bitwise the by-address gather (moved).  Model against model: the
 standing dense-vs-dense bound, rtol 1e-4 and atol 2e-5, on the loss and the predictions of ONE step (the inputs of the two runs
 differ in the last bit where the host rounds the float64 tint to float32 once and the kernel rounds twice)."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -232,6 +234,69 @@ def test_argument_checks_return_the_error_code(dev):
   assert call(a, k, s, None, 2, K, H, W, C, o, None) == 0                 # ... and the good call still runs (colour may be NULL)
   torch.cuda.synchronize()
   assert not torch.isnan(out).any()
+
+
+# ================================================================================================
+# the recorded values of the kernel this entry point launched before the builders shared one body (DESIGN 5.26)
+# ================================================================================================
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'augmented_gather.npz')
+# 5 x 5 x 3: rows of 15 elements, the one-element path, and frames of 75 bytes at changing residues; 4 x 8 x 3: the vector path;
+# 4 x 8 x 1: the C = 1 instance.  N = 3 windows of K = 3 frames from starts 0, 2, 1 of ONE episode of 5 frames.
+GOLDEN_CASES = [(5, 5, 3, 'uint8'), (4, 8, 3, 'uint8'), (4, 8, 3, 'float32'), (4, 8, 1, 'float32'), (4, 8, 1, 'uint8')]
+GOLDEN_STARTS = (0, 2, 1)
+
+
+def golden_shifts(H, W):
+  """[2 launches][3 windows][2]: interior, the right and the left edge groups; three ways out of the frame."""
+  return np.asarray([[(0, 0), (1, -2), (-1, 3)], [(0, W), (H, 0), (-H - 1, W + 1)]], np.int32)
+
+
+def golden_offsets(dtype):
+  """Elements between a 16-byte aligned address and the episode: byte residues 0..3 (uint8), 16- and 4-byte alignment (float32)."""
+  return (0, 1, 2, 3) if dtype == 'uint8' else (0, 1)
+
+
+def golden_gather(dev, episode, offset, H, W, C, shift, colour, entry='augmented'):
+  """[3][3][H][W][C] float32: the GOLDEN_STARTS windows of ``episode`` (host [5][H * W * C]) resident ``offset`` elements behind
+  an aligned address, through ONE launch of ``entry``: 'augmented', 'scene' without extras, 'frames' with the consecutive table."""
+  from geeco_amd import ops
+  fe, n, k = H * W * C, len(GOLDEN_STARTS), 3
+  flat = torch.from_numpy(np.ascontiguousarray(episode).ravel())
+  buf = torch.zeros(offset + flat.numel(), dtype=flat.dtype, device=dev)
+  buf[offset:] = flat.to(dev)
+  size = buf.element_size()
+  assert buf.data_ptr() % 16 == 0
+  addr = np.asarray([buf.data_ptr() + (offset + st * fe) * size for st in GOLDEN_STARTS], np.int64)
+  if entry == 'frames':
+    addr = addr[:, None] + np.arange(k, dtype=np.int64)[None, :] * fe * size
+  addr = torch.from_numpy(addr).to(dev)
+  kind = torch.full((n,), 0 if size == 1 else 1, dtype=torch.int32, device=dev)
+  shift = torch.from_numpy(np.ascontiguousarray(shift, np.int32)).to(dev)
+  col = None if colour is None else torch.from_numpy(np.ascontiguousarray(colour, np.float32)).to(dev)
+  got = torch.full((n, k, H, W, C), float('nan'), device=dev)
+  if entry == 'augmented':
+    ops.gather_windows_augmented_into(got, addr, kind, shift, col, n, k, H, W, C)
+  else:
+    getattr(ops, 'gather_windows_%s_into' % entry)(got, addr, kind, shift, col, None, None, None, 0.0, 0, n, k, H, W, C)
+  torch.cuda.synchronize()
+  return got.cpu().numpy()
+
+
+def test_augmented_gather_reproduces_the_recorded_values(dev):
+  """Bitwise the arrays scripts/record_augmented_golden.py recorded from the kernel geeco_gather_windows_augmented launched
+  before it took an instance of the shared body -- every case, residue, shift launch, with and without colour -- and the scene
+  entry without extras (C = 3) and the frames entry under the consecutive table write the same values."""
+  gold = np.load(GOLDEN)
+  for i, (H, W, C, dtype) in enumerate(GOLDEN_CASES):
+    episode, colour, want = gold['episode%d' % i], gold['colour%d' % i], gold['out%d' % i]
+    assert episode.dtype == np.dtype(dtype) and want.dtype == np.float32
+    assert want.shape == (len(golden_offsets(dtype)), 2, 2, 3, 3, H, W, C)
+    for a, offset in enumerate(golden_offsets(dtype)):
+      for b, shift in enumerate(golden_shifts(H, W)):
+        for c, col in enumerate((colour, None)):
+          for entry in ('augmented', 'frames') + (('scene',) if C == 3 else ()):
+            got = golden_gather(dev, episode, offset, H, W, C, shift, col, entry)
+            assert np.array_equal(got.view(np.uint32), want[a, b, c].view(np.uint32)), (H, W, C, dtype, offset, b, col is None, entry)
 
 
 # ================================================================================================
