@@ -316,6 +316,8 @@ def test_losses_tf_published_values(dev):
                                         (40, 'velocity', 128, 128), (9, 'cartesian', 100, 64), (6, 'cartesian', 64, 96),
                                         (5, 'velocity', 160, 128)])
 def test_heads_loss(dev, N, mode, H, F):
+  """(tests/test_decoder_tail_variants_gpu.py holds every instantiation, launch form, size edge and target layout of this tail under a
+  bound per element.)"""
   from geeco_amd import ops
   names_expected = ['heads_sample_kernel<false>', 'heads_finish_kernel'] if (H <= 128 and F in (64, 128)) else ['heads_loss_kernel']
   g = torch.Generator().manual_seed(100 + N)

@@ -110,6 +110,8 @@ KERNEL_CASES = [(1, 'cartesian', 128, 128), (7, 'cartesian', 128, 128), (33, 'ca
 
 @pytest.mark.parametrize('N,mode,H,F', KERNEL_CASES)
 def test_shaped_tail_against_fp64(dev, N, mode, H, F):
+  """(tests/test_decoder_tail_variants_gpu.py holds every shaped instantiation, launch form, size edge and layout under a bound per
+  element.)"""
   from geeco_amd import ops
   cart = mode == 'cartesian'
   huber = (0, 3) if cart else (0, 2)      # Huber on two regression heads, weighted MSE on the others
