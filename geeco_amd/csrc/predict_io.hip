@@ -68,12 +68,18 @@ extern "C" int geeco_predict_range_check(const float* frames, int B, int64_t HW,
   const int nblk = (int)std::min<long long>(cdiv64(work, 256 * 4), 64);
   dim3 grid((unsigned)nblk, (unsigned)B);
   hipStream_t s = (hipStream_t)stream;
-  if (vec) {
-    if (C == 3) hipLaunchKernelGGL(range_check_kernel<3>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
-    else hipLaunchKernelGGL(range_check_kernel<4>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
+  if (vec && C == 3) {
+    geeco_note_kernel("range_check_kernel<3>");
+    hipLaunchKernelGGL(range_check_kernel<3>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
+  } else if (vec) {
+    geeco_note_kernel("range_check_kernel<4>");
+    hipLaunchKernelGGL(range_check_kernel<4>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
+  } else if (C == 3) {
+    geeco_note_kernel("range_check_scalar_kernel<3>");
+    hipLaunchKernelGGL(range_check_scalar_kernel<3>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
   } else {
-    if (C == 3) hipLaunchKernelGGL(range_check_scalar_kernel<3>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
-    else hipLaunchKernelGGL(range_check_scalar_kernel<4>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
+    geeco_note_kernel("range_check_scalar_kernel<4>");
+    hipLaunchKernelGGL(range_check_scalar_kernel<4>, grid, dim3(256), 0, s, frames, (long long)HW, lo, hi, ctl, B);
   }
   GEECO_LAUNCH_CHECK();
   return 0;
@@ -216,15 +222,19 @@ __global__ __launch_bounds__(256) void push_dense_kernel(const void* __restrict_
 template <int PIX>
 static void launch_push_dense(dim3 grid, hipStream_t s, const void* frames, int u8, int C, const float* jnt, const int* reset,
                               const int* any_bad, int K, long long HW, int J, float* rgb, float* depth, float* jnt_state) {
-  if (u8)
+  if (u8) {
+    geeco_note_kernel("push_dense_kernel<%d, 3, true>", PIX);
     hipLaunchKernelGGL((push_dense_kernel<PIX, 3, true>), grid, dim3(256), 0, s, frames, jnt, reset, any_bad, K, HW, J, rgb,
                        depth, jnt_state);
-  else if (C == 3)
+  } else if (C == 3) {
+    geeco_note_kernel("push_dense_kernel<%d, 3, false>", PIX);
     hipLaunchKernelGGL((push_dense_kernel<PIX, 3, false>), grid, dim3(256), 0, s, frames, jnt, reset, any_bad, K, HW, J, rgb,
                        depth, jnt_state);
-  else
+  } else {
+    geeco_note_kernel("push_dense_kernel<%d, 4, false>", PIX);
     hipLaunchKernelGGL((push_dense_kernel<PIX, 4, false>), grid, dim3(256), 0, s, frames, jnt, reset, any_bad, K, HW, J, rgb,
                        depth, jnt_state);
+  }
 }
 
 extern "C" int geeco_predict_push_dense(const void* frames, int frames_u8, const float* jnt, const int* reset, const int* any_bad,
@@ -307,14 +317,17 @@ extern "C" int geeco_predict_push_ring(const unsigned char* frames, const float*
   if (v16) {
     typedef unsigned __attribute__((ext_vector_type(4))) u32x4;
     dim3 grid((unsigned)(cdiv64(FB / 16, 256) + 1), (unsigned)B);
+    geeco_note_kernel("push_ring_kernel<u32x4>");
     hipLaunchKernelGGL(push_ring_kernel<u32x4>, grid, dim3(256), 0, s, frames, jnt, reset, any_bad, heads, K, FB, J, ring,
                        jnt_state);
   } else {
     dim3 grid((unsigned)(cdiv64(FB / 4, 256) + 1), (unsigned)B);
+    geeco_note_kernel("push_ring_kernel<unsigned>");
     hipLaunchKernelGGL(push_ring_kernel<unsigned>, grid, dim3(256), 0, s, frames, jnt, reset, any_bad, heads, K, FB, J, ring,
                        jnt_state);
   }
   GEECO_LAUNCH_CHECK();
+  geeco_note_kernel("ring_advance_kernel");
   hipLaunchKernelGGL(ring_advance_kernel, dim3((unsigned)cdiv(B, 64)), dim3(64), 0, s, any_bad, B, K, FB,
                      (const unsigned char*)ring, heads, (long long*)win_table);
   GEECO_LAUNCH_CHECK();
@@ -339,9 +352,16 @@ __global__ __launch_bounds__(256) void pack_newest_kernel(const void* __restrict
 
 template <int PIX>
 static void launch_pack_newest(dim3 grid, hipStream_t s, const void* frames, int u8, int C, long long HW, float* x_in) {
-  if (u8) hipLaunchKernelGGL((pack_newest_kernel<PIX, 3, true>), grid, dim3(256), 0, s, frames, HW, x_in);
-  else if (C == 3) hipLaunchKernelGGL((pack_newest_kernel<PIX, 3, false>), grid, dim3(256), 0, s, frames, HW, x_in);
-  else hipLaunchKernelGGL((pack_newest_kernel<PIX, 4, false>), grid, dim3(256), 0, s, frames, HW, x_in);
+  if (u8) {
+    geeco_note_kernel("pack_newest_kernel<%d, 3, true>", PIX);
+    hipLaunchKernelGGL((pack_newest_kernel<PIX, 3, true>), grid, dim3(256), 0, s, frames, HW, x_in);
+  } else if (C == 3) {
+    geeco_note_kernel("pack_newest_kernel<%d, 3, false>", PIX);
+    hipLaunchKernelGGL((pack_newest_kernel<PIX, 3, false>), grid, dim3(256), 0, s, frames, HW, x_in);
+  } else {
+    geeco_note_kernel("pack_newest_kernel<%d, 4, false>", PIX);
+    hipLaunchKernelGGL((pack_newest_kernel<PIX, 4, false>), grid, dim3(256), 0, s, frames, HW, x_in);
+  }
 }
 
 extern "C" int geeco_predict_pack_newest(const void* frames, int frames_u8, int B, int64_t HW, int C, float* x_in, void* stream) {
@@ -457,12 +477,15 @@ extern "C" int geeco_predict_push_features(const float* feat, const float* jnt, 
                        reinterpret_cast<uintptr_t>(feat_ring);
   const bool vec = ch % 4 == 0 && (al & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
-  if (vec)
+  if (vec) {
+    geeco_note_kernel("push_features_kernel<4>");
     hipLaunchKernelGGL(push_features_kernel<4>, dim3((unsigned)B), dim3(GEECO_PREDICT_FEAT_THREADS), 0, s, feat, jnt, reset,
                        any_bad, tgt_feat, mode, B, K, cells, ch, J, feat_ring, jnt_ring, heads, states, (long long)state_stride);
-  else
+  } else {
+    geeco_note_kernel("push_features_kernel<1>");
     hipLaunchKernelGGL(push_features_kernel<1>, dim3((unsigned)B), dim3(GEECO_PREDICT_FEAT_THREADS), 0, s, feat, jnt, reset,
                        any_bad, tgt_feat, mode, B, K, cells, ch, J, feat_ring, jnt_ring, heads, states, (long long)state_stride);
+  }
   GEECO_LAUNCH_CHECK();
   return 0;
 }
@@ -549,6 +572,7 @@ extern "C" int geeco_predict_pack(const float* preds, int P, int B, int nseg, co
                       reinterpret_cast<uintptr_t>(img_out)) & 15) == 0, "predict_pack: images must be 16-byte aligned");
   }
   hipStream_t s = (hipStream_t)stream;
+  geeco_note_kernel("pack_preds_kernel");
   hipLaunchKernelGGL(pack_preds_kernel, dim3((unsigned)cdiv(B + 1, 256)), dim3(256), 0, s, preds, P, B, sg, F, out, ctl,
                      ctl_out);
   GEECO_LAUNCH_CHECK();
@@ -556,6 +580,7 @@ extern "C" int geeco_predict_pack(const float* preds, int P, int B, int nseg, co
   int k = 0;
   for (int i = 0; i < 2; ++i) {
     if (!src[i]) continue;
+    geeco_note_kernel("pack_image_kernel");
     hipLaunchKernelGGL(pack_image_kernel, dim3((unsigned)cdiv64(HW, 256), (unsigned)B), dim3(256), 0, s, src[i],
                        (long long)HW, C, img_out + (long long)k * B * HW * C);
     GEECO_LAUNCH_CHECK();
