@@ -180,16 +180,19 @@ extern "C" int geeco_dynimg_fwd(const float* frames, const float* frames2, int64
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)p.nblk, (unsigned)N);
   const bool aligned = (sample_stride % 4 == 0) && (frame_stride % 4 == 0);
-  if (C == 3 && Cpad == 4 && (HW & 3) == 0 && aligned)
+  if (C == 3 && Cpad == 4 && (HW & 3) == 0 && aligned) {
+    geeco_note_kernel("dynimg_wsum3_kernel<false>");
     hipLaunchKernelGGL(dynimg_wsum3_kernel<false>, grid, dim3(256), 0, s, p);
-  else {
+  } else {
     GEECO_CHECK_ARG(C != 4 || aligned, "dynimg_fwd: C == 4 needs 16-byte aligned frames");
     p.nblk = (int)cdiv64(HW, 256);
     grid.x = p.nblk;
+    geeco_note_kernel("dynimg_wsum_generic_kernel");
     hipLaunchKernelGGL(dynimg_wsum_generic_kernel, grid, dim3(256), 0, s, p);
   }
   GEECO_LAUNCH_CHECK();
   dim3 g2((unsigned)cdiv64(HW * Cpad, 1024), (unsigned)N);
+  geeco_note_kernel("dynimg_norm_kernel");
   hipLaunchKernelGGL(dynimg_norm_kernel, g2, dim3(256), 0, s, out, (const float*)ws, p.nblk, (long long)HW, C, Cpad);
   GEECO_LAUNCH_CHECK();
   return 0;
@@ -211,9 +214,11 @@ extern "C" int geeco_dynimg_rgbd_fwd(const float* rgb, const float* rgb2, int64_
   p.nblk = dyn_nblk(HW, 3);
   for (int t = 0; t < K; ++t) p.alpha[t] = alpha_host[t];
   hipStream_t s = (hipStream_t)stream;
+  geeco_note_kernel("dynimg_wsum3_kernel<true>");
   hipLaunchKernelGGL(dynimg_wsum3_kernel<true>, dim3((unsigned)p.nblk, (unsigned)N), dim3(256), 0, s, p);
   GEECO_LAUNCH_CHECK();
   dim3 g2((unsigned)cdiv64(HW * 4, 1024), (unsigned)N);
+  geeco_note_kernel("dynimg_norm_kernel");
   hipLaunchKernelGGL(dynimg_norm_kernel, g2, dim3(256), 0, s, out, (const float*)ws, p.nblk, (long long)HW, 4, 4);
   GEECO_LAUNCH_CHECK();
   return 0;
