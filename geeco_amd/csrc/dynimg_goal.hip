@@ -135,6 +135,208 @@ __device__ __forceinline__ void dyn_collect(DynCtl* c, const f32x4* slots, unsig
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The per-lane work of the stage, once for both kernels below.  A lane owns UPT unit slots of 4 pixels; what differs between the
+// kernels is how many slots, how many frames of loads are in flight, and what happens between the samples of a block.
+// Every helper is inlined and indexes its arrays with constants only (#pragma unroll): a dynamic index would send the
+// accumulators to scratch.  dyn_to_units holds barriers, so its callers (dyn_last_frame, dyn_emit) are called by EVERY thread of
+// a block, on block-uniform paths, and branch on `live` only behind it.
+// ------------------------------------------------------------------------------------------------------------------
+// Where a lane stands for unit slot j of a block whose first unit is ub.  Two register layouts of the 12 RGB floats of a slot
+// (the depths, one float4 per unit, always belong to unit ub + j * THREADS + tid):
+//   unit layout (U8 source): x[c] = c-th float4 of unit ub + j * THREADS + tid (one dwordx3 of bytes per lane and frame);
+//   flat layout (fp32 source): x[c] = float4 number (j * 3 + c) * THREADS + tid of the block's stretch of the frame, so
+//     every load instruction of a wave reads 1 KiB contiguous (the unit layout reads 16 of every 48 bytes per instruction:
+//     three times the cache-line requests; measured on the first form of this kernel).  Sums, products and min / max do not
+//     care which pixel a float belongs to; the three arrays that are stored per pixel (current frame, both images) go through
+//     an LDS transposition (dyn_to_units) once, after the frame loop.
+// Threads past the end of a ragged last block read the frame's last unit / float4 again and drop what they computed: the frame
+// loop has no branch.  Positions are 32-bit BYTE offsets from wave-uniform frame addresses: one VGPR each, and the loads take
+// the scalar-base form; a frame is at most HW * 16 bytes, checked by the launcher to stay below 2^31.
+struct DynLane {
+  unsigned uc, fo[3];      // unit index (clamped); byte offset of the slot's c-th float4 in the frame (flat layout)
+  bool live, flive[3];     // the unit / the c-th float4 lies inside the frame
+};
+
+template <int THREADS, bool U8>
+__device__ __forceinline__ DynLane dyn_lane(long long ub, int j, int tid, long long U) {
+  DynLane l;
+  const long long u = ub + (long long)j * THREADS + tid;
+  l.live = u < U;
+  l.uc = (unsigned)(l.live ? u : U - 1);
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const long long f = ub * 3 + (long long)(j * 3 + c) * THREADS + tid;
+    l.flive[c] = U8 ? l.live : f < 3 * U;
+    l.fo[c] = (unsigned)((f < 3 * U ? f : 3 * U - 1) * 16);
+  }
+  return l;
+}
+
+// 16 bytes, non-temporal (global address space said explicitly: a pointer rebuilt from integers would load "flat")
+__device__ __forceinline__ f32x4 dyn_ld4(const void* q) {
+  typedef const __attribute__((address_space(1))) f32x4* gptr;
+  return __builtin_nontemporal_load((gptr)q);
+}
+
+// flat layout -> unit layout of one slot's three float4 through LDS (fp32 source only; every thread of the block takes part)
+template <int THREADS, bool U8>
+__device__ __forceinline__ void dyn_to_units(int tid, f32x4& x0, f32x4& x1, f32x4& x2) {
+  if constexpr (!U8) {
+    __shared__ f32x4 tbuf[THREADS * 3];
+    __syncthreads();
+    tbuf[tid] = x0; tbuf[THREADS + tid] = x1; tbuf[2 * THREADS + tid] = x2;
+    __syncthreads();
+    x0 = tbuf[3 * tid]; x1 = tbuf[3 * tid + 1]; x2 = tbuf[3 * tid + 2];
+  }
+}
+
+// frame t of sample n (wbase = p.win[n], U8 only) / the sample's target frame: three RGB float4 and, with DEPTH, the depths
+template <bool DEPTH, bool U8>
+__device__ __forceinline__ void dyn_load_frame(const DynParams& p, const unsigned char* wbase, int n, int t, const DynLane& l, f32x4 (&v)[4]) {
+  if (U8) {
+    load_u8_unit(wbase + (long long)t * p.HW * 3, l.uc, v[0], v[1], v[2]);
+  } else {
+    const char* src = dyn_uniform(p.frames + (long long)n * p.sample_stride + (long long)t * p.frame_stride);
+    v[0] = dyn_ld4(src + l.fo[0]); v[1] = dyn_ld4(src + l.fo[1]); v[2] = dyn_ld4(src + l.fo[2]);
+  }
+  if (DEPTH) v[3] = dyn_ld4(dyn_uniform(p.depth + (long long)n * p.dsample_stride + (long long)t * p.dframe_stride) + l.uc * 16u);
+}
+
+template <bool DEPTH, bool U8>
+__device__ __forceinline__ void dyn_load_target(const DynParams& p, int n, const DynLane& l, f32x4 (&g)[4]) {
+  if (U8) {
+    load_u8_unit(p.tgt_u8[n], l.uc, g[0], g[1], g[2]);
+  } else {
+    const char* ts = dyn_uniform(p.tgt + (long long)n * p.HW * 3);
+    g[0] = dyn_ld4(ts + l.fo[0]); g[1] = dyn_ld4(ts + l.fo[1]); g[2] = dyn_ld4(ts + l.fo[2]);
+  }
+  if (DEPTH) g[3] = dyn_ld4(dyn_uniform(p.tgt_depth + (long long)n * p.HW) + l.uc * 16u);
+}
+
+template <bool DEPTH>
+__device__ __forceinline__ void dyn_axpy(f32x4 (&X)[4], float w, const f32x4 (&v)[4]) {
+  X[0] += w * v[0]; X[1] += w * v[1]; X[2] += w * v[2];
+  if (DEPTH) X[3] += w * v[3];
+}
+
+// Frames 0 .. K-2 into the buffer image A, software-pipelined: a ring of UNR frames of staging registers; a frame's registers are
+// refilled with the frame UNR ahead as soon as its products are taken, so a wave always has ~UNR * UPT * 3 loads in flight.
+// mid() is called once, by every thread, about half-way through the frames (block-uniform: it may hold barriers).
+template <bool DEPTH, bool U8, int UNR, int UPT, class Mid>
+__device__ __forceinline__ void dyn_walk_frames(const DynParams& p, const unsigned char* wbase, int n, const DynLane (&l)[UPT],
+                                                f32x4 (&A)[UPT][4], Mid&& mid) {
+  const int KM = p.K - 1;
+  const int groups = KM / UNR;
+  const int gmid = groups >> 1;
+  bool called = false;
+  if (groups > 0) {
+    f32x4 v[UNR][UPT][4];
+#pragma unroll
+    for (int k = 0; k < UNR; ++k)
+#pragma unroll
+      for (int j = 0; j < UPT; ++j) dyn_load_frame<DEPTH, U8>(p, wbase, n, k, l[j], v[k][j]);
+    for (int g = 0; g + 1 < groups; ++g) {      // steady state: no condition inside but mid's
+      if (g == gmid) {
+        mid();
+        called = true;
+      }
+#pragma unroll
+      for (int k = 0; k < UNR; ++k) {
+        const float w = p.alpha[g * UNR + k];
+#pragma unroll
+        for (int j = 0; j < UPT; ++j) dyn_axpy<DEPTH>(A[j], w, v[k][j]);
+#pragma unroll
+        for (int j = 0; j < UPT; ++j) dyn_load_frame<DEPTH, U8>(p, wbase, n, (g + 1) * UNR + k, l[j], v[k][j]);
+        __builtin_amdgcn_sched_barrier(0);      // keep this order: (consume frame k, refill its registers), next k -- the scheduler
+      }                                         // otherwise sinks all refills behind the last wait of the round
+    }
+#pragma unroll
+    for (int k = 0; k < UNR; ++k) {
+      const float w = p.alpha[(groups - 1) * UNR + k];
+#pragma unroll
+      for (int j = 0; j < UPT; ++j) dyn_axpy<DEPTH>(A[j], w, v[k][j]);
+    }
+  }
+  if (!called) mid();
+  for (int t = groups * UNR; t < KM; ++t) {     // K - 1 not a multiple of UNR: the remaining frames one by one
+    const float w = p.alpha[t];
+#pragma unroll
+    for (int j = 0; j < UPT; ++j) {
+      f32x4 v[4];
+      dyn_load_frame<DEPTH, U8>(p, wbase, n, t, l[j], v);
+      dyn_axpy<DEPTH>(A[j], w, v);
+    }
+  }
+}
+
+// 4 pixels of a channel-padded [N][HW][4] image: where the lane's unit lies, and its three RGB float4 interleaved with its four
+// fourth-channel values
+__device__ __forceinline__ f32x4* dyn_pixels(float* img, const DynParams& p, int n, const DynLane& l) {
+  return reinterpret_cast<f32x4*>(img + ((long long)n * p.HW + (long long)l.uc * 4) * 4);
+}
+
+__device__ __forceinline__ void dyn_store_pixels4(f32x4* dst, const f32x4 v0, const f32x4 v1, const f32x4 v2, const f32x4 v3) {
+  dst[0] = f32x4{v0.x, v0.y, v0.z, v3.x};
+  dst[1] = f32x4{v0.w, v1.x, v1.y, v3.y};
+  dst[2] = f32x4{v1.z, v1.w, v2.x, v3.z};
+  dst[3] = f32x4{v2.y, v2.z, v2.w, v3.w};
+}
+
+// The window's last frame = the current frame: the last term of A, the ConvEncoder's input (its padded copy goes to p.last) and
+// the first term of the pair image D, summed in the order of the two-frame pass: 0 + alpha2[0] * current, + alpha2[1] * target
+template <bool DEPTH, bool U8, int THREADS, int UPT>
+__device__ __forceinline__ void dyn_last_frame(const DynParams& p, const unsigned char* wbase, int n, int tid, const DynLane (&l)[UPT],
+                                               f32x4 (&A)[UPT][4], f32x4 (&D)[UPT][4]) {
+  const float w = p.alpha[p.K - 1], w0 = p.alpha2[0], w1 = p.alpha2[1];
+  f32x4 c[UPT][4], g[UPT][4];
+#pragma unroll
+  for (int j = 0; j < UPT; ++j) {
+    c[j][3] = g[j][3] = f32x4{0.f, 0.f, 0.f, 0.f};
+    dyn_load_frame<DEPTH, U8>(p, wbase, n, p.K - 1, l[j], c[j]);
+    dyn_load_target<DEPTH, U8>(p, n, l[j], g[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < UPT; ++j) {
+    dyn_axpy<DEPTH>(A[j], w, c[j]);
+    dyn_axpy<DEPTH>(D[j], w0, c[j]);
+    dyn_axpy<DEPTH>(D[j], w1, g[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < UPT; ++j) {
+    dyn_to_units<THREADS, U8>(tid, c[j][0], c[j][1], c[j][2]);
+    if (l[j].live) dyn_store_pixels4(dyn_pixels(p.last, p, n, l[j]), c[j][0], c[j][1], c[j][2], c[j][3]);
+  }
+}
+
+// one slot's part of the lane's min / max of both images
+template <bool DEPTH>
+__device__ __forceinline__ void dyn_lane_minmax(const DynLane& l, const f32x4 (&A)[4], const f32x4 (&D)[4], float& mn1, float& mx1,
+                                                float& mn2, float& mx2) {
+#pragma unroll
+  for (int q = 0; q < (DEPTH ? 4 : 3); ++q) {
+    if (!(q < 3 ? l.flive[q] : l.live)) continue;
+    const f32x4 a = A[q], d = D[q];
+    mn1 = fminf(fminf(mn1, fminf(a.x, a.y)), fminf(a.z, a.w));
+    mx1 = fmaxf(fmaxf(mx1, fmaxf(a.x, a.y)), fmaxf(a.z, a.w));
+    mn2 = fminf(fminf(mn2, fminf(d.x, d.y)), fminf(d.z, d.w));
+    mx2 = fmaxf(fmaxf(mx2, fmaxf(d.x, d.y)), fmaxf(d.z, d.w));
+  }
+}
+
+// One image of one slot: normalise in place, transpose, store.  (One image at a time: half the live registers of both together.)
+template <bool DEPTH, bool U8, int THREADS>
+__device__ __forceinline__ void dyn_emit(f32x4 (&X)[4], float m, float r, float* img, const DynParams& p, int n, int tid, const DynLane& l) {
+#pragma unroll
+  for (int q = 0; q < (DEPTH ? 4 : 3); ++q) {
+    X[q].x = (X[q].x - m) / r; X[q].y = (X[q].y - m) / r; X[q].z = (X[q].z - m) / r; X[q].w = (X[q].w - m) / r;
+  }
+  dyn_to_units<THREADS, U8>(tid, X[0], X[1], X[2]);
+  if (!l.live) return;
+  dyn_store_pixels4(dyn_pixels(img, p, n, l), X[0], X[1], X[2], DEPTH ? X[3] : f32x4{0.f, 0.f, 0.f, 0.f});
+}
+
+// One sample per block, UPT unit slots per thread.
 template <bool DEPTH, bool U8, int THREADS, int UPT>
 __global__ __launch_bounds__(THREADS) void dynimg_goal_onepass_kernel(const DynParams p, DynCtl* ctl, int bps, unsigned polls) {
   constexpr int NW = THREADS / 64;
@@ -143,162 +345,21 @@ __global__ __launch_bounds__(THREADS) void dynimg_goal_onepass_kernel(const DynP
   [[maybe_unused]] const unsigned char* wbase = U8 ? p.win[n] : nullptr;
   const long long U = p.HW >> 2;             // units of 4 pixels per frame
   const long long ub = (long long)b * (THREADS * UPT);      // first unit of this block
-  // Two register layouts of a thread's 12 RGB floats per unit slot j (the depths, one float4 per unit, always belong to unit
-  // ub + j * THREADS + tid):
-  //   unit layout (U8 source): x[j][c] = c-th float4 of unit ub + j * THREADS + tid (one dwordx3 of bytes per lane and frame);
-  //   flat layout (fp32 source): x[j][c] = float4 number (j * 3 + c) * THREADS + tid of the block's stretch of the frame, so
-  //     every load instruction of a wave reads 1 KiB contiguous (the unit layout reads 16 of every 48 bytes per instruction:
-  //     three times the cache-line requests; measured on the first form of this kernel).  Sums, products and min / max do not
-  //     care which pixel a float belongs to; the three arrays that are stored per pixel (current frame, both images) go through
-  //     an LDS transposition (to_units) once, after the frame loop.
   f32x4 A[UPT][4], D[UPT][4];      // buffer image / pair image: [slot][three RGB float4, the 4 depths]
-#pragma unroll
-  for (int j = 0; j < UPT; ++j)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) A[j][q] = D[j][q] = f32x4{0.f, 0.f, 0.f, 0.f};
-  const float w0 = p.alpha2[0], w1 = p.alpha2[1];
-  // Threads past the end of a ragged last block read the frame's last unit / float4 again and drop what they computed: the frame
-  // loop has no branch.
-  // (per-lane positions as 32-bit BYTE offsets from wave-uniform frame addresses: one VGPR each, and the loads take the
-  // scalar-base form; a frame is at most HW * 16 bytes, checked by the launcher to stay below 2^31)
-  unsigned uc[UPT], fo[UPT][3];      // unit index (clamped); byte offset of the slot's c-th float4 in the frame (flat layout)
-  bool live[UPT], flive[UPT][3];
+  DynLane l[UPT];
 #pragma unroll
   for (int j = 0; j < UPT; ++j) {
-    const long long u = ub + (long long)j * THREADS + tid;
-    live[j] = u < U;
-    uc[j] = (unsigned)(live[j] ? u : U - 1);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const long long f = ub * 3 + (long long)(j * 3 + c) * THREADS + tid;
-      flive[j][c] = U8 ? live[j] : f < 3 * U;
-      fo[j][c] = (unsigned)((f < 3 * U ? f : 3 * U - 1) * 16);
-    }
+    for (int q = 0; q < 4; ++q) A[j][q] = D[j][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    l[j] = dyn_lane<THREADS, U8>(ub, j, tid, U);
   }
-  auto ld4 = [](const f32x4* q0) {      // (global address space said explicitly: a pointer rebuilt from integers would load "flat")
-    typedef const __attribute__((address_space(1))) f32x4* gptr;
-    gptr q = (gptr)q0;
-    return __builtin_nontemporal_load(q);
-  };
-  auto load = [&](int t, int j, f32x4& v0, f32x4& v1, f32x4& v2, f32x4& v3) {
-    if (U8) {
-      load_u8_unit(wbase + (long long)t * p.HW * 3, uc[j], v0, v1, v2);
-    } else {
-      const char* src = dyn_uniform(p.frames + (long long)n * p.sample_stride + (long long)t * p.frame_stride);
-      v0 = ld4(reinterpret_cast<const f32x4*>(src + fo[j][0])); v1 = ld4(reinterpret_cast<const f32x4*>(src + fo[j][1]));
-      v2 = ld4(reinterpret_cast<const f32x4*>(src + fo[j][2]));
-    }
-    if (DEPTH) v3 = ld4(reinterpret_cast<const f32x4*>(dyn_uniform(p.depth + (long long)n * p.dsample_stride + (long long)t * p.dframe_stride) + uc[j] * 16u));
-  };
-  // Frames 0 .. K-2, software-pipelined: a ring of UNR frames of staging registers; a frame's registers are refilled with the
-  // frame UNR ahead as soon as its products are taken, so a wave always has ~UNR * UPT * 3 loads in flight.
-  constexpr int UNR = DEPTH ? 2 : 3;      // (the pair image's registers are not live yet in this loop)
-  const int KM = p.K - 1;
-  const int groups = KM / UNR;
-  if (groups > 0) {
-    f32x4 v[UNR][UPT][4];
-#pragma unroll
-    for (int k = 0; k < UNR; ++k)
-#pragma unroll
-      for (int j = 0; j < UPT; ++j) load(k, j, v[k][j][0], v[k][j][1], v[k][j][2], v[k][j][3]);
-    for (int g = 0; g + 1 < groups; ++g) {      // steady state: no condition inside
-#pragma unroll
-      for (int k = 0; k < UNR; ++k) {
-        const float w = p.alpha[g * UNR + k];
-#pragma unroll
-        for (int j = 0; j < UPT; ++j) {
-          A[j][0] += w * v[k][j][0]; A[j][1] += w * v[k][j][1]; A[j][2] += w * v[k][j][2];
-          if (DEPTH) A[j][3] += w * v[k][j][3];
-        }
-#pragma unroll
-        for (int j = 0; j < UPT; ++j) load((g + 1) * UNR + k, j, v[k][j][0], v[k][j][1], v[k][j][2], v[k][j][3]);
-        __builtin_amdgcn_sched_barrier(0);      // keep this order: (consume frame k, refill its registers), next k -- the scheduler
-      }                                         // otherwise sinks all refills behind the last wait of the round
-    }
-#pragma unroll
-    for (int k = 0; k < UNR; ++k) {
-      const float w = p.alpha[(groups - 1) * UNR + k];
-#pragma unroll
-      for (int j = 0; j < UPT; ++j) {
-        A[j][0] += w * v[k][j][0]; A[j][1] += w * v[k][j][1]; A[j][2] += w * v[k][j][2];
-        if (DEPTH) A[j][3] += w * v[k][j][3];
-      }
-    }
-  }
-  for (int t = groups * UNR; t < KM; ++t) {     // K - 1 not a multiple of UNR: the remaining frames one by one
-    const float w = p.alpha[t];
-#pragma unroll
-    for (int j = 0; j < UPT; ++j) {
-      f32x4 v0, v1, v2, v3;
-      load(t, j, v0, v1, v2, v3);
-      A[j][0] += w * v0; A[j][1] += w * v1; A[j][2] += w * v2;
-      if (DEPTH) A[j][3] += w * v3;
-    }
-  }
-  // flat layout -> unit layout of one slot's three float4 through LDS (fp32 source only; every thread of the block takes part)
-  __shared__ f32x4 tbuf[U8 ? 1 : THREADS * 3];
-  auto to_units = [&](f32x4& x0, f32x4& x1, f32x4& x2) {
-    if (U8) return;
-    __syncthreads();
-    tbuf[tid] = x0; tbuf[THREADS + tid] = x1; tbuf[2 * THREADS + tid] = x2;
-    __syncthreads();
-    x0 = tbuf[3 * tid]; x1 = tbuf[3 * tid + 1]; x2 = tbuf[3 * tid + 2];
-  };
-  {   // the window's last frame = the current frame: also the ConvEncoder's input and the first term of the pair image
-    const float w = p.alpha[p.K - 1];
-    f32x4 c[UPT][4], g[UPT][4];
-#pragma unroll
-    for (int j = 0; j < UPT; ++j) {
-      c[j][3] = g[j][3] = f32x4{0.f, 0.f, 0.f, 0.f};
-      load(p.K - 1, j, c[j][0], c[j][1], c[j][2], c[j][3]);
-      if (U8) {
-        load_u8_unit(p.tgt_u8[n], uc[j], g[j][0], g[j][1], g[j][2]);
-      } else {
-        const char* ts = dyn_uniform(p.tgt + (long long)n * p.HW * 3);
-        g[j][0] = ld4(reinterpret_cast<const f32x4*>(ts + fo[j][0])); g[j][1] = ld4(reinterpret_cast<const f32x4*>(ts + fo[j][1]));
-        g[j][2] = ld4(reinterpret_cast<const f32x4*>(ts + fo[j][2]));
-      }
-      if (DEPTH) g[j][3] = ld4(reinterpret_cast<const f32x4*>(dyn_uniform(p.tgt_depth + (long long)n * p.HW) + uc[j] * 16u));
-    }
-#pragma unroll
-    for (int j = 0; j < UPT; ++j) {
-      A[j][0] += w * c[j][0]; A[j][1] += w * c[j][1]; A[j][2] += w * c[j][2];
-      if (DEPTH) A[j][3] += w * c[j][3];
-      // the pair image, summed in the order of the two-frame pass: 0 + alpha2[0] * current, + alpha2[1] * target
-      D[j][0] += w0 * c[j][0]; D[j][1] += w0 * c[j][1]; D[j][2] += w0 * c[j][2];
-      D[j][0] += w1 * g[j][0]; D[j][1] += w1 * g[j][1]; D[j][2] += w1 * g[j][2];
-      if (DEPTH) {
-        D[j][3] += w0 * c[j][3];
-        D[j][3] += w1 * g[j][3];
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < UPT; ++j) {
-      to_units(c[j][0], c[j][1], c[j][2]);
-      if (live[j]) {
-        const f32x4 v0 = c[j][0], v1 = c[j][1], v2 = c[j][2], v3 = c[j][3];
-        f32x4* lo = reinterpret_cast<f32x4*>(p.last + ((long long)n * p.HW + (long long)uc[j] * 4) * 4);
-        lo[0] = f32x4{v0.x, v0.y, v0.z, v3.x};
-        lo[1] = f32x4{v0.w, v1.x, v1.y, v3.y};
-        lo[2] = f32x4{v1.z, v1.w, v2.x, v3.z};
-        lo[3] = f32x4{v2.y, v2.z, v2.w, v3.w};
-      }
-    }
-  }
+  constexpr int UNR = DEPTH ? 2 : 3;      // frames in flight (the pair image's registers are not live yet in this loop)
+  dyn_walk_frames<DEPTH, U8, UNR, UPT>(p, wbase, n, l, A, [] {});
+  dyn_last_frame<DEPTH, U8, THREADS, UPT>(p, wbase, n, tid, l, A, D);
   // ---- per-sample min / max of both images --------------------------------------------------------------------------
   float mn1 = INFINITY, mx1 = -INFINITY, mn2 = INFINITY, mx2 = -INFINITY;
 #pragma unroll
-  for (int j = 0; j < UPT; ++j) {
-#pragma unroll
-    for (int q = 0; q < (DEPTH ? 4 : 3); ++q) {
-      if (!(q < 3 ? flive[j][q] : live[j])) continue;
-      const f32x4 a = A[j][q], d = D[j][q];
-      mn1 = fminf(fminf(mn1, fminf(a.x, a.y)), fminf(a.z, a.w));
-      mx1 = fmaxf(fmaxf(mx1, fmaxf(a.x, a.y)), fmaxf(a.z, a.w));
-      mn2 = fminf(fminf(mn2, fminf(d.x, d.y)), fminf(d.z, d.w));
-      mx2 = fmaxf(fmaxf(mx2, fmaxf(d.x, d.y)), fmaxf(d.z, d.w));
-    }
-  }
+  for (int j = 0; j < UPT; ++j) dyn_lane_minmax<DEPTH>(l[j], A[j], D[j], mn1, mx1, mn2, mx2);
   __shared__ float red[NW][4];
   __shared__ float s_norm[4];      // min1, range1, min2, range2
   mn1 = wave_reduce_min(mn1); mx1 = wave_reduce_max(mx1);
@@ -321,32 +382,8 @@ __global__ __launch_bounds__(THREADS) void dynimg_goal_onepass_kernel(const DynP
   // ---- normalise in registers, store once ---------------------------------------------------------------------------------
 #pragma unroll
   for (int j = 0; j < UPT; ++j) {
-    to_units(A[j][0], A[j][1], A[j][2]);
-    to_units(D[j][0], D[j][1], D[j][2]);
-    if (!live[j]) continue;
-    const long long u = (long long)uc[j];
-    float e[12], f[12], e4[4] = {0.f, 0.f, 0.f, 0.f}, f4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      e[4 * q + 0] = (A[j][q].x - m1) / r1; e[4 * q + 1] = (A[j][q].y - m1) / r1;
-      e[4 * q + 2] = (A[j][q].z - m1) / r1; e[4 * q + 3] = (A[j][q].w - m1) / r1;
-      f[4 * q + 0] = (D[j][q].x - m2) / r2; f[4 * q + 1] = (D[j][q].y - m2) / r2;
-      f[4 * q + 2] = (D[j][q].z - m2) / r2; f[4 * q + 3] = (D[j][q].w - m2) / r2;
-    }
-    if (DEPTH) {
-      e4[0] = (A[j][3].x - m1) / r1; e4[1] = (A[j][3].y - m1) / r1; e4[2] = (A[j][3].z - m1) / r1; e4[3] = (A[j][3].w - m1) / r1;
-      f4[0] = (D[j][3].x - m2) / r2; f4[1] = (D[j][3].y - m2) / r2; f4[2] = (D[j][3].z - m2) / r2; f4[3] = (D[j][3].w - m2) / r2;
-    }
-    f32x4* dst = reinterpret_cast<f32x4*>(p.out + ((long long)n * p.HW + u * 4) * 4);
-    dst[0] = f32x4{e[0], e[1], e[2], e4[0]};
-    dst[1] = f32x4{e[3], e[4], e[5], e4[1]};
-    dst[2] = f32x4{e[6], e[7], e[8], e4[2]};
-    dst[3] = f32x4{e[9], e[10], e[11], e4[3]};
-    f32x4* dd = reinterpret_cast<f32x4*>(p.diff_out + ((long long)n * p.HW + u * 4) * 4);
-    dd[0] = f32x4{f[0], f[1], f[2], f4[0]};
-    dd[1] = f32x4{f[3], f[4], f[5], f4[1]};
-    dd[2] = f32x4{f[6], f[7], f[8], f4[2]};
-    dd[3] = f32x4{f[9], f[10], f[11], f4[3]};
+    dyn_emit<DEPTH, U8, THREADS>(A[j], m1, r1, p.out, p, n, tid, l[j]);
+    dyn_emit<DEPTH, U8, THREADS>(D[j], m2, r2, p.diff_out, p, n, tid, l[j]);
   }
 }
 
@@ -363,131 +400,23 @@ __global__ __launch_bounds__(THREADS) void dynimg_goal_onepass2_kernel(const Dyn
   constexpr int NW = THREADS / 64;
   const int pi = blockIdx.x / bps, b = blockIdx.x - pi * bps;
   const int tid = threadIdx.x, wid = tid >> 6;
-  const long long U = p.HW >> 2;
-  const long long ub = (long long)b * THREADS;
-  unsigned uc, fo[3];
-  bool live, flive[3];
-  {
-    const long long u = ub + tid;
-    live = u < U;
-    uc = (unsigned)(live ? u : U - 1);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const long long f = ub * 3 + (long long)c * THREADS + tid;
-      flive[c] = U8 ? live : f < 3 * U;
-      fo[c] = (unsigned)((f < 3 * U ? f : 3 * U - 1) * 16);
-    }
-  }
-  const float w0 = p.alpha2[0], w1 = p.alpha2[1];
-  __shared__ f32x4 tbuf[U8 ? 1 : THREADS * 3];
+  const DynLane l[1] = {dyn_lane<THREADS, U8>((long long)b * THREADS, 0, tid, p.HW >> 2)};
   __shared__ float red[NW][4];
   __shared__ float s_norm[4];
-  auto ld4 = [](const f32x4* q0) {
-    typedef const __attribute__((address_space(1))) f32x4* gptr;
-    return __builtin_nontemporal_load((gptr)q0);
-  };
-  auto to_units = [&](f32x4& x0, f32x4& x1, f32x4& x2) {
-    if (U8) return;
-    __syncthreads();
-    tbuf[tid] = x0; tbuf[THREADS + tid] = x1; tbuf[2 * THREADS + tid] = x2;
-    __syncthreads();
-    x0 = tbuf[3 * tid]; x1 = tbuf[3 * tid + 1]; x2 = tbuf[3 * tid + 2];
-  };
   // ---- frame loop + last frame of sample n: A = buffer image, D = pair image (flat layout for fp32 sources); `mid()` is called
   // once, about half-way through the frames
-  auto accumulate = [&](int n, f32x4 (&A)[4], f32x4 (&D)[4], auto&& mid) {
+  auto accumulate = [&](int n, f32x4 (&A)[1][4], f32x4 (&D)[1][4], auto&& mid) {
     [[maybe_unused]] const unsigned char* wbase = U8 ? p.win[n] : nullptr;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) A[q] = D[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto load = [&](int t, f32x4& v0, f32x4& v1, f32x4& v2, f32x4& v3) {
-      if (U8) {
-        load_u8_unit(wbase + (long long)t * p.HW * 3, uc, v0, v1, v2);
-      } else {
-        const char* src = dyn_uniform(p.frames + (long long)n * p.sample_stride + (long long)t * p.frame_stride);
-        v0 = ld4(reinterpret_cast<const f32x4*>(src + fo[0])); v1 = ld4(reinterpret_cast<const f32x4*>(src + fo[1]));
-        v2 = ld4(reinterpret_cast<const f32x4*>(src + fo[2]));
-      }
-      if (DEPTH) v3 = ld4(reinterpret_cast<const f32x4*>(dyn_uniform(p.depth + (long long)n * p.dsample_stride + (long long)t * p.dframe_stride) + uc * 16u));
-    };
+    for (int q = 0; q < 4; ++q) A[0][q] = D[0][q] = f32x4{0.f, 0.f, 0.f, 0.f};
     constexpr int UNR = DEPTH ? 3 : 4;      // frames in flight: 12 loads of 16 B per lane (the first sample's images stay live meanwhile)
-    const int KM = p.K - 1;
-    const int groups = KM / UNR;
-    const int gmid = groups >> 1;
-    bool called = false;
-    if (groups > 0) {
-      f32x4 v[UNR][4];
-#pragma unroll
-      for (int k = 0; k < UNR; ++k) load(k, v[k][0], v[k][1], v[k][2], v[k][3]);
-      for (int g = 0; g + 1 < groups; ++g) {
-        if (g == gmid) {
-          mid();
-          called = true;
-        }
-#pragma unroll
-        for (int k = 0; k < UNR; ++k) {
-          const float w = p.alpha[g * UNR + k];
-          A[0] += w * v[k][0]; A[1] += w * v[k][1]; A[2] += w * v[k][2];
-          if (DEPTH) A[3] += w * v[k][3];
-          load((g + 1) * UNR + k, v[k][0], v[k][1], v[k][2], v[k][3]);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < UNR; ++k) {
-        const float w = p.alpha[(groups - 1) * UNR + k];
-        A[0] += w * v[k][0]; A[1] += w * v[k][1]; A[2] += w * v[k][2];
-        if (DEPTH) A[3] += w * v[k][3];
-      }
-    }
-    if (!called) mid();
-    for (int t = groups * UNR; t < KM; ++t) {
-      const float w = p.alpha[t];
-      f32x4 v0, v1, v2, v3;
-      load(t, v0, v1, v2, v3);
-      A[0] += w * v0; A[1] += w * v1; A[2] += w * v2;
-      if (DEPTH) A[3] += w * v3;
-    }
-    const float w = p.alpha[p.K - 1];
-    f32x4 c[4], g[4];
-    c[3] = g[3] = f32x4{0.f, 0.f, 0.f, 0.f};
-    load(p.K - 1, c[0], c[1], c[2], c[3]);
-    if (U8) {
-      load_u8_unit(p.tgt_u8[n], uc, g[0], g[1], g[2]);
-    } else {
-      const char* ts = dyn_uniform(p.tgt + (long long)n * p.HW * 3);
-      g[0] = ld4(reinterpret_cast<const f32x4*>(ts + fo[0])); g[1] = ld4(reinterpret_cast<const f32x4*>(ts + fo[1]));
-      g[2] = ld4(reinterpret_cast<const f32x4*>(ts + fo[2]));
-    }
-    if (DEPTH) g[3] = ld4(reinterpret_cast<const f32x4*>(dyn_uniform(p.tgt_depth + (long long)n * p.HW) + uc * 16u));
-    A[0] += w * c[0]; A[1] += w * c[1]; A[2] += w * c[2];
-    if (DEPTH) A[3] += w * c[3];
-    D[0] += w0 * c[0]; D[1] += w0 * c[1]; D[2] += w0 * c[2];
-    D[0] += w1 * g[0]; D[1] += w1 * g[1]; D[2] += w1 * g[2];
-    if (DEPTH) {
-      D[3] += w0 * c[3];
-      D[3] += w1 * g[3];
-    }
-    to_units(c[0], c[1], c[2]);
-    if (live) {
-      f32x4* lo = reinterpret_cast<f32x4*>(p.last + ((long long)n * p.HW + (long long)uc * 4) * 4);
-      lo[0] = f32x4{c[0].x, c[0].y, c[0].z, c[3].x};
-      lo[1] = f32x4{c[0].w, c[1].x, c[1].y, c[3].y};
-      lo[2] = f32x4{c[1].z, c[1].w, c[2].x, c[3].z};
-      lo[3] = f32x4{c[2].y, c[2].z, c[2].w, c[3].w};
-    }
+    dyn_walk_frames<DEPTH, U8, UNR, 1>(p, wbase, n, l, A, mid);
+    dyn_last_frame<DEPTH, U8, THREADS, 1>(p, wbase, n, tid, l, A, D);
   };
   // ---- block min / max of sample n -> its slot; count the block in
-  auto publish = [&](int n, const f32x4 (&A)[4], const f32x4 (&D)[4]) {
+  auto publish = [&](int n, const f32x4 (&A)[1][4], const f32x4 (&D)[1][4]) {
     float mn1 = INFINITY, mx1 = -INFINITY, mn2 = INFINITY, mx2 = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < (DEPTH ? 4 : 3); ++q) {
-      if (!(q < 3 ? flive[q] : live)) continue;
-      const f32x4 a = A[q], d = D[q];
-      mn1 = fminf(fminf(mn1, fminf(a.x, a.y)), fminf(a.z, a.w));
-      mx1 = fmaxf(fmaxf(mx1, fmaxf(a.x, a.y)), fmaxf(a.z, a.w));
-      mn2 = fminf(fminf(mn2, fminf(d.x, d.y)), fminf(d.z, d.w));
-      mx2 = fmaxf(fmaxf(mx2, fmaxf(d.x, d.y)), fmaxf(d.z, d.w));
-    }
+    dyn_lane_minmax<DEPTH>(l[0], A[0], D[0], mn1, mx1, mn2, mx2);
     mn1 = wave_reduce_min(mn1); mx1 = wave_reduce_max(mx1);
     mn2 = wave_reduce_min(mn2); mx2 = wave_reduce_max(mx2);
     __syncthreads();                     // (red may still be read by the previous sample's publish)
@@ -499,7 +428,7 @@ __global__ __launch_bounds__(THREADS) void dynimg_goal_onepass2_kernel(const Dyn
     if (tid == 0) dyn_publish_arrive<NW>(ctl + n, reinterpret_cast<f32x4*>(ctl + p.N) + (long long)n * bps, b, red, mn1, mx1, mn2, mx2);
   };
   // ---- wait for sample n's blocks, fold their slots, normalise this block's part in registers and store it
-  auto finish = [&](int n, f32x4 (&A)[4], f32x4 (&D)[4]) {
+  auto finish = [&](int n, f32x4 (&A)[1][4], f32x4 (&D)[1][4]) {
     __syncthreads();                     // (s_norm may still be read by the previous sample's finish)
     if (wid == 0) {
       DynCtl* c = ctl + n;
@@ -508,30 +437,15 @@ __global__ __launch_bounds__(THREADS) void dynimg_goal_onepass2_kernel(const Dyn
       dyn_collect(c, reinterpret_cast<const f32x4*>(ctl + p.N) + (long long)n * bps, got, bps, polls, tid, s_norm);
     }
     __syncthreads();
-    // one image at a time (normalise in place, transpose, store): half the live registers of doing both together
-    auto emit = [&](f32x4 (&X)[4], float m, float r, float* out) {
-#pragma unroll
-      for (int q = 0; q < (DEPTH ? 4 : 3); ++q) {
-        X[q].x = (X[q].x - m) / r; X[q].y = (X[q].y - m) / r; X[q].z = (X[q].z - m) / r; X[q].w = (X[q].w - m) / r;
-      }
-      to_units(X[0], X[1], X[2]);
-      if (!live) return;
-      const f32x4 z = DEPTH ? X[3] : f32x4{0.f, 0.f, 0.f, 0.f};
-      f32x4* dst = reinterpret_cast<f32x4*>(out + ((long long)n * p.HW + (long long)uc * 4) * 4);
-      dst[0] = f32x4{X[0].x, X[0].y, X[0].z, z.x};
-      dst[1] = f32x4{X[0].w, X[1].x, X[1].y, z.y};
-      dst[2] = f32x4{X[1].z, X[1].w, X[2].x, z.z};
-      dst[3] = f32x4{X[2].y, X[2].z, X[2].w, z.w};
-    };
-    emit(A, s_norm[0], s_norm[1], p.out);
-    emit(D, s_norm[2], s_norm[3], p.diff_out);
+    dyn_emit<DEPTH, U8, THREADS>(A[0], s_norm[0], s_norm[1], p.out, p, n, tid, l[0]);
+    dyn_emit<DEPTH, U8, THREADS>(D[0], s_norm[2], s_norm[3], p.diff_out, p, n, tid, l[0]);
   };
   const int nA = pi, nB = pi + half;
-  f32x4 AA[4], DA[4];
+  f32x4 AA[1][4], DA[1][4];
   accumulate(nA, AA, DA, [] {});
   publish(nA, AA, DA);
   if (nB < p.N) {
-    f32x4 AB[4], DB[4];
+    f32x4 AB[1][4], DB[1][4];
     accumulate(nB, AB, DB, [&] { finish(nA, AA, DA); });
     publish(nB, AB, DB);
     finish(nB, AB, DB);
