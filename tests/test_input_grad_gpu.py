@@ -3,7 +3,13 @@ the whole pass against the oracle under the device's ReLU decisions, head select
 
 Tolerances: conv1's input gradient to the per-kernel standard of tests/test_kernels_gpu.py (rtol 2e-5 + atol 2e-5 at unit-scale
 inputs); everything that normalises or sums over a sample to ``rel_max`` and ``rel_l2`` <= 2e-5 of tests/_relu_taps.py; the channel
-pack's adjoint bitwise (it moves floats and adds at most once per element)."""
+pack's adjoint bitwise (it moves floats and adds at most once per element).
+
+tests/test_input_grad_variants_gpu.py holds the three entry points at every instantiation and launch form (the one-float dynimg
+kernels, strided and misaligned layouts, ties across blocks, the flat sample, null outputs) with NaN slack and a derived bound per
+element, and the chunk loop of ``input_gradient`` with repeated calls.  What this file still holds on its own: the whole pass against
+the oracle under the device's ReLU decisions in every mode, with the training step's bitwise twin; head selection through the
+Estimator; scripts/saliency.py."""
 import hashlib
 import importlib.util
 import os
