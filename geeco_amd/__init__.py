@@ -5,3 +5,11 @@ include/geeco_hip.h); the Python modules mirror the reference's call surface
 (``params``, ``graph``, ``estimator``, ``input_fn``) on top of it.
 """
 __version__ = '0.1.0'
+
+
+def __getattr__(name):
+  """``geeco_amd.EpisodeReplay`` (replay.py), imported on first use: the package itself imports neither torch nor the library."""
+  if name == 'EpisodeReplay':
+    from .replay import EpisodeReplay
+    return EpisodeReplay
+  raise AttributeError('module %r has no attribute %r' % (__name__, name))

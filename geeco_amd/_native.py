@@ -64,6 +64,8 @@ ADAM_SEGMENTS_MAX = 8
 
 VARSTATS_CHUNK, VARSTATS_CLASSES = 4096, 40      # GEECO_VARSTATS_* of include/geeco_hip.h
 
+REPLAY_MAXK, REPLAY_MAXHEADS = 64, 8      # the window lengths geeco_replay_states takes; GEECO_REPLAY_MAXHEADS of include/geeco_hip.h
+
 LR_KINDS = ('constant', 'exponential', 'cosine', 'piecewise')      # GEECO_LR_* of include/geeco_hip.h, in order
 LR_BOUNDARIES_MAX = 8
 
@@ -191,6 +193,9 @@ SIGNATURES = {
     'geeco_pack_pixels_bwd': (_I, [_P, _P, _L, _I, _P, _L, _I, _I, _L, _I, _I, _I, _P]),
     'geeco_dynimg_bwd_ws_bytes': (_L, [_I, _L, _I]),
     'geeco_dynimg_bwd': (_I, [_P, _P, _P, _L, _L, _P, _I, _I, _L, _I, _I, _P, _L, _L, _I, _P, _I, _P, _P]),
+    # additive within ABI 7: episode replay
+    'geeco_replay_states': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
+    'geeco_replay_errors': (_I, [_P, _P, _I, _I, _I, POINTER(_I), POINTER(_I), POINTER(_I), _P, _P, _P]),
 }
 
 _lib = None

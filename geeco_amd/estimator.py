@@ -818,3 +818,26 @@ class Estimator:
       out['loss'] = float(model.loss)
       out.update({k: v.detach().cpu().numpy().copy() for k, v in model.predictions().items()})
       yield out
+
+  def replay(self, input_fn_or_episodes, checkpoint_path=None, max_frames=512, chunk_frames=None):
+    """The controller's commands over whole recorded episodes, a generator beside ``predict()`` and ``input_gradients()`` (DESIGN
+    5.27): one ``EpisodeReplay.replay`` result per episode of ``input_fn_or_episodes`` -- a callable that returns the episodes, or
+    the episodes themselves, each a mapping as ``replay.dataset_episodes`` yields them ('rgb', 'jnt_state', the recorded per-frame
+    arrays, 'target_rgb' for a goal model).  Errors are computed when the episode carries the recorded arrays of the model's heads.
+    ``checkpoint_path`` (a checkpoint prefix or a model_dir): parameters from there instead of ``model_dir``'s latest checkpoint.
+    Per-frame controllers only (``replay.check_replay_config`` says which and why); the pass reads the checkpoint into a store of its
+    own and touches neither the estimator's parameters nor its step counter."""
+    from .replay import EpisodeReplay
+    cfg = self.params['e2evmc_config']
+    goal = self._model_fn is goal_e2evmc_model_fn
+    if not goal and self._model_fn is not e2evmc_model_fn:
+      raise ValueError('replay: needs an Estimator built on e2evmc_model_fn or goal_e2evmc_model_fn')
+    if checkpoint_path is not None:
+      prefix = _checkpoint_prefix(os.fspath(checkpoint_path))
+      model_dir, name = os.path.dirname(prefix), os.path.basename(prefix)
+    else:
+      model_dir, name = self.model_dir, None
+    rp = EpisodeReplay(model_dir, name, device=self._device(), max_frames=max_frames, chunk_frames=chunk_frames, goal=goal, cfg=cfg)
+    label_keys = ('cmd',) if cfg.control_mode == 'cartesian' else ('vel_target', 'ee_target', 'grp_target')
+    for ep in (input_fn_or_episodes() if callable(input_fn_or_episodes) else input_fn_or_episodes):
+      yield rp.replay(ep, labels=hasattr(ep, 'keys') and all(k in ep for k in label_keys + ('ee_state', 'obj_state')))

@@ -303,6 +303,60 @@ def predict_push_features_into(states, feat_ring, jnt_ring, heads, feat, jnt, re
                                            _stream()), 'geeco_predict_push_features')
 
 
+# -- episode replay (csrc/replay.hip; geeco_amd/replay.py) ---------------------------------------------------------------------
+def replay_states_into(states, feat, jnt, mode, T, t0, t1, K, cells, ch, J, tgt_feat=None):
+  """feat [T][cells][ch] / jnt [T][J] of one episode -> states [K][N][state_stride] (a contiguous 3-D tensor, N >= t1 - t0): row
+  t - t0 of step k <- frame max(0, t - K + 1 + k) for the windows t0 <= t < t1, in the columns of predict_push_features_into for
+  ``mode`` ('plain', 'constant', 'residual'; tgt_feat [cells][ch] for the last two).  Rows t1 - t0 .. N - 1 are not touched.  Bad
+  arguments raise ValueError before anything is queued."""
+  if mode not in PREDICT_FEAT_MODES:
+    raise ValueError("replay_states: mode=%r must be 'plain', 'constant' or 'residual'" % (mode,))
+  if not 1 <= int(K) <= _native.REPLAY_MAXK:
+    raise ValueError('replay_states: K=%d outside 1..%d' % (K, _native.REPLAY_MAXK))
+  if not (T >= 1 and 0 <= t0 < t1 <= T):
+    raise ValueError('replay_states: windows [%d, %d) outside the %d frames' % (t0, t1, T))
+  if (mode == 'plain') != (tgt_feat is None):
+    raise ValueError("replay_states: tgt_feat goes with the modes 'constant' and 'residual' (mode=%r)" % (mode,))
+  if min(cells, ch, J) < 1:
+    raise ValueError('replay_states: cells=%d ch=%d J=%d' % (cells, ch, J))
+  width = cells * (ch + J + (ch if mode == 'constant' else 0))
+  if states.dim() != 3 or not states.is_contiguous() or states.shape[0] != K or states.shape[1] < t1 - t0 or states.shape[2] < width:
+    raise ValueError('replay_states: states of shape %s for K=%d steps of >= %d windows of %d columns (contiguous [K][N][stride])'
+                     % (tuple(states.shape), K, t1 - t0, width))
+  if feat.numel() < T * cells * ch or jnt.numel() < T * J or (tgt_feat is not None and tgt_feat.numel() < cells * ch):
+    raise ValueError('replay_states: feat / jnt / tgt_feat of %d / %d / %s floats for T=%d cells=%d ch=%d J=%d'
+                     % (feat.numel(), jnt.numel(), None if tgt_feat is None else tgt_feat.numel(), T, cells, ch, J))
+  check(_lib().geeco_replay_states(_p(feat), _p(jnt), _p(tgt_feat), PREDICT_FEAT_MODES[mode], T, t0, t1, states.shape[1], K, cells, ch,
+                                   J, _p(states), states.shape[2], _stream()), 'geeco_replay_states')
+
+
+REPLAY_SQUARED_ERROR, REPLAY_CLASS_HIT = 0, 1      # head kinds of geeco_replay_errors
+
+
+def replay_errors_into(out_frame, out_episode, preds, labels, T, heads):
+  """preds / labels [>= T][P] -> out_frame [T][len(heads)] and out_episode [len(heads)] (the mean over the frames, one fixed order):
+  heads = (first column, columns, kind) per head; kind REPLAY_SQUARED_ERROR: the mean over the head's columns of the squared
+  difference; REPLAY_CLASS_HIT: 1 where the argmax of the logits (first maximum) is the class index labels[t][first column], else
+  0.  NaN predictions give NaN.  Bad arguments raise ValueError before anything is queued."""
+  heads = [tuple(int(v) for v in h) for h in heads]
+  if not 1 <= len(heads) <= _native.REPLAY_MAXHEADS:
+    raise ValueError('replay_errors: %d heads outside 1..%d' % (len(heads), _native.REPLAY_MAXHEADS))
+  if preds.dim() != 2 or labels.dim() != 2 or preds.shape[1] != labels.shape[1] or not (preds.is_contiguous() and labels.is_contiguous()):
+    raise ValueError('replay_errors: preds %s and labels %s must be contiguous [T][P] tensors of one width' % (tuple(preds.shape), tuple(labels.shape)))
+  P = int(preds.shape[1])
+  if not 1 <= T <= min(preds.shape[0], labels.shape[0]):
+    raise ValueError('replay_errors: T=%d outside 1..%d rows' % (T, min(preds.shape[0], labels.shape[0])))
+  for i, (off, size, kind) in enumerate(heads):
+    if not (1 <= size <= 64 and off >= 0 and off + size <= P):
+      raise ValueError('replay_errors: head %d [%d, +%d) outside the %d prediction columns (1..64 columns per head)' % (i, off, size, P))
+    if kind not in (REPLAY_SQUARED_ERROR, REPLAY_CLASS_HIT):
+      raise ValueError('replay_errors: head %d kind=%d must be 0 (squared error) or 1 (class hit)' % (i, kind))
+  if out_frame.numel() < T * len(heads) or out_episode.numel() < len(heads) or not (out_frame.is_contiguous() and out_episode.is_contiguous()):
+    raise ValueError('replay_errors: outputs of %d / %d floats for T=%d and %d heads' % (out_frame.numel(), out_episode.numel(), T, len(heads)))
+  check(_lib().geeco_replay_errors(_p(preds), _p(labels), T, P, len(heads), _iarr([h[0] for h in heads]), _iarr([h[1] for h in heads]),
+                                   _iarr([h[2] for h in heads]), _p(out_frame), _p(out_episode), _stream()), 'geeco_replay_errors')
+
+
 # -- shared-frame training (csrc/shared_frames.hip; graph.py: shared_frames=F) ------------------------------------------------
 def pack_frames_by_address_into(x_in, table, F, HW, frames_u8):
   """table [F] int64 device addresses of resident RGB frames (uint8 or float32, one kind per call; 0 = unused slot) -> the

@@ -33,7 +33,7 @@ extern "C" {
  * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled, geeco_variable_stats_ws_bytes, geeco_variable_stats,
  * geeco_heads_loss_shaped_fwd_bwd, geeco_lstm_step_heads_shaped_fwd_bwd, geeco_loss_shaping_sizeof,
  * geeco_grad_accumulate_segments, geeco_conv1_dgrad, geeco_pack_pixels_bwd, geeco_dynimg_bwd_ws_bytes, geeco_dynimg_bwd,
- * geeco_gather_windows_frames */
+ * geeco_gather_windows_frames, geeco_replay_states, geeco_replay_errors */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -818,6 +818,32 @@ int geeco_dynimg_bwd(const float* g, const float* frames, const float* frames2, 
                      const float* alpha_host, int N, int K, int64_t HW, int C, int Cpad, float* d_frames,
                      int64_t d_sample_stride, int64_t d_frame_stride, int accumulate, float* d_frames2, int accumulate2,
                      void* ws, void* stream);
+
+/* ---- episode replay: a controller's commands for a whole recorded episode (replay.py; additive within ABI 7) ----
+ * The per-frame controllers (e2e_vmc; goal_e2evmc 'sequence' x 'constant' / 'residual') over the T frames of one episode, every
+ * frame encoded once.  Both entries only enqueue on `stream`; neither uses atomics. */
+/* Window builder.  feat [T][cells][ch]: the encoder's features of the episode's frames; jnt [T][J]; tgt_feat [cells][ch]: the
+ * features of the episode's goal frame (NULL for PLAIN).  Writes the windows t = t0 .. t1 - 1 into states [K][N][state_stride]
+ * (N >= t1 - t0: the row count of a step; window t is row t - t0, rows t1 - t0 .. N - 1 are not touched): slot k (oldest first)
+ * of window t shows frame max(0, t - K + 1 + k), what the predictor holds after a reset at frame 0 and t pushes
+ * (predictor.py:192-200); the joint-state columns follow the same index.  Per cell the columns of geeco_predict_push_features for
+ * `mode`, bit for bit (a copy; one subtraction tgt - feat in RESIDUAL).  Grid-stride over (k, window, unit): no cap on T * K.
+ * 16-byte loads when ch % 4 == 0 and the sources are aligned; 16-byte stores when also J % 4 == 0, state_stride % 4 == 0 and
+ * states is aligned (with J = 7 a cell's columns start at odd offsets), else one float per lane.  K: 1..64;
+ * 0 <= t0 < t1 <= T. */
+int geeco_replay_states(const float* feat, const float* jnt, const float* tgt_feat, int mode, int T, int t0, int t1, int N, int K,
+                        int cells, int ch, int J, float* states, int64_t state_stride, void* stream);
+/* Error reduction.  preds [T][P]: the decoder's heads side by side; labels [T][P]: the recorded values in the same columns (a
+ * class head holds the class index in its first column).  Head h covers columns [head_off[h], + head_size[h]); head_kind[h] 0:
+ * out_frame[t][h] = (sum_c (preds - labels)^2, c ascending, every product and sum rounded to float32) / head_size[h];
+ * head_kind[h] 1: 1.0f where the argmax of the logits (first maximum on ties) equals the recorded class, else 0.0f, NaN when a
+ * logit is NaN.  A NaN prediction gives a NaN error.  out_episode[h] = the mean of out_frame[.][h] over the T frames, formed by
+ * ONE block of 256 threads: thread i adds the frames i, i + 256, .. in ascending order, the 256 partial sums are folded by halves
+ * (128, 64, .., 1: element j takes j + half), the result is divided by T -- two runs are bitwise equal.  The head_* arrays are
+ * host memory, nheads <= GEECO_REPLAY_MAXHEADS, head_size <= 64.  Two launches. */
+#define GEECO_REPLAY_MAXHEADS 8
+int geeco_replay_errors(const float* preds, const float* labels, int T, int P, int nheads, const int* head_off,
+                        const int* head_size, const int* head_kind, float* out_frame, float* out_episode, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,155 @@
+#!/usr/bin/env python
+"""What episode replay costs beside stepping a batch-1 incremental predictor through the same episode.
+
+One process, the forms alternating (scripts/_step_ab.py); e2e_vmc with seeded random weights, one ``--frames``-frame ``--size`` x
+``--size`` uint8 episode at K = ``--window_size``:
+  stepped_batch1:        ``E2EVMCPredictor(incremental=True)``: reset(), then predict(frame, jnt) per frame (float32 frames, the class's
+                         host-side frame checks, one graph replay and one round trip per frame);
+  stepped_core_uint8:    the engine below it, ``BatchedE2EVMCPredictor(num_envs=1, frame_dtype='uint8', incremental=True)``, fed the
+                         recorded uint8 frames (no host-side frame check, a quarter of the upload);
+  replay_resident:       ``EpisodeReplay.replay`` on the episode's frames resident in HBM (one read at the end);
+  replay_dense:          the same on the dense host array (adds the upload of the frames).
+Those are host-clock times around whole episodes, each ending in a device synchronise.  ``--stepped_only`` measures the two stepped
+forms alone: it imports nothing of the replay, so the same file run in the parent's tree gives the baseline from the parent.
+The two new kernels alone, device events around blocks of launches, each beside a plain device copy of the same bytes:
+  replay_states at T x K windows (bytes: the states written + the feature / joint-state tables read once);
+  replay_errors at T frames (its two launches).
+Also reported: the largest difference between the replayed and the stepped predictions at this size.
+Writes one JSON file (default profiles/episode_replay/replay.json).  Needs the GPU: there is no fallback.
+"""
+import json
+import os
+import statistics
+import tempfile
+import time
+
+import _step_ab as ab
+
+
+def host_blocks(forms, rounds, n, warm=1):
+  """{name: [milliseconds per call of a block of ``n`` calls, per round]} by the host clock; every call ends in a synchronise."""
+  import torch
+  for fn in forms.values():
+    for _ in range(warm):
+      fn()
+  blocks = {k: [] for k in forms}
+  for _ in range(rounds):
+    for k, fn in forms.items():
+      torch.cuda.synchronize()
+      t0 = time.perf_counter()
+      for _ in range(n):
+        fn()
+      torch.cuda.synchronize()
+      blocks[k].append((time.perf_counter() - t0) * 1e3 / n)
+  return blocks
+
+
+def main():
+  ap = ab.arguments('episode_replay', steps_help='episodes per timed block')
+  ap.set_defaults(steps=5, out=os.path.join(ab.ROOT, 'profiles', 'episode_replay', 'replay.json'))
+  ap.add_argument('--frames', type=int, default=100)
+  ap.add_argument('--stepped_only', action='store_true', help='the stepped forms alone (works in a tree without the replay)')
+  args = ap.parse_args()
+
+  import numpy as np
+  import torch
+  if not torch.cuda.is_available():
+    raise SystemExit('episode_replay_step.py measures on the GPU; none is visible')
+  from geeco_amd import estimator as est
+  from geeco_amd.batched_predictor import BatchedE2EVMCPredictor
+  from geeco_amd.graph import model_variable_shapes
+  from geeco_amd.params import create_e2evmc_config
+  from geeco_amd.predictor import E2EVMCPredictor
+  from geeco_amd.variables import VariableStore
+
+  H, K, T = args.size, args.window_size, args.frames
+  dev = torch.device('cuda', torch.cuda.current_device())
+  cfg = create_e2evmc_config(dict(window_size=K, img_height=H, img_width=H))
+  r = np.random.default_rng(7)
+  rgb = r.integers(0, 256, (T, H, H, 3), dtype=np.uint8)
+  rgb_f = rgb.astype(np.float32) / np.float32(255)
+  jnt = r.standard_normal((T, cfg.dim_jnt_state)).astype(np.float32)
+
+  with tempfile.TemporaryDirectory() as md:
+    json.dump(cfg._asdict(), open(os.path.join(md, 'e2evmc_config.json'), 'w'))
+    st = VariableStore(model_variable_shapes(cfg, False), 'cpu')
+    st.initialize(seed=4)
+    est.save_checkpoint(st, md, keep_max=1)
+    b1 = E2EVMCPredictor(md, memcap=None, device=dev, incremental=True)
+    core = BatchedE2EVMCPredictor(md, 1, memcap=None, device=dev, frame_dtype='uint8', incremental=True)
+
+    def stepped_batch1():
+      b1.reset()
+      return [b1.predict(rgb_f[t], jnt[t]) for t in range(T)]
+
+    def stepped_core():
+      core.reset()
+      return [core.predict(rgb[t:t + 1], jnt[t:t + 1]) for t in range(T)]
+
+    forms = {'stepped_batch1': stepped_batch1, 'stepped_core_uint8': stepped_core}
+    results = {
+        'shape': dict(size=H, window_size=K, frames=T, model='e2e_vmc', frames_dtype='uint8'),
+        'timing': dict(episodes_per_block=args.steps, rounds=args.rounds,
+                       method='whole episodes by the host clock, each call ending in a device synchronise, the forms alternating in one '
+                              'process, medians of the blocks; kernels alone between device events, 50 launches per block'),
+        'device': torch.cuda.get_device_name(dev),
+    }
+    if not args.stepped_only:
+      from geeco_amd import ops
+      from geeco_amd.replay import EpisodeReplay, error_heads, recorded_labels
+      rp = EpisodeReplay(md, device=dev, max_frames=T)
+      resident = torch.from_numpy(rgb).to(dev)
+      forms['replay_resident'] = lambda: rp.replay((resident, jnt), labels=False)
+      forms['replay_dense'] = lambda: rp.replay((rgb, jnt), labels=False)
+      results['shape'].update(chunk_frames=rp.chunk_frames, chunk_windows=rp.chunk_windows)
+      # the same commands?
+      out = rp.replay((resident, jnt), labels=False)
+      b1.reset()
+      worst, bitwise = 0.0, True
+      for t in range(T):
+        b1.predict(rgb_f[t], jnt[t])
+        for k, v in b1._model.predictions().items():
+          s = v[0].cpu().numpy()
+          worst, bitwise = max(worst, float(np.abs(out[k][t] - s).max())), bitwise and np.array_equal(out[k][t], s)
+      results['replay_vs_stepped'] = dict(max_abs_diff=worst, bitwise=bitwise)
+
+    blocks = host_blocks(forms, args.rounds, args.steps)
+    med = {k: statistics.median(v) for k, v in blocks.items()}
+    results['episode_ms'] = {k: round(v, 4) for k, v in med.items()}
+    results['episode_ms_blocks'] = ab.rounded(blocks, 4)
+    results['per_frame_ms'] = {k: round(v / T, 5) for k, v in med.items()}
+    if args.stepped_only:
+      return ab.write(results, args.out)
+    results['stepped_over_replay'] = {s: round(med[s] / med['replay_resident'], 2) for s in ('stepped_batch1', 'stepped_core_uint8')}
+
+    # the kernels alone, each beside a copy of the same bytes (a copy reads and writes: half the bytes each way)
+    d, J, cells, ch = rp.decoder, cfg.dim_jnt_state, 4, rp.ch
+    feat, jd = torch.randn(T, cells, ch, device=dev), torch.from_numpy(jnt).to(dev)
+    states = torch.empty(K, T, d.D, device=dev)
+    s_bytes = 4 * (states.numel() + feat.numel() + jd.numel())
+    src, dst = torch.empty(s_bytes // 8, device=dev), torch.empty(s_bytes // 8, device=dev)
+    k_blocks = ab.alternate({'replay_states': lambda: ops.replay_states_into(states, feat, jd, 'plain', T, 0, T, K, cells, ch, J),
+                             'copy_same_bytes': lambda: dst.copy_(src)}, args.rounds, 50, warm=10, scale=1e3)
+    heads = error_heads(cfg)
+    P = sum(h[1] for h in heads)
+    preds, labels = torch.randn(T, P, device=dev), torch.zeros(T, P, device=dev)
+    of, oe = torch.empty(T, len(heads), device=dev), torch.empty(len(heads), device=dev)
+    e_bytes = 4 * (2 * preds.numel() + 2 * of.numel() + oe.numel())
+    src2, dst2 = torch.empty(max(e_bytes // 8, 1), device=dev), torch.empty(max(e_bytes // 8, 1), device=dev)
+    e_blocks = ab.alternate({'replay_errors': lambda: ops.replay_errors_into(of, oe, preds, labels, T, heads),
+                             'copy_same_bytes': lambda: dst2.copy_(src2)}, args.rounds, 50, warm=10, scale=1e3)
+    k_med, e_med = ab.medians(k_blocks), ab.medians(e_blocks)
+    results.update({
+        'replay_states_us': {k: round(v, 2) for k, v in k_med.items()}, 'replay_states_us_blocks': ab.rounded(k_blocks, 2),
+        'replay_states_bytes': s_bytes, 'replay_states_GBps': round(s_bytes / k_med['replay_states'] / 1e3, 1),
+        'replay_states_over_copy': round(k_med['replay_states'] / k_med['copy_same_bytes'], 3),
+        'replay_errors_us': {k: round(v, 2) for k, v in e_med.items()}, 'replay_errors_us_blocks': ab.rounded(e_blocks, 2),
+        'replay_errors_bytes': e_bytes,
+        'not_measured': ['the goal models', 'float32 frames', 'any shape but this one', 'episodes read from disk (the reader and the '
+                         'upload of a new episode are outside these times)', 'replay beside other work on the device'],
+    })
+    ab.write(results, args.out)
+
+
+if __name__ == '__main__':
+  main()
