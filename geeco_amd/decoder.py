@@ -200,6 +200,24 @@ class LSTMDecoder:
     ops.gemm_into(self.dstates, self.dz, Wx, T * N, D, 4 * H, 4 * H, 4 * H, D, tb=True, ws=self.gemm_ws)
     return False
 
+  def sample_losses(self):
+    """float64 [N]: each sample's share of the last forward's loss (no L2 term), so that their sum is ``losses[0]`` up to rounding --
+    or None where the rows do not exist.  Every forward of the per-sample heads kernel (csrc/decoder_heads.hip: heads_sample_kernel,
+    both the fused step and ``heads_loss_into``) leaves the raw loss term of sample n and head h at ``heads_ws[2 N F + 32 N + 32 F + 8 n
+    + h]`` (HeadsParams::lterm): the sum of squared differences of a regression head, the cross-entropy of the gripper head; the
+    finish role turns their batch sums into means (1 / (N size), 1 / N) and weights them, which is repeated here per sample.  None:
+    the single-workgroup heads kernel wrote the losses (dim_h_fc outside {64, 128}, dim_h_lstm > 128 or more than 32 outputs: it
+    keeps no rows), the one-launch inference decoder ran (no losses at all), or ``loss_shaping`` is on (the rows then hold weighted
+    terms whose means are taken over batch-wide counts)."""
+    N, F = self.N, self.F
+    if self.loss_shaping is not None or self.one_launch or not (self.H <= 128 and F in (64, 128) and self.OT <= 32):
+      return None
+    off = 2 * N * F + 32 * N + 32 * F
+    rows = self.heads_ws[off:off + 8 * N].view(N, 8)[:, :len(self.heads)].double()
+    weights = self.head_weights or [h[4] for h in self.heads]
+    coef = [w / (N * size) if kind == 0 else w / N for (_, _, size, kind, _), w in zip(self.heads, weights)]
+    return rows @ torch.tensor(coef, dtype=torch.float64, device=rows.device)
+
   def predictions(self):
     """The heads' slices of ``preds`` by prediction key (estimator.py:48-61 / 183-197)."""
     out, off = {}, 0

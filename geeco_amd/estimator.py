@@ -770,12 +770,46 @@ class Estimator:
     prefix or a model_dir): parameters from there, in a store of their own, instead of the estimator's.
     The model of this pass is training-capable but takes no training option, runs eagerly and never calls the optimiser: parameters,
     optimiser state and the step counter are only read."""
+    def run(model):
+      model.forward(backward_too=True)
+      model.backward()
+      grads = model.input_gradients()
+      torch.cuda.synchronize()
+      model.check_device_errors()
+      out = {k: v.detach().cpu().numpy().copy() for k, v in grads.items()}
+      out['loss'] = float(model.loss)
+      return out
+    return self._input_pass('input_gradients', input_fn, heads, checkpoint_path, run)
+
+  def attributions(self, input_fn, method='integrated_gradients', steps=16, baseline=None, noise_std=0.0, seed=0, heads=None,
+                   checkpoint_path=None):
+    """Integrated-gradients or SmoothGrad attributions per batch of ``input_fn``, a generator beside
+    ``input_gradients()`` with its store handling, its ``heads`` and ``checkpoint_path`` and its refusals.  ``method``, ``steps``,
+    ``baseline``, ``noise_std``, ``seed``: ``_ModelBase.attributions``.  Yields numpy arrays: the attributions per image input
+    ('rgb', 'target_rgb', 'depth', 'target_depth' as the model has them), 'saliency' (and 'saliency_target' for goal models),
+    'sample_sum', 'loss' (at the clean input), for integrated gradients 'loss_baseline' and 'completeness_gap' ([N], per sample; see
+    there), and the predictions ``predict()`` yields.  The whole loop runs on the device; one read per batch."""
+    from .attribution import check_attribution_arguments
+    check_attribution_arguments(method, steps, noise_std, seed)
+
+    def run(model):
+      res = model.attributions(method, steps, baseline=baseline, noise_std=noise_std, seed=seed)
+      torch.cuda.synchronize()
+      model.check_device_errors()
+      out = {k: v.detach().cpu().numpy().copy() for k, v in res.items() if torch.is_tensor(v) and k not in ('loss', 'loss_baseline')}
+      out.update({k: float(res[k]) for k in ('loss', 'loss_baseline') if k in res})
+      return out
+    return self._input_pass('attributions', input_fn, heads, checkpoint_path, run)
+
+  def _input_pass(self, who, input_fn, heads, checkpoint_path, run):
+    """The batch loop of ``input_gradients`` and ``attributions``: the store, the refusals, one eager training-capable model per
+    batch size; ``run(model)`` -> the pass's numpy results on the loaded batch, to which the predictions are added."""
     cfg = self.params['e2evmc_config']
     goal = self._model_fn is goal_e2evmc_model_fn
     if not goal and self._model_fn is not e2evmc_model_fn:
-      raise ValueError('input_gradients: needs an Estimator built on e2evmc_model_fn or goal_e2evmc_model_fn')
+      raise ValueError('%s: needs an Estimator built on e2evmc_model_fn or goal_e2evmc_model_fn' % who)
     if self.params.get('shared_frames'):
-      raise ValueError("input_gradients: params['shared_frames'] encodes frame slots, not windows; use dense windows for this pass")
+      raise ValueError("%s: params['shared_frames'] encodes frame slots, not windows; use dense windows for this pass" % who)
     dev = self._device()
     if checkpoint_path is not None:
       store = graph.build_store(cfg, goal, dev)
@@ -788,14 +822,14 @@ class Estimator:
       self._restore_once()
       store = self._store
     if store.ema is not None:
-      raise ValueError("input_gradients: the estimator's store keeps averaged weights (params['ema_decay']); pass checkpoint_path= to "
-                       "differentiate a checkpoint's parameters")
+      raise ValueError("%s: the estimator's store keeps averaged weights (params['ema_decay']); pass checkpoint_path= to "
+                       "differentiate a checkpoint's parameters" % who)
     models = {}
     for batch in input_fn():
       feats, labels = batch if isinstance(batch, tuple) else (batch, None)
       for k, v in feats.items():
         if hasattr(v, 'pointers'):
-          raise ValueError("input_gradients: feature '%s' comes as device windows; this pass takes dense float32 batches" % k)
+          raise ValueError("%s: feature '%s' comes as device windows; this pass takes dense float32 batches" % (who, k))
       n = int(feats['rgb'].shape[0])
       if n not in models:
         ctor = graph.GoalE2EVMC if goal else graph.E2EVMC
@@ -809,13 +843,7 @@ class Estimator:
       model = models[n]
       as_t = lambda d: {k: torch.as_tensor(v) for k, v in (d or {}).items()}
       model.load_batch(as_t(feats), as_t(labels))
-      model.forward(backward_too=True)
-      model.backward()
-      grads = model.input_gradients()
-      torch.cuda.synchronize()
-      model.check_device_errors()
-      out = {k: v.detach().cpu().numpy().copy() for k, v in grads.items()}
-      out['loss'] = float(model.loss)
+      out = run(model)
       out.update({k: v.detach().cpu().numpy().copy() for k, v in model.predictions().items()})
       yield out
 

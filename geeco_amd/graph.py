@@ -25,6 +25,7 @@ import contextlib
 import torch
 
 from . import ops
+from .attribution import Attributions
 from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .optimizer import OptimizerStep
@@ -80,8 +81,9 @@ class BesideBottom:
     self.main.wait_stream(self.side)
 
 
-class _ModelBase(OptimizerStep):
-  """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398)."""
+class _ModelBase(OptimizerStep, Attributions):
+  """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398).  ``attributions()`` (integrated gradients,
+  SmoothGrad), the loop around ``input_gradients()``, is attribution.Attributions'."""
 
   def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, options=None, **raw):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training

@@ -33,7 +33,8 @@ extern "C" {
  * geeco_adam_tf_segments_guard, geeco_adam_tf_segments_scaled, geeco_variable_stats_ws_bytes, geeco_variable_stats,
  * geeco_heads_loss_shaped_fwd_bwd, geeco_lstm_step_heads_shaped_fwd_bwd, geeco_loss_shaping_sizeof,
  * geeco_grad_accumulate_segments, geeco_conv1_dgrad, geeco_pack_pixels_bwd, geeco_dynimg_bwd_ws_bytes, geeco_dynimg_bwd,
- * geeco_gather_windows_frames, geeco_replay_states, geeco_replay_errors */
+ * geeco_gather_windows_frames, geeco_replay_states, geeco_replay_errors, geeco_attr_path_point, geeco_attr_accumulate,
+ * geeco_attr_finish */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -844,6 +845,39 @@ int geeco_replay_states(const float* feat, const float* jnt, const float* tgt_fe
 #define GEECO_REPLAY_MAXHEADS 8
 int geeco_replay_errors(const float* preds, const float* labels, int T, int P, int nheads, const int* head_off,
                         const int* head_size, const int* head_kind, float* out_frame, float* out_episode, void* stream);
+
+/* ---- attributions: integrated gradients and SmoothGrad (attribution.py; additive within ABI 7) -------------------
+ * Many input gradients along a family of perturbed inputs, summed on the device.  The three entries are the streaming stages
+ * around the model's own forward, backward and input-gradient pass; no training step launches them.  Each only enqueues on
+ * `stream`; none uses atomics; 16-byte accesses when the tensors are 16-byte aligned (and, for a broadcast baseline, its period
+ * is a multiple of 4 floats), one float per access otherwise -- the values are the same bits on every path.  Every difference,
+ * product and sum below is rounded to float32 on its own (no fused multiply-add).  All pointers are device memory, 4-byte
+ * aligned.  Bad arguments return GEECO_EINVAL before anything is launched. */
+/* The path point:  dst[i] = b + alpha * (x[i] - b) + sigma * z(key, step, i),  b = baseline[i % baseline_period], i < n.
+ * baseline_period = n for a full baseline, one frame's element count for one frame broadcast over the frames; it must divide n.
+ * baseline == NULL: b = 0 (the period is ignored).  sigma == 0 draws nothing and adds no noise term.  z ~ N(0, 1) comes from the
+ * Philox4x32-10 / Box-Muller routine of the scene noise (csrc/philox_normal.h): element i takes normal i % 4 of the counter
+ * (c0, c1, c2, c3) = (low word of i / 4, high word of i / 4, step, 0) under the key (low word of key, high word of key).
+ * There is NO clamp: the result may leave [0, 1] (a path point is not an image; SmoothGrad's noise is not clipped).  dst may not
+ * overlap x.  With baseline == NULL, alpha == 1 and sigma == 0 the result is x, bit for bit (-0 becomes +0). */
+int geeco_attr_path_point(float* dst, const float* x, const float* baseline, int64_t baseline_period, float alpha, float sigma,
+                          uint64_t key, uint32_t step, int64_t n, void* stream);
+/* The running sum:  acc[i] = (overwrite ? 0 : acc[i]) + weight * g[i], the product rounded, then the sum.  overwrite != 0: acc is
+ * not read.  acc may not overlap g. */
+int geeco_attr_accumulate(float* acc, const float* g, float weight, int64_t n, int overwrite, void* stream);
+/* The finish, on tensors [N][frames_per_sample][HW][C] (acc, x, attr; C in 1..4) and [N][frames_per_sample][HW] (saliency):
+ *   attr[i] = multiply_by_input ? (x[i] - b) * acc[i] : acc[i]      (b as above; x and baseline are not read otherwise)
+ *   saliency[pixel] = max_c |attr[pixel][c]|                         (NaN when one of them is NaN)
+ *   sample_sum[n] = the sum of attr over sample n, in ONE fixed order: the sample's S = frames_per_sample * HW * C elements are
+ *   taken in groups of four consecutive elements; group q belongs to slot q % 1024; a slot adds its groups in ascending order,
+ *   the elements of a group in ascending order, starting from +0; the 1024 slot sums are folded by halves (512, 256, .., 1: slot
+ *   j takes slot j + half); slot 0 is the result.  Two runs are bitwise equal, and tests/_attribution_ref.py restates the order.
+ * Two launches: the elementwise one over the whole grid, then one block of 1024 threads per sample that reads attr back (there
+ * is no workspace argument; the finish runs once per pass).  attr may be acc itself (in place); a partial overlap of the two, or any overlap of attr with x or
+ * another output, is refused. */
+int geeco_attr_finish(float* attr, float* saliency, float* sample_sum, const float* acc, const float* x, const float* baseline,
+                      int64_t baseline_period, int multiply_by_input, int N, int frames_per_sample, int64_t HW, int C,
+                      void* stream);
 
 #ifdef __cplusplus
 }

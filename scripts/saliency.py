@@ -9,6 +9,10 @@ writes, per window (leading axis = window):
   saliency [n][K][H][W]                     max over the colour channels of |grad_rgb|, per frame;
   saliency_target [n][H][W]                 the same of the target frame (goal models);
   loss [batches]                            the loss that was differentiated, per batch.
+--method integrated_gradients | smoothgrad (default gradient: the plain gradient above, same output as ever) puts the
+attributions of Estimator.attributions in the grad_* arrays' place under attr_*, takes saliency / saliency_target from the device's
+finish, and adds sample_sum and, for integrated gradients, completeness_gap per window and loss_baseline per batch; --steps, --noise_std and
+--baseline black | FILE.npy (a [H][W][3] frame or an array shaped like a batch's rgb) go with it.
 --heads picks the heads whose losses are summed (default: the training loss).  --synthetic runs on generated frames and random
 initial weights when --model_dir holds no checkpoint (a smoke run of the whole path, no dataset needed).
 """
@@ -43,6 +47,10 @@ def parse_args(argv=None):
   ap.add_argument('--num_windows', type=int, default=8)
   ap.add_argument('--batch_size', type=int, default=4)
   ap.add_argument('--heads', default=None, help='comma-separated head names, e.g. cmd_ee or cmd_grp; default: the training loss')
+  ap.add_argument('--method', default='gradient', choices=('gradient', 'integrated_gradients', 'smoothgrad'))
+  ap.add_argument('--steps', type=int, default=16, help='--method integrated_gradients / smoothgrad: path points / noise draws')
+  ap.add_argument('--noise_std', type=float, default=0.1, help='--method smoothgrad: the noise\'s standard deviation')
+  ap.add_argument('--baseline', default='black', help="--method integrated_gradients: 'black' or FILE.npy")
   ap.add_argument('--out', required=True, help='OUT.npz')
   ap.add_argument('--synthetic', action='store_true', help='generated frames instead of a dataset')
   ap.add_argument('--img_size', type=int, default=256, help='--synthetic: frame height and width')
@@ -84,16 +92,30 @@ def main(argv=None):
   kept, outs = [], []
   e = est.Estimator(model_fn=goal_e2evmc_model_fn if goal else e2evmc_model_fn, model_dir=args.model_dir,
                     params={'e2evmc_config': cfg})
-  for out in e.input_gradients(input_fn, heads=heads):
+  if args.method == 'gradient':
+    passes = e.input_gradients(input_fn, heads=heads)
+  else:
+    ig = args.method == 'integrated_gradients'
+    baseline = None if (args.baseline == 'black' or not ig) else np.load(args.baseline).astype(np.float32)
+    passes = e.attributions(input_fn, method=args.method, steps=args.steps, baseline=baseline, noise_std=0.0 if ig else args.noise_std,
+                            heads=heads)
+  for out in passes:
     outs.append(out)
   if not outs:
     raise SystemExit('saliency.py: the input produced no full batch of %d windows' % N)
   cat = lambda dicts, k: np.concatenate([d[k] for d in dicts], axis=0)[:args.num_windows]
   arrays = {k: cat(kept, k) for k in kept[0]}
-  arrays.update({'grad_' + k: cat(outs, k) for k in IMAGE_KEYS if k in outs[0]})
-  arrays['saliency'] = saliency_of(arrays['grad_rgb'])
-  if goal:
-    arrays['saliency_target'] = saliency_of(arrays['grad_target_rgb'])
+  if args.method == 'gradient':
+    arrays.update({'grad_' + k: cat(outs, k) for k in IMAGE_KEYS if k in outs[0]})
+    arrays['saliency'] = saliency_of(arrays['grad_rgb'])
+    if goal:
+      arrays['saliency_target'] = saliency_of(arrays['grad_target_rgb'])
+  else:
+    arrays.update({'attr_' + k: cat(outs, k) for k in IMAGE_KEYS if k in outs[0]})
+    arrays.update({k: cat(outs, k) for k in ('saliency', 'saliency_target', 'sample_sum') if k in outs[0]})
+    if 'completeness_gap' in outs[0]:      # per window; per batch for a decoder that keeps no per-sample loss terms
+      arrays['completeness_gap'] = np.concatenate([np.atleast_1d(o['completeness_gap']) for o in outs]).astype(np.float64)[:args.num_windows]
+      arrays['loss_baseline'] = np.asarray([o['loss_baseline'] for o in outs], np.float64)
   arrays['loss'] = np.asarray([o['loss'] for o in outs], np.float32)
   np.savez(args.out, **arrays)
   print('saliency.py: %d windows, heads %s -> %s (%s)' % (arrays['saliency'].shape[0], heads or 'training loss', args.out,
