@@ -196,6 +196,10 @@ SIGNATURES = {
     # additive within ABI 7: episode replay
     'geeco_replay_states': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
     'geeco_replay_errors': (_I, [_P, _P, _I, _I, _I, POINTER(_I), POINTER(_I), POINTER(_I), _P, _P, _P]),
+    # additive within ABI 7: episode replay for the dynamic-image controllers
+    'geeco_replay_images_ws_bytes': (_L, [_I, _L]),
+    'geeco_replay_images': (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
+    'geeco_replay_states_pair': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
     # additive within ABI 7: attributions
     'geeco_attr_path_point': (_I, [_P, _P, _P, _L, _F, _F, ctypes.c_uint64, ctypes.c_uint32, _L, _P]),
     'geeco_attr_accumulate': (_I, [_P, _P, _F, _L, _I, _P]),

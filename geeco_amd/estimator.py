@@ -853,9 +853,10 @@ class Estimator:
     the episodes themselves, each a mapping as ``replay.dataset_episodes`` yields them ('rgb', 'jnt_state', the recorded per-frame
     arrays, 'target_rgb' for a goal model).  Errors are computed when the episode carries the recorded arrays of the model's heads.
     ``checkpoint_path`` (a checkpoint prefix or a model_dir): parameters from there instead of ``model_dir``'s latest checkpoint.
-    Per-frame controllers only (``replay.check_replay_config`` says which and why); the pass reads the checkpoint into a store of its
-    own and touches neither the estimator's parameters nor its step counter."""
-    from .replay import EpisodeReplay
+    The per-frame controllers go through ``EpisodeReplay``, geeco-f and 'sequence' x 'dyndiff' through ``DynamicImageReplay`` (5.29;
+    ``replay_dynimg.open_replay`` picks); the pass reads the checkpoint into a store of its own and touches neither the estimator's
+    parameters nor its step counter."""
+    from .replay_dynimg import open_replay
     cfg = self.params['e2evmc_config']
     goal = self._model_fn is goal_e2evmc_model_fn
     if not goal and self._model_fn is not e2evmc_model_fn:
@@ -865,7 +866,7 @@ class Estimator:
       model_dir, name = os.path.dirname(prefix), os.path.basename(prefix)
     else:
       model_dir, name = self.model_dir, None
-    rp = EpisodeReplay(model_dir, name, device=self._device(), max_frames=max_frames, chunk_frames=chunk_frames, goal=goal, cfg=cfg)
+    rp = open_replay(model_dir, name, goal=goal, cfg=cfg, device=self._device(), max_frames=max_frames, chunk_frames=chunk_frames)
     label_keys = ('cmd',) if cfg.control_mode == 'cartesian' else ('vel_target', 'ee_target', 'grp_target')
     for ep in (input_fn_or_episodes() if callable(input_fn_or_episodes) else input_fn_or_episodes):
       yield rp.replay(ep, labels=hasattr(ep, 'keys') and all(k in ep for k in label_keys + ('ee_state', 'obj_state')))

@@ -357,6 +357,71 @@ def replay_errors_into(out_frame, out_episode, preds, labels, T, heads):
                                    _iarr([h[2] for h in heads]), _p(out_frame), _p(out_episode), _stream()), 'geeco_replay_errors')
 
 
+# -- episode replay for the dynamic-image controllers (csrc/replay_dynimg.hip; geeco_amd/replay_dynimg.py) ------------------------
+def replay_images_ws(windows, HW, device):
+  """The workspace of replay_images_into for up to ``windows`` windows per call (per-block min / max; no zero-fill contract)."""
+  return torch.empty(max(int(_lib().geeco_replay_images_ws_bytes(int(windows), int(HW))) // 4, 4), dtype=torch.float32, device=device)
+
+
+def replay_images_into(cur_out, buf_out, diff_out, frame_addr, goal, T, t0, t1, K, HW, ws):
+  """The conv1 inputs of the windows t0 <= t < t1 of one episode, read from its resident frames: frame_addr [>= T] int64 DEVICE
+  addresses of the frames ([HW][3], uint8 or float32 as ``goal`` is), goal one frame of the same kind -> row t - t0 of cur_out
+  (frame t as R, G, B, 0), diff_out (the normalised pair image of frame t and the goal) and buf_out (the normalised dynamic image
+  of the frames max(0, t - K + 1 + k); None skips it), each a contiguous float32 [>= t1 - t0][HW][4].  Bitwise the images of
+  goal_dynimgs_into / goal_dynimgs_u8_into on the explicitly built windows (include/geeco_hip.h: geeco_replay_images).  Bad arguments
+  raise ValueError before anything is queued."""
+  if not 1 <= int(K) <= _native.REPLAY_MAXK:
+    raise ValueError('replay_images: K=%d outside 1..%d' % (K, _native.REPLAY_MAXK))
+  if HW < 4 or HW % 4:
+    raise ValueError('replay_images: HW=%d must be a multiple of 4' % (HW,))
+  if not (T >= 1 and 0 <= t0 < t1 <= T):
+    raise ValueError('replay_images: windows [%d, %d) outside the %d frames' % (t0, t1, T))
+  if cur_out is None or diff_out is None:
+    raise ValueError('replay_images: cur_out and diff_out are always written (only buf_out may be None)')
+  n = t1 - t0
+  for name, o in (('cur_out', cur_out), ('buf_out', buf_out), ('diff_out', diff_out)):
+    if o is not None and (o.dtype != torch.float32 or not o.is_contiguous() or o.numel() < n * HW * 4):
+      raise ValueError('replay_images: %s must be a contiguous float32 tensor of >= %d x %d x 4 values, got %s %s'
+                       % (name, n, HW, o.dtype, tuple(o.shape)))
+    if o is not None and o.data_ptr() % 16:
+      raise ValueError('replay_images: %s is misaligned (16 bytes)' % name)
+  if goal.dtype not in (torch.uint8, torch.float32) or goal.numel() != HW * 3 or not goal.is_contiguous():
+    raise ValueError('replay_images: the goal must be one contiguous uint8 or float32 [%d][3] frame, got %s %s' % (HW, goal.dtype, tuple(goal.shape)))
+  u8 = goal.dtype == torch.uint8
+  if goal.data_ptr() % (4 if u8 else 16):
+    raise ValueError('replay_images: the goal frame is misaligned (%d bytes)' % (4 if u8 else 16))
+  if frame_addr.dtype != torch.int64 or not frame_addr.is_contiguous() or frame_addr.numel() < T:
+    raise ValueError('replay_images: frame_addr must be a contiguous int64 table of >= T=%d addresses' % (T,))
+  need = n * -(-(HW // 4) // 256) * 4
+  if ws.dtype != torch.float32 or ws.numel() < need or ws.data_ptr() % 16:
+    raise ValueError('replay_images: ws of %d floats for %d windows of %d pixels (replay_images_ws), 16-byte aligned' % (ws.numel(), n, HW))
+  check(_lib().geeco_replay_images(_p(frame_addr), _p(goal), 1 if u8 else 0, ctypes.cast(_alpha_buf(K), ctypes.c_void_p),
+                                   ctypes.cast(_alpha_buf(2), ctypes.c_void_p), T, t0, t1, K, HW, _p(cur_out), _p(buf_out), _p(diff_out),
+                                   _p(ws), _stream()), 'geeco_replay_images')
+
+
+def replay_states_pair_into(states, feat, tgt_feat, jnt, T, t0, t1, K, cells, ch, ch_t, J):
+  """replay_states_into with a per-frame second table: feat [T][cells][ch], tgt_feat [T][cells][ch_t], jnt [T][J] -> states
+  [K][N][state_stride] (contiguous, N >= t1 - t0), per cell the columns [feat | jnt | tgt] of the dense 'sequence' x 'dyndiff' model
+  (state_concat_fwd_into with jnt_pos = 1).  Rows t1 - t0 .. N - 1 are not touched.  Bad arguments raise ValueError before anything
+  is queued."""
+  if not 1 <= int(K) <= _native.REPLAY_MAXK:
+    raise ValueError('replay_states_pair: K=%d outside 1..%d' % (K, _native.REPLAY_MAXK))
+  if not (T >= 1 and 0 <= t0 < t1 <= T):
+    raise ValueError('replay_states_pair: windows [%d, %d) outside the %d frames' % (t0, t1, T))
+  if min(cells, ch, ch_t, J) < 1:
+    raise ValueError('replay_states_pair: cells=%d ch=%d ch_t=%d J=%d' % (cells, ch, ch_t, J))
+  width = cells * (ch + J + ch_t)
+  if states.dim() != 3 or not states.is_contiguous() or states.shape[0] != K or states.shape[1] < t1 - t0 or states.shape[2] < width:
+    raise ValueError('replay_states_pair: states of shape %s for K=%d steps of >= %d windows of %d columns (contiguous [K][N][stride])'
+                     % (tuple(states.shape), K, t1 - t0, width))
+  if feat.numel() < T * cells * ch or tgt_feat.numel() < T * cells * ch_t or jnt.numel() < T * J:
+    raise ValueError('replay_states_pair: feat / tgt_feat / jnt of %d / %d / %d floats for T=%d cells=%d ch=%d ch_t=%d J=%d'
+                     % (feat.numel(), tgt_feat.numel(), jnt.numel(), T, cells, ch, ch_t, J))
+  check(_lib().geeco_replay_states_pair(_p(feat), _p(tgt_feat), _p(jnt), T, t0, t1, states.shape[1], K, cells, ch, ch_t, J, _p(states),
+                                        states.shape[2], _stream()), 'geeco_replay_states_pair')
+
+
 # -- attributions (csrc/attribution.hip; geeco_amd/attribution.py) --------------------------------------------------------------
 def _attr_flat(who, **tensors):
   """ValueError unless every given tensor is a contiguous float32 device tensor; returns their element counts."""

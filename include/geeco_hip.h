@@ -34,7 +34,7 @@ extern "C" {
  * geeco_heads_loss_shaped_fwd_bwd, geeco_lstm_step_heads_shaped_fwd_bwd, geeco_loss_shaping_sizeof,
  * geeco_grad_accumulate_segments, geeco_conv1_dgrad, geeco_pack_pixels_bwd, geeco_dynimg_bwd_ws_bytes, geeco_dynimg_bwd,
  * geeco_gather_windows_frames, geeco_replay_states, geeco_replay_errors, geeco_attr_path_point, geeco_attr_accumulate,
- * geeco_attr_finish */
+ * geeco_attr_finish, geeco_replay_images_ws_bytes, geeco_replay_images, geeco_replay_states_pair */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -845,6 +845,41 @@ int geeco_replay_states(const float* feat, const float* jnt, const float* tgt_fe
 #define GEECO_REPLAY_MAXHEADS 8
 int geeco_replay_errors(const float* preds, const float* labels, int T, int P, int nheads, const int* head_off,
                         const int* head_size, const int* head_kind, float* out_frame, float* out_episode, void* stream);
+
+/* ---- episode replay for the dynamic-image controllers (replay_dynimg.py; additive within ABI 7) -----------------
+ * geeco-f (proc_obs 'dynimg') and 'sequence' x 'dyndiff' over the T frames of one episode with the goal frame fixed: every conv1
+ * input is then a function of the frame number alone. */
+/* Input stage, read straight from the resident episode.  frame_addr: a DEVICE array of T frame addresses; a frame is [HW][3],
+ * uint8 (frames_u8 != 0; 4-byte aligned, read as float(u8) / 255 correctly rounded) or float32 in [0, 1] (16-byte aligned); goal:
+ * one frame of the same kind.  alpha_host [K] / alpha2_host [2]: geeco_dynimg_alpha(K) / (2), host memory.  For the windows
+ * t = t0 .. t1 - 1 (row t - t0 of each output, [t1 - t0][HW][4], 16-byte aligned):
+ *   cur_out  = frame t as (R, G, B, 0);
+ *   diff_out = the normalised two-frame dynamic image alpha2[0] frame_t + alpha2[1] goal;
+ *   buf_out  = the normalised dynamic image sum_k alpha[k] frame_{max(0, t - K + 1 + k)}, k = 0 .. K - 1 ascending (the window the
+ *              predictor holds after a reset at frame 0 and t pushes, predictor.py:192-200); buf_out == NULL skips the K-frame
+ *              walk (the per-frame form of 'sequence' x 'dyndiff').
+ * normalised = (D - min D) / (max D - min D + 1e-6f) over the window's HW x 3 values, the fourth channel 0.  The sums and the
+ * normalisation are those of geeco_dynimg_fwd (C = 3, Cpad = 4), so every output is bitwise what geeco_goal_dynimgs_fwd /
+ * geeco_goal_dynimgs_u8_fwd write for the explicitly built dense windows.  NOTE window 0 of buf_out: its K frames are equal and
+ * sum alpha = 0, so its raw image is float32 rounding residue (exactly 0 at K <= 3) and its normalised image is that residue
+ * scaled up: the reference's own behaviour after a reset, reproduced bit for bit, but nothing a float64 model predicts.
+ * Two launches: (1) per block the min / max of both raw images into ws, (2) the window's partials folded in a fixed order, both
+ * images formed again and stored normalised, once.  No block waits for another and there are no atomics: two runs are bitwise
+ * equal.  ws: geeco_replay_images_ws_bytes(t1 - t0, HW) bytes, 16-byte aligned, no zero-fill needed.  Blocks stride over
+ * (window, 1024-pixel block): no cap on T.  K: 1..64; HW % 4 == 0; 0 <= t0 < t1 <= T.  Nothing outside rows [0, t1 - t0) of the
+ * outputs is written. */
+int64_t geeco_replay_images_ws_bytes(int windows, int64_t HW);
+int geeco_replay_images(const void* const* frame_addr, const void* goal, int frames_u8, const float* alpha_host,
+                        const float* alpha2_host, int T, int t0, int t1, int K, int64_t HW, float* cur_out, float* buf_out,
+                        float* diff_out, void* ws, void* stream);
+/* geeco_replay_states with a per-frame second feature table: feat [T][cells][ch], tgt_feat [T][cells][ch_t], jnt [T][J] ->
+ * states [K][N][state_stride]; slot k of window t (row t - t0) takes frame max(0, t - K + 1 + k) from all three.  Per cell the
+ * columns are [feat (ch) | jnt (J) | tgt (ch_t)]: what geeco_state_concat_fwd writes for the dense 'sequence' x 'dyndiff' model
+ * (features ConvEncoder, DynDiffEncoder; jnt_pos = 1), the reference's tf.concat([feat, jnt, tgt_feat]) (graph.py:146-167).
+ * A copy, bit for bit.  16-byte loads when ch % 4 == 0, ch_t % 4 == 0 and both tables are aligned; 16-byte stores when also
+ * J % 4 == 0, state_stride % 4 == 0 and states is aligned.  N >= t1 - t0; rows t1 - t0 .. N - 1 are not touched. */
+int geeco_replay_states_pair(const float* feat, const float* tgt_feat, const float* jnt, int T, int t0, int t1, int N, int K,
+                             int cells, int ch, int ch_t, int J, float* states, int64_t state_stride, void* stream);
 
 /* ---- attributions: integrated gradients and SmoothGrad (attribution.py; additive within ABI 7) -------------------
  * Many input gradients along a family of perturbed inputs, summed on the device.  The three entries are the streaming stages

@@ -44,12 +44,129 @@ def host_blocks(forms, rounds, n, warm=1):
   return blocks
 
 
+DYNIMG_MODELS = {'geeco_f': dict(proc_obs='dynimg', proc_tgt='dyndiff'), 'seq_dyndiff': dict(proc_obs='sequence', proc_tgt='dyndiff')}
+
+
+def dynimg_main(args):
+  """``--model geeco_f`` / ``seq_dyndiff``: the same four forms for the dynamic-image controllers -- the stepped ones are
+  the NON-incremental predictors (``GoalE2EVMCPredictor``, ``BatchedGoalE2EVMCPredictor(1, frame_dtype='uint8')``; these models have
+  no incremental form), the replay is ``DynamicImageReplay`` -- and the two new kernels alone: geeco_replay_images (both launches) at
+  the replay's chunk beside a device copy that writes the bytes it must write, geeco_replay_states_pair at T x K windows beside a copy
+  of its bytes.  ``--stepped_only`` imports nothing of the replay."""
+  import numpy as np
+  import torch
+  from geeco_amd import estimator as est
+  from geeco_amd.batched_predictor import BatchedGoalE2EVMCPredictor
+  from geeco_amd.graph import model_variable_shapes
+  from geeco_amd.params import create_e2evmc_config
+  from geeco_amd.predictor import GoalE2EVMCPredictor
+  from geeco_amd.variables import VariableStore
+  H, K, T = args.size, args.window_size, args.frames
+  dev = torch.device('cuda', torch.cuda.current_device())
+  cfg = create_e2evmc_config(dict(window_size=K, img_height=H, img_width=H, **DYNIMG_MODELS[args.model]))
+  r = np.random.default_rng(7)
+  rgb = r.integers(0, 256, (T, H, H, 3), dtype=np.uint8)
+  goal = r.integers(0, 256, (H, H, 3), dtype=np.uint8)
+  rgb_f, goal_f = rgb.astype(np.float32) / np.float32(255), goal.astype(np.float32) / np.float32(255)
+  jnt = r.standard_normal((T, cfg.dim_jnt_state)).astype(np.float32)
+  with tempfile.TemporaryDirectory() as md:
+    json.dump(cfg._asdict(), open(os.path.join(md, 'e2evmc_config.json'), 'w'))
+    st = VariableStore(model_variable_shapes(cfg, True), 'cpu')
+    st.initialize(seed=4)
+    est.save_checkpoint(st, md, keep_max=1)
+    b1 = GoalE2EVMCPredictor(md, memcap=None, device=dev)
+    b1.set_goal(goal_f)
+    core = BatchedGoalE2EVMCPredictor(md, 1, memcap=None, device=dev, frame_dtype='uint8')
+    core.set_goal(goal[None])
+
+    def stepped_batch1():
+      b1.reset()
+      return [b1.predict(rgb_f[t], jnt[t]) for t in range(T)]
+
+    def stepped_core():
+      core.reset()
+      return [core.predict(rgb[t:t + 1], jnt[t:t + 1]) for t in range(T)]
+
+    forms = {'stepped_batch1': stepped_batch1, 'stepped_core_uint8': stepped_core}
+    results = {
+        'shape': dict(size=H, window_size=K, frames=T, model=args.model, frames_dtype='uint8'),
+        'timing': dict(episodes_per_block=args.steps, rounds=args.rounds,
+                       method='whole episodes by the host clock, each call ending in a device synchronise, the forms alternating in one '
+                              'process, medians of the blocks; kernels alone between device events, 50 launches per block'),
+        'device': torch.cuda.get_device_name(dev),
+    }
+    if not args.stepped_only:
+      from geeco_amd import ops
+      from geeco_amd.replay_dynimg import DynamicImageReplay
+      rp = DynamicImageReplay(md, device=dev, max_frames=T)
+      resident, goal_dev = torch.from_numpy(rgb).to(dev), torch.from_numpy(goal).to(dev)
+      forms['replay_resident'] = lambda: rp.replay((resident, jnt), goal_frame=goal_dev, labels=False)
+      forms['replay_dense'] = lambda: rp.replay((rgb, jnt), goal_frame=goal, labels=False)
+      results['shape'].update(chunk_frames=rp.chunk_frames, chunk_windows=rp.chunk_windows, encoder_stacks=len(rp.encs))
+      out = rp.replay((resident, jnt), goal_frame=goal_dev, labels=False)
+      core.reset()
+      worst, bitwise = 0.0, True
+      for t in range(T):
+        core.predict(rgb[t:t + 1], jnt[t:t + 1])
+        for k, v in core._model.predictions().items():
+          s = v[0].cpu().numpy()
+          worst, bitwise = max(worst, float(np.abs(out[k][t] - s).max())), bitwise and np.array_equal(out[k][t], s)
+      results['replay_vs_stepped'] = dict(max_abs_diff=worst, bitwise=bitwise, frames='all, frame 0 included')
+    blocks = host_blocks(forms, args.rounds, args.steps)
+    med = {k: statistics.median(v) for k, v in blocks.items()}
+    results['episode_ms'] = {k: round(v, 4) for k, v in med.items()}
+    results['episode_ms_blocks'] = ab.rounded(blocks, 4)
+    results['per_frame_ms'] = {k: round(v / T, 5) for k, v in med.items()}
+    if args.stepped_only:
+      return ab.write(results, args.out)
+    results['stepped_over_replay'] = {s: round(med[s] / med['replay_resident'], 2) for s in ('stepped_batch1', 'stepped_core_uint8')}
+
+    # the image stage alone (both launches) at one chunk, beside a copy that writes the bytes the stage must write
+    HW, F, geeco_f = H * H, rp.chunk_frames, args.model == 'geeco_f'
+    n = min(F, T)
+    addr = torch.from_numpy(resident.data_ptr() + np.arange(T, dtype=np.int64) * HW * 3).to(dev)
+    imgs = [torch.empty(n, HW, 4, device=dev) for _ in range(3)]
+    ws = ops.replay_images_ws(n, HW, dev)
+    w_bytes = (3 if geeco_f else 2) * n * HW * 16
+    src, dst = torch.empty(w_bytes // 4, device=dev), torch.empty(w_bytes // 4, device=dev)
+    i_blocks = ab.alternate({'replay_images': lambda: ops.replay_images_into(imgs[0], imgs[1] if geeco_f else None, imgs[2], addr, goal_dev.view(HW, 3),
+                                                                             T, 0, n, K, HW, ws),
+                             'copy_written_bytes': lambda: dst.copy_(src)}, args.rounds, 50, warm=10, scale=1e3)
+    i_med = ab.medians(i_blocks)
+    results.update({'replay_images_us': {k: round(v, 2) for k, v in i_med.items()}, 'replay_images_us_blocks': ab.rounded(i_blocks, 2),
+                    'replay_images_windows': n, 'replay_images_written_bytes': w_bytes,
+                    'replay_images_share_of_pass': round(i_med['replay_images'] * -(-T // n) / 1e3 / med['replay_resident'], 3)})
+    if not geeco_f:
+      d, J, cells = rp.decoder, cfg.dim_jnt_state, 4
+      feat, tgt = torch.randn(T, cells, rp.dims[0], device=dev), torch.randn(T, cells, rp.dims[1], device=dev)
+      jd, states = torch.from_numpy(jnt).to(dev), torch.empty(K, T, d.D, device=dev)
+      s_bytes = 4 * (states.numel() + feat.numel() + tgt.numel() + jd.numel())
+      src2, dst2 = torch.empty(s_bytes // 8, device=dev), torch.empty(s_bytes // 8, device=dev)
+      s_blocks = ab.alternate({'replay_states_pair': lambda: ops.replay_states_pair_into(states, feat, tgt, jd, T, 0, T, K, cells, rp.dims[0], rp.dims[1], J),
+                               'copy_same_bytes': lambda: dst2.copy_(src2)}, args.rounds, 50, warm=10, scale=1e3)
+      s_med = ab.medians(s_blocks)
+      results.update({'replay_states_pair_us': {k: round(v, 2) for k, v in s_med.items()}, 'replay_states_pair_us_blocks': ab.rounded(s_blocks, 2),
+                      'replay_states_pair_bytes': s_bytes})
+    results['not_measured'] = ['float32 frames', 'any shape but this one', 'episodes read from disk', 'replay beside other work on the device',
+                               'the stepped forms in the parent tree unless run there with --stepped_only']
+    ab.write(results, args.out)
+
+
 def main():
   ap = ab.arguments('episode_replay', steps_help='episodes per timed block')
-  ap.set_defaults(steps=5, out=os.path.join(ab.ROOT, 'profiles', 'episode_replay', 'replay.json'))
+  default_out = os.path.join(ab.ROOT, 'profiles', 'episode_replay', 'replay.json')
+  ap.set_defaults(steps=5, out=default_out)
   ap.add_argument('--frames', type=int, default=100)
   ap.add_argument('--stepped_only', action='store_true', help='the stepped forms alone (works in a tree without the replay)')
+  ap.add_argument('--model', choices=('e2e_vmc',) + tuple(DYNIMG_MODELS), default='e2e_vmc',
+                  help='geeco_f / seq_dyndiff: the dynamic-image controllers (DESIGN 5.29) -> profiles/episode_replay/dynimg.json')
   args = ap.parse_args()
+  if args.model != 'e2e_vmc':
+    if args.out == default_out:
+      args.out = os.path.join(ab.ROOT, 'profiles', 'episode_replay', 'dynimg.json' if args.model == 'geeco_f' else 'dynimg_%s.json' % args.model)
+    if not __import__('torch').cuda.is_available():
+      raise SystemExit('episode_replay_step.py measures on the GPU; none is visible')
+    return dynimg_main(args)
 
   import numpy as np
   import torch

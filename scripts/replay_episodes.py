@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Replays a trained per-frame controller over the recorded episodes of a dataset split: what would it have commanded at every
-frame, and how far is that from what was recorded?
+"""Replays a trained controller over the recorded episodes of a dataset split: what would it have commanded at every frame, and
+how far is that from what was recorded?  The per-frame controllers go through EpisodeReplay, geeco-f (proc_obs 'dynimg') and
+'sequence' x 'dyndiff' through DynamicImageReplay (geeco_amd.open_replay picks by the run's config).
 
   python scripts/replay_episodes.py --model_dir RUN --dataset_dir DATA --split val --out replay.npz
 
@@ -21,6 +22,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from geeco_amd import replay as rp      # noqa: E402
+from geeco_amd.replay_dynimg import open_replay      # noqa: E402
 
 
 def parse_args(argv=None):
@@ -45,8 +47,7 @@ def table(title, keys, values):
 def main(argv=None):
   args = parse_args(argv)
   mode = 'eval' if args.split == 'val' else args.split
-  r = rp.EpisodeReplay(args.model_dir, args.checkpoint_name, use_ema=args.use_ema, max_frames=args.max_frames,
-                       chunk_frames=args.chunk_frames)
+  r = open_replay(args.model_dir, args.checkpoint_name, use_ema=args.use_ema, max_frames=args.max_frames, chunk_frames=args.chunk_frames)
   keys = [k for k, _, _ in r.heads]
   outs, names = [], []
   for ep in rp.dataset_episodes(args.dataset_dir, args.split_name, mode, r.device, fetch_target=r.goal):
