@@ -1,70 +1,90 @@
-// Episode replay (geeco_amd/replay.py): what a per-frame controller would have commanded at every frame of a
-// recorded episode, and how far that is from what was recorded.  The T frames are encoded once each (frame pack by address +
-// the encoder stack, shared_frames.hip / encoder.py); what is here is
-//   1. replay_states: feat [T][cells][ch] + jnt [T][J] (+ tgt_feat [cells][ch]) -> the decoder's states [K][N][D] of the windows
+// Episode replay (geeco_amd/replay.py, replay_dynimg.py): what a controller would have commanded at every
+// frame of a recorded episode, and how far that is from what was recorded.  The T frames are encoded once each (the encoder
+// stacks, fed by shared_frames.hip or by the image stage of replay_dynimg.hip); what is here is
+//   1. the window states: per-frame tables [T][cells][cw] + jnt [T][J] -> the decoder's states [K][N][D] of the windows
 //                     t0 .. t1 - 1, slot k of window t showing frame max(0, t - K + 1 + k) (the predictor's window after a reset
-//                     at frame 0 and t pushes, predictor.py:192-200); columns: state_layout.h;
+//                     at frame 0 and t pushes, predictor.py:192-200).  ONE kernel behind both entry points:
+//                     replay_states       one table and a constant target row, the columns of state_layout.h;
+//                     replay_states_pair  two tables, per cell [feat (ch) | jnt (J) | tgt (ch_t)]: what the dense 'sequence' x
+//                                         'dyndiff' model's concat writes (state_concat_fwd with jnt_pos = 1; graph.py:146-167
+//                                         of the reference: tf.concat([feat, jnt, tgt_feat]));
 //   2. replay_errors: preds [T][P] against the recorded values -> per frame and head the mean squared error (regression heads) or
 //                     the hit of the gripper class (logit heads), and their means over the episode in one fixed order.
 // The first is a pure HBM gather (every feature row is read up to K times, from L2 after the first), grid-stride with 16-byte
 // accesses where the layout allows; the second is tiny.  No atomics.
 //
-// From frame_ingest.h: ld_vec; from state_layout.h: the state columns and check_state_layout.
-#include "dynimg_internal.h"      // DYN_MAXK
+// From replay_internal.h: RP_THREADS, RP_MAX_BLOCKS, RP_MAXK and check_replay_windows (shared with replay_dynimg.hip); from
+// frame_ingest.h: ld_vec; from state_layout.h: the state columns and check_state_layout.
+#include "replay_internal.h"
 #include "frame_ingest.h"
 #include "state_layout.h"
 
-#define RP_THREADS 256
-#define RP_MAXK DYN_MAXK          // the window lengths the predictors take
-#define RP_MAX_BLOCKS 2048        // 8 blocks of 256 threads per CU: the grid-stride loop takes the rest
-
 // ---- 1. window states ----------------------------------------------------------------------------------------------------------
-// A unit = V floats of one feature row (ch % V == 0: a unit stays inside one cell); units are numbered (k, window, q) with q
-// fastest, so a wave reads and writes consecutive addresses.  V = 4: 16-byte loads; VS: 16-byte stores as well (J % 4 == 0 and
-// state_stride % 4 == 0, so every cell's columns start at a multiple of 4 floats).  The joint-state columns follow in a second
-// loop of the same grid, one float per lane.
+// What the kernel reads by value: where every column of a cell comes from.
+enum { RP_TGT_NONE = 0, RP_TGT_APPEND = 1, RP_TGT_RESIDUAL = 2 };
+struct ReplayTable {
+  const float* src;      // [T][cells][cw], indexed by the frame a slot shows; null: no such table
+  int cw, c0;            // its width and its first column within a cell
+};
+struct ReplayStatesDesc {
+  ReplayTable tab[2];
+  int jnt_off;           // first joint-state column of a cell
+  int Ctot;              // columns of one cell
+  const float* tgt;      // [cells][tab[0].cw], constant over the episode; goes with table 0
+  int tgt_op;            // RP_TGT_NONE; _APPEND: copied to the columns from tgt_c0; _RESIDUAL: the table's columns hold tgt - feat
+  int tgt_c0;
+};
+
+// A unit = V floats of one table row (cw % V == 0: a unit stays inside one cell); units are numbered (k, window, q) with q
+// fastest, so a wave reads and writes consecutive addresses; the tables one after the other.  V = 4: 16-byte loads; VS: 16-byte
+// stores as well (J % 4 == 0 and state_stride % 4 == 0, so every table's columns start at a multiple of 4 floats).  The
+// joint-state columns follow in a second loop of the same grid, one float per lane.
 template <int V, bool VS>
-__global__ __launch_bounds__(RP_THREADS) void replay_states_kernel(const float* __restrict__ feat, const float* __restrict__ jnt,
-                                                                  const float* __restrict__ tgt, int mode, int t0, int n, int N,
-                                                                  int K, int cells, int ch, int J, float* __restrict__ states,
+__global__ __launch_bounds__(RP_THREADS) void replay_states_kernel(const ReplayStatesDesc d, const float* __restrict__ jnt, int t0,
+                                                                  int n, int N, int K, int cells, int J, float* __restrict__ states,
                                                                   long long state_stride) {
-  const int FE = cells * ch;
-  const StateLayout<int> L = state_layout(mode, ch, J);
-  const int nq = FE / V;
   const long long step = (long long)gridDim.x * RP_THREADS;
   const long long first = (long long)blockIdx.x * RP_THREADS + threadIdx.x;
-  const long long units = (long long)K * n * nq;
-  for (long long u = first; u < units; u += step) {
-    const int q = (int)(u % nq);
-    const long long r = u / nq;                  // = k * n + w
-    const int w = (int)(r % n), k = (int)(r / n);
-    int f = t0 + w - K + 1 + k;                  // the frame slot k of window t0 + w shows
-    if (f < 0) f = 0;                            // first-frame padding after the reset at frame 0
-    float v[V];
-    ld_vec<V>(feat + (long long)f * FE + q * V, v);
-    const int cell = (q * V) / ch, c = q * V - cell * ch;
-    float* o = states + ((long long)k * N + w) * state_stride + cell * L.Ctot + c;
-    if (mode != GEECO_PREDICT_FEAT_PLAIN) {
-      float g[V];
-      ld_vec<V>(tgt + q * V, g);
-      if (mode == GEECO_PREDICT_FEAT_CONSTANT) {
-        float* og = o + L.jnt_off + J;           // (= L.tgt_off, without its select)
-        if (VS) {
-          *reinterpret_cast<f32x4*>(og) = f32x4{g[0], g[1], g[2], g[3]};
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const float* __restrict__ src = d.tab[s].src;
+    if (!src) break;
+    const int cw = d.tab[s].cw, c0 = d.tab[s].c0;
+    const int op = s == 0 ? d.tgt_op : RP_TGT_NONE;
+    const int FE = cells * cw, nq = FE / V;
+    const long long units = (long long)K * n * nq;
+    for (long long u = first; u < units; u += step) {
+      const int q = (int)(u % nq);
+      const long long r = u / nq;                  // = k * n + w
+      const int w = (int)(r % n), k = (int)(r / n);
+      int f = t0 + w - K + 1 + k;                  // the frame slot k of window t0 + w shows
+      if (f < 0) f = 0;                            // first-frame padding after the reset at frame 0
+      float v[V];
+      ld_vec<V>(src + (long long)f * FE + q * V, v);
+      const int cell = (q * V) / cw, c = q * V - cell * cw;
+      float* o = states + ((long long)k * N + w) * state_stride + cell * d.Ctot + c0 + c;
+      if (op != RP_TGT_NONE) {
+        float g[V];
+        ld_vec<V>(d.tgt + q * V, g);
+        if (op == RP_TGT_APPEND) {
+          float* og = o + (d.tgt_c0 - c0);
+          if (VS) {
+            *reinterpret_cast<f32x4*>(og) = f32x4{g[0], g[1], g[2], g[3]};
+          } else {
+#pragma unroll
+            for (int i = 0; i < V; ++i) og[i] = g[i];
+          }
         } else {
 #pragma unroll
-          for (int i = 0; i < V; ++i) og[i] = g[i];
+          for (int i = 0; i < V; ++i) v[i] = g[i] - v[i];
         }
+      }
+      if (VS) {
+        *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
       } else {
 #pragma unroll
-        for (int i = 0; i < V; ++i) v[i] = g[i] - v[i];
+        for (int i = 0; i < V; ++i) o[i] = v[i];
       }
-    }
-    if (VS) {
-      *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
-    } else {
-#pragma unroll
-      for (int i = 0; i < V; ++i) o[i] = v[i];
     }
   }
   const int CJ = cells * J;
@@ -76,30 +96,32 @@ __global__ __launch_bounds__(RP_THREADS) void replay_states_kernel(const float* 
     int f = t0 + w - K + 1 + k;
     if (f < 0) f = 0;
     const int cell = i / J, j = i - cell * J;
-    states[((long long)k * N + w) * state_stride + cell * L.Ctot + L.jnt_off + j] = jnt[(long long)f * J + j];
+    states[((long long)k * N + w) * state_stride + cell * d.Ctot + d.jnt_off + j] = jnt[(long long)f * J + j];
   }
 }
 
-extern "C" int geeco_replay_states(const float* feat, const float* jnt, const float* tgt_feat, int mode, int T, int t0, int t1,
-                                   int N, int K, int cells, int ch, int J, float* states, int64_t state_stride, void* stream) {
-  GEECO_CHECK_ARG(feat && jnt && states, "replay_states: null pointer");
-  if (int rc = check_state_layout("replay_states", mode, cells, ch, J, state_stride)) return rc;
-  GEECO_CHECK_ARG(mode == GEECO_PREDICT_FEAT_PLAIN || tgt_feat, "replay_states: null pointer (tgt_feat, mode %d)", mode);
-  GEECO_CHECK_ARG(K >= 1 && K <= RP_MAXK, "replay_states: K=%d outside 1..%d", K, RP_MAXK);
-  GEECO_CHECK_ARG(T >= 1 && t0 >= 0 && t0 < t1 && t1 <= T, "replay_states: windows [%d, %d) outside the %d frames", t0, t1, T);
-  GEECO_CHECK_ARG(N >= t1 - t0, "replay_states: N=%d rows per step for %d windows", N, t1 - t0);
-  const int n = t1 - t0;
-  const uintptr_t src = reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(tgt_feat);
-  const bool vec = ch % 4 == 0 && (src & 15) == 0;
+// The one launch behind both entry points (arguments checked by the caller).  16-byte loads when EVERY table's width is a
+// multiple of 4 and every source is 16-byte aligned -- a mixed case takes the scalar form as a whole --, 16-byte stores when J,
+// the row pitch and states allow them as well; the grid covers the longest of the kernel's loops.
+static int launch_replay_states(const ReplayStatesDesc& d, const float* jnt, int t0, int n, int N, int K, int cells, int J,
+                                float* states, int64_t state_stride, hipStream_t s) {
+  uintptr_t src = reinterpret_cast<uintptr_t>(d.tgt);
+  int widths = 0, widest = 0;
+  for (const ReplayTable& t : d.tab) {
+    if (!t.src) continue;
+    src |= reinterpret_cast<uintptr_t>(t.src);
+    widths |= t.cw;
+    widest = std::max(widest, t.cw);
+  }
+  const bool vec = widths % 4 == 0 && (src & 15) == 0;
   const bool vst = vec && J % 4 == 0 && state_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(states) & 15) == 0;
-  const long long units = std::max<long long>((long long)K * n * (cells * ch / (vec ? 4 : 1)), (long long)K * n * cells * J);
-  const unsigned grid = (unsigned)std::min<long long>(cdiv64(units, RP_THREADS), RP_MAX_BLOCKS);
-  hipStream_t s = (hipStream_t)stream;
+  const long long per = std::max<long long>(cells * widest / (vec ? 4 : 1), (long long)cells * J);
+  const unsigned grid = (unsigned)std::min<long long>(cdiv64((long long)K * n * per, RP_THREADS), RP_MAX_BLOCKS);
 #define RP_LAUNCH(V, VS)                                                                                                        \
   do {                                                                                                                          \
     geeco_note_kernel("replay_states_kernel<%d, %s>", V, VS ? "true" : "false");                                              \
-    hipLaunchKernelGGL((replay_states_kernel<V, VS>), dim3(grid), dim3(RP_THREADS), 0, s, feat, jnt, tgt_feat, mode, t0, n, N, K, \
-                       cells, ch, J, states, (long long)state_stride);                                                          \
+    hipLaunchKernelGGL((replay_states_kernel<V, VS>), dim3(grid), dim3(RP_THREADS), 0, s, d, jnt, t0, n, N, K, cells, J, states, \
+                       (long long)state_stride);                                                                                \
   } while (0)
   if (vst) RP_LAUNCH(4, true);
   else if (vec) RP_LAUNCH(4, false);
@@ -107,6 +129,43 @@ extern "C" int geeco_replay_states(const float* feat, const float* jnt, const fl
 #undef RP_LAUNCH
   GEECO_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int geeco_replay_states(const float* feat, const float* jnt, const float* tgt_feat, int mode, int T, int t0, int t1,
+                                   int N, int K, int cells, int ch, int J, float* states, int64_t state_stride, void* stream) {
+  GEECO_CHECK_ARG(feat && jnt && states, "replay_states: null pointer");
+  if (int rc = check_state_layout("replay_states", mode, cells, ch, J, state_stride)) return rc;
+  GEECO_CHECK_ARG(mode == GEECO_PREDICT_FEAT_PLAIN || tgt_feat, "replay_states: null pointer (tgt_feat, mode %d)", mode);
+  if (int rc = check_replay_windows("replay_states", T, t0, t1, N, K)) return rc;
+  const StateLayout<int> L = state_layout(mode, ch, J);
+  ReplayStatesDesc d = {};
+  d.tab[0] = {feat, ch, 0};
+  d.jnt_off = L.jnt_off;
+  d.Ctot = L.Ctot;
+  if (mode != GEECO_PREDICT_FEAT_PLAIN) {
+    d.tgt = tgt_feat;
+    d.tgt_op = mode == GEECO_PREDICT_FEAT_CONSTANT ? RP_TGT_APPEND : RP_TGT_RESIDUAL;
+    d.tgt_c0 = L.tgt_off;
+  }
+  return launch_replay_states(d, jnt, t0, t1 - t0, N, K, cells, J, states, state_stride, (hipStream_t)stream);
+}
+
+extern "C" int geeco_replay_states_pair(const float* feat, const float* tgt_feat, const float* jnt, int T, int t0, int t1, int N,
+                                        int K, int cells, int ch, int ch_t, int J, float* states, int64_t state_stride,
+                                        void* stream) {
+  GEECO_CHECK_ARG(feat && tgt_feat && jnt && states, "replay_states_pair: null pointer");
+  GEECO_CHECK_ARG(cells >= 1 && ch >= 1 && ch_t >= 1 && J >= 1 && (int64_t)cells * ch <= (1 << 24) && (int64_t)cells * ch_t <= (1 << 24) &&
+                      J <= (1 << 24),
+                  "replay_states_pair: cells=%d ch=%d ch_t=%d J=%d", cells, ch, ch_t, J);
+  GEECO_CHECK_ARG(state_stride >= (int64_t)cells * ((int64_t)ch + J + ch_t), "replay_states_pair: state_stride=%lld below cells * %lld columns",
+                  (long long)state_stride, (long long)ch + J + ch_t);
+  if (int rc = check_replay_windows("replay_states_pair", T, t0, t1, N, K)) return rc;
+  ReplayStatesDesc d = {};
+  d.tab[0] = {feat, ch, 0};
+  d.tab[1] = {tgt_feat, ch_t, ch + J};
+  d.jnt_off = ch;
+  d.Ctot = ch + J + ch_t;
+  return launch_replay_states(d, jnt, t0, t1 - t0, N, K, cells, J, states, state_stride, (hipStream_t)stream);
 }
 
 // ---- 2. errors -------------------------------------------------------------------------------------------------------------------

@@ -1,10 +1,11 @@
 // Episode replay for the dynamic-image controllers (geeco_amd/replay_dynimg.py): geeco-f (proc_obs 'dynimg') and
 // 'sequence' x 'dyndiff'.  With the goal fixed for the episode every conv1 input of these models is a function of the frame
 // number alone, so the episode's inputs are built in chunks of many frames, straight from the resident frames:
-//   1. replay_images: for the windows t0 .. t1 - 1 the current frame (R, G, B, 0), the normalised pair image of (frame t, goal)
+//      replay_images: for the windows t0 .. t1 - 1 the current frame (R, G, B, 0), the normalised pair image of (frame t, goal)
 //                     and the normalised buffer image of the frames max(0, t - K + 1 + k), k = 0 .. K - 1 (the predictor's window
 //                     after a reset at frame 0 and t pushes, predictor.py:192-200; replay.window_frames);
-//   2. replay_states_pair: replay_states (replay.hip) with a per-frame second feature table, [feat | jnt | tgt] per cell.
+// and nothing else: the window states of the 'sequence' x 'dyndiff' model (geeco_replay_states_pair) come from the one state
+// kernel in replay.hip, and the window checks, thread and block constants every replay entry point uses from replay_internal.h.
 //
 // The image stage is TWO launches and no block waits for another block: launch 1 forms both raw images in registers and leaves
 // each block's min / max of them in ws; launch 2 folds a window's partials, forms the images AGAIN and stores them normalised,
@@ -24,14 +25,10 @@
 // conversion is u8x4_unit of frame_ingest.h.  Both launches run ONE inlined body (ri_images), so launch 2 normalises exactly
 // the values launch 1 took the extrema of.  Min / max are folded in a fixed order without atomics: two runs are bitwise equal.
 //
-// From dynimg_internal.h: DYN_MAXK; from frame_ingest.h: u8x4_unit, ld_vec.
-#include "dynimg_internal.h"
+// From replay_internal.h: RP_THREADS, RP_MAX_BLOCKS, check_replay_windows, DYN_MAXK; from frame_ingest.h: u8x4_unit, ld_vec.
+#include "replay_internal.h"
 #include "frame_ingest.h"
 
-#define RI_THREADS 256
-#define RI_MAX_BLOCKS 2048        // 8 blocks of 256 threads per CU: the block-stride loop takes the rest
-
-// ---- 1. the images --------------------------------------------------------------------------------------------------------------
 struct ReplayImgParams {
   const unsigned long long* addr;      // [T] device addresses of the episode's frames ([HW][3], uint8 or float32)
   const void* goal;                    // one frame of the same kind
@@ -155,13 +152,13 @@ __device__ __forceinline__ void ri_normalise(f32x4 (&X)[3], float m, float r) {
 // A work item = (window, block of 256 units); a block takes the items blockIdx.x, + gridDim.x, ..
 // Launch 1: the item's min / max of both raw images -> part[item]
 template <bool U8, bool BUF>
-__global__ __launch_bounds__(RI_THREADS) void replay_images_minmax_kernel(const ReplayImgParams p) {
+__global__ __launch_bounds__(RP_THREADS) void replay_images_minmax_kernel(const ReplayImgParams p) {
   __shared__ float red[4][4];
   const long long U = p.HW >> 2;
   const long long items = (long long)p.n * p.bpw;
   for (long long it = blockIdx.x; it < items; it += gridDim.x) {
     const int w = (int)(it / p.bpw), b = (int)(it - (long long)w * p.bpw);
-    const long long u = (long long)b * RI_THREADS + threadIdx.x;
+    const long long u = (long long)b * RP_THREADS + threadIdx.x;
     float mn1 = INFINITY, mx1 = -INFINITY, mn2 = INFINITY, mx2 = -INFINITY;
     if (u < U) {
       f32x4 c[3], A[3], D[3];
@@ -178,15 +175,15 @@ __global__ __launch_bounds__(RI_THREADS) void replay_images_minmax_kernel(const 
 // Launch 2: the window's partials folded (a thread over the blocks i, i + 256, .. ascending, then as a block's), both images formed
 // again, normalised and stored with the current frame's padded copy
 template <bool U8, bool BUF>
-__global__ __launch_bounds__(RI_THREADS) void replay_images_emit_kernel(const ReplayImgParams p) {
+__global__ __launch_bounds__(RP_THREADS) void replay_images_emit_kernel(const ReplayImgParams p) {
   __shared__ float red[4][4];
   const long long U = p.HW >> 2;
   const long long items = (long long)p.n * p.bpw;
   for (long long it = blockIdx.x; it < items; it += gridDim.x) {
     const int w = (int)(it / p.bpw), b = (int)(it - (long long)w * p.bpw);
-    const long long u = (long long)b * RI_THREADS + threadIdx.x;
+    const long long u = (long long)b * RP_THREADS + threadIdx.x;
     float mn1 = INFINITY, mx1 = -INFINITY, mn2 = INFINITY, mx2 = -INFINITY;
-    for (int i = threadIdx.x; i < p.bpw; i += RI_THREADS) {
+    for (int i = threadIdx.x; i < p.bpw; i += RP_THREADS) {
       const f32x4 q = *reinterpret_cast<const f32x4*>(p.part + ((long long)w * p.bpw + i) * 4);
       mn1 = fminf(mn1, q.x);
       mx1 = fmaxf(mx1, q.y);
@@ -211,16 +208,15 @@ __global__ __launch_bounds__(RI_THREADS) void replay_images_emit_kernel(const Re
 
 extern "C" int64_t geeco_replay_images_ws_bytes(int windows, int64_t HW) {
   if (windows <= 0 || HW <= 0) return 0;
-  return (int64_t)windows * cdiv64(HW >> 2, RI_THREADS) * 16;
+  return (int64_t)windows * cdiv64(HW >> 2, RP_THREADS) * 16;
 }
 
 extern "C" int geeco_replay_images(const void* const* frame_addr, const void* goal, int frames_u8, const float* alpha_host,
                                    const float* alpha2_host, int T, int t0, int t1, int K, int64_t HW, float* cur_out,
                                    float* buf_out, float* diff_out, void* ws, void* stream) {
   GEECO_CHECK_ARG(frame_addr && goal && alpha_host && alpha2_host && cur_out && diff_out && ws, "replay_images: null pointer");
-  GEECO_CHECK_ARG(K >= 1 && K <= DYN_MAXK, "replay_images: K=%d outside 1..%d", K, DYN_MAXK);
   GEECO_CHECK_ARG(HW >= 4 && (HW & 3) == 0 && HW < (1ll << 40), "replay_images: HW=%lld must be a multiple of 4", (long long)HW);
-  GEECO_CHECK_ARG(T >= 1 && t0 >= 0 && t0 < t1 && t1 <= T, "replay_images: windows [%d, %d) outside the %d frames", t0, t1, T);
+  if (int rc = check_replay_windows("replay_images", T, t0, t1, t1 - t0, K)) return rc;      // (one output row per window)
   const uintptr_t outs = reinterpret_cast<uintptr_t>(cur_out) | reinterpret_cast<uintptr_t>(buf_out) |
                          reinterpret_cast<uintptr_t>(diff_out) | reinterpret_cast<uintptr_t>(ws);
   GEECO_CHECK_ARG((outs & 15) == 0, "replay_images: outputs and ws must be 16-byte aligned");
@@ -230,19 +226,19 @@ extern "C" int geeco_replay_images(const void* const* frame_addr, const void* go
   p.addr = reinterpret_cast<const unsigned long long*>(frame_addr);
   p.goal = goal;
   p.t0 = t0; p.n = t1 - t0; p.K = K; p.HW = HW;
-  p.bpw = (int)cdiv64(HW >> 2, RI_THREADS);
+  p.bpw = (int)cdiv64(HW >> 2, RP_THREADS);
   p.cur_out = cur_out; p.buf_out = buf_out; p.diff_out = diff_out; p.part = (float*)ws;
   for (int k = 0; k < K; ++k) p.alpha[k] = alpha_host[k];
   p.alpha2[0] = alpha2_host[0]; p.alpha2[1] = alpha2_host[1];
-  const unsigned grid = (unsigned)std::min<long long>((long long)p.n * p.bpw, RI_MAX_BLOCKS);
+  const unsigned grid = (unsigned)std::min<long long>((long long)p.n * p.bpw, RP_MAX_BLOCKS);
   hipStream_t s = (hipStream_t)stream;
 #define RI_LAUNCH(U8, BUF)                                                                                                      \
   do {                                                                                                                          \
     geeco_note_kernel("replay_images_minmax_kernel<%s, %s>", U8 ? "true" : "false", BUF ? "true" : "false");                    \
-    hipLaunchKernelGGL((replay_images_minmax_kernel<U8, BUF>), dim3(grid), dim3(RI_THREADS), 0, s, p);                          \
+    hipLaunchKernelGGL((replay_images_minmax_kernel<U8, BUF>), dim3(grid), dim3(RP_THREADS), 0, s, p);                          \
     GEECO_LAUNCH_CHECK();                                                                                                       \
     geeco_note_kernel("replay_images_emit_kernel<%s, %s>", U8 ? "true" : "false", BUF ? "true" : "false");                     \
-    hipLaunchKernelGGL((replay_images_emit_kernel<U8, BUF>), dim3(grid), dim3(RI_THREADS), 0, s, p);                           \
+    hipLaunchKernelGGL((replay_images_emit_kernel<U8, BUF>), dim3(grid), dim3(RP_THREADS), 0, s, p);                           \
   } while (0)
   if (frames_u8) {
     if (buf_out) RI_LAUNCH(true, true);
@@ -252,89 +248,6 @@ extern "C" int geeco_replay_images(const void* const* frame_addr, const void* go
     else RI_LAUNCH(false, false);
   }
 #undef RI_LAUNCH
-  GEECO_LAUNCH_CHECK();
-  return 0;
-}
-
-// ---- 2. window states with a per-frame target table -----------------------------------------------------------------------------
-// replay_states_kernel (replay.hip) with tgt [T][cells][ch_t] indexed by the same frame as feat.  Per cell the columns are
-// [feat (ch) | jnt (J) | tgt (ch_t)]: what the dense 'sequence' x 'dyndiff' model's concat writes, state_concat_fwd with the
-// features (ConvEncoder, DynDiffEncoder) and jnt_pos = 1 (graph.py: _concat_states; representation_concatenation of the
-// reference, graph.py:146-167: tf.concat([feat, jnt, tgt_feat])).  Same units, vector widths and grid as replay_states_kernel.
-template <int V, bool VS>
-__global__ __launch_bounds__(RI_THREADS) void replay_states_pair_kernel(const float* __restrict__ feat, const float* __restrict__ tgt,
-                                                                       const float* __restrict__ jnt, int t0, int n, int N, int K,
-                                                                       int cells, int ch, int ch_t, int J, float* __restrict__ states,
-                                                                       long long state_stride) {
-  const int Ctot = ch + J + ch_t;
-  const long long step = (long long)gridDim.x * RI_THREADS;
-  const long long first = (long long)blockIdx.x * RI_THREADS + threadIdx.x;
-  // the two feature tables, one after the other: table s has width cw and starts at column c0 of a cell
-  for (int s = 0; s < 2; ++s) {
-    const float* src = s ? tgt : feat;
-    const int cw = s ? ch_t : ch, c0 = s ? ch + J : 0;
-    const int FE = cells * cw, nq = FE / V;
-    const long long units = (long long)K * n * nq;
-    for (long long u = first; u < units; u += step) {
-      const int q = (int)(u % nq);
-      const long long r = u / nq;                  // = k * n + w
-      const int w = (int)(r % n), k = (int)(r / n);
-      int f = t0 + w - K + 1 + k;                  // the frame slot k of window t0 + w shows
-      if (f < 0) f = 0;                            // first-frame padding after the reset at frame 0
-      float v[V];
-      ld_vec<V>(src + (long long)f * FE + q * V, v);
-      const int cell = (q * V) / cw, c = q * V - cell * cw;
-      float* o = states + ((long long)k * N + w) * state_stride + cell * Ctot + c0 + c;
-      if (VS) {
-        *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
-      } else {
-#pragma unroll
-        for (int i = 0; i < V; ++i) o[i] = v[i];
-      }
-    }
-  }
-  const int CJ = cells * J;
-  const long long junits = (long long)K * n * CJ;
-  for (long long u = first; u < junits; u += step) {
-    const int i = (int)(u % CJ);
-    const long long r = u / CJ;
-    const int w = (int)(r % n), k = (int)(r / n);
-    int f = t0 + w - K + 1 + k;
-    if (f < 0) f = 0;
-    const int cell = i / J, j = i - cell * J;
-    states[((long long)k * N + w) * state_stride + cell * Ctot + ch + j] = jnt[(long long)f * J + j];
-  }
-}
-
-extern "C" int geeco_replay_states_pair(const float* feat, const float* tgt_feat, const float* jnt, int T, int t0, int t1, int N,
-                                        int K, int cells, int ch, int ch_t, int J, float* states, int64_t state_stride,
-                                        void* stream) {
-  GEECO_CHECK_ARG(feat && tgt_feat && jnt && states, "replay_states_pair: null pointer");
-  GEECO_CHECK_ARG(cells >= 1 && ch >= 1 && ch_t >= 1 && J >= 1 && (int64_t)cells * ch <= (1 << 24) && (int64_t)cells * ch_t <= (1 << 24) &&
-                      J <= (1 << 24),
-                  "replay_states_pair: cells=%d ch=%d ch_t=%d J=%d", cells, ch, ch_t, J);
-  GEECO_CHECK_ARG(state_stride >= (int64_t)cells * ((int64_t)ch + J + ch_t), "replay_states_pair: state_stride=%lld below cells * %lld columns",
-                  (long long)state_stride, (long long)ch + J + ch_t);
-  GEECO_CHECK_ARG(K >= 1 && K <= DYN_MAXK, "replay_states_pair: K=%d outside 1..%d", K, DYN_MAXK);
-  GEECO_CHECK_ARG(T >= 1 && t0 >= 0 && t0 < t1 && t1 <= T, "replay_states_pair: windows [%d, %d) outside the %d frames", t0, t1, T);
-  GEECO_CHECK_ARG(N >= t1 - t0, "replay_states_pair: N=%d rows per step for %d windows", N, t1 - t0);
-  const int n = t1 - t0;
-  const uintptr_t src = reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(tgt_feat);
-  const bool vec = ch % 4 == 0 && ch_t % 4 == 0 && (src & 15) == 0;
-  const bool vst = vec && J % 4 == 0 && state_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(states) & 15) == 0;
-  const long long per = std::max<long long>(cells * std::max(ch, ch_t) / (vec ? 4 : 1), (long long)cells * J);
-  const unsigned grid = (unsigned)std::min<long long>(cdiv64((long long)K * n * per, RI_THREADS), RI_MAX_BLOCKS);
-  hipStream_t s = (hipStream_t)stream;
-#define RP_LAUNCH(V, VS)                                                                                                        \
-  do {                                                                                                                          \
-    geeco_note_kernel("replay_states_pair_kernel<%d, %s>", V, VS ? "true" : "false");                                          \
-    hipLaunchKernelGGL((replay_states_pair_kernel<V, VS>), dim3(grid), dim3(RI_THREADS), 0, s, feat, tgt_feat, jnt, t0, n, N, K, \
-                       cells, ch, ch_t, J, states, (long long)state_stride);                                                    \
-  } while (0)
-  if (vst) RP_LAUNCH(4, true);
-  else if (vec) RP_LAUNCH(4, false);
-  else RP_LAUNCH(1, false);
-#undef RP_LAUNCH
   GEECO_LAUNCH_CHECK();
   return 0;
 }

@@ -304,6 +304,21 @@ def predict_push_features_into(states, feat_ring, jnt_ring, heads, feat, jnt, re
 
 
 # -- episode replay (csrc/replay.hip; geeco_amd/replay.py) ---------------------------------------------------------------------
+def _replay_windows(who, T, t0, t1, K):
+  """ValueError unless K is a window length the predictors take and the windows [t0, t1) lie inside the T frames."""
+  if not 1 <= int(K) <= _native.REPLAY_MAXK:
+    raise ValueError('%s: K=%d outside 1..%d' % (who, K, _native.REPLAY_MAXK))
+  if not (T >= 1 and 0 <= t0 < t1 <= T):
+    raise ValueError('%s: windows [%d, %d) outside the %d frames' % (who, t0, t1, T))
+
+
+def _replay_states_shape(who, states, K, n, width):
+  """ValueError unless ``states`` is a contiguous [K][N][stride] with N >= n windows and stride >= width columns."""
+  if states.dim() != 3 or not states.is_contiguous() or states.shape[0] != K or states.shape[1] < n or states.shape[2] < width:
+    raise ValueError('%s: states of shape %s for K=%d steps of >= %d windows of %d columns (contiguous [K][N][stride])'
+                     % (who, tuple(states.shape), K, n, width))
+
+
 def replay_states_into(states, feat, jnt, mode, T, t0, t1, K, cells, ch, J, tgt_feat=None):
   """feat [T][cells][ch] / jnt [T][J] of one episode -> states [K][N][state_stride] (a contiguous 3-D tensor, N >= t1 - t0): row
   t - t0 of step k <- frame max(0, t - K + 1 + k) for the windows t0 <= t < t1, in the columns of predict_push_features_into for
@@ -311,18 +326,12 @@ def replay_states_into(states, feat, jnt, mode, T, t0, t1, K, cells, ch, J, tgt_
   arguments raise ValueError before anything is queued."""
   if mode not in PREDICT_FEAT_MODES:
     raise ValueError("replay_states: mode=%r must be 'plain', 'constant' or 'residual'" % (mode,))
-  if not 1 <= int(K) <= _native.REPLAY_MAXK:
-    raise ValueError('replay_states: K=%d outside 1..%d' % (K, _native.REPLAY_MAXK))
-  if not (T >= 1 and 0 <= t0 < t1 <= T):
-    raise ValueError('replay_states: windows [%d, %d) outside the %d frames' % (t0, t1, T))
+  _replay_windows('replay_states', T, t0, t1, K)
   if (mode == 'plain') != (tgt_feat is None):
     raise ValueError("replay_states: tgt_feat goes with the modes 'constant' and 'residual' (mode=%r)" % (mode,))
   if min(cells, ch, J) < 1:
     raise ValueError('replay_states: cells=%d ch=%d J=%d' % (cells, ch, J))
-  width = cells * (ch + J + (ch if mode == 'constant' else 0))
-  if states.dim() != 3 or not states.is_contiguous() or states.shape[0] != K or states.shape[1] < t1 - t0 or states.shape[2] < width:
-    raise ValueError('replay_states: states of shape %s for K=%d steps of >= %d windows of %d columns (contiguous [K][N][stride])'
-                     % (tuple(states.shape), K, t1 - t0, width))
+  _replay_states_shape('replay_states', states, K, t1 - t0, cells * (ch + J + (ch if mode == 'constant' else 0)))
   if feat.numel() < T * cells * ch or jnt.numel() < T * J or (tgt_feat is not None and tgt_feat.numel() < cells * ch):
     raise ValueError('replay_states: feat / jnt / tgt_feat of %d / %d / %s floats for T=%d cells=%d ch=%d J=%d'
                      % (feat.numel(), jnt.numel(), None if tgt_feat is None else tgt_feat.numel(), T, cells, ch, J))
@@ -357,7 +366,7 @@ def replay_errors_into(out_frame, out_episode, preds, labels, T, heads):
                                    _iarr([h[2] for h in heads]), _p(out_frame), _p(out_episode), _stream()), 'geeco_replay_errors')
 
 
-# -- episode replay for the dynamic-image controllers (csrc/replay_dynimg.hip; geeco_amd/replay_dynimg.py) ------------------------
+# -- episode replay for the dynamic-image controllers (csrc/replay_dynimg.hip, the state kernel of replay.hip; replay_dynimg.py) --
 def replay_images_ws(windows, HW, device):
   """The workspace of replay_images_into for up to ``windows`` windows per call (per-block min / max; no zero-fill contract)."""
   return torch.empty(max(int(_lib().geeco_replay_images_ws_bytes(int(windows), int(HW))) // 4, 4), dtype=torch.float32, device=device)
@@ -370,12 +379,9 @@ def replay_images_into(cur_out, buf_out, diff_out, frame_addr, goal, T, t0, t1, 
   of the frames max(0, t - K + 1 + k); None skips it), each a contiguous float32 [>= t1 - t0][HW][4].  Bitwise the images of
   goal_dynimgs_into / goal_dynimgs_u8_into on the explicitly built windows (include/geeco_hip.h: geeco_replay_images).  Bad arguments
   raise ValueError before anything is queued."""
-  if not 1 <= int(K) <= _native.REPLAY_MAXK:
-    raise ValueError('replay_images: K=%d outside 1..%d' % (K, _native.REPLAY_MAXK))
   if HW < 4 or HW % 4:
     raise ValueError('replay_images: HW=%d must be a multiple of 4' % (HW,))
-  if not (T >= 1 and 0 <= t0 < t1 <= T):
-    raise ValueError('replay_images: windows [%d, %d) outside the %d frames' % (t0, t1, T))
+  _replay_windows('replay_images', T, t0, t1, K)
   if cur_out is None or diff_out is None:
     raise ValueError('replay_images: cur_out and diff_out are always written (only buf_out may be None)')
   n = t1 - t0
@@ -405,16 +411,10 @@ def replay_states_pair_into(states, feat, tgt_feat, jnt, T, t0, t1, K, cells, ch
   [K][N][state_stride] (contiguous, N >= t1 - t0), per cell the columns [feat | jnt | tgt] of the dense 'sequence' x 'dyndiff' model
   (state_concat_fwd_into with jnt_pos = 1).  Rows t1 - t0 .. N - 1 are not touched.  Bad arguments raise ValueError before anything
   is queued."""
-  if not 1 <= int(K) <= _native.REPLAY_MAXK:
-    raise ValueError('replay_states_pair: K=%d outside 1..%d' % (K, _native.REPLAY_MAXK))
-  if not (T >= 1 and 0 <= t0 < t1 <= T):
-    raise ValueError('replay_states_pair: windows [%d, %d) outside the %d frames' % (t0, t1, T))
+  _replay_windows('replay_states_pair', T, t0, t1, K)
   if min(cells, ch, ch_t, J) < 1:
     raise ValueError('replay_states_pair: cells=%d ch=%d ch_t=%d J=%d' % (cells, ch, ch_t, J))
-  width = cells * (ch + J + ch_t)
-  if states.dim() != 3 or not states.is_contiguous() or states.shape[0] != K or states.shape[1] < t1 - t0 or states.shape[2] < width:
-    raise ValueError('replay_states_pair: states of shape %s for K=%d steps of >= %d windows of %d columns (contiguous [K][N][stride])'
-                     % (tuple(states.shape), K, t1 - t0, width))
+  _replay_states_shape('replay_states_pair', states, K, t1 - t0, cells * (ch + J + ch_t))
   if feat.numel() < T * cells * ch or tgt_feat.numel() < T * cells * ch_t or jnt.numel() < T * J:
     raise ValueError('replay_states_pair: feat / tgt_feat / jnt of %d / %d / %d floats for T=%d cells=%d ch=%d ch_t=%d J=%d'
                      % (feat.numel(), tgt_feat.numel(), jnt.numel(), T, cells, ch, ch_t, J))

@@ -5,8 +5,10 @@ Semantics.  The window at frame ``t`` of a T-frame episode is what the reference
 by ``t`` pushes (src/models/e2evmc/predictor.py:192-200, :144-146): slot ``k`` (oldest first) shows frame ``max(0, t - K + 1 + k)``
 and the joint-state rows follow the same index (``window_frames``).  A goal model's target frame is constant over the episode and
 comes from the caller, as ``set_goal`` takes it.  So ``replay`` returns, row for row, what a batch-1 predictor stepped through the
-episode after ``reset()`` returns -- without the per-frame graph replay and round trip, and with every frame encoded ONCE: the T
-frames go through ``ops.pack_frames_by_address_into`` and one ``ConvEncoderStack`` in chunks of at most ``chunk_frames`` frames, their
+episode after ``reset()`` returns -- without the per-frame graph replay and round trip, and with every frame encoded ONCE.
+``ReplayPass`` is that pass, shared with the dynamic-image controllers (replay_dynimg.py): validate, one upload, the
+frames into feature tables, per ``chunk_windows`` windows the decoder's states and the decoder, the errors, one read.  What
+``EpisodeReplay`` adds: the T frames go through ``ops.pack_frames_by_address_into`` and one ``ConvEncoderStack`` in chunks of at most ``chunk_frames`` frames, their
 features wait in a table [T][cells][ch], ``ops.replay_states_into`` builds the decoder's states of up to ``chunk_windows`` windows per
 launch from it (csrc/replay.hip) and the one-launch K-step decoder (``LSTMDecoder(one_launch=True)``) runs on them.
 
@@ -146,15 +148,21 @@ def _resident_frames(x, what):
   return x
 
 
-class EpisodeReplay:
-  """The per-frame controllers (e2e_vmc; goal_e2evmc 'sequence' x 'constant' / 'residual', RGB) over whole recorded episodes."""
+class ReplayPass:
+  """What every replay class shares: the restored store, one inference encoder stack per encoder scope with its feature table
+  [frames][cells][ch], ONE decoder, every buffer allocated once, and the pass itself (``_pass``).  A subclass supplies the models it
+  serves (``_check_config``), the decoder's shape (``_decoder_shape``), its own buffers (``_allocate``), the frames' way into the
+  tables (``_encode``) and the decoder's states of a range of windows (``_build_states``)."""
+
+  pad_tables = False      # tables and joint states padded to whole decoder launches of chunk_windows rows
 
   def __init__(self, model_dir, checkpoint_name=None, use_ema=False, device=None, max_frames=512, chunk_frames=None,
                chunk_windows=None, goal=None, cfg=None):
-    """Restores ``model_dir``'s checkpoint (``restore_for_inference``), builds ONE inference encoder stack at ``chunk_frames`` frames
-    (default: ``default_chunk_frames``, from the activation footprint) and ONE decoder at ``chunk_windows`` windows per launch
-    (default min(max_frames, 256)), and allocates every buffer once.  ``goal``: goal_e2evmc (True) or e2e_vmc (False); None reads it
-    off the checkpoint's variable names.  ``cfg``: the model's config instead of ``model_dir``/e2evmc_config.json."""
+    """Restores ``model_dir``'s checkpoint (``restore_for_inference``), builds one inference encoder stack per encoder scope at
+    ``chunk_frames`` frames (default: the class's ``default_chunk_frames``, from the activation footprint) and ONE decoder at
+    ``chunk_windows`` windows per launch (default min(max_frames, 256)), and allocates every buffer once.  ``goal``: goal_e2evmc
+    (True) or e2e_vmc (False); None reads it off the checkpoint's variable names.  ``cfg``: the model's config instead of
+    ``model_dir``/e2evmc_config.json."""
     import torch
     from . import estimator as est
     from .batched_predictor import _Layout
@@ -166,50 +174,48 @@ class EpisodeReplay:
     if goal is None:
       goal = checkpoint_is_goal(model_dir, checkpoint_name)
     self.cfg, self.goal = cfg, bool(goal)
-    scope, ch, mode = check_replay_config(cfg, self.goal)
+    scopes, dims = self._check_config()
     self.max_frames = int(max_frames)
     if self.max_frames < 1:
       raise ValueError('max_frames must be >= 1, got %r' % (max_frames,))
-    F = default_chunk_frames(cfg, ch, self.max_frames) if chunk_frames is None else int(chunk_frames)
+    F = self._default_chunk_frames(dims) if chunk_frames is None else int(chunk_frames)
     W = min(self.max_frames, 256) if chunk_windows is None else int(chunk_windows)
     if not 1 <= F <= 65535 or W < 1:
       raise ValueError('chunk_frames=%r must lie in 1..65535 and chunk_windows=%r be >= 1' % (chunk_frames, chunk_windows))
-    check_image_size(cfg.img_height, cfg.img_width)
+    H, Wd = cfg.img_height, cfg.img_width
+    check_image_size(H, Wd)
+    self.K, self.J, self.HW = cfg.window_size, cfg.dim_jnt_state, H * Wd
+    self._check_image()
     if not torch.cuda.is_available():
       raise RuntimeError('geeco_amd episode replay needs an MI355X (no CPU fallback)')
     dev = torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device())
     if dev.index is None:
       dev = torch.device('cuda', torch.cuda.current_device())
-    self.device, self.chunk_frames, self.chunk_windows, self.ch, self.mode = dev, F, W, ch, mode
-    self.K, self.J, self.HW = cfg.window_size, cfg.dim_jnt_state, cfg.img_height * cfg.img_width
-    K, J, M = self.K, self.J, self.max_frames
+    self.device, self.chunk_frames, self.chunk_windows, self.dims = dev, F, W, dims
+    J, M = self.J, self.max_frames
+    rows = -(-M // W) * W if self.pad_tables else M
     f32 = dict(dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-      self.store = VariableStore(model_variable_shapes(cfg, self.goal), dev, uniform_scopes=[scope + '/ConvEncoder'])
+      self.store = VariableStore(model_variable_shapes(cfg, self.goal), dev)
       est.restore_for_inference(self.store, model_dir, checkpoint_name, use_ema=use_ema)
-      self.enc = ConvEncoderStack(self.store, [scope + '/ConvEncoder'], F, cfg.img_height, cfg.img_width, 3, ch, False)
-      D = _CELLS * (ch + J + (ch if mode == 'constant' else 0))
-      self.decoder = d = LSTMDecoder(self.store, scope + '/LSTMDecoder', cfg, W, K, D, False, one_launch=True)
+      self.encs = [ConvEncoderStack(self.store, [sc], F, H, Wd, 3, ch, False) for sc, ch in zip(scopes, dims)]
+      steps, D = self._decoder_shape()
+      self.decoder = d = LSTMDecoder(self.store, ('GoalVMC' if self.goal else 'VMC') + '/LSTMDecoder', cfg, W, steps, D, False, one_launch=True)
       d.states.zero_()
-      # K == 1: the decoder's one-step chain computes loss terms beside the predictions; zero labels nobody reads (step_models.py)
+      # one step: the decoder's one-step chain computes loss terms beside the predictions; zero labels nobody reads (step_models.py)
       width = max(8, max(h[2] for h in d.heads))
       no_labels = torch.zeros(W, width, **f32)
       d.targets, d.target_strides = [no_labels] * len(d.heads), [width] * len(d.heads)
       self.heads = [(key, off, size) for (_, key, size, _, _), (off, _, _) in zip(d.heads, error_heads(cfg))]
       self._err_heads = error_heads(cfg)
       P, nh = d.OT, len(d.heads)
-      # chunk c of an episode encodes the frames [c F - g, (c + 1) F - g) (g = 1 for a goal model: its target frame rides in slot 0 of
-      # the first chunk); one table row per chunk, uploaded in one copy
-      self.n_chunks = -(-(M + 1) // F)
-      self._h_table = torch.zeros(self.n_chunks, F, dtype=torch.int64, pin_memory=True)
-      self._d_table = torch.zeros(self.n_chunks, F, dtype=torch.int64, device=dev)
-      self.feat = torch.zeros(M, _CELLS, ch, **f32)
-      self.tgt_feat = torch.zeros(_CELLS, ch, **f32) if mode != 'plain' else None
+      self.tables = [torch.zeros(rows, _CELLS, ch, **f32) for ch in dims]
       self._goal_in = {np.dtype(np.uint8): torch.zeros(1, self.HW, 3, dtype=torch.uint8, device=dev),
                        np.dtype(np.float32): torch.zeros(1, self.HW, 3, **f32)} if self.goal else {}
+      self._allocate()
       # what one replay uploads beside the frames (joint states, recorded values) and downloads (predictions, errors)
       up, down = _Layout(), _Layout()
-      up.add('jnt', (M, J), np.float32)
+      up.add('jnt', (rows, J), np.float32)
       up.add('labels', (M, P), np.float32)
       down.add('preds', (M, P), np.float32)
       down.add('errors', (M, nh), np.float32)
@@ -219,6 +225,36 @@ class EpisodeReplay:
       self._hu, self._du, self._hd, self._dd = up.host(self._h_up), up.device(self._d_up), down.host(self._h_down), down.device(self._d_down)
       self._dense = {}      # frames of dense host episodes, per dtype: [max_frames][HW * 3], allocated on the first such episode
       torch.cuda.synchronize(dev)
+
+  # -- what a subclass supplies (the first two before any allocation; the rest with self.device current) -------------------------
+  def _check_config(self):
+    """(encoder scopes, their conv8 widths) of ``self.cfg`` / ``self.goal``, or the ValueError that says what is not served."""
+    raise NotImplementedError
+
+  def _default_chunk_frames(self, dims):
+    raise NotImplementedError
+
+  def _check_image(self):
+    """Further conditions on the image size."""
+
+  def _decoder_shape(self):
+    """(steps, input width) of the decoder."""
+    raise NotImplementedError
+
+  def _allocate(self):
+    """The class's own buffers."""
+
+  def _check_inputs(self, frames, u8, goal_dev):
+    """Further conditions on the resident frames and the goal frame of one episode."""
+
+  def _encode(self, addr, T, u8, goal_dev, return_images):
+    """Every frame once: ``addr`` (int64 [T], the frames' device addresses) -> rows [0, T) of ``self.tables``.  Returns the device
+    tensors [T][HW][3] to hand back as images, by key."""
+    raise NotImplementedError
+
+  def _build_states(self, w0, w1, T):
+    """The decoder's states of the windows [w0, w1) -> rows [0, w1 - w0) of ``self.decoder.states``."""
+    raise NotImplementedError
 
   # -- inputs ------------------------------------------------------------------------------------------------------------------
   def _frames_on_device(self, rgb):
@@ -296,10 +332,13 @@ class EpisodeReplay:
     Returns numpy arrays: one per head under the keys ``Estimator.predict`` yields ('cmd_ee', 'logits_cmd_grp', ...), each [T][size],
     row t = the prediction on the window at frame t; with labels 'errors' [T][heads] (the heads in ``decoder.head_table`` order) and
     'episode_errors' {head: float}.  Everything is queued on the current stream; the host reads once, at the end."""
+    return self._pass(episode, goal_frame, labels, False)
+
+  def _pass(self, episode, goal_frame, labels, return_images):
     import torch
     if isinstance(episode, (tuple, list)):
       episode = {'rgb': episode[0], 'jnt_state': episode[1]}
-    F, W, K, J, HW = self.chunk_frames, self.chunk_windows, self.K, self.J, self.HW
+    W, J = self.chunk_windows, self.J
     with torch.cuda.device(self.device):
       frames, T, u8 = self._frames_on_device(episode['rgb'])
       if T < 1:
@@ -316,50 +355,90 @@ class EpisodeReplay:
         if goal_frame is None:
           raise ValueError("episode replay: a goal model needs goal_frame= (or the episode's 'target_rgb')")
         goal_dev = self._goal_on_device(goal_frame)
+      self._check_inputs(frames, u8, goal_dev)
       lab = None
       if labels is not False and labels is not None:
         lab = recorded_labels(self.cfg, episode if labels is True else labels, T)
-      # one upload: the chunks' frame addresses; joint states and recorded values
-      g = 1 if self.goal else 0
-      nc = -(-(T + g) // F)
-      addr = np.zeros(nc * F, np.int64)
-      addr[g:g + T] = frames.data_ptr() + np.arange(T, dtype=np.int64) * (HW * 3 * (1 if u8 else 4))
-      self._h_table[:nc].copy_(torch.from_numpy(addr.reshape(nc, F)))
-      self._d_table[:nc].copy_(self._h_table[:nc], non_blocking=True)
+      # one upload: joint states and recorded values (and, in _encode, the frames' addresses)
       self._hu['jnt'][:T] = jnt
       if lab is not None:
         self._hu['labels'][:T] = lab
       self._d_up.copy_(self._h_up, non_blocking=True)
       # every frame once
-      x0, feats = self.enc.x_in[0], None
-      for c in range(nc):
-        lo, hi = max(c * F - g, 0), min((c + 1) * F - g, T)
-        ops.pack_frames_by_address_into(x0, self._d_table[c], F, HW, u8)
-        if g and c == 0:
-          ops.predict_pack_newest_into(x0[0:1], goal_dev, 1, HW, 3)      # slot 0 (address 0: zeros) <- the target frame
-        self.enc.forward()
-        feats = self.enc.features[0].view(F, _CELLS, self.ch)
-        first = g if c == 0 else 0
-        if hi > lo:
-          self.feat[lo:hi].copy_(feats[first:first + hi - lo])
-        if g and c == 0:
-          self.tgt_feat.copy_(feats[0])
+      addr = frames.data_ptr() + np.arange(T, dtype=np.int64) * (self.HW * 3 * (1 if u8 else 4))
+      images = self._encode(addr, T, u8, goal_dev, return_images)
       # the windows, chunk_windows per decoder launch (always the full launch: rows past the last window keep what they held)
       d, preds = self.decoder, self._dd['preds']
       for w0 in range(0, T, W):
         w1 = min(w0 + W, T)
-        ops.replay_states_into(d.states, self.feat, self._du['jnt'], self.mode, T, w0, w1, K, _CELLS, self.ch, J, tgt_feat=self.tgt_feat)
+        self._build_states(w0, w1, T)
         d.forward(False)
         preds[w0:w1].copy_(d.preds[:w1 - w0])
       if lab is not None:
         ops.replay_errors_into(self._dd['errors'], self._dd['episode'], preds, self._du['labels'], T, self._err_heads)
       self._h_down.copy_(self._d_down, non_blocking=True)      # the one read
       torch.cuda.current_stream().synchronize()
+      images = {k: v.cpu().numpy().reshape(T, self.cfg.img_height, self.cfg.img_width, 3) for k, v in images.items()}
     out = {key: self._hd['preds'][:T, off:off + size].copy() for key, off, size in self.heads}
     if lab is not None:
       out['errors'] = self._hd['errors'][:T].copy()
       out['episode_errors'] = {key: float(self._hd['episode'][i]) for i, (key, _, _) in enumerate(self.heads)}
+    out.update(images)
     return out
+
+
+class EpisodeReplay(ReplayPass):
+  """The per-frame controllers (e2e_vmc; goal_e2evmc 'sequence' x 'constant' / 'residual', RGB) over whole recorded episodes: ONE
+  encoder stack, the frames packed by address, the goal frame riding in slot 0 of the first chunk."""
+
+  def _check_config(self):
+    scope, self.ch, self.mode = check_replay_config(self.cfg, self.goal)
+    return [scope + '/ConvEncoder'], [self.ch]
+
+  def _default_chunk_frames(self, dims):
+    return default_chunk_frames(self.cfg, dims[0], self.max_frames)
+
+  def _decoder_shape(self):
+    return self.K, _CELLS * (self.ch + self.J + (self.ch if self.mode == 'constant' else 0))
+
+  def _allocate(self):
+    import torch
+    F = self.chunk_frames
+    self.enc, self.feat = self.encs[0], self.tables[0]
+    self.tgt_feat = torch.zeros(_CELLS, self.ch, dtype=torch.float32, device=self.device) if self.mode != 'plain' else None
+    # chunk c of an episode encodes the frames [c F - g, (c + 1) F - g) (g = 1 for a goal model: its target frame rides in slot 0 of
+    # the first chunk); one table row per chunk, uploaded in one copy
+    self.n_chunks = -(-(self.max_frames + 1) // F)
+    self._h_table = torch.zeros(self.n_chunks, F, dtype=torch.int64, pin_memory=True)
+    self._d_table = torch.zeros(self.n_chunks, F, dtype=torch.int64, device=self.device)
+
+  def _encode(self, addr, T, u8, goal_dev, return_images):
+    import torch
+    F, HW = self.chunk_frames, self.HW
+    g = 1 if self.goal else 0
+    nc = -(-(T + g) // F)
+    table = np.zeros(nc * F, np.int64)
+    table[g:g + T] = addr
+    self._h_table[:nc].copy_(torch.from_numpy(table.reshape(nc, F)))
+    self._d_table[:nc].copy_(self._h_table[:nc], non_blocking=True)
+    x0 = self.enc.x_in[0]
+    for c in range(nc):
+      lo, hi = max(c * F - g, 0), min((c + 1) * F - g, T)
+      ops.pack_frames_by_address_into(x0, self._d_table[c], F, HW, u8)
+      if g and c == 0:
+        ops.predict_pack_newest_into(x0[0:1], goal_dev, 1, HW, 3)      # slot 0 (address 0: zeros) <- the target frame
+      self.enc.forward()
+      feats = self.enc.features[0].view(F, _CELLS, self.ch)
+      first = g if c == 0 else 0
+      if hi > lo:
+        self.feat[lo:hi].copy_(feats[first:first + hi - lo])
+      if g and c == 0:
+        self.tgt_feat.copy_(feats[0])
+    return {}
+
+  def _build_states(self, w0, w1, T):
+    ops.replay_states_into(self.decoder.states, self.feat, self._du['jnt'], self.mode, T, w0, w1, self.K, _CELLS, self.ch, self.J,
+                           tgt_feat=self.tgt_feat)
 
 
 def dataset_episodes(dataset_dir, split_name, mode, device, fetch_target=False):

@@ -115,8 +115,9 @@ def test_replay_images_are_the_goal_input_stage_bitwise(dev, HW, K, u8):
 
 
 # ---- geeco_replay_states_pair -------------------------------------------------------------------------------------------------
-# (ch, ch_t, J, pad): 16-byte loads and stores / 16-byte loads, one-float stores (J = 7, odd stride) / one float everywhere
-PAIR_LAYOUTS = [(8, 4, 8, 4), (8, 4, 7, 5), (6, 3, 7, 3)]
+# (ch, ch_t, J, pad): 16-byte loads and stores / 16-byte loads, one-float stores (J = 7, odd stride) / one float everywhere / mixed: the
+# first table could take 16-byte loads, the second (ch_t = 3) cannot, so the whole call takes one float everywhere
+PAIR_LAYOUTS = [(8, 4, 8, 4), (8, 4, 7, 5), (6, 3, 7, 3), (8, 3, 8, 4)]
 
 
 @pytest.mark.parametrize('K', [1, 4])
@@ -140,6 +141,26 @@ def test_replay_states_pair_matches_host_model_bitwise(dev, K, ch, ch_t, J, pad)
       got = states.cpu().numpy()
       np.testing.assert_array_equal(got[:, :n, :Dw], D.states_pair_ref(feat, tgt, jnt, K, t0, t1), err_msg='T=%d [%d, %d)' % (T, t0, t1))
       assert (got[:, n:] == -7.0).all() and (got[:, :, Dw:] == -7.0).all()
+
+
+@pytest.mark.parametrize('which', ['feat', 'tgt'])
+def test_replay_states_pair_from_a_table_that_is_not_16_byte_aligned(dev, which):
+  """ch % 4 == 0 and ch_t % 4 == 0, but one table starts 4 bytes past a 16-byte boundary: the call takes the one-float form and equals
+  the host model bit for bit; the guard cells keep -7."""
+  from geeco_amd import ops
+  from test_replay_gpu import _view_4_bytes_in
+  T, K, cells, ch, ch_t, J, pad = 5, 4, 4, 8, 4, 8, 4
+  Dw = cells * (ch + J + ch_t)
+  r = np.random.default_rng(78)
+  feat = r.standard_normal((T, cells, ch)).astype(np.float32)
+  tgt = r.standard_normal((T, cells, ch_t)).astype(np.float32)
+  jnt = r.standard_normal((T, J)).astype(np.float32)
+  fd, td = (_view_4_bytes_in(a, dev) if which == name else torch.from_numpy(a).to(dev) for name, a in (('feat', feat), ('tgt', tgt)))
+  states = torch.full((K, T + 2, Dw + pad), -7.0, device=dev)
+  ops.replay_states_pair_into(states, fd, td, torch.from_numpy(jnt).to(dev), T, 0, T, K, cells, ch, ch_t, J)
+  got = states.cpu().numpy()
+  np.testing.assert_array_equal(got[:, :T, :Dw], D.states_pair_ref(feat, tgt, jnt, K, 0, T))
+  assert (got[:, T:] == -7.0).all() and (got[:, :, Dw:] == -7.0).all()
 
 
 def test_replay_states_pair_columns_are_the_dense_models_concat(dev):

@@ -53,6 +53,34 @@ def test_replay_states_matches_host_model_bitwise(dev, mode, K, ch, J, pad):
       assert (got[:, n:] == -7.0).all() and (got[:, :, D:] == -7.0).all()
 
 
+def _view_4_bytes_in(a, dev):
+  """``a`` on the device as a contiguous view that starts 4 bytes into its allocation (allocations are at least 16-byte aligned)."""
+  buf = torch.zeros(a.size + 1, device=dev)
+  buf[1:].copy_(torch.from_numpy(a).reshape(-1))
+  view = buf[1:].view(a.shape)
+  assert view.data_ptr() % 16 == 4 and view.is_contiguous()
+  return view
+
+
+@pytest.mark.parametrize('mode', ['plain', 'constant', 'residual'])
+def test_replay_states_from_a_table_that_is_not_16_byte_aligned(dev, mode):
+  """ch % 4 == 0, but the feature table starts 4 bytes past a 16-byte boundary: the call takes the one-float form and equals the host
+  model bit for bit; the guard cells keep -7."""
+  from geeco_amd import ops
+  T, K, cells, ch, J, pad = 5, 4, 4, 8, 8, 4
+  D = R.state_width(mode, cells, ch, J)
+  r = np.random.default_rng(77)
+  feat = r.standard_normal((T, cells, ch)).astype(np.float32)
+  jnt = r.standard_normal((T, J)).astype(np.float32)
+  tgt = r.standard_normal((cells, ch)).astype(np.float32)
+  td = torch.from_numpy(tgt).to(dev) if mode != 'plain' else None
+  states = torch.full((K, T + 2, D + pad), -7.0, device=dev)
+  ops.replay_states_into(states, _view_4_bytes_in(feat, dev), torch.from_numpy(jnt).to(dev), mode, T, 0, T, K, cells, ch, J, tgt_feat=td)
+  got = states.cpu().numpy()
+  np.testing.assert_array_equal(got[:, :T, :D], R.states_ref(feat, jnt, tgt, mode, K, 0, T))
+  assert (got[:, T:] == -7.0).all() and (got[:, :, D:] == -7.0).all()
+
+
 def test_replay_states_columns_are_push_features_columns(dev):
   """Window t of the replay equals, bit for bit, what geeco_predict_push_features gathers after a reset at frame 0 and t pushes."""
   from geeco_amd import ops
