@@ -60,11 +60,16 @@ class AdamSegment(Structure):
   _fields_ = [('g', c_void_p), ('p_off', c_int64), ('count', c_int64)]
 
 
+# The constants of include/geeco_hip.h the package mirrors live here and nowhere else (tests/test_abi_cpu.py compares each to its #define).
 ADAM_SEGMENTS_MAX = 8
+SLAB_REDUCE_MAX = 8
+
+PREDICT_FEAT_MODES = {'plain': 0, 'constant': 1, 'residual': 2}     # GEECO_PREDICT_FEAT_* of include/geeco_hip.h
 
 VARSTATS_CHUNK, VARSTATS_CLASSES = 4096, 40      # GEECO_VARSTATS_* of include/geeco_hip.h
 
 REPLAY_MAXK, REPLAY_MAXHEADS = 64, 8      # the window lengths geeco_replay_states takes; GEECO_REPLAY_MAXHEADS of include/geeco_hip.h
+REPLAY_SQUARED_ERROR, REPLAY_CLASS_HIT = 0, 1      # head kinds of geeco_replay_errors
 
 LR_KINDS = ('constant', 'exponential', 'cosine', 'piecewise')      # GEECO_LR_* of include/geeco_hip.h, in order
 LR_BOUNDARIES_MAX = 8

@@ -22,10 +22,11 @@ import socket
 import struct
 import time
 
+from ._native import VARSTATS_CLASSES as CLASSES
 from .tfrecord import _enc_len, _enc_varint, masked_crc32c
 
 
-CLASSES = 40      # GEECO_VARSTATS_CLASSES of include/geeco_hip.h: class k holds 2^(k-32) <= |x| < 2^(k-31), clamped at both ends
+# CLASSES = GEECO_VARSTATS_CLASSES of include/geeco_hip.h: class k holds 2^(k-32) <= |x| < 2^(k-31), clamped at both ends
 _DBL_MAX = 1.7976931348623157e308
 
 

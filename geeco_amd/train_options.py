@@ -16,6 +16,8 @@ import re
 
 import numpy as np
 
+from ._native import LR_BOUNDARIES_MAX, LR_KINDS      # GEECO_LR_* of include/geeco_hip.h (importing _native loads no library)
+
 
 def check_ema_decay(value, key='ema_decay'):
   """The decay of the shadow weights: None or 0 = off (returns None), else a float in (0, 1); anything else raises ValueError
@@ -179,8 +181,6 @@ def check_lr_multipliers(value, names, key='lr_multipliers'):
   return None if all(mul == 1.0 for mul in out.values()) else out
 
 
-LR_KINDS = ('constant', 'exponential', 'cosine', 'piecewise')
-LR_BOUNDARIES_MAX = 8      # GEECO_LR_BOUNDARIES_MAX of include/geeco_hip.h
 _LR_FIELDS = ('kind', 'warmup_steps', 'decay_steps', 'decay_rate', 'alpha', 'staircase', 'boundaries', 'values')
 
 

@@ -11,6 +11,8 @@ import pytest
 
 import _grad_accum_ref as GA
 
+import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = 'geeco_grad_accumulate_segments'
 
@@ -63,27 +65,10 @@ def test_cli_flag_reaches_params():
 # ================================================================================================
 # header, library, binding
 # ================================================================================================
-def _declared_arguments(name):
-  """The ctypes of ``name``'s declaration in include/geeco_hip.h: (restype, [argtypes])."""
-  from geeco_amd import _native
-  src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read(), flags=re.S)
-  res, args = re.search(r'\b(int64_t|int)\s+%s\s*\(([^)]*)\)\s*;' % name, src).groups()
-
-  def ctype(decl):
-    decl = decl.strip()
-    if '*' in decl:
-      return _native._P
-    kind = decl.rsplit(None, 1)[0].replace('const', '').strip()
-    return {'int': _native._I, 'int64_t': _native._L, 'float': _native._F}[kind]
-  return ctype(res + ' x'), [ctype(a) for a in args.split(',')]
-
-
 def test_header_library_and_binding_agree_and_the_abi_version_is_unchanged():
   from geeco_amd import _native, ops
-  hdr = open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read()
-  assert '#define GEECO_ABI_VERSION 7 ' in hdr and _native.ABI_VERSION == 7
-  assert NEW in re.search(r'added within 7.*?\*/', hdr, flags=re.S).group(0)
-  assert _native.SIGNATURES[NEW] == _declared_arguments(NEW)
+  assert _abi.define('GEECO_ABI_VERSION') == 7 == _native.ABI_VERSION
+  assert NEW in _abi.added_within(7)
   assert _native.SIGNATURES[NEW] == (_native._I, [_native._P, _native._P, _native._I, _native._L, _native._I, _native._P])
   lib = _native.load()
   assert hasattr(lib, NEW) and int(lib.geeco_abi_version()) == 7

@@ -619,6 +619,43 @@ def test_encoder_and_decoder_import_neither_graph_nor_each_other(module):
   assert subprocess.run([sys.executable, '-c', code], cwd=root).returncode == 0
 
 
+OPS_FAMILIES = ('input_stage', 'windows', 'predict_io', 'replay_ops', 'attr_ops', 'conv', 'decoder_ops', 'optim', 'varstats_ops')
+
+
+def test_ops_reexports_its_submodules_functions_as_the_same_objects():
+  import importlib
+  from geeco_amd import _native, ops
+  for family in OPS_FAMILIES + ('_marshal',):
+    module = importlib.import_module('geeco_amd.ops.' + family)
+    for name, obj in vars(module).items():
+      if getattr(obj, '__module__', None) == module.__name__ and (not name.startswith('_') or name in ('_p', '_stream', '_ws', '_lib')):
+        assert getattr(ops, name) is obj, (family, name)
+  assert ops._native is _native and ops.VariableStatsPlan.__module__ == 'geeco_amd.ops'
+
+
+@pytest.mark.parametrize('family', OPS_FAMILIES + ('_marshal',))
+def test_ops_submodules_import_one_way(family):
+  """A family imports _native and _marshal, conv also optim (the schedule form of slab_reduce_batch): never another family, never
+  the package namespace.  Read from the source: importing a submodule runs the package's __init__ whatever the submodule imports."""
+  import ast
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  tree = ast.parse(open(os.path.join(root, 'geeco_amd', 'ops', family + '.py')).read())
+  allowed = {(2, None): {'_native'}, (2, '_native'): None}
+  if family != '_marshal':
+    allowed[(1, '_marshal')] = None
+  if family == 'conv':
+    allowed[(1, 'optim')] = None
+  for node in ast.walk(tree):
+    if isinstance(node, ast.Import):
+      assert not any(a.name.startswith('geeco_amd') for a in node.names), ast.dump(node)
+    if isinstance(node, ast.ImportFrom) and node.level:
+      assert (node.level, node.module) in allowed, (family, node.level, node.module)
+      names = allowed[(node.level, node.module)]
+      assert names is None or {a.name for a in node.names} <= names, (family, [a.name for a in node.names])
+    if isinstance(node, ast.ImportFrom) and not node.level:
+      assert not node.module.startswith('geeco_amd'), (family, node.module)
+
+
 def test_eval_encoder_stack_has_every_flag_false_or_empty():
   """The training-only decisions of ConvEncoderStack exist on every stack, so no reader has to probe for them."""
   from geeco_amd.encoder import ConvEncoderStack

@@ -12,6 +12,8 @@ import torch
 from oracle import geeco_oracle as O
 from test_batched_predictor_cpu import Batch1Window
 
+import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ('geeco_predict_pack_newest', 'geeco_predict_push_features')
 MODES = {'plain': 0, 'constant': 1, 'residual': 2}
@@ -64,16 +66,10 @@ class FeatureRingModel:
     return self.feat[b, order], self.jnt[b, order]
 
 
-def _declared():
-  src = open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read()
-  return re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-
-
 def test_entries_declared_exported_typed_at_abi_7():
   from geeco_amd import _native, ops
-  hdr = _declared()
   for name in ENTRIES:
-    assert re.search(r'\b%s\s*\(' % name, hdr), name
+    assert name in _abi.functions(), name
     assert name in _native.SIGNATURES, name
   lib = ctypes.CDLL(_native.LIB_PATH)
   for name in ENTRIES:
@@ -81,7 +77,7 @@ def test_entries_declared_exported_typed_at_abi_7():
   assert _native.ABI_VERSION == 7 and _native.load().geeco_abi_version() == 7
   for mode, v in MODES.items():
     assert ops.PREDICT_FEAT_MODES[mode] == v
-    assert re.search(r'#define GEECO_PREDICT_FEAT_%s %d\b' % (mode.upper(), v), hdr), mode
+    assert _abi.define('GEECO_PREDICT_FEAT_' + mode.upper()) == v, mode
   assert callable(ops.predict_pack_newest_into) and callable(ops.predict_push_features_into)
 
 

@@ -11,6 +11,8 @@ import torch
 import _input_grad_ref as R
 from oracle import geeco_oracle as O
 
+import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ('geeco_conv1_dgrad', 'geeco_pack_pixels_bwd', 'geeco_dynimg_bwd_ws_bytes', 'geeco_dynimg_bwd')
 
@@ -100,20 +102,18 @@ def test_pack_bwd_ref_is_the_adjoint_of_the_channel_pack():
 
 def test_header_library_and_binding_export_the_entry_points():
   from geeco_amd import _native
-  header = open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read()
-  assert re.search(r'#define GEECO_ABI_VERSION 7\b', header) and _native.ABI_VERSION == 7
+  assert _abi.define('GEECO_ABI_VERSION') == 7 == _native.ABI_VERSION
   lib = ctypes.CDLL(_native.LIB_PATH)
   lib.geeco_abi_version.restype = ctypes.c_int
   assert lib.geeco_abi_version() == 7
   for name in SYMBOLS:
-    assert re.search(r'\b%s\(' % name, header), name
+    assert name in _abi.functions(), name
     assert name in _native.SIGNATURES, name
     assert hasattr(lib, name), name
   assert 'input_grad' in open(os.path.join(ROOT, 'geeco_amd', 'csrc', 'sources.sh')).read().split('"')[1].split()
   # the argument counts of binding and header agree
   for name in SYMBOLS:
-    decl = re.search(r'\b%s\(([^;]*)\);' % name, header).group(1)
-    assert len(decl.split(',')) == len(_native.SIGNATURES[name][1]), name
+    assert len(_abi.functions()[name][1]) == len(_native.SIGNATURES[name][1]), name
   lib.geeco_dynimg_bwd_ws_bytes.restype = ctypes.c_int64
   lib.geeco_dynimg_bwd_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int]
   assert lib.geeco_dynimg_bwd_ws_bytes(2, 136 * 136, 3) >= 2 * (-(-136 * 136 * 3 // 1024)) * 32

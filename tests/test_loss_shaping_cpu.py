@@ -13,6 +13,8 @@ import torch
 
 import _loss_shaping_ref as R
 
+import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('geeco_heads_loss_shaped_fwd_bwd', 'geeco_lstm_step_heads_shaped_fwd_bwd', 'geeco_loss_shaping_sizeof')
 
@@ -233,9 +235,8 @@ def test_input_fn_refuses_bad_weights(dataset, fn, what):
 # ================================================================================================
 def test_abi_version_symbols_and_struct_layout():
   from geeco_amd import _native
-  hdr = open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read()
-  assert int(re.search(r'#define GEECO_ABI_VERSION (\d+)', hdr).group(1)) == 7 == _native.ABI_VERSION
-  added = re.search(r'/\* added within 7.*?\*/', hdr, flags=re.S).group(0)
+  assert _abi.define('GEECO_ABI_VERSION') == 7 == _native.ABI_VERSION
+  added = _abi.added_within(7)
   lib = _native.load()
   for name in NEW:
     assert name in added, name
@@ -246,8 +247,7 @@ def test_abi_version_symbols_and_struct_layout():
   assert fields == [('sample_weight', 0, 8), ('sample_weight_stride', 8, 8), ('class_weight', 16, 8), ('label_smoothing', 24, 4),
                     ('huber_delta', 28, 20)]
   assert ctypes.sizeof(S) == 48 == lib.geeco_loss_shaping_sizeof()
-  decl = re.search(r'typedef struct geeco_loss_shaping \{(.*?)\} geeco_loss_shaping;', hdr, flags=re.S).group(1)
-  assert re.findall(r'(\w+)(?:\[\d+\])?;', decl) == [n for n, _ in S._fields_]
+  assert [f[0] for f in _abi.struct_fields('geeco_loss_shaping')] == [n for n, _ in S._fields_]
   # the shaped entry points: the signatures they extend with the struct behind Hfc
   for base, shaped in (('geeco_heads_loss_fwd_bwd', NEW[0]), ('geeco_lstm_step_heads_fwd_bwd', NEW[1])):
     a, b = _native.SIGNATURES[base][1], _native.SIGNATURES[shaped][1]

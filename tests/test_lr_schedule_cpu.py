@@ -11,6 +11,8 @@ import pytest
 
 import _lr_schedule_ref as L
 
+import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('geeco_adam_prepare_schedule', 'geeco_slab_reduce_batch_prepare_schedule', 'geeco_lr_schedule_eval')
 BIG = 2 ** 31 + 12345                      # a step count an int32 does not hold
@@ -262,57 +264,27 @@ def test_cli_flags_reach_params():
   assert 'lr_schedule' not in create_e2evmc_config({})._asdict()      # not a field of the model config
 
 
-def _declared_arguments(name):
-  """The ctypes of ``name``'s declaration in include/geeco_hip.h: (restype, [argtypes])."""
-  from geeco_amd import _native
-  src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read(), flags=re.S)
-  res, args = re.search(r'\b(int64_t|int)\s+%s\s*\(([^)]*)\)\s*;' % name, src).groups()
-  pointers = {'geeco_lr_schedule': ctypes.POINTER(_native.LrSchedule), 'geeco_slab_reduce': ctypes.POINTER(_native.SlabReduce),
-              'double': ctypes.POINTER(ctypes.c_double)}
-
-  def ctype(decl):
-    decl = decl.strip()
-    kind = decl.rsplit(None, 1)[0].replace('const', '').replace('*', '').strip()
-    if '*' in decl:
-      return pointers.get(kind, _native._P)
-    return {'int': _native._I, 'int64_t': _native._L, 'float': _native._F}[kind]
-  return ctype(res + ' x'), [ctype(a) for a in args.split(',')]
-
-
 @pytest.mark.parametrize('name', NEW)
 def test_header_and_binding_agree(name):
   from geeco_amd import _native
-  assert _native.SIGNATURES[name] == _declared_arguments(name)
+  assert len(_native.SIGNATURES[name][1]) == len(_abi.functions()[name][1])      # (every type: test_abi_cpu.py::test_signature_matches_the_header)
   assert hasattr(_native.load(), name)
 
 
 def test_struct_and_header_agree():
   """geeco_lr_schedule field by field: names, order, types and array lengths; the kinds in the header's order."""
   from geeco_amd import _native, variables
-  src = open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read()
-  body = re.sub(r'/\*.*?\*/', '', re.search(r'typedef struct geeco_lr_schedule \{(.*?)\} geeco_lr_schedule;', src, flags=re.S).group(1), flags=re.S)
-  nmax = int(re.search(r'#define GEECO_LR_BOUNDARIES_MAX (\d+)', src).group(1))
-  assert nmax == _native.LR_BOUNDARIES_MAX == variables.LR_BOUNDARIES_MAX == 8
+  assert _abi.define('GEECO_LR_BOUNDARIES_MAX') == _native.LR_BOUNDARIES_MAX == variables.LR_BOUNDARIES_MAX == 8
   types = {'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float}
-  want = []
-  for decl in body.split(';'):
-    if decl.strip():
-      ctype, names = decl.split(None, 1)
-      for n in names.split(','):
-        m = re.match(r'\s*(\w+)(?:\[(.*)\])?\s*$', n)
-        length = eval(m.group(2), {'GEECO_LR_BOUNDARIES_MAX': nmax}) if m.group(2) else None
-        want.append((m.group(1), types[ctype] * length if length else types[ctype]))
+  want = [(field, types[ctype] * length if length else types[ctype]) for field, ctype, length in _abi.struct_fields('geeco_lr_schedule')]
   assert _native.LrSchedule._fields_ == want
   assert ctypes.sizeof(_native.LrSchedule) == 144
   for i, kind in enumerate(_native.LR_KINDS):
-    assert re.search(r'#define GEECO_LR_%s %d\b' % (kind.upper(), i), src), kind
+    assert _abi.define('GEECO_LR_' + kind.upper()) == i, kind
   assert _native.LR_KINDS == variables.LR_KINDS
 
 
 def test_abi_version_is_unchanged_and_the_additions_are_listed():
   from geeco_amd import _native
-  hdr = open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read()
-  assert '#define GEECO_ABI_VERSION 7 ' in hdr and _native.ABI_VERSION == 7
-  added = re.search(r'added within 7.*?\*/', hdr, flags=re.S).group(0)
-  for name in NEW:
-    assert name in added, name
+  assert _abi.define('GEECO_ABI_VERSION') == 7 == _native.ABI_VERSION
+  assert set(NEW) <= set(_abi.added_within(7))

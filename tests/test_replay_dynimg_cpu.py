@@ -15,6 +15,8 @@ import torch
 import _replay_dynimg_ref as D
 import _replay_ref as R
 
+import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -217,14 +219,12 @@ def test_library_refuses_bad_arguments_before_any_launch():
 
 def test_header_declares_and_library_exports_the_new_entries():
   from geeco_amd import _native
-  hdr = open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read()
   lib = ctypes.CDLL(_native.LIB_PATH)
-  listed = re.search(r'/\* added within 7 .*?\*/', hdr, flags=re.S).group(0)
-  code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+  listed = _abi.added_within(7)
   for name in ('geeco_replay_images', 'geeco_replay_states_pair', 'geeco_replay_images_ws_bytes'):
-    assert re.search(r'\b(int|int64_t) %s\s*\(' % name, code), name
+    assert _abi.functions()[name][0] in ('int', 'int64_t'), name
     assert name in listed and name in _native.SIGNATURES and hasattr(lib, name), name
-  assert int(re.search(r'#define GEECO_ABI_VERSION (\d+)', hdr).group(1)) == 7 == _native.ABI_VERSION
+  assert _abi.define('GEECO_ABI_VERSION') == 7 == _native.ABI_VERSION
   src = open(os.path.join(ROOT, 'geeco_amd', 'csrc', 'sources.sh')).read()
   assert re.search(r'HIP_SOURCES="[^"]*\breplay_dynimg\b', src)
 

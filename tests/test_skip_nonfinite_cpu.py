@@ -11,6 +11,8 @@ import pytest
 
 import _guard_ref as G
 
+import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('geeco_guard_decide', 'geeco_adam_tf_segments_guard')
 
@@ -87,36 +89,18 @@ def test_cli_flags_reach_params():
   assert 'skip_nonfinite' not in create_e2evmc_config({})._asdict()
 
 
-def _declared_arguments(name):
-  """The ctypes of ``name``'s declaration in include/geeco_hip.h: (restype, [argtypes])."""
-  from geeco_amd import _native
-  src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read(), flags=re.S)
-  res, args = re.search(r'\b(int64_t|int)\s+%s\s*\(([^)]*)\)\s*;' % name, src).groups()
-
-  def ctype(decl):
-    decl = decl.strip()
-    if '*' in decl:
-      return _native._P
-    kind = decl.rsplit(None, 1)[0].replace('const', '').strip()
-    return {'int': _native._I, 'int64_t': _native._L, 'float': _native._F}[kind]
-  return ctype(res + ' x'), [ctype(a) for a in args.split(',')]
-
-
 @pytest.mark.parametrize('name', NEW)
 def test_header_and_binding_agree(name):
   from geeco_amd import _native, ops
-  assert _native.SIGNATURES[name] == _declared_arguments(name)
+  assert len(_native.SIGNATURES[name][1]) == len(_abi.functions()[name][1])      # (every type: test_abi_cpu.py::test_signature_matches_the_header)
   assert hasattr(_native.load(), name)
   assert callable(getattr(ops, name[len('geeco_'):]))
 
 
 def test_abi_version_is_unchanged_and_the_additions_are_listed():
   from geeco_amd import _native
-  hdr = open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read()
-  assert '#define GEECO_ABI_VERSION 7 ' in hdr and _native.ABI_VERSION == 7
-  added = re.search(r'added within 7.*?\*/', hdr, flags=re.S).group(0)
-  for name in NEW:
-    assert name in added, name
+  assert _abi.define('GEECO_ABI_VERSION') == 7 == _native.ABI_VERSION
+  assert set(NEW) <= set(_abi.added_within(7))
   sources = open(os.path.join(ROOT, 'geeco_amd', 'csrc', 'sources.sh')).read()
   assert ' guard ' in re.search(r'HIP_SOURCES="([^"]*)"', sources).group(1)
 

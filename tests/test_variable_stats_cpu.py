@@ -11,6 +11,8 @@ import pytest
 
 import _varstats_ref as V
 
+import _abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ('geeco_variable_stats', 'geeco_variable_stats_ws_bytes')
 CH = 4096
@@ -217,15 +219,13 @@ def test_histogram_proto_bytes_read_back(tmp_path):
 
 def test_header_declares_and_binding_binds():
   from geeco_amd import _native, ops
-  hdr = open(os.path.join(ROOT, 'include', 'geeco_hip.h')).read()
-  added = re.search(r'added within 7.*?\*/', hdr, flags=re.S).group(0)
-  code = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+  added = _abi.added_within(7)
   for name in NEW:
-    assert name in added and re.search(r'\b%s\s*\(' % name, code), name
+    assert name in added and name in _abi.functions(), name
     assert name in _native.SIGNATURES
-  assert len(_native.SIGNATURES['geeco_variable_stats'][1]) == len(re.search(r'geeco_variable_stats\((.*?)\);', code, flags=re.S).group(1).split(','))
-  assert int(re.search(r'#define GEECO_VARSTATS_CHUNK (\d+)', hdr).group(1)) == _native.VARSTATS_CHUNK == CH
-  assert int(re.search(r'#define GEECO_VARSTATS_CLASSES (\d+)', hdr).group(1)) == _native.VARSTATS_CLASSES == V.CLASSES
+  assert len(_native.SIGNATURES['geeco_variable_stats'][1]) == len(_abi.functions()['geeco_variable_stats'][1])
+  assert _abi.define('GEECO_VARSTATS_CHUNK') == _native.VARSTATS_CHUNK == CH
+  assert _abi.define('GEECO_VARSTATS_CLASSES') == _native.VARSTATS_CLASSES == V.CLASSES
   lib = _native.load()
   assert lib.geeco_variable_stats_ws_bytes(1) * 3 == lib.geeco_variable_stats_ws_bytes(3)
   # the record as numpy reads it is the struct the header declares: 8 + 2 * (16 + 16 + 2 * 40 * 8) + 8 + 8 bytes
