@@ -81,6 +81,15 @@ class LrSchedule(Structure):
               ('alpha', c_float), ('staircase', c_int32), ('n_boundaries', c_int32), ('boundaries', c_int64 * LR_BOUNDARIES_MAX),
               ('values', c_float * (LR_BOUNDARIES_MAX + 1))]
 
+PERTURB_METHODS = ('occlusion', 'rise')      # GEECO_PERTURB_* of include/geeco_hip.h, in order
+
+
+class PerturbDesc(Structure):
+  """geeco_perturb_desc (include/geeco_hip.h): the occluder grid or the RISE masks of a perturbation pass."""
+  _fields_ = [('method', c_int32), ('H', c_int32), ('W', c_int32), ('ph', c_int32), ('pw', c_int32), ('sy', c_int32), ('sx', c_int32),
+              ('grid', c_int32), ('keep_threshold', ctypes.c_uint32), ('reserved', ctypes.c_uint32), ('key', ctypes.c_uint64)]
+
+
 # symbol -> (restype, argtypes); mirrors include/geeco_hip.h one to one
 SIGNATURES = {
     'geeco_abi_version': (_I, []),
@@ -209,6 +218,13 @@ SIGNATURES = {
     'geeco_attr_path_point': (_I, [_P, _P, _P, _L, _F, _F, ctypes.c_uint64, ctypes.c_uint32, _L, _P]),
     'geeco_attr_accumulate': (_I, [_P, _P, _F, _L, _I, _P]),
     'geeco_attr_finish': (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _L, _I, _P]),
+    # additive within ABI 7: perturbation attributions; the description is a host PerturbDesc, passed by address
+    'geeco_perturb_desc_sizeof': (_L, []),
+    'geeco_perturb_patch': (_I, [_P, _I, POINTER(c_int32)]),
+    'geeco_perturb_apply': (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'geeco_perturb_score': (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    'geeco_perturb_accumulate': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'geeco_perturb_finish': (_I, [_P, _P, _P, _L, _P]),
 }
 
 _lib = None

@@ -6,67 +6,13 @@
 //   3. attr_finish:      attr = (x - b) acc or acc, saliency = max_c |attr| per pixel, sample_sum = sum of attr per sample.
 // All are HBM-streaming: 16-byte accesses where the pointers (and, for a broadcast baseline, its period) allow, one float per
 // access otherwise, grid-stride, no LDS but the sample sum's fold, no atomics.  Every product, difference and sum is rounded to
-// float32 on its own (no contraction into an FMA, see below), so the 16-byte body, the scalar form and
+// float32 on its own (no contraction into an FMA: attr_stream.h), so the 16-byte body, the scalar form and
 // numpy's float32 arithmetic give the same bits (tests/_attribution_ref.py).
-#include <algorithm>
-
 #include "geeco_common.h"
 #include "philox_normal.h"
+#include "attr_stream.h"      // the uncontracted float32 operations, the four-element accesses, the baseline rule, the grid
 
-// No contraction: hipcc fuses a product into the sum behind it by default, and the __f*_rn intrinsics do not stop it (they are
-// inline functions of plain operators that carry the header's contraction flag into the caller).  Contraction is switched off for
-// everything below, and every rounded operation goes through these three, which are compiled under that setting.  The generator of
-// philox_normal.h, included above, keeps the form it has in the gather.
-#pragma clang fp contract(off)
-__device__ __forceinline__ float at_add(float a, float b) { return a + b; }
-__device__ __forceinline__ float at_sub(float a, float b) { return a - b; }
-__device__ __forceinline__ float at_mul(float a, float b) { return a * b; }
-
-#define AT_THREADS 256
-#define AT_MAX_BLOCKS 2048        // 8 blocks of 256 threads per CU: the grid-stride loop takes the rest
 #define AT_SUM_THREADS 1024       // the sample sum: one block per sample
-
-// baseline[(e + j) % period], j = 0..3, for a group that starts at element e (a multiple of 4).  BV: period % 4 == 0 and the
-// baseline is 16-byte aligned, so the four lie side by side in one aligned word.  ``small``: n < 2^32, the remainder in 32 bits.
-template <bool BV>
-__device__ __forceinline__ void attr_baseline4(const float* __restrict__ baseline, long long period, bool small, long long e, int cnt,
-                                               float b[4]) {
-  b[0] = b[1] = b[2] = b[3] = 0.f;
-  if (!baseline) return;
-  long long r = small ? (long long)((unsigned)e % (unsigned)period) : e % period;
-  if (BV) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(baseline + r);
-    b[0] = v.x, b[1] = v.y, b[2] = v.z, b[3] = v.w;
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (j < cnt) b[j] = baseline[r];
-    if (++r == period) r = 0;
-  }
-}
-
-template <bool V>
-__device__ __forceinline__ void attr_load4(const float* __restrict__ p, long long e, int cnt, float v[4]) {
-  if (V && cnt == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p + e);
-    v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = j < cnt ? p[e + j] : 0.f;
-}
-
-template <bool V>
-__device__ __forceinline__ void attr_store4(float* __restrict__ p, long long e, int cnt, const float v[4]) {
-  if (V && cnt == 4) {
-    *reinterpret_cast<f32x4*>(p + e) = f32x4{v[0], v[1], v[2], v[3]};
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (j < cnt) p[e + j] = v[j];
-}
 
 // ---- 1. the path point ---------------------------------------------------------------------------------------------------------
 // A thread owns groups of four consecutive elements (the last group of n may hold fewer), on either access path, so ONE Philox
@@ -98,18 +44,6 @@ __global__ __launch_bounds__(AT_THREADS) void attr_path_point_kernel(float* __re
     }
     attr_store4<V>(dst, e, cnt, o);
   }
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-static unsigned attr_grid(long long units) { return (unsigned)std::min<long long>(cdiv64(units, AT_THREADS), AT_MAX_BLOCKS); }
-
-// the baseline rule of path_point and finish: NULL = zeros (the period is not looked at), else a period >= 1 that divides n
-static int check_baseline(const char* who, const float* baseline, int64_t period, int64_t n) {
-  if (!baseline) return 0;
-  GEECO_CHECK_ARG(period >= 1 && period <= n && n % period == 0, "%s: baseline_period=%lld does not divide n=%lld", who,
-                  (long long)period, (long long)n);
-  GEECO_CHECK_ARG((reinterpret_cast<uintptr_t>(baseline) & 3) == 0, "%s: the baseline must be 4-byte aligned", who);
-  return 0;
 }
 
 extern "C" int geeco_attr_path_point(float* dst, const float* x, const float* baseline, int64_t baseline_period, float alpha,

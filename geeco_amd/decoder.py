@@ -209,14 +209,22 @@ class LSTMDecoder:
     the single-workgroup heads kernel wrote the losses (dim_h_fc outside {64, 128}, dim_h_lstm > 128 or more than 32 outputs: it
     keeps no rows), the one-launch inference decoder ran (no losses at all), or ``loss_shaping`` is on (the rows then hold weighted
     terms whose means are taken over batch-wide counts)."""
+    terms = self.sample_loss_terms()
+    if terms is None:
+      return None
+    rows, coef = terms
+    return rows.double() @ torch.tensor(coef, dtype=torch.float64, device=rows.device)
+
+  def sample_loss_terms(self):
+    """What ``sample_losses`` is made of: (the float32 view [N][heads] of the raw per-sample loss terms in the heads workspace -- it
+    shows the last forward's, whenever it is read -- and each head's coefficient), or None where the rows do not exist."""
     N, F = self.N, self.F
     if self.loss_shaping is not None or self.one_launch or not (self.H <= 128 and F in (64, 128) and self.OT <= 32):
       return None
     off = 2 * N * F + 32 * N + 32 * F
-    rows = self.heads_ws[off:off + 8 * N].view(N, 8)[:, :len(self.heads)].double()
+    rows = self.heads_ws[off:off + 8 * N].view(N, 8)[:, :len(self.heads)]
     weights = self.head_weights or [h[4] for h in self.heads]
-    coef = [w / (N * size) if kind == 0 else w / N for (_, _, size, kind, _), w in zip(self.heads, weights)]
-    return rows @ torch.tensor(coef, dtype=torch.float64, device=rows.device)
+    return rows, [w / (N * size) if kind == 0 else w / N for (_, _, size, kind, _), w in zip(self.heads, weights)]
 
   def predictions(self):
     """The heads' slices of ``preds`` by prediction key (estimator.py:48-61 / 183-197)."""

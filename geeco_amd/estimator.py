@@ -801,9 +801,29 @@ class Estimator:
       return out
     return self._input_pass('attributions', input_fn, heads, checkpoint_path, run)
 
-  def _input_pass(self, who, input_fn, heads, checkpoint_path, run):
-    """The batch loop of ``input_gradients`` and ``attributions``: the store, the refusals, one eager training-capable model per
-    batch size; ``run(model)`` -> the pass's numpy results on the loaded batch, to which the predictions are added."""
+  def perturbation_attributions(self, input_fn, method='occlusion', patch=None, stride=None, grid=7, keep_prob=0.5, steps=64, fill=None,
+                                score='prediction', heads=None, seed=0, inputs=None, checkpoint_path=None):
+    """Occlusion-sensitivity or RISE maps per batch of ``input_fn``, a generator beside ``attributions()`` with its
+    store handling and its ``checkpoint_path``; every argument between: ``_ModelBase.perturbation_attributions``.  Gradient-free:
+    the model of this pass is built with training=False, and labels are needed for ``score='loss'`` alone.  Yields numpy arrays:
+    'saliency' [N][H][W] (one map per window), 'coverage', 'scores' [M][N], 'patch_scores' [Gy][Gx][N] (occlusion), the same with
+    '_target' behind the name for goal models, and the predictions ``predict()`` yields.  The whole loop runs on the device; one
+    read per batch."""
+    from .perturbation import check_perturbation_arguments
+    check_perturbation_arguments(method, patch, stride, grid, keep_prob, steps, score, seed)
+
+    def run(model):
+      res = model.perturbation_attributions(method, patch=patch, stride=stride, grid=grid, keep_prob=keep_prob, steps=steps, fill=fill,
+                                            score=score, heads=heads, seed=seed, inputs=inputs)
+      torch.cuda.synchronize()
+      model.check_device_errors()
+      return {k: v.detach().cpu().numpy().copy() for k, v in res.items() if torch.is_tensor(v)}
+    return self._input_pass('perturbation_attributions', input_fn, None, checkpoint_path, run, training=False)
+
+  def _input_pass(self, who, input_fn, heads, checkpoint_path, run, training=True):
+    """The batch loop of ``input_gradients``, ``attributions`` and ``perturbation_attributions``: the store, the refusals, one eager
+    model per batch size (training-capable unless ``training`` is False: the gradient-free pass); ``run(model)`` -> the pass's numpy
+    results on the loaded batch, to which the predictions are added."""
     cfg = self.params['e2evmc_config']
     goal = self._model_fn is goal_e2evmc_model_fn
     if not goal and self._model_fn is not e2evmc_model_fn:
@@ -835,7 +855,7 @@ class Estimator:
         ctor = graph.GoalE2EVMC if goal else graph.E2EVMC
         # built beside the training stack: it re-derives its weight copies on every forward and never becomes the store's primary
         primary = store.primary_stack
-        models[n] = ctor(cfg, n, dev, training=True, store=store)
+        models[n] = ctor(cfg, n, dev, training=training, store=store)
         if primary is None:
           store.primary_stack = None
           models[n].enc.lazy_refresh = False

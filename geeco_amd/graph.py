@@ -26,6 +26,7 @@ import torch
 
 from . import ops
 from .attribution import Attributions
+from .perturbation import Perturbations
 from .decoder import LSTMDecoder, head_table  # noqa: F401
 from .encoder import ConvEncoderStack, check_image_size
 from .optimizer import OptimizerStep
@@ -81,9 +82,12 @@ class BesideBottom:
     self.main.wait_stream(self.side)
 
 
-class _ModelBase(OptimizerStep, Attributions):
+class _ModelBase(OptimizerStep, Attributions, Perturbations):
   """Static input buffers shared by both controllers (feed contract: geeco_gym.py:375-398).  ``attributions()`` (integrated gradients,
-  SmoothGrad), the loop around ``input_gradients()``, is attribution.Attributions'."""
+  SmoothGrad), the loop around ``input_gradients()``, is attribution.Attributions'; ``perturbation_attributions()``
+  (occlusion sensitivity, RISE), the loop around the forward alone, is perturbation.Perturbations'."""
+
+  labels_missing = None      # set by load_batch
 
   def __init__(self, cfg, N, device, goal, training, store=None, shared_frames=None, options=None, **raw):
     self.cfg, self.N, self.goal, self.training = cfg, N, goal, training
@@ -195,12 +199,14 @@ class _ModelBase(OptimizerStep, Attributions):
 
   def load_batch(self, features, labels=None):
     """Copies one batch into the static input buffers (H2D or D2D; torch is plumbing here)."""
+    self.labels_missing = []      # the label inputs this batch left as they were (perturbation_attributions(score='loss') asks)
     for k, buf in self.inputs.items():
       if hasattr(buf, 'pointers'):
         raise RuntimeError("load_batch: input '%s' is fed through window addresses (input_fn.WindowFeed.feed)" % k)
       src = labels.get(k) if (labels is not None and k in self.label_keys) else features.get(k)
       if src is None:
         if k in self.label_keys:
+          self.labels_missing.append(k)
           continue
         raise KeyError("missing feature '%s'" % k)
       src = torch.as_tensor(src)

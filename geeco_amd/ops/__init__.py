@@ -23,6 +23,8 @@ from .predict_io import (predict_pack_into, predict_pack_newest_into, predict_pu
                          predict_push_ring_into, predict_range_check_into)
 from .replay_ops import (replay_errors_into, replay_images_into, replay_images_ws, replay_states_into, replay_states_pair_into)
 from .attr_ops import attr_accumulate_into, attr_finish_into, attr_path_point_into
+from .perturb_ops import (perturb_accumulate_into, perturb_apply_into, perturb_desc, perturb_finish_into, perturb_patch,
+                          perturb_score_into, perturb_steps)
 from .conv import (conv1_dgrad_into, conv1_fwd_relu_bits_into, conv1_fwd_relu_bits_rgb_into, conv2_dgrad_conv1_wgrad_bits_into,
                    conv2_dgrad_conv1_wgrad_into, conv2_dgrad_conv1_wgrad_ws_bytes, conv2_fwd_relu_fields_into,
                    conv3_dgrad_relu_fields_into, conv3_fwd_relu_fields_into, conv3x3, conv3x3_dgrad, conv3x3_dgrad_into,

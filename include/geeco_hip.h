@@ -34,7 +34,8 @@ extern "C" {
  * geeco_heads_loss_shaped_fwd_bwd, geeco_lstm_step_heads_shaped_fwd_bwd, geeco_loss_shaping_sizeof,
  * geeco_grad_accumulate_segments, geeco_conv1_dgrad, geeco_pack_pixels_bwd, geeco_dynimg_bwd_ws_bytes, geeco_dynimg_bwd,
  * geeco_gather_windows_frames, geeco_replay_states, geeco_replay_errors, geeco_attr_path_point, geeco_attr_accumulate,
- * geeco_attr_finish, geeco_replay_images_ws_bytes, geeco_replay_images, geeco_replay_states_pair */
+ * geeco_attr_finish, geeco_replay_images_ws_bytes, geeco_replay_images, geeco_replay_states_pair, geeco_perturb_desc_sizeof,
+ * geeco_perturb_patch, geeco_perturb_apply, geeco_perturb_score, geeco_perturb_accumulate, geeco_perturb_finish */
 
 #define GEECO_EINVAL  (-1)   /* bad shape / alignment / null pointer */
 #define GEECO_ENOSUP  (-2)   /* shape outside what the kernels were built for */
@@ -913,6 +914,67 @@ int geeco_attr_accumulate(float* acc, const float* g, float weight, int64_t n, i
 int geeco_attr_finish(float* attr, float* saliency, float* sample_sum, const float* acc, const float* x, const float* baseline,
                       int64_t baseline_period, int multiply_by_input, int N, int frames_per_sample, int64_t HW, int C,
                       void* stream);
+
+/* ---- perturbation attributions: occlusion sensitivity and RISE (perturbation.py; additive within ABI 7) ----------
+ * Hide a region of the input, run the model's forward, see how far the command moves.  The entries are the streaming stages
+ * around that forward; no training step launches them.  Conventions as for the attribution entries above: each only enqueues on
+ * `stream`; no atomics; 16-byte accesses when the tensors are 16-byte aligned and every frame (for the sums: every sample) holds
+ * a multiple of four floats, one float per access otherwise -- the same bits on every path; every float32 operation is rounded on
+ * its own (no fused multiply-add); device pointers are 4-byte aligned; bad arguments return GEECO_EINVAL before anything is
+ * launched.
+ *
+ * Step m of a pass has an OCCLUSION WEIGHT o(m, sample, y, x) in [0, 1], shared by all frames and channels of the pixel.  It is
+ * a function of the description below, the step and the sample alone -- never of the launch geometry, the access path or which
+ * entry asks -- and is never stored: apply and accumulate recompute it with one device function.
+ *
+ * GEECO_PERTURB_OCCLUSION: a hard patch on a grid.  The patch is (min(ph, H), min(pw, W)) (one larger than the image is clipped
+ * to it).  Along y there are Gy = 1 positions if ph >= H, else ceil((H - ph) / sy) + 1; position j starts at min(j * sy, H - ph)
+ * (the last one is clamped, so every pixel is covered); Gx likewise along x.  Step m = j * Gx + i, 0 <= m < Gy * Gx.  o = 1
+ * inside the patch, 0 outside, for every sample.
+ *
+ * GEECO_PERTURB_RISE: a random smooth mask per (step, sample).  g = grid (2..31), cells (ch, cw) = (ceil(H / g), ceil(W / g)).
+ * The draws are 32-bit words of the Philox4x32-10 routine of csrc/philox_normal.h: word i is output i % 4 of the counter
+ * (c0, c1, c2, c3) = (i / 4, sample, step, 1) under the key (low word of key, high word of key); `sample` counts from the
+ * entry's sample0.  Words 0 .. (g + 1)^2 - 1 decide the keep-bits, row-major: bit[r][c] = word[r * (g + 1) + c] < keep_threshold
+ * (an integer compare; the caller forms the threshold from the keep probability).  dy = word[(g + 1)^2] % ch,
+ * dx = word[(g + 1)^2 + 1] % cw.  Then, in float32, each operation rounded, with yy = y + dy, r = yy / ch (integers), r1 =
+ * min(r + 1, g), fy = float(yy - r * ch) * (1.0f / float(ch)) (the reciprocal rounded first), and xx, c, c1, fx likewise:
+ *   top = bit[r][c] + fx * (bit[r][c1] - bit[r][c]);  bot = bit[r1][c] + fx * (bit[r1][c1] - bit[r1][c]);
+ *   keep = top + fy * (bot - top);  o = 1 - keep. */
+#define GEECO_PERTURB_OCCLUSION 0
+#define GEECO_PERTURB_RISE 1
+typedef struct geeco_perturb_desc {
+  int32_t method;              /* GEECO_PERTURB_* */
+  int32_t H, W;                /* the image */
+  int32_t ph, pw, sy, sx;      /* occlusion: patch and stride (>= 1); not read for RISE */
+  int32_t grid;                /* RISE: g; not read for occlusion */
+  uint32_t keep_threshold;     /* RISE: >= 1 */
+  uint32_t reserved;
+  uint64_t key;                /* RISE: the generator's key */
+} geeco_perturb_desc;
+int64_t geeco_perturb_desc_sizeof(void);
+/* Host only, nothing is launched: out[0..5] = Gy, Gx and the patch of `step`, rows [y0, y1) x columns [x0, x1), as
+ * (y0, y1, x0, x1).  RISE: Gy = Gx = 0 and an empty patch.  `desc` here and below: a host geeco_perturb_desc, read during the call. */
+int geeco_perturb_patch(const void* desc, int step, int32_t* out);
+/* The occluded input, tensors [N][frames][H * W][C], C in 1..4:
+ *   dst[e] = x[e] where o == 0;  f where o == 1;  x[e] + o * (f - x[e]) otherwise;   f = fill[e % fill_period], e the element's
+ * index in the tensor (fill == NULL: 0; periods as geeco_attr_path_point's baseline: C for a colour, H * W * C for a frame, the
+ * tensor's size for a full array).  The two exact cases are copies (a -0 stays -0).  prev_step == -1 writes the whole input.
+ * prev_step >= 0 with GEECO_PERTURB_OCCLUSION: dst holds the result of prev_step on the same x and fill; only the previous patch
+ * (x again) and the step's own are written -- the same bits as the whole rewrite.  (RISE rewrites everything whatever prev_step.)
+ * dst may not overlap x. */
+int geeco_perturb_apply(float* dst, const float* x, const float* fill, int64_t fill_period, const void* desc, int step,
+                        int prev_step, int sample0, int N, int frames, int C, void* stream);
+/* The score: d[n] = sum_j w[j] * (preds[n][j] - preds0[n][j])^2 over j = 0 .. OT - 1 ascending from +0; difference, square,
+ * weighting and sum each rounded. */
+int geeco_perturb_score(float* d, const float* preds, const float* preds0, const float* w, int N, int OT, void* stream);
+/* The running sums num, den [N][H * W]: where o != 0, num = (overwrite ? 0 : num) + d[n] * o and den = (overwrite ? 0 : den) + o;
+ * where o == 0 the step adds nothing (overwrite: the pixel becomes +0), so a NaN score reaches exactly the pixels its step hid.
+ * d: device, one score per sample of this launch.  overwrite != 0: num and den are not read. */
+int geeco_perturb_accumulate(float* num, float* den, const float* d, const void* desc, int step, int sample0, int N, int overwrite,
+                             void* stream);
+/* saliency[i] = den[i] > 0 ? num[i] / den[i] : +0, i < n.  saliency may not overlap num or den. */
+int geeco_perturb_finish(float* saliency, const float* num, const float* den, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,10 @@ writes, per window (leading axis = window):
 attributions of Estimator.attributions in the grad_* arrays' place under attr_*, takes saliency / saliency_target from the device's
 finish, and adds sample_sum and, for integrated gradients, completeness_gap per window and loss_baseline per batch; --steps, --noise_std and
 --baseline black | FILE.npy (a [H][W][3] frame or an array shaped like a batch's rgb) go with it.
+--method occlusion | rise (Estimator.perturbation_attributions: gradient-free, forwards only) writes instead of the
+gradients saliency [n][H][W] (ONE map per window: the occluder is shared by its frames), coverage [n][H][W], scores [n][M] and, for
+occlusion, patch_scores [n][Gy][Gx], and the same under *_target for goal models; --patch, --stride (occlusion), --grid, --keep_prob,
+--steps (rise), --fill black | R,G,B | FILE.npy and --score prediction | loss go with them; --heads then picks the scored heads.
 --heads picks the heads whose losses are summed (default: the training loss).  --synthetic runs on generated frames and random
 initial weights when --model_dir holds no checkpoint (a smoke run of the whole path, no dataset needed).
 """
@@ -47,10 +51,16 @@ def parse_args(argv=None):
   ap.add_argument('--num_windows', type=int, default=8)
   ap.add_argument('--batch_size', type=int, default=4)
   ap.add_argument('--heads', default=None, help='comma-separated head names, e.g. cmd_ee or cmd_grp; default: the training loss')
-  ap.add_argument('--method', default='gradient', choices=('gradient', 'integrated_gradients', 'smoothgrad'))
+  ap.add_argument('--method', default='gradient', choices=('gradient', 'integrated_gradients', 'smoothgrad', 'occlusion', 'rise'))
   ap.add_argument('--steps', type=int, default=16, help='--method integrated_gradients / smoothgrad: path points / noise draws')
   ap.add_argument('--noise_std', type=float, default=0.1, help='--method smoothgrad: the noise\'s standard deviation')
   ap.add_argument('--baseline', default='black', help="--method integrated_gradients: 'black' or FILE.npy")
+  ap.add_argument('--patch', type=int, default=None, help='--method occlusion: the square patch\'s side (default: a quarter of the image)')
+  ap.add_argument('--stride', type=int, default=None, help='--method occlusion: the grid\'s stride (default: half the patch)')
+  ap.add_argument('--grid', type=int, default=7, help='--method rise: the mask grid g, 2..31')
+  ap.add_argument('--keep_prob', type=float, default=0.5, help='--method rise: the probability that a grid cell is kept')
+  ap.add_argument('--fill', default='black', help="--method occlusion / rise: what a hidden pixel shows: 'black', R,G,B or FILE.npy")
+  ap.add_argument('--score', default='prediction', choices=('prediction', 'loss'), help='--method occlusion / rise')
   ap.add_argument('--out', required=True, help='OUT.npz')
   ap.add_argument('--synthetic', action='store_true', help='generated frames instead of a dataset')
   ap.add_argument('--img_size', type=int, default=256, help='--synthetic: frame height and width')
@@ -92,8 +102,14 @@ def main(argv=None):
   kept, outs = [], []
   e = est.Estimator(model_fn=goal_e2evmc_model_fn if goal else e2evmc_model_fn, model_dir=args.model_dir,
                     params={'e2evmc_config': cfg})
+  perturbation = args.method in ('occlusion', 'rise')
   if args.method == 'gradient':
     passes = e.input_gradients(input_fn, heads=heads)
+  elif perturbation:
+    fill = None if args.fill == 'black' else (np.load(args.fill) if args.fill.endswith('.npy') else np.array(args.fill.split(','), np.float32))
+    passes = e.perturbation_attributions(input_fn, method=args.method, patch=args.patch, stride=args.stride, grid=args.grid,
+                                         keep_prob=args.keep_prob, steps=args.steps, fill=None if fill is None else fill.astype(np.float32),
+                                         score=args.score, heads=heads)
   else:
     ig = args.method == 'integrated_gradients'
     baseline = None if (args.baseline == 'black' or not ig) else np.load(args.baseline).astype(np.float32)
@@ -110,15 +126,20 @@ def main(argv=None):
     arrays['saliency'] = saliency_of(arrays['grad_rgb'])
     if goal:
       arrays['saliency_target'] = saliency_of(arrays['grad_target_rgb'])
+  elif perturbation:      # per window first: scores [M][N] -> [N][M], patch_scores [Gy][Gx][N] -> [N][Gy][Gx]
+    for o in outs:
+      o.update({k: np.moveaxis(v, -1, 0) for k, v in o.items() if k.startswith(('scores', 'patch_scores'))})
+    arrays.update({k: cat(outs, k) for k in outs[0] if k.startswith(('saliency', 'coverage', 'scores', 'patch_scores'))})
   else:
     arrays.update({'attr_' + k: cat(outs, k) for k in IMAGE_KEYS if k in outs[0]})
     arrays.update({k: cat(outs, k) for k in ('saliency', 'saliency_target', 'sample_sum') if k in outs[0]})
     if 'completeness_gap' in outs[0]:      # per window; per batch for a decoder that keeps no per-sample loss terms
       arrays['completeness_gap'] = np.concatenate([np.atleast_1d(o['completeness_gap']) for o in outs]).astype(np.float64)[:args.num_windows]
       arrays['loss_baseline'] = np.asarray([o['loss_baseline'] for o in outs], np.float64)
-  arrays['loss'] = np.asarray([o['loss'] for o in outs], np.float32)
+  if not perturbation:
+    arrays['loss'] = np.asarray([o['loss'] for o in outs], np.float32)
   np.savez(args.out, **arrays)
-  print('saliency.py: %d windows, heads %s -> %s (%s)' % (arrays['saliency'].shape[0], heads or 'training loss', args.out,
+  print('saliency.py: %d windows, heads %s -> %s (%s)' % (arrays['saliency'].shape[0], heads or ('all' if perturbation else 'training loss'), args.out,
                                                            ', '.join('%s %s' % (k, v.shape) for k, v in sorted(arrays.items()))))
 
 
