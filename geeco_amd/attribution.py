@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .attr_pass import check_steps_seed, clean_inputs, periodic_operands
 
 IMAGE_KEYS = ('rgb', 'target_rgb', 'depth', 'target_depth')
 METHODS = ('integrated_gradients', 'smoothgrad')
@@ -27,14 +28,12 @@ def check_attribution_arguments(method, steps, noise_std, seed):
   """ValueError, with the reason, for arguments no model serves."""
   if method not in METHODS:
     raise ValueError('attributions: method=%r must be one of %s' % (method, ', '.join(repr(m) for m in METHODS)))
-  if int(steps) != steps or not 1 <= int(steps) <= 1 << 20:
-    raise ValueError('attributions: steps=%r must be an integer >= 1' % (steps,))
+  check_steps_seed('attributions', steps=steps)
   if not float(noise_std) >= 0.0 or not np.isfinite(float(noise_std)):
     raise ValueError('attributions: noise_std=%r must be a finite number >= 0' % (noise_std,))
   if method == 'integrated_gradients' and float(noise_std) != 0.0:
     raise ValueError("attributions: noise_std goes with method='smoothgrad' (integrated gradients follows the straight path)")
-  if int(seed) != seed or int(seed) < 0:
-    raise ValueError('attributions: seed=%r must be an integer >= 0' % (seed,))
+  check_steps_seed('attributions', seed=seed)
 
 
 class Attributions:
@@ -59,34 +58,6 @@ class Attributions:
           a['stage'][k] = torch.empty_like(buf)
       self._attr = a
     return self._attr
-
-  def _attr_baselines(self, baseline, a):
-    """None (black) or the device view of each input's baseline: a [H][W][C] frame (broadcast over the frames) or an array shaped
-    like the input, given for all inputs at once (one array: 'rgb' alone, or every input when their shapes agree) or per key."""
-    out = {k: None for k in a['keys']}
-    if baseline is None:
-      return out
-    if isinstance(baseline, dict):
-      per_key = baseline
-    else:      # one array: 'rgb', and 'target_rgb' where its shape fits that input too (a frame always does)
-      shape = tuple(np.shape(baseline))
-      fits = lambda k: shape in (tuple(self.inputs[k].shape), tuple(self.inputs[k].shape[-3:]))
-      per_key = {k: baseline for k in a['keys'] if k == 'rgb' or (k == 'target_rgb' and fits(k))}
-    unknown = sorted(set(per_key) - set(a['keys']))
-    if unknown:
-      raise ValueError('attributions: baseline for %s, but the model\'s image inputs are %s' % (', '.join(unknown), ', '.join(a['keys'])))
-    for k, b in per_key.items():
-      if b is None:
-        continue
-      b = torch.as_tensor(b, dtype=torch.float32)
-      full, frame = tuple(self.inputs[k].shape), tuple(self.inputs[k].shape[-3:])
-      if tuple(b.shape) not in (full, frame):
-        raise ValueError("attributions: baseline for '%s' of shape %s; a frame %s or the whole input %s" % (k, tuple(b.shape), frame, full))
-      if k not in a['base'] or a['base'][k].numel() != b.numel():      # (kept for the next call with a baseline of this size)
-        a['base'][k] = torch.empty(b.numel(), dtype=torch.float32, device=self.device)
-      a['base'][k].copy_(b.reshape(-1), non_blocking=True)
-      out[k] = a['base'][k]
-    return out
 
   def _attr_gradient_sources(self, a):
     """The contiguous tensor per input that holds the step's gradient after ``input_gradients()``: the pass's own buffers for RGB
@@ -139,35 +110,31 @@ class Attributions:
     M, ig = int(steps), method == 'integrated_gradients'
     a = self._attr_buffers()
     keys = a['keys']
-    base = self._attr_baselines(baseline if ig else None, a)
-    for k in keys:
-      a['clean'][k].copy_(self.inputs[k])
+    # None (black) or per input a [H][W][C] frame, broadcast over the frames, or an array shaped like the input
+    base = periodic_operands(self, 'attributions', 'baseline', baseline if ig else None, keys,
+                             lambda k: (tuple(self.inputs[k].shape), tuple(self.inputs[k].shape[-3:])), a['base'])
+    d = self.decoder
 
     def point(alpha, sigma, m):
       for k in keys:
         ops.attr_path_point_into(self.inputs[k], a['clean'][k], base[k], alpha, sigma, input_key(seed, k), m)
 
-    if ig:      # loss(baseline): the path point at alpha = 0 is the baseline itself
-      point(0.0, 0.0, 0)
-      self.forward()
-      a['losses'][1:2].copy_(self.loss.reshape(1))
-      per_sample = self.decoder.sample_losses()
-      if per_sample is not None:
-        a['sample_losses'][1].copy_(per_sample)
-    for m in range(M):
-      point((m + 0.5) / M if ig else 1.0, 0.0 if ig else float(noise_std), m)
-      self.forward(backward_too=True)
-      self.backward()
-      self.input_gradients(chunk_frames)
-      for k, g in self._attr_gradient_sources(a).items():
-        ops.attr_accumulate_into(a['acc'][k], g, 1.0 / M, overwrite=m == 0)
-    for k in keys:
-      self.inputs[k].copy_(a['clean'][k])
+    with clean_inputs(self, keys, a['clean']):
+      if ig:      # loss(baseline): the path point at alpha = 0 is the baseline itself
+        point(0.0, 0.0, 0)
+        self.forward()
+        a['losses'][1:2].copy_(self.loss.reshape(1))
+        d.sample_losses_into(a['sample_losses'][1])
+      for m in range(M):
+        point((m + 0.5) / M if ig else 1.0, 0.0 if ig else float(noise_std), m)
+        self.forward(backward_too=True)
+        self.backward()
+        self.input_gradients(chunk_frames)
+        for k, g in self._attr_gradient_sources(a).items():
+          ops.attr_accumulate_into(a['acc'][k], g, 1.0 / M, overwrite=m == 0)
     self.forward()      # the clean input's loss and predictions
     a['losses'][0:1].copy_(self.loss.reshape(1))
-    per_sample = self.decoder.sample_losses()
-    if per_sample is not None:
-      a['sample_losses'][0].copy_(per_sample)
+    per_sample = d.sample_losses_into(a['sample_losses'][0])
     out = {}
     for k in keys:
       shape = self.inputs[k].shape
@@ -183,7 +150,7 @@ class Attributions:
     out['loss'] = a['losses'][0]
     if ig:
       out['loss_baseline'] = a['losses'][1]
-      if per_sample is not None:
+      if per_sample:
         out['completeness_gap'] = out['sample_sum'].double() - (a['sample_losses'][0] - a['sample_losses'][1])
       else:      # no per-sample loss terms for this decoder shape: the batch's gap
         out['completeness_gap'] = (out['sample_sum'].double().sum() - (a['losses'][0].double() - a['losses'][1].double())).reshape(1)

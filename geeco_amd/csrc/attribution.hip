@@ -7,10 +7,12 @@
 // All are HBM-streaming: 16-byte accesses where the pointers (and, for a broadcast baseline, its period) allow, one float per
 // access otherwise, grid-stride, no LDS but the sample sum's fold, no atomics.  Every product, difference and sum is rounded to
 // float32 on its own (no contraction into an FMA: attr_stream.h), so the 16-byte body, the scalar form and
-// numpy's float32 arithmetic give the same bits (tests/_attribution_ref.py).
+// numpy's float32 arithmetic give the same bits (tests/_attribution_ref.py).  The loop over groups of four elements, the pointer
+// checks and the step from runtime flags to template arguments are attr_stream.h's, shared with perturbation.hip;
+// tests/test_attr_variants_gpu.py pins the name of every instantiation an entry point can launch.
 #include "geeco_common.h"
 #include "philox_normal.h"
-#include "attr_stream.h"      // the uncontracted float32 operations, the four-element accesses, the baseline rule, the grid
+#include "attr_stream.h"      // the uncontracted float32 operations, the four-element accesses and their loop, the baseline rule, the launch path
 
 #define AT_SUM_THREADS 1024       // the sample sum: one block per sample
 
@@ -23,11 +25,9 @@ __global__ __launch_bounds__(AT_THREADS) void attr_path_point_kernel(float* __re
                                                                     const float* __restrict__ baseline, long long period,
                                                                     float alpha, float sigma, unsigned k0, unsigned k1,
                                                                     unsigned step, long long n) {
-  const long long groups = (n + 3) >> 2, stride = (long long)gridDim.x * AT_THREADS;
   const bool small = n <= 0xffffffffLL;
-  for (long long g = (long long)blockIdx.x * AT_THREADS + threadIdx.x; g < groups; g += stride) {
-    const long long e = g << 2;
-    const int cnt = n - e >= 4 ? 4 : (int)(n - e);
+  attr_for_groups4(n, [&](long long e, int cnt) {
+    const long long g = e >> 2;
     float xv[4], b[4], o[4];
     attr_load4<V>(x, e, cnt, xv);
     attr_baseline4<BV>(baseline, period, small, e, cnt, b);
@@ -43,7 +43,7 @@ __global__ __launch_bounds__(AT_THREADS) void attr_path_point_kernel(float* __re
       for (int j = 0; j < 4; ++j) o[j] = at_add(o[j], at_mul(sigma, z[j]));
     }
     attr_store4<V>(dst, e, cnt, o);
-  }
+  });
 }
 
 extern "C" int geeco_attr_path_point(float* dst, const float* x, const float* baseline, int64_t baseline_period, float alpha,
@@ -53,24 +53,17 @@ extern "C" int geeco_attr_path_point(float* dst, const float* x, const float* ba
   if (int rc = check_baseline("attr_path_point", baseline, baseline_period, n)) return rc;
   GEECO_CHECK_ARG(sigma >= 0.f && sigma == sigma && alpha == alpha, "attr_path_point: alpha=%g, sigma=%g (sigma >= 0, no NaN)",
                   (double)alpha, (double)sigma);
-  GEECO_CHECK_ARG(((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(x)) & 3) == 0, "attr_path_point: dst and x must be 4-byte aligned");
-  const uintptr_t d_lo = reinterpret_cast<uintptr_t>(dst), x_lo = reinterpret_cast<uintptr_t>(x), bytes = 4 * (uintptr_t)n;
-  GEECO_CHECK_ARG(d_lo + bytes <= x_lo || x_lo + bytes <= d_lo, "attr_path_point: dst overlaps x (the clean input is read by every step)");
-  const bool v = aligned16(dst) && aligned16(x);
-  const bool bv = baseline && baseline_period % 4 == 0 && aligned16(baseline);
+  GEECO_CHECK_ARG(attr_aligned<4>(dst, x), "attr_path_point: dst and x must be 4-byte aligned");
+  GEECO_CHECK_ARG(attr_apart(dst, 4 * (uintptr_t)n, x, 4 * (uintptr_t)n), "attr_path_point: dst overlaps x (the clean input is read by every step)");
+  const bool v = attr_aligned<16>(dst, x);
+  const bool bv = baseline && baseline_period % 4 == 0 && attr_aligned<16>(baseline);
   const unsigned grid = attr_grid((n + 3) >> 2);
   const unsigned k0 = (unsigned)key, k1 = (unsigned)(key >> 32);
-#define AT_LAUNCH(V, BV)                                                                                                        \
-  do {                                                                                                                          \
-    geeco_note_kernel("attr_path_point_kernel<%s, %s>", V ? "true" : "false", BV ? "true" : "false");                         \
-    hipLaunchKernelGGL((attr_path_point_kernel<V, BV>), dim3(grid), dim3(AT_THREADS), 0, (hipStream_t)stream, dst, x, baseline, \
-                       (long long)(baseline ? baseline_period : 1), alpha, sigma, k0, k1, (unsigned)step, (long long)n);        \
-  } while (0)
-  if (v && bv) AT_LAUNCH(true, true);
-  else if (v) AT_LAUNCH(true, false);
-  else if (bv) AT_LAUNCH(false, true);
-  else AT_LAUNCH(false, false);
-#undef AT_LAUNCH
+  attr_select([&](auto V, auto BV) {
+    geeco_note_kernel("attr_path_point_kernel<%s, %s>", attr_tf(V()), attr_tf(BV()));
+    hipLaunchKernelGGL((attr_path_point_kernel<V(), BV()>), dim3(grid), dim3(AT_THREADS), 0, (hipStream_t)stream, dst, x, baseline,
+                       (long long)(baseline ? baseline_period : 1), alpha, sigma, k0, k1, (unsigned)step, (long long)n);
+  }, v, bv);
   GEECO_LAUNCH_CHECK();
   return 0;
 }
@@ -81,38 +74,26 @@ extern "C" int geeco_attr_path_point(float* dst, const float* x, const float* ba
 template <bool V, bool OVERWRITE>
 __global__ __launch_bounds__(AT_THREADS) void attr_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, float weight,
                                                                     long long n) {
-  const long long groups = (n + 3) >> 2, stride = (long long)gridDim.x * AT_THREADS;
-  for (long long q = (long long)blockIdx.x * AT_THREADS + threadIdx.x; q < groups; q += stride) {
-    const long long e = q << 2;
-    const int cnt = n - e >= 4 ? 4 : (int)(n - e);
+  attr_for_groups4(n, [&](long long e, int cnt) {
     float gv[4], a[4] = {0.f, 0.f, 0.f, 0.f};
     attr_load4<V>(g, e, cnt, gv);
     if (!OVERWRITE) attr_load4<V>(acc, e, cnt, a);
 #pragma unroll
     for (int j = 0; j < 4; ++j) a[j] = at_add(a[j], at_mul(weight, gv[j]));
     attr_store4<V>(acc, e, cnt, a);
-  }
+  });
 }
 
 extern "C" int geeco_attr_accumulate(float* acc, const float* g, float weight, int64_t n, int overwrite, void* stream) {
   GEECO_CHECK_ARG(acc && g, "attr_accumulate: null pointer");
   GEECO_CHECK_ARG(n >= 1, "attr_accumulate: n=%lld must be >= 1", (long long)n);
-  GEECO_CHECK_ARG(((reinterpret_cast<uintptr_t>(acc) | reinterpret_cast<uintptr_t>(g)) & 3) == 0, "attr_accumulate: acc and g must be 4-byte aligned");
-  const uintptr_t a_lo = reinterpret_cast<uintptr_t>(acc), g_lo = reinterpret_cast<uintptr_t>(g), bytes = 4 * (uintptr_t)n;
-  GEECO_CHECK_ARG(a_lo + bytes <= g_lo || g_lo + bytes <= a_lo, "attr_accumulate: acc overlaps g");
-  const bool v = aligned16(acc) && aligned16(g);
+  GEECO_CHECK_ARG(attr_aligned<4>(acc, g), "attr_accumulate: acc and g must be 4-byte aligned");
+  GEECO_CHECK_ARG(attr_apart(acc, 4 * (uintptr_t)n, g, 4 * (uintptr_t)n), "attr_accumulate: acc overlaps g");
   const unsigned grid = attr_grid((n + 3) >> 2);
-#define AT_LAUNCH(V, O)                                                                                                          \
-  do {                                                                                                                          \
-    geeco_note_kernel("attr_accumulate_kernel<%s, %s>", V ? "true" : "false", O ? "true" : "false");                          \
-    hipLaunchKernelGGL((attr_accumulate_kernel<V, O>), dim3(grid), dim3(AT_THREADS), 0, (hipStream_t)stream, acc, g, weight,     \
-                       (long long)n);                                                                                           \
-  } while (0)
-  if (v && overwrite) AT_LAUNCH(true, true);
-  else if (v) AT_LAUNCH(true, false);
-  else if (overwrite) AT_LAUNCH(false, true);
-  else AT_LAUNCH(false, false);
-#undef AT_LAUNCH
+  attr_select([&](auto V, auto O) {
+    geeco_note_kernel("attr_accumulate_kernel<%s, %s>", attr_tf(V()), attr_tf(O()));
+    hipLaunchKernelGGL((attr_accumulate_kernel<V(), O()>), dim3(grid), dim3(AT_THREADS), 0, (hipStream_t)stream, acc, g, weight, (long long)n);
+  }, attr_aligned<16>(acc, g), overwrite != 0);
   GEECO_LAUNCH_CHECK();
   return 0;
 }
@@ -177,7 +158,7 @@ __global__ __launch_bounds__(AT_SUM_THREADS) void attr_sample_sum_kernel(const f
   const float* a = attr + (long long)blockIdx.x * S;
   const long long groups = (S + 3) >> 2;
   float s = 0.f;
-  for (long long q = threadIdx.x; q < groups; q += AT_SUM_THREADS) {
+  for (long long q = threadIdx.x; q < groups; q += AT_SUM_THREADS) {      // (its own loop: a shared one cost the finish 1 %, profiles/attr_core)
     const long long e = q << 2;
     const int cnt = S - e >= 4 ? 4 : (int)(S - e);
     float v[4];
@@ -206,52 +187,31 @@ extern "C" int geeco_attr_finish(float* attr, float* saliency, float* sample_sum
   const long long pixels = (long long)N * frames_per_sample * HW, n = pixels * C, S = (long long)frames_per_sample * HW * C;
   if (multiply_by_input)
     if (int rc = check_baseline("attr_finish", baseline, baseline_period, n)) return rc;
-  auto misaligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
-  GEECO_CHECK_ARG(!misaligned(attr) && !misaligned(saliency) && !misaligned(sample_sum) && !misaligned(acc) && !misaligned(x),
-                  "attr_finish: every pointer must be 4-byte aligned");
-  const uintptr_t t_lo = reinterpret_cast<uintptr_t>(attr), bytes = 4 * (uintptr_t)n;
-  auto apart = [&](const void* p, uintptr_t len) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return t_lo + bytes <= lo || lo + len <= t_lo;
-  };
-  GEECO_CHECK_ARG(apart(saliency, 4 * (uintptr_t)pixels) && apart(sample_sum, 4 * (uintptr_t)N), "attr_finish: attr overlaps another output");
+  GEECO_CHECK_ARG(attr_aligned<4>(attr, saliency, sample_sum, acc, x), "attr_finish: every pointer must be 4-byte aligned");
+  const uintptr_t bytes = 4 * (uintptr_t)n;
+  GEECO_CHECK_ARG(attr_apart(attr, bytes, saliency, 4 * (uintptr_t)pixels) && attr_apart(attr, bytes, sample_sum, 4 * (uintptr_t)N),
+                  "attr_finish: attr overlaps another output");
   // in place (attr == acc: a thread reads exactly what it writes) or apart; a partial overlap would let one thread read what another wrote
-  GEECO_CHECK_ARG(attr == acc || apart(acc, bytes), "attr_finish: attr overlaps acc in part (attr == acc or disjoint)");
-  GEECO_CHECK_ARG(!multiply_by_input || apart(x, bytes), "attr_finish: attr overlaps x");
-  const bool v = aligned16(attr) && aligned16(saliency) && aligned16(acc) && (!multiply_by_input || aligned16(x));
-  const bool bv = multiply_by_input && baseline && baseline_period % 4 == 0 && aligned16(baseline);
+  GEECO_CHECK_ARG(attr == acc || attr_apart(attr, bytes, acc, bytes), "attr_finish: attr overlaps acc in part (attr == acc or disjoint)");
+  GEECO_CHECK_ARG(!multiply_by_input || attr_apart(attr, bytes, x, bytes), "attr_finish: attr overlaps x");
+  const bool v = attr_aligned<16>(attr, saliency, acc) && (!multiply_by_input || attr_aligned<16>(x));
+  const bool bv = multiply_by_input && baseline && baseline_period % 4 == 0 && attr_aligned<16>(baseline);
   const unsigned grid = attr_grid((pixels + 3) >> 2);
   const long long period = (multiply_by_input && baseline) ? baseline_period : 1;
   const float* bl = multiply_by_input ? baseline : nullptr;
   hipStream_t s = (hipStream_t)stream;
-#define AT_LAUNCH(C_, V, BV)                                                                                                     \
-  do {                                                                                                                          \
-    geeco_note_kernel("attr_finish_kernel<%d, %s, %s>", C_, V ? "true" : "false", BV ? "true" : "false");                     \
-    hipLaunchKernelGGL((attr_finish_kernel<C_, V, BV>), dim3(grid), dim3(AT_THREADS), 0, s, attr, saliency, acc, x, bl, period,   \
-                       multiply_by_input, pixels);                                                                              \
-  } while (0)
-#define AT_FORMS(C_)                      \
-  do {                                    \
-    if (v && bv) AT_LAUNCH(C_, true, true);        \
-    else if (v) AT_LAUNCH(C_, true, false);        \
-    else if (bv) AT_LAUNCH(C_, false, true);       \
-    else AT_LAUNCH(C_, false, false);              \
-  } while (0)
-  switch (C) {
-    case 1: AT_FORMS(1); break;
-    case 2: AT_FORMS(2); break;
-    case 3: AT_FORMS(3); break;
-    default: AT_FORMS(4); break;
-  }
-#undef AT_FORMS
-#undef AT_LAUNCH
+  attr_channels(C, [&](auto C_) {
+    attr_select([&](auto V, auto BV) {
+      geeco_note_kernel("attr_finish_kernel<%d, %s, %s>", C_(), attr_tf(V()), attr_tf(BV()));
+      hipLaunchKernelGGL((attr_finish_kernel<C_(), V(), BV()>), dim3(grid), dim3(AT_THREADS), 0, s, attr, saliency, acc, x, bl, period,
+                         multiply_by_input, pixels);
+    }, v, bv);
+  });
   GEECO_LAUNCH_CHECK();
-  const bool sv = aligned16(attr) && S % 4 == 0;
-  geeco_note_kernel("attr_sample_sum_kernel<%s>", sv ? "true" : "false");
-  if (sv)
-    hipLaunchKernelGGL(attr_sample_sum_kernel<true>, dim3((unsigned)N), dim3(AT_SUM_THREADS), 0, s, (const float*)attr, S, sample_sum);
-  else
-    hipLaunchKernelGGL(attr_sample_sum_kernel<false>, dim3((unsigned)N), dim3(AT_SUM_THREADS), 0, s, (const float*)attr, S, sample_sum);
+  attr_select([&](auto V) {
+    geeco_note_kernel("attr_sample_sum_kernel<%s>", attr_tf(V()));
+    hipLaunchKernelGGL(attr_sample_sum_kernel<V()>, dim3((unsigned)N), dim3(AT_SUM_THREADS), 0, s, (const float*)attr, S, sample_sum);
+  }, attr_aligned<16>(attr) && S % 4 == 0);
   GEECO_LAUNCH_CHECK();
   return 0;
 }

@@ -1,6 +1,6 @@
 // Perturbation attributions: occlusion sensitivity and RISE (geeco_amd/perturbation.py).  Hide a region of the input,
 // run the model's own forward, see how far the command moves -- no backward.  What is here are the streaming stages around that
-// forward, on the skeleton of attribution.hip:
+// forward, on the launch path and the group loop of attr_stream.h, which attribution.hip shares:
 //   1. perturb_apply:       dst = x where o == 0, fill where o == 1, x + o (fill - x) otherwise    the occluded input;
 //   2. perturb_score:       d[n] = sum_j w_j (p[n][j] - p0[n][j])^2                                how far the command moved;
 //   3. perturb_accumulate:  num += d[n] o, den += o  where o != 0                                   the running sums per pixel;
@@ -60,13 +60,23 @@ __device__ __forceinline__ float perturb_weight(const PerturbStep& s, const floa
   return at_sub(1.f, at_add(top, at_mul(fy, at_sub(bot, top))));
 }
 
-// the weights of the (up to) four pixels p0 .. p0 + np - 1 of a unit
-template <bool RISE>
-__device__ __forceinline__ void perturb_weights4(const PerturbStep& s, const float* keep, const int* shift, int p0, int np, float o[4]) {
+// f(p0, np, o) for the units of four consecutive pixels p0 .. p0 + np - 1 of sample blockIdx.y that one thread owns (the last
+// unit of HW may hold np < 4), o[j] their weights (0 past np): the sample's draws are prepared once per block, in LDS.
+template <bool RISE, class F>
+__device__ __forceinline__ void perturb_for_units(const PerturbStep& s, int HW, F&& f) {
+  __shared__ float keep[RISE ? PT_MAXBITS : 1];
+  __shared__ int shift[2];
+  perturb_prepare<RISE>(s, s.sample0 + blockIdx.y, keep, shift);
+  const int units = (HW + 3) >> 2;
+  for (int u = blockIdx.x * AT_THREADS + threadIdx.x; u < units; u += gridDim.x * AT_THREADS) {
+    const int p0 = u << 2, np = HW - p0 >= 4 ? 4 : HW - p0;
+    float o[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int p = p0 + j, y = p / s.W;
-    o[j] = j < np ? perturb_weight<RISE>(s, keep, shift, y, p - y * s.W) : 0.f;
+    for (int j = 0; j < 4; ++j) {
+      const int p = p0 + j, y = p / s.W;
+      o[j] = j < np ? perturb_weight<RISE>(s, keep, shift, y, p - y * s.W) : 0.f;
+    }
+    f(p0, np, o);
   }
 }
 
@@ -77,17 +87,9 @@ template <int C, bool V, bool RISE>
 __global__ __launch_bounds__(AT_THREADS) void perturb_apply_kernel(float* __restrict__ dst, const float* __restrict__ x,
                                                                   const float* __restrict__ fill, long long period, int bv,
                                                                   PerturbStep s, int frames, int HW, long long n) {
-  __shared__ float keep[RISE ? PT_MAXBITS : 1];
-  __shared__ int shift[2];
-  const int sample = blockIdx.y;
-  perturb_prepare<RISE>(s, s.sample0 + sample, keep, shift);
-  const long long base = (long long)sample * frames * HW * C;
+  const long long base = (long long)blockIdx.y * frames * HW * C;
   const bool small = n <= 0xffffffffLL;
-  const int units = (HW + 3) >> 2;
-  for (int u = blockIdx.x * AT_THREADS + threadIdx.x; u < units; u += gridDim.x * AT_THREADS) {
-    const int p0 = u << 2, np = HW - p0 >= 4 ? 4 : HW - p0;
-    float o[4];
-    perturb_weights4<RISE>(s, keep, shift, p0, np, o);
+  perturb_for_units<RISE>(s, HW, [&](int p0, int np, const float o[4]) {
     const bool hidden = o[0] != 0.f || o[1] != 0.f || o[2] != 0.f || o[3] != 0.f;
     for (int f = 0; f < frames; ++f) {
       const long long e0 = base + ((long long)f * HW + p0) * C;
@@ -110,7 +112,7 @@ __global__ __launch_bounds__(AT_THREADS) void perturb_apply_kernel(float* __rest
         attr_store4<V>(dst, e, cnt, xv);
       }
     }
-  }
+  });
 }
 
 // The incremental form of the occlusion grid: dst holds the input of the previous step.  Only two patches change: the step's own
@@ -167,19 +169,12 @@ __global__ __launch_bounds__(64) void perturb_score_kernel(float* __restrict__ d
 template <bool V, bool RISE, bool OVERWRITE>
 __global__ __launch_bounds__(AT_THREADS) void perturb_accumulate_kernel(float* __restrict__ num, float* __restrict__ den,
                                                                        const float* __restrict__ d, PerturbStep s, int HW) {
-  __shared__ float keep[RISE ? PT_MAXBITS : 1];
-  __shared__ int shift[2];
-  const int sample = blockIdx.y;
-  perturb_prepare<RISE>(s, s.sample0 + sample, keep, shift);
-  const float dn = d[sample];
-  const long long base = (long long)sample * HW;
-  const int units = (HW + 3) >> 2;
-  for (int u = blockIdx.x * AT_THREADS + threadIdx.x; u < units; u += gridDim.x * AT_THREADS) {
-    const int p0 = u << 2, np = HW - p0 >= 4 ? 4 : HW - p0;
-    float o[4], a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
-    perturb_weights4<RISE>(s, keep, shift, p0, np, o);
+  const float dn = d[blockIdx.y];
+  const long long base = (long long)blockIdx.y * HW;
+  perturb_for_units<RISE>(s, HW, [&](int p0, int np, const float o[4]) {
+    float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
     if (!OVERWRITE) {
-      if (o[0] == 0.f && o[1] == 0.f && o[2] == 0.f && o[3] == 0.f) continue;
+      if (o[0] == 0.f && o[1] == 0.f && o[2] == 0.f && o[3] == 0.f) return;
       attr_load4<V>(num, base + p0, np, a);
       attr_load4<V>(den, base + p0, np, b);
     }
@@ -188,24 +183,21 @@ __global__ __launch_bounds__(AT_THREADS) void perturb_accumulate_kernel(float* _
       if (o[j] != 0.f) a[j] = at_add(a[j], at_mul(dn, o[j])), b[j] = at_add(b[j], o[j]);
     attr_store4<V>(num, base + p0, np, a);
     attr_store4<V>(den, base + p0, np, b);
-  }
+  });
 }
 
 // ---- 4. the finish -------------------------------------------------------------------------------------------------------------
 template <bool V>
 __global__ __launch_bounds__(AT_THREADS) void perturb_finish_kernel(float* __restrict__ saliency, const float* __restrict__ num,
                                                                    const float* __restrict__ den, long long n) {
-  const long long groups = (n + 3) >> 2, stride = (long long)gridDim.x * AT_THREADS;
-  for (long long q = (long long)blockIdx.x * AT_THREADS + threadIdx.x; q < groups; q += stride) {
-    const long long e = q << 2;
-    const int cnt = n - e >= 4 ? 4 : (int)(n - e);
+  attr_for_groups4(n, [&](long long e, int cnt) {
     float a[4], b[4], o[4];
     attr_load4<V>(num, e, cnt, a);
     attr_load4<V>(den, e, cnt, b);
 #pragma unroll
     for (int j = 0; j < 4; ++j) o[j] = b[j] > 0.f ? a[j] / b[j] : 0.f;
     attr_store4<V>(saliency, e, cnt, o);
-  }
+  });
 }
 
 // ---- the host side -------------------------------------------------------------------------------------------------------------
@@ -274,55 +266,32 @@ extern "C" int geeco_perturb_apply(float* dst, const float* x, const float* fill
   const int HW = s.H * s.W;
   const long long n = (long long)N * frames * HW * C;
   if (int rc = check_baseline("perturb_apply", fill, fill_period, n)) return rc;
-  GEECO_CHECK_ARG(((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(x)) & 3) == 0, "perturb_apply: dst and x must be 4-byte aligned");
-  const uintptr_t d_lo = reinterpret_cast<uintptr_t>(dst), x_lo = reinterpret_cast<uintptr_t>(x), bytes = 4 * (uintptr_t)n;
-  GEECO_CHECK_ARG(d_lo + bytes <= x_lo || x_lo + bytes <= d_lo, "perturb_apply: dst overlaps x (the clean input is read by every step)");
+  GEECO_CHECK_ARG(attr_aligned<4>(dst, x), "perturb_apply: dst and x must be 4-byte aligned");
+  GEECO_CHECK_ARG(attr_apart(dst, 4 * (uintptr_t)n, x, 4 * (uintptr_t)n), "perturb_apply: dst overlaps x (the clean input is read by every step)");
   const long long period = fill ? fill_period : 1;
   hipStream_t st = (hipStream_t)stream;
   if (patch) {
     const int items = (s.y1 - s.y0) * (s.x1 - s.x0) + (prev.y1 - prev.y0) * (prev.x1 - prev.x0);
     const dim3 grid = sample_grid(items, N);
-#define PT_PATCH(C_)                                                                                                             \
-  do {                                                                                                                          \
-    geeco_note_kernel("perturb_apply_patch_kernel<%d>", C_);                                                                  \
-    hipLaunchKernelGGL((perturb_apply_patch_kernel<C_>), grid, dim3(AT_THREADS), 0, st, dst, x, fill, period, s, prev.y0, prev.y1, \
-                       prev.x0, prev.x1, frames, HW, n);                                                                        \
-  } while (0)
-    switch (C) {
-      case 1: PT_PATCH(1); break;
-      case 2: PT_PATCH(2); break;
-      case 3: PT_PATCH(3); break;
-      default: PT_PATCH(4); break;
-    }
-#undef PT_PATCH
+    attr_channels(C, [&](auto C_) {
+      geeco_note_kernel("perturb_apply_patch_kernel<%d>", C_());
+      hipLaunchKernelGGL((perturb_apply_patch_kernel<C_()>), grid, dim3(AT_THREADS), 0, st, dst, x, fill, period, s, prev.y0, prev.y1,
+                         prev.x0, prev.x1, frames, HW, n);
+    });
     GEECO_LAUNCH_CHECK();
     return 0;
   }
   // 16-byte accesses: every frame of every sample starts on a multiple of four floats
   const bool frames_aligned = ((long long)HW * C) % 4 == 0;
-  const bool v = frames_aligned && aligned16(dst) && aligned16(x);
-  const int bv = frames_aligned && fill && fill_period % 4 == 0 && aligned16(fill);
+  const bool v = frames_aligned && attr_aligned<16>(dst, x);
+  const int bv = frames_aligned && fill && fill_period % 4 == 0 && attr_aligned<16>(fill);
   const dim3 grid = sample_grid((HW + 3) >> 2, N);
-#define PT_LAUNCH(C_, V, R)                                                                                                      \
-  do {                                                                                                                          \
-    geeco_note_kernel("perturb_apply_kernel<%d, %s, %s>", C_, V ? "true" : "false", R ? "true" : "false");                    \
-    hipLaunchKernelGGL((perturb_apply_kernel<C_, V, R>), grid, dim3(AT_THREADS), 0, st, dst, x, fill, period, bv, s, frames, HW, n); \
-  } while (0)
-#define PT_FORMS(C_)                               \
-  do {                                             \
-    if (v && rise) PT_LAUNCH(C_, true, true);      \
-    else if (v) PT_LAUNCH(C_, true, false);        \
-    else if (rise) PT_LAUNCH(C_, false, true);     \
-    else PT_LAUNCH(C_, false, false);              \
-  } while (0)
-  switch (C) {
-    case 1: PT_FORMS(1); break;
-    case 2: PT_FORMS(2); break;
-    case 3: PT_FORMS(3); break;
-    default: PT_FORMS(4); break;
-  }
-#undef PT_FORMS
-#undef PT_LAUNCH
+  attr_channels(C, [&](auto C_) {
+    attr_select([&](auto V, auto R) {
+      geeco_note_kernel("perturb_apply_kernel<%d, %s, %s>", C_(), attr_tf(V()), attr_tf(R()));
+      hipLaunchKernelGGL((perturb_apply_kernel<C_(), V(), R()>), grid, dim3(AT_THREADS), 0, st, dst, x, fill, period, bv, s, frames, HW, n);
+    }, v, rise);
+  });
   GEECO_LAUNCH_CHECK();
   return 0;
 }
@@ -330,8 +299,7 @@ extern "C" int geeco_perturb_apply(float* dst, const float* x, const float* fill
 extern "C" int geeco_perturb_score(float* d, const float* preds, const float* preds0, const float* w, int N, int OT, void* stream) {
   GEECO_CHECK_ARG(d && preds && preds0 && w, "perturb_score: null pointer");
   GEECO_CHECK_ARG(N >= 1 && OT >= 1 && OT <= 1 << 16, "perturb_score: N=%d, OT=%d must be >= 1", N, OT);
-  GEECO_CHECK_ARG(((reinterpret_cast<uintptr_t>(d) | reinterpret_cast<uintptr_t>(preds) | reinterpret_cast<uintptr_t>(preds0) |
-                    reinterpret_cast<uintptr_t>(w)) & 3) == 0, "perturb_score: every pointer must be 4-byte aligned");
+  GEECO_CHECK_ARG(attr_aligned<4>(d, preds, preds0, w), "perturb_score: every pointer must be 4-byte aligned");
   geeco_note_kernel("perturb_score_kernel");
   hipLaunchKernelGGL(perturb_score_kernel, dim3((unsigned)cdiv(N, 64)), dim3(64), 0, (hipStream_t)stream, d, preds, preds0, w, N, OT);
   GEECO_LAUNCH_CHECK();
@@ -347,32 +315,15 @@ extern "C" int geeco_perturb_accumulate(float* num, float* den, const float* d, 
   if (int rc = perturb_step("perturb_accumulate", desc, step, sample0, &s, &Gy, &Gx)) return rc;
   const bool rise = Gy == 0;
   const int HW = s.H * s.W;
-  GEECO_CHECK_ARG(((reinterpret_cast<uintptr_t>(num) | reinterpret_cast<uintptr_t>(den) | reinterpret_cast<uintptr_t>(d)) & 3) == 0,
-                  "perturb_accumulate: every pointer must be 4-byte aligned");
-  const uintptr_t a_lo = reinterpret_cast<uintptr_t>(num), b_lo = reinterpret_cast<uintptr_t>(den), d_lo = reinterpret_cast<uintptr_t>(d);
+  GEECO_CHECK_ARG(attr_aligned<4>(num, den, d), "perturb_accumulate: every pointer must be 4-byte aligned");
   const uintptr_t bytes = 4 * (uintptr_t)N * HW, d_bytes = 4 * (uintptr_t)N;
-  GEECO_CHECK_ARG(a_lo + bytes <= b_lo || b_lo + bytes <= a_lo, "perturb_accumulate: num overlaps den");
-  GEECO_CHECK_ARG((a_lo + bytes <= d_lo || d_lo + d_bytes <= a_lo) && (b_lo + bytes <= d_lo || d_lo + d_bytes <= b_lo),
-                  "perturb_accumulate: d overlaps num or den");
-  const bool v = HW % 4 == 0 && aligned16(num) && aligned16(den);
+  GEECO_CHECK_ARG(attr_apart(num, bytes, den, bytes), "perturb_accumulate: num overlaps den");
+  GEECO_CHECK_ARG(attr_apart(num, bytes, d, d_bytes) && attr_apart(den, bytes, d, d_bytes), "perturb_accumulate: d overlaps num or den");
   const dim3 grid = sample_grid((HW + 3) >> 2, N);
-  hipStream_t st = (hipStream_t)stream;
-#define PT_LAUNCH(V, R, O)                                                                                                       \
-  do {                                                                                                                          \
-    geeco_note_kernel("perturb_accumulate_kernel<%s, %s, %s>", V ? "true" : "false", R ? "true" : "false", O ? "true" : "false"); \
-    hipLaunchKernelGGL((perturb_accumulate_kernel<V, R, O>), grid, dim3(AT_THREADS), 0, st, num, den, d, s, HW);                 \
-  } while (0)
-#define PT_FORMS(V, R)                      \
-  do {                                      \
-    if (overwrite) PT_LAUNCH(V, R, true);   \
-    else PT_LAUNCH(V, R, false);            \
-  } while (0)
-  if (v && rise) PT_FORMS(true, true);
-  else if (v) PT_FORMS(true, false);
-  else if (rise) PT_FORMS(false, true);
-  else PT_FORMS(false, false);
-#undef PT_FORMS
-#undef PT_LAUNCH
+  attr_select([&](auto V, auto R, auto O) {
+    geeco_note_kernel("perturb_accumulate_kernel<%s, %s, %s>", attr_tf(V()), attr_tf(R()), attr_tf(O()));
+    hipLaunchKernelGGL((perturb_accumulate_kernel<V(), R(), O()>), grid, dim3(AT_THREADS), 0, (hipStream_t)stream, num, den, d, s, HW);
+  }, HW % 4 == 0 && attr_aligned<16>(num, den), rise, overwrite != 0);
   GEECO_LAUNCH_CHECK();
   return 0;
 }
@@ -380,19 +331,14 @@ extern "C" int geeco_perturb_accumulate(float* num, float* den, const float* d, 
 extern "C" int geeco_perturb_finish(float* saliency, const float* num, const float* den, int64_t n, void* stream) {
   GEECO_CHECK_ARG(saliency && num && den, "perturb_finish: null pointer");
   GEECO_CHECK_ARG(n >= 1, "perturb_finish: n=%lld must be >= 1", (long long)n);
-  GEECO_CHECK_ARG(((reinterpret_cast<uintptr_t>(saliency) | reinterpret_cast<uintptr_t>(num) | reinterpret_cast<uintptr_t>(den)) & 3) == 0,
-                  "perturb_finish: every pointer must be 4-byte aligned");
-  const uintptr_t s_lo = reinterpret_cast<uintptr_t>(saliency), bytes = 4 * (uintptr_t)n;
-  auto apart = [&](const void* p) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return s_lo + bytes <= lo || lo + bytes <= s_lo;
-  };
-  GEECO_CHECK_ARG(apart(num) && apart(den), "perturb_finish: saliency overlaps num or den");
-  const bool v = aligned16(saliency) && aligned16(num) && aligned16(den);
+  GEECO_CHECK_ARG(attr_aligned<4>(saliency, num, den), "perturb_finish: every pointer must be 4-byte aligned");
+  const uintptr_t bytes = 4 * (uintptr_t)n;
+  GEECO_CHECK_ARG(attr_apart(saliency, bytes, num, bytes) && attr_apart(saliency, bytes, den, bytes), "perturb_finish: saliency overlaps num or den");
   const unsigned grid = attr_grid((n + 3) >> 2);
-  geeco_note_kernel("perturb_finish_kernel<%s>", v ? "true" : "false");
-  if (v) hipLaunchKernelGGL(perturb_finish_kernel<true>, dim3(grid), dim3(AT_THREADS), 0, (hipStream_t)stream, saliency, num, den, (long long)n);
-  else hipLaunchKernelGGL(perturb_finish_kernel<false>, dim3(grid), dim3(AT_THREADS), 0, (hipStream_t)stream, saliency, num, den, (long long)n);
+  attr_select([&](auto V) {
+    geeco_note_kernel("perturb_finish_kernel<%s>", attr_tf(V()));
+    hipLaunchKernelGGL(perturb_finish_kernel<V()>, dim3(grid), dim3(AT_THREADS), 0, (hipStream_t)stream, saliency, num, den, (long long)n);
+  }, attr_aligned<16>(saliency, num, den));
   GEECO_LAUNCH_CHECK();
   return 0;
 }

@@ -26,6 +26,17 @@ def head_table(cfg, loss_shaping=None):
   return [(name, key, size, 2 if kind == 0 and key in huber else kind, w) for name, key, size, kind, w in heads]
 
 
+def resolve_heads(table, heads):
+  """The prediction keys of the heads ``heads`` names in the head table ``table`` (rows (variable, key, size, kind, weight)): one
+  name or several, 'logits_cmd_grp' also as 'cmd_grp'; None = every head.  ValueError for an empty selection or an unknown name."""
+  keys = [h[1] for h in table]
+  short = {k.replace('logits_', ''): k for k in keys}
+  picked = set(keys) if heads is None else {short.get(h, h) for h in ([heads] if isinstance(heads, str) else heads)}
+  if not picked or picked - set(keys):
+    raise ValueError('heads=%r: this model has the heads %s' % (heads, ', '.join(sorted(short))))
+  return picked
+
+
 class LSTMDecoder:
   """T LSTM steps over states [T][N][D] from a zero state, fc1 + heads on the last output."""
 
@@ -64,6 +75,7 @@ class LSTMDecoder:
       self.class_weight = torch.tensor(loss_shaping['grp_class_weights'], **f32)
     self.heads_pending, self.dz_from_heads = None, False
     self.head_weights = None      # select_loss_heads: the loss weights of an eager pass of its own; None = the table's (training)
+    self._sample_loss_scratch = None      # sample_losses_into: made on first use
 
   def select_loss_heads(self, heads=None):
     """The loss this decoder differentiates from now on: the sum of the named heads' losses with weight 1, every other head 0
@@ -73,13 +85,8 @@ class LSTMDecoder:
     if heads is None:
       self.head_weights = None
       return
-    keys = [h[1] for h in self.heads]
-    short = {k.replace('logits_', ''): k for k in keys}
-    picked = {short.get(h, h) for h in ([heads] if isinstance(heads, str) else heads)}
-    unknown = sorted(picked - set(keys))
-    if unknown or not picked:
-      raise ValueError('heads=%r: this model has the heads %s' % (heads, ', '.join(sorted(short))))
-    self.head_weights = [1.0 if k in picked else 0.0 for k in keys]
+    picked = resolve_heads(self.heads, heads)
+    self.head_weights = [1.0 if h[1] in picked else 0.0 for h in self.heads]
 
   def _alloc_chain(self):
     """The per-step buffers of the launch-per-step chain."""
@@ -209,11 +216,27 @@ class LSTMDecoder:
     the single-workgroup heads kernel wrote the losses (dim_h_fc outside {64, 128}, dim_h_lstm > 128 or more than 32 outputs: it
     keeps no rows), the one-launch inference decoder ran (no losses at all), or ``loss_shaping`` is on (the rows then hold weighted
     terms whose means are taken over batch-wide counts)."""
+    out = torch.empty(self.N, dtype=torch.float64, device=self.preds.device)
+    return out if self.sample_losses_into(out) else None
+
+  def sample_losses_into(self, out):
+    """``sample_losses`` into ``out`` (float64 [N]) without an allocation on the device: the rows widened into the decoder's own
+    scratch, then one matrix-vector product with the coefficients (uploaded when they change: ``select_loss_heads``).  False, and
+    ``out`` untouched, where the rows do not exist."""
     terms = self.sample_loss_terms()
     if terms is None:
-      return None
+      return False
     rows, coef = terms
-    return rows.double() @ torch.tensor(coef, dtype=torch.float64, device=rows.device)
+    if self._sample_loss_scratch is None:      # (N and the head table are fixed per decoder: so are the two shapes)
+      f64 = dict(dtype=torch.float64, device=rows.device)
+      self._sample_loss_scratch = dict(rows=torch.empty(rows.shape, **f64), coef=torch.empty(len(coef), **f64), host=None)
+    sc = self._sample_loss_scratch
+    if sc['host'] != coef:
+      sc['coef'].copy_(torch.tensor(coef, dtype=torch.float64), non_blocking=True)
+      sc['host'] = coef
+    sc['rows'].copy_(rows)
+    torch.mv(sc['rows'], sc['coef'], out=out)
+    return True
 
   def sample_loss_terms(self):
     """What ``sample_losses`` is made of: (the float32 view [N][heads] of the raw per-sample loss terms in the heads workspace -- it

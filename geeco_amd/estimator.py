@@ -460,6 +460,16 @@ def _eval_metric_fn(model):
 # ================================================================================================
 # Estimator
 # ================================================================================================
+def _host_results(model, res, scalars=()):
+  """What a pass of ``Estimator._input_pass`` yields for ``res``, its device results: one synchronisation, the device-error check, then
+  every tensor as a numpy copy and the ones named in ``scalars`` as floats (entries that are no tensors are left out)."""
+  torch.cuda.synchronize()
+  model.check_device_errors()
+  out = {k: v.detach().cpu().numpy().copy() for k, v in res.items() if torch.is_tensor(v) and k not in scalars}
+  out.update({k: float(res[k]) for k in scalars if k in res})
+  return out
+
+
 class Estimator:
   """tf.estimator.Estimator counterpart (train_e2evmc.py:260-264, 284-291)."""
 
@@ -773,12 +783,7 @@ class Estimator:
     def run(model):
       model.forward(backward_too=True)
       model.backward()
-      grads = model.input_gradients()
-      torch.cuda.synchronize()
-      model.check_device_errors()
-      out = {k: v.detach().cpu().numpy().copy() for k, v in grads.items()}
-      out['loss'] = float(model.loss)
-      return out
+      return _host_results(model, dict(model.input_gradients(), loss=model.loss), ('loss',))
     return self._input_pass('input_gradients', input_fn, heads, checkpoint_path, run)
 
   def attributions(self, input_fn, method='integrated_gradients', steps=16, baseline=None, noise_std=0.0, seed=0, heads=None,
@@ -793,12 +798,7 @@ class Estimator:
     check_attribution_arguments(method, steps, noise_std, seed)
 
     def run(model):
-      res = model.attributions(method, steps, baseline=baseline, noise_std=noise_std, seed=seed)
-      torch.cuda.synchronize()
-      model.check_device_errors()
-      out = {k: v.detach().cpu().numpy().copy() for k, v in res.items() if torch.is_tensor(v) and k not in ('loss', 'loss_baseline')}
-      out.update({k: float(res[k]) for k in ('loss', 'loss_baseline') if k in res})
-      return out
+      return _host_results(model, model.attributions(method, steps, baseline=baseline, noise_std=noise_std, seed=seed), ('loss', 'loss_baseline'))
     return self._input_pass('attributions', input_fn, heads, checkpoint_path, run)
 
   def perturbation_attributions(self, input_fn, method='occlusion', patch=None, stride=None, grid=7, keep_prob=0.5, steps=64, fill=None,
@@ -813,11 +813,8 @@ class Estimator:
     check_perturbation_arguments(method, patch, stride, grid, keep_prob, steps, score, seed)
 
     def run(model):
-      res = model.perturbation_attributions(method, patch=patch, stride=stride, grid=grid, keep_prob=keep_prob, steps=steps, fill=fill,
-                                            score=score, heads=heads, seed=seed, inputs=inputs)
-      torch.cuda.synchronize()
-      model.check_device_errors()
-      return {k: v.detach().cpu().numpy().copy() for k, v in res.items() if torch.is_tensor(v)}
+      return _host_results(model, model.perturbation_attributions(method, patch=patch, stride=stride, grid=grid, keep_prob=keep_prob, steps=steps,
+                                                                  fill=fill, score=score, heads=heads, seed=seed, inputs=inputs))
     return self._input_pass('perturbation_attributions', input_fn, None, checkpoint_path, run, training=False)
 
   def _input_pass(self, who, input_fn, heads, checkpoint_path, run, training=True):

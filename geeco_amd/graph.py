@@ -295,17 +295,22 @@ class _ModelBase(OptimizerStep, Attributions, Perturbations):
 
   # -- input gradients: d(loss)/d(frames), for saliency maps ---------------------------------------------
 
+  def _refuse_sparse_inputs(self, who, slot_reason, address_reason):
+    """ValueError unless the model reads dense float32 windows: what ``who`` (a pass that takes gradients with respect to the image
+    inputs, or writes into them) cannot serve, with its own reason for each of the two."""
+    if self.shared_frames is not None:
+      raise ValueError('%s: shared_frames encodes frame slots, not windows: %s; use a model with dense windows' % (who, slot_reason))
+    bound = [k for k, buf in self.inputs.items() if hasattr(buf, 'pointers')]
+    if bound:
+      raise ValueError("%s: input%s %s bound as uint8 window addresses: %s; feed dense float32 windows"
+                       % (who, 's' if len(bound) > 1 else '', ', '.join("'%s'" % k for k in bound), address_reason))
+
   def check_input_gradients(self):
     """ValueError, with the reason, unless ``input_gradients`` serves this model."""
     if not self.training:
       raise ValueError('input_gradients: the model was built with training=False and has no backward; build it with training=True')
-    if self.shared_frames is not None:
-      raise ValueError('input_gradients: shared_frames encodes frame slots, not windows: a slot\'s gradient is the sum over every window '
-                       'that holds the frame; use a model with dense windows')
-    bound = [k for k, buf in self.inputs.items() if hasattr(buf, 'pointers')]
-    if bound:
-      raise ValueError("input_gradients: input%s %s bound as uint8 window addresses: the gradient is taken with respect to float32 "
-                       "frames; feed dense float32 windows" % ('s' if len(bound) > 1 else '', ', '.join("'%s'" % k for k in bound)))
+    self._refuse_sparse_inputs('input_gradients', "a slot's gradient is the sum over every window that holds the frame",
+                               'the gradient is taken with respect to float32 frames')
     if self.backward_cut != 'full':
       raise ValueError("input_gradients: backward_cut=%r (lr_multipliers froze the encoder bottom) stops the backward above conv2; "
                        "the pass needs the full backward" % (self.backward_cut,))

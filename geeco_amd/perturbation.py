@@ -7,7 +7,7 @@ shared by the frames and channels of the occluded input, and
     saliency[n][pixel] = sum_m d_m[n] o_m / sum_m o_m        (+0 where no step hid the pixel)
 
 is the mean change of the command over the steps that hid the pixel, weighted by how much they hid it.  The skeleton is
-attribution.py's: the occluded input is written into the model's own buffers (csrc/perturbation.hip: geeco_perturb_apply), the
+attribution.py's, its shared pieces in attr_pass.py: the occluded input is written into the model's own buffers (csrc/perturbation.hip: geeco_perturb_apply), the
 model's forward runs untouched, the step's score (geeco_perturb_score) goes into the running sums (geeco_perturb_accumulate) and
 one finish forms the map.  Nothing is copied to the host inside the loop and nothing is allocated there.
 """
@@ -17,7 +17,9 @@ import numpy as np
 import torch
 
 from . import ops
+from .attr_pass import check_steps_seed, clean_inputs, periodic_operands
 from .attribution import input_key
+from .decoder import resolve_heads
 
 METHODS = ('occlusion', 'rise')
 SCORES = ('prediction', 'loss')
@@ -49,10 +51,8 @@ def check_perturbation_arguments(method, patch=None, stride=None, grid=7, keep_p
       raise ValueError('perturbation_attributions: grid=%r must be an integer in 2..31' % (grid,))
     if not 0.0 < float(keep_prob) < 1.0:
       raise ValueError('perturbation_attributions: keep_prob=%r must lie in (0, 1)' % (keep_prob,))
-    if int(steps) != steps or not 1 <= int(steps) <= 1 << 20:
-      raise ValueError('perturbation_attributions: steps=%r must be an integer >= 1' % (steps,))
-  if int(seed) != seed or int(seed) < 0:
-    raise ValueError('perturbation_attributions: seed=%r must be an integer >= 0' % (seed,))
+    check_steps_seed('perturbation_attributions', steps=steps)
+  check_steps_seed('perturbation_attributions', seed=seed)
 
 
 class Perturbations:
@@ -62,20 +62,15 @@ class Perturbations:
 
   def check_perturbation_attributions(self):
     """ValueError, with the reason, unless ``perturbation_attributions`` serves this model (any ``training``)."""
-    if self.shared_frames is not None:
-      raise ValueError('perturbation_attributions: shared_frames encodes frame slots, not windows: an occluder on a slot would hide '
-                       'the frame in every window that holds it; use a model with dense windows')
-    bound = [k for k, buf in self.inputs.items() if hasattr(buf, 'pointers')]
-    if bound:
-      raise ValueError("perturbation_attributions: input%s %s bound as uint8 window addresses: the occluded input is written as float32 "
-                       "frames; feed dense float32 windows" % ('s' if len(bound) > 1 else '', ', '.join("'%s'" % k for k in bound)))
+    self._refuse_sparse_inputs('perturbation_attributions', 'an occluder on a slot would hide the frame in every window that holds it',
+                               'the occluded input is written as float32 frames')
 
   def _perturb_buffers(self, passes, M):
     if self._perturb is None:
       f32 = dict(dtype=torch.float32, device=self.device)
       d = self.decoder
       self._perturb = dict(clean={}, fill={}, sums={}, scores={}, preds0=torch.empty_like(d.preds), w=torch.empty(d.OT, **f32),
-                           losses=torch.empty(2, self.N, dtype=torch.float64, device=self.device), rows=None, coef=None)
+                           losses=torch.empty(2, self.N, dtype=torch.float64, device=self.device))
     p = self._perturb
     for name in passes:
       for k in PASSES[name]:
@@ -87,44 +82,10 @@ class Perturbations:
         p['scores'][name] = torch.empty(M, self.N, dtype=torch.float32, device=self.device)
     return p
 
-  def _perturb_fills(self, fill, keys, p):
-    """None (black) or the device view of each occluded input's fill: a [C] colour, a [H][W][C] frame or an array shaped like the
-    input, given for the rgb inputs at once (one array: 'rgb', and 'target_rgb' where it fits that input too) or per key."""
-    out = {k: None for k in keys}
-    if fill is None:
-      return out
-    forms = lambda k: (tuple(self.inputs[k].shape), tuple(self.inputs[k].shape[-3:]), tuple(self.inputs[k].shape[-1:]))
-    if isinstance(fill, dict):
-      per_key = fill
-      unknown = sorted(set(per_key) - {k for ks in PASSES.values() for k in ks if k in self.inputs})
-      if unknown:
-        raise ValueError('perturbation_attributions: fill for %s, but the model\'s image inputs are %s'
-                         % (', '.join(unknown), ', '.join(k for ks in PASSES.values() for k in ks if k in self.inputs)))
-    else:
-      shape = tuple(np.shape(fill))
-      per_key = {k: fill for k in keys if k == 'rgb' or (k == 'target_rgb' and shape in forms(k))}
-    for k, b in per_key.items():
-      if b is None or k not in out:
-        continue
-      b = torch.as_tensor(b, dtype=torch.float32)
-      if tuple(b.shape) not in forms(k):
-        raise ValueError("perturbation_attributions: fill for '%s' of shape %s; a colour %s, a frame %s or the whole input %s"
-                         % ((k, tuple(b.shape)) + forms(k)[::-1]))
-      if k not in p['fill'] or p['fill'][k].numel() != b.numel():      # (kept for the next call with a fill of this size)
-        p['fill'][k] = torch.empty(b.numel(), dtype=torch.float32, device=self.device)
-      p['fill'][k].copy_(b.reshape(-1), non_blocking=True)
-      out[k] = p['fill'][k]
-    return out
-
   def _perturb_head_weights(self, heads):
     """w_j of the prediction score: 1 on the columns of the selected heads (names as ``LSTMDecoder.select_loss_heads`` takes them)."""
-    table = self.decoder.heads
-    keys = [h[1] for h in table]
-    short = {k.replace('logits_', ''): k for k in keys}
-    picked = set(keys) if heads is None else {short.get(h, h) for h in ([heads] if isinstance(heads, str) else heads)}
-    if not picked or picked - set(keys):
-      raise ValueError('heads=%r: this model has the heads %s' % (heads, ', '.join(sorted(short))))
-    return [1.0 if k in picked else 0.0 for _, k, size, _, _ in table for _ in range(size)]
+    picked = resolve_heads(self.decoder.heads, heads)
+    return [1.0 if k in picked else 0.0 for _, k, size, _, _ in self.decoder.heads for _ in range(size)]
 
   def perturbation_attributions(self, method, patch=None, stride=None, grid=7, keep_prob=0.5, steps=64, fill=None, score='prediction',
                                 heads=None, seed=0, inputs=None):
@@ -183,69 +144,59 @@ class Perturbations:
       if self.labels_missing is None or self.labels_missing:
         raise ValueError("perturbation_attributions: score='loss' needs the labels; the batch was loaded without %s (load_batch(features, "
                          "labels)); score='prediction' needs none" % (', '.join(self.labels_missing or self.label_keys),))
-      selected = d.head_weights
-      d.select_loss_heads(heads)
-    restore = (lambda: setattr(d, 'head_weights', selected)) if by_loss else (lambda: None)
+    selected = d.head_weights
     try:
-      return self._perturbation_pass(passes, descs, M, (Gy, Gx) if occlusion else None, fill, w, by_loss, restore)
-    finally:
-      restore()
+      if by_loss:
+        d.select_loss_heads(heads)
+      out, preds0 = self._perturbation_pass(passes, descs, M, (Gy, Gx) if occlusion else None, fill, w, by_loss)
+    finally:      # score='loss' with ``heads``: the last forward is the model's own again, its losses the ones it had
+      d.head_weights = selected
+    self.forward()      # the model holds the forward at the clean inputs again
+    out['predictions'], off = {}, 0
+    for _, key, size, _, _ in d.heads:
+      out['predictions'][key] = preds0[:, off:off + size]
+      off += size
+    return out
 
-  def _perturbation_pass(self, passes, descs, M, grid_shape, fill, w, by_loss, restore_heads):
+  def _perturbation_pass(self, passes, descs, M, grid_shape, fill, w, by_loss):
     d = self.decoder
     p = self._perturb_buffers(passes, M)
     keys = [k for name in passes for k in PASSES[name] if k in self.inputs]
-    fills = self._perturb_fills(fill, keys, p)
+    # None (black) or per occluded input a [C] colour, a [H][W][C] frame or an array shaped like the input
+    fills = periodic_operands(self, 'perturbation_attributions', 'fill', fill, keys,
+                              lambda k: (tuple(self.inputs[k].shape), tuple(self.inputs[k].shape[-3:]), tuple(self.inputs[k].shape[-1:])), p['fill'],
+                              known=[k for ks in PASSES.values() for k in ks if k in self.inputs])
     if by_loss:
-      terms = d.sample_loss_terms()
-      if terms is None:
+      if d.sample_loss_terms() is None:
         raise ValueError("perturbation_attributions: score='loss' needs the decoder's per-sample loss terms, which this one does not keep "
                          "(LSTMDecoder.sample_losses: dim_h_fc outside {64, 128}, dim_h_lstm > 128, more than 32 outputs, loss_shaping "
                          "or the one-launch decoder); use score='prediction'")
-      rows, coef = terms
-      if p['rows'] is None:
-        p['rows'], p['coef'] = torch.empty(rows.shape, dtype=torch.float64, device=self.device), torch.empty(len(coef), dtype=torch.float64, device=self.device)
-      p['coef'].copy_(torch.tensor(coef, dtype=torch.float64), non_blocking=True)
     else:
       p['w'].copy_(torch.tensor(w, dtype=torch.float32), non_blocking=True)
-    for k in keys:
-      p['clean'][k].copy_(self.inputs[k])
-
-    def sample_losses_into(out):      # LSTMDecoder.sample_losses of the last forward, without an allocation
-      p['rows'].copy_(rows)
-      torch.mv(p['rows'], p['coef'], out=out)
-
     self.forward()      # the clean input: p_0, loss_n(x)
     p['preds0'].copy_(d.preds)
     if by_loss:
-      sample_losses_into(p['losses'][0])
+      d.sample_losses_into(p['losses'][0])
     out = {}
     for name in passes:
       desc, scores = descs[name], p['scores'][name]
       num, den, sal = p['sums'][name]
       group = [k for k in PASSES[name] if k in self.inputs]
-      for m in range(M):
-        for k in group:      # occlusion: only the previous patch and the step's own are written
-          ops.perturb_apply_into(self.inputs[k], p['clean'][k], fills[k], desc, m, prev_step=m - 1 if grid_shape else -1)
-        self.forward()
-        if by_loss:
-          sample_losses_into(p['losses'][1])
-          p['losses'][1].sub_(p['losses'][0])
-          scores[m].copy_(p['losses'][1])
-        else:
-          ops.perturb_score_into(scores[m], d.preds, p['preds0'], p['w'])
-        ops.perturb_accumulate_into(num, den, scores[m], desc, m, overwrite=m == 0)
-      for k in group:
-        self.inputs[k].copy_(p['clean'][k])
+      with clean_inputs(self, group, p['clean']):
+        for m in range(M):
+          for k in group:      # occlusion: only the previous patch and the step's own are written
+            ops.perturb_apply_into(self.inputs[k], p['clean'][k], fills[k], desc, m, prev_step=m - 1 if grid_shape else -1)
+          self.forward()
+          if by_loss:
+            d.sample_losses_into(p['losses'][1])
+            p['losses'][1].sub_(p['losses'][0])
+            scores[m].copy_(p['losses'][1])
+          else:
+            ops.perturb_score_into(scores[m], d.preds, p['preds0'], p['w'])
+          ops.perturb_accumulate_into(num, den, scores[m], desc, m, overwrite=m == 0)
       ops.perturb_finish_into(sal, num, den)
       tail = '' if name == 'rgb' else '_target'
       out['saliency' + tail], out['coverage' + tail], out['scores' + tail] = sal, den, scores
       if grid_shape:
         out['patch_scores' + tail] = scores.view(grid_shape[0], grid_shape[1], self.N)
-    restore_heads()      # score='loss' with ``heads``: the last forward is the model's own again, its losses the ones it had
-    self.forward()      # the model holds the forward at the clean inputs again
-    out['predictions'], off = {}, 0
-    for _, key, size, _, _ in d.heads:
-      out['predictions'][key] = p['preds0'][:, off:off + size]
-      off += size
-    return out
+    return out, p['preds0']

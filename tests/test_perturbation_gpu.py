@@ -452,6 +452,58 @@ def test_loss_score_and_refusals(dev):
     bound.perturbation_attributions('occlusion')
 
 
+def test_sample_losses_into_is_the_allocating_product(dev):
+  """``LSTMDecoder.sample_losses_into(out)``, the form both passes call inside their loops, gives the bits of the product
+  ``sample_losses()`` used to allocate for: rows.double() @ coef, under the training loss and under a selection of heads."""
+  model, feats, labels = _model(PASS_CASES[0], dev)
+  d = model.decoder
+  results = []
+  for heads in (None, ('cmd_ee',), None):
+    d.select_loss_heads(heads)
+    model.forward()
+    rows, coef = d.sample_loss_terms()
+    want = rows.double() @ torch.tensor(coef, dtype=torch.float64, device=rows.device)
+    out = torch.full((N2,), float('nan'), dtype=torch.float64, device=dev)
+    assert d.sample_losses_into(out) is True
+    assert torch.equal(out.view(torch.int64), want.view(torch.int64)) and bool(want.all()), heads
+    assert torch.equal(d.sample_losses().view(torch.int64), want.view(torch.int64)), heads
+    results.append(want)
+  assert not torch.equal(results[0], results[1]) and torch.equal(results[0], results[2])      # the coefficients follow the selection
+
+
+@pytest.mark.parametrize('who', ['perturb_accumulate_into', 'attr_accumulate_into'])
+def test_an_exception_inside_a_pass_leaves_the_loaded_batch(dev, monkeypatch, who):
+  """A ValueError raised on the host by the second accumulation of a pass reaches the caller; afterwards every image input holds the
+  loaded batch's bits, not the step's perturbed input, and the decoder's selection of heads is what it was."""
+  from geeco_amd import ops
+  model, feats, labels = _model(PASS_CASES[0], dev)
+  d = model.decoder
+  d.select_loss_heads(('cmd_ee',))
+  selected = list(d.head_weights)
+  real, calls = getattr(ops, who), []
+
+  def second_call_raises(*args, **kw):
+    calls.append(1)
+    if len(calls) == 2:
+      raise ValueError('the second call of %s' % who)
+    return real(*args, **kw)
+  monkeypatch.setattr(ops, who, second_call_raises)
+  with pytest.raises(ValueError, match='the second call of %s' % who):
+    if who == 'perturb_accumulate_into':
+      model.perturbation_attributions('occlusion', score='loss', heads=('cmd_grp',), **OCC)
+    else:
+      model.attributions('integrated_gradients', 3)
+  monkeypatch.setattr(ops, who, real)
+  torch.cuda.synchronize()
+  model.check_device_errors()
+  assert len(calls) == 2
+  for k in [k for ks in P_KEYS.values() for k in ks if k in feats]:
+    assert _same(model.inputs[k], feats[k]), k
+  assert d.head_weights == selected
+  out = model.perturbation_attributions('occlusion', **OCC)      # the next pass starts from the loaded batch
+  assert _same(model.inputs['rgb'], feats['rgb']) and bool(out['scores'].any())
+
+
 # ---- through the Estimator and the script ------------------------------------------------------------------------------------------
 def test_estimator_perturbation_attributions(dev, tmp_path):
   from geeco_amd import estimator as est, graph
