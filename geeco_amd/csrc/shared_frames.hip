@@ -67,10 +67,13 @@ extern "C" int geeco_pack_frames_by_address(const int64_t* table, int F, int fra
   const long long units = HW % 4 == 0 ? HW / 4 : HW;
   dim3 grid((unsigned)cdiv64(units, SF_THREADS), (unsigned)F);
   hipStream_t s = (hipStream_t)stream;
-  if (frames_u8)
+  if (frames_u8) {
+    geeco_note_kernel("pack_frames_kernel<true>");
     hipLaunchKernelGGL(pack_frames_kernel<true>, grid, dim3(SF_THREADS), 0, s, (const long long*)table, (long long)HW, x_in);
-  else
+  } else {
+    geeco_note_kernel("pack_frames_kernel<false>");
     hipLaunchKernelGGL(pack_frames_kernel<false>, grid, dim3(SF_THREADS), 0, s, (const long long*)table, (long long)HW, x_in);
+  }
   GEECO_LAUNCH_CHECK();
   return 0;
 }
@@ -139,12 +142,15 @@ extern "C" int geeco_window_states_fwd(const float* feat, const int* idx, const 
   const bool vec = ch % 4 == 0 && (reinterpret_cast<uintptr_t>(feat) & 15) == 0;
   dim3 grid((unsigned)N, (unsigned)K);
   hipStream_t s = (hipStream_t)stream;
-  if (vec)
+  if (vec) {
+    geeco_note_kernel("window_states_fwd_kernel<4>");
     hipLaunchKernelGGL(window_states_fwd_kernel<4>, grid, dim3(SF_THREADS), 0, s, feat, idx, jnt, tgt_idx, mode, F, N, K, cells, ch, J,
                        states, (long long)state_stride);
-  else
+  } else {
+    geeco_note_kernel("window_states_fwd_kernel<1>");
     hipLaunchKernelGGL(window_states_fwd_kernel<1>, grid, dim3(SF_THREADS), 0, s, feat, idx, jnt, tgt_idx, mode, F, N, K, cells, ch, J,
                        states, (long long)state_stride);
+  }
   GEECO_LAUNCH_CHECK();
   return 0;
 }
@@ -238,12 +244,15 @@ extern "C" int geeco_window_states_bwd(const float* dstates, int64_t state_strid
   const uintptr_t al = reinterpret_cast<uintptr_t>(feat) | reinterpret_cast<uintptr_t>(dfeat);
   const bool vec = ch % 4 == 0 && (al & 15) == 0;
   hipStream_t s = (hipStream_t)stream;
-  if (vec)
+  if (vec) {
+    geeco_note_kernel("window_states_bwd_kernel<4>");
     hipLaunchKernelGGL(window_states_bwd_kernel<4>, dim3((unsigned)F), dim3(SF_THREADS), 0, s, dstates, (long long)state_stride, feat,
                        idx, tgt_idx, mode, N, K, cells, ch, J, dfeat);
-  else
+  } else {
+    geeco_note_kernel("window_states_bwd_kernel<1>");
     hipLaunchKernelGGL(window_states_bwd_kernel<1>, dim3((unsigned)F), dim3(SF_THREADS), 0, s, dstates, (long long)state_stride, feat,
                        idx, tgt_idx, mode, N, K, cells, ch, J, dfeat);
+  }
   GEECO_LAUNCH_CHECK();
   return 0;
 }

@@ -21,6 +21,7 @@ import torch
 
 from oracle import geeco_oracle as O
 import _relu_taps as T
+from _table_builder_cases import window_states_bwd_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -134,19 +135,7 @@ def test_window_states_bwd_is_the_scatter_sum(dev, mode, ch, N, K, overlap, shif
   r = np.random.default_rng(ch + K)
   dst = (r.standard_normal([K, N, D]) if overlap else 0.5 + r.random([K, N, D])).astype(np.float32)
   feat = r.standard_normal([F, CELLS, ch]).astype(np.float32)
-  d4 = dst.astype(np.float64).reshape(K, N, CELLS, Ctot)
-  ref, mag = np.zeros([F, CELLS, ch]), np.zeros([F, CELLS, ch])
-  sign = -1.0 if mode == 'residual' else 1.0
-  for n in range(N):
-    for t in range(K):
-      ref[idx[n, t]] += sign * d4[t, n, :, :ch]
-      mag[idx[n, t]] += np.abs(d4[t, n, :, :ch])
-      if mode != 'plain':
-        cols = d4[t, n, :, ch + J:] if mode == 'constant' else d4[t, n, :, :ch]
-        ref[tgt[n]] += cols
-        mag[tgt[n]] += np.abs(cols)
-  ref *= feat > 0                                   # ReluGrad of the encoder's last layer
-  mag *= feat > 0
+  ref, mag = window_states_bwd_ref(dst, feat, idx, tgt, mode, J)      # the float64 scatter-sum, masked by feat > 0
   feat_d = _place(torch.from_numpy(feat), dev, shift)
   args = (torch.from_numpy(dst).to(dev), D, torch.from_numpy(idx).to(dev), feat_d, mode, F, N, K, CELLS, ch, J)
   kw = dict(tgt_idx=None if mode == 'plain' else torch.from_numpy(tgt).to(dev))
